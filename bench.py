@@ -2,20 +2,33 @@
 """Benchmark of the radiate() hot path (BASELINE.json: `radiate() calls/sec`, 200-layer
 ModernEarth column, full solar+IR correlated-k bin grid).
 
-  python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+  python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--full] [--dump-outputs DIR]
 
 A "step" is ONE full `Radtran%radiate` call -- opacity assembly + IR + solar two-stream +
 spectral integration -- on the ModernEarth column of tests/test_radtran.f90 (config 2:
 nz=200, nw=1000 opacity bins (600 IR / 600 solar), 8 g-points, 8 zenith angles, 5
 k-distribution species, synthetic tables: SURVEY.md 8(d)).  Inputs (tables and the
-column) are resident in HBM before the timed region starts.
+column) are resident in HBM before the timed region starts; they are built from fixed seeds,
+so the same arguments give the same inputs on every run.
+
+A plain run sets up, runs W warm-up steps, times exactly K steps in one loop and prints the
+headline line: metric, value, unit, higher_is_better, dtype, ms_per_step, olr_W_m2 / isr_W_m2.
+Everything else below (the per-kernel pass and roofline, repeats of the timed loop, per-call
+latencies, the RCE-Jacobian batch, the N > 1 column-parallel figure, the CPU baseline and the
+oracle comparison) is measured only with --full.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64): the
+level fluxes ir_fup_n, ir_fdn_n, sol_fup_n, sol_fdn_n and f_total, and (unsharded) the per-bin
+arrays of radtran_spectra_get_all (ir_/sol_fup_a, _fdn_a, _tau_band, sol_amean), ~7 MB at
+config 2; config 4 writes the batch's isr and olr.
 
 What the one JSON line carries (rank 0):
   value          = `pipelined_calls_per_s`: the driver's contract -- K calls enqueued back to back on the
-                 handle's stream, bracketed by barrier + synchronise, inputs resident; the MEDIAN of at
-                 least `--repeats` such K-step timings, and of as many as it takes to time ~0.3 s in all
-                 (a 20-step run is 2.5 ms: one timing is a sample of the clock ramp); their spread is in
-                 `repeats_calls_per_s`.  It is NOT the per-call latency of SURVEY.md 8(d) "Metric"; those are:
+                 handle's stream, bracketed by barrier + synchronise, inputs resident; with --full the
+                 MEDIAN of at least `--repeats` such K-step timings, and of as many as it takes to time
+                 ~0.3 s in all (a 20-step run is 2.5 ms: one timing is a sample of the clock ramp); their
+                 spread is in `repeats_calls_per_s`.  It is NOT the per-call latency of SURVEY.md 8(d)
+                 "Metric"; those are (--full):
   resident_sync  one `radiate_resident` + `synchronize` per call (column in HBM, one host round trip per
                  call), timed call by call inside the library; median, p10, p90 over 200 calls.
   sync_api_c     the drop-in call of SURVEY.md 8(d) "Metric": `radtran_toa_fluxes_wrapper` with host
@@ -139,9 +152,17 @@ def main():
     ap.add_argument("--nz", type=int, default=None)
     ap.add_argument("--nzen", type=int, default=None)
     ap.add_argument("--ncol", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-jacobian", action="store_true", help="skip the RCE-Jacobian batch figure (rce_jacobian_batch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the per-kernel pass and roofline, repeats of the "
+                         "timed loop (--repeats), per-call latencies, the RCE-Jacobian batch, the CPU baseline and the oracle "
+                         "comparison; without it a run times exactly --steps steps and prints the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-jacobian", action="store_true", help="(--full) skip the RCE-Jacobian batch figure (rce_jacobian_batch)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -258,28 +279,7 @@ def main():
         rad.synchronize()
         torch.cuda.synchronize()
 
-    for _ in range(args.warmup):
-        step()
-    # HIP events bracket the dominant kernel on the library's stream during the timed region, on
-    # every EVENT_STRIDE-th launch (an event pair drains the queue for ~5 us; sampled, the
-    # measurement costs the measured throughput ~0.3 us per step instead): the average of these
-    # durations is roofline.achieved's denominator.
-    # The short fully instrumented pass (per-kernel breakdown) runs first, so that the timed
-    # region is not also the one in which the device clocks settle.
-    rad.profile_stride(1)
-    rad.profile(True)
-    rad.profile_reset()
-    for _ in range(min(max(args.steps, 1), 50)):
-        step()
-    barrier()
-    kt = [rad.kernel_time(i) for i in range(4)]
-    kt_all = list(kt)          # the fully instrumented pass, kept apart from the timed region's own sample of the dominant kernel
-    rad.profile(2)
-    rad.profile_stride(EVENT_STRIDE)
-    rad.profile_reset()
-    dts = []
-    repeats = max(args.repeats, 1)
-    while len(dts) < repeats:
+    def timed_loop():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -290,18 +290,89 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t[0])
-        dts.append(dt)
-        if len(dts) == 1:
-            # a short K-step loop (the driver's 20 steps are 2.5 ms) is repeated until ~0.3 s have been timed
-            # in all, so that the median is taken at settled clocks (at most 200 repeats; with N ranks dt is
-            # the all-reduced maximum, the same number on every rank, so all of them loop alike)
-            repeats = max(repeats, min(200, int(0.3 / max(dt, 1e-6)) + 1))
-    dt = float(np.median(dts))
-    kt_dom = rad.kernel_time(1)
-    if kt_dom[1] > 0:
-        kt[1] = kt_dom
-    rad.profile_stride(1)
-    rad.profile(False)
+        return dt
+
+    for _ in range(args.warmup):
+        step()
+    if not args.full:
+        # the headline figure alone: exactly --steps steps, one timed loop, no events on the stream
+        dt = timed_loop()
+    else:
+        # HIP events bracket the dominant kernel on the library's stream during the timed region, on
+        # every EVENT_STRIDE-th launch (an event pair drains the queue for ~5 us; sampled, the
+        # measurement costs the measured throughput ~0.3 us per step instead): the average of these
+        # durations is roofline.achieved's denominator.
+        # The short fully instrumented pass (per-kernel breakdown) runs first, so that the timed
+        # region is not also the one in which the device clocks settle.
+        rad.profile_stride(1)
+        rad.profile(True)
+        rad.profile_reset()
+        for _ in range(min(max(args.steps, 1), 50)):
+            step()
+        barrier()
+        kt = [rad.kernel_time(i) for i in range(4)]
+        kt_all = list(kt)          # the fully instrumented pass, kept apart from the timed region's own sample of the dominant kernel
+        rad.profile(2)
+        rad.profile_stride(EVENT_STRIDE)
+        rad.profile_reset()
+        dts = []
+        repeats = max(args.repeats, 1)
+        while len(dts) < repeats:
+            dts.append(timed_loop())
+            if len(dts) == 1:
+                # a short K-step loop (the driver's 20 steps are 2.5 ms) is repeated until ~0.3 s have been timed
+                # in all, so that the median is taken at settled clocks (at most 200 repeats; with N ranks dt is
+                # the all-reduced maximum, the same number on every rank, so all of them loop alike)
+                repeats = max(repeats, min(200, int(0.3 / max(dts[0], 1e-6)) + 1))
+        dt = float(np.median(dts))
+        kt_dom = rad.kernel_time(1)
+        if kt_dom[1] > 0:
+            kt[1] = kt_dom
+        rad.profile_stride(1)
+        rad.profile(False)
+
+    # what the last timed step left behind: level fluxes (with torch's all-reduce: the reduced rows of the
+    # aliased tensor), f_total and, unsharded, the per-bin arrays of both channels
+    if dist_on and torch_ar:
+        rows = flux.detach().cpu().numpy().astype(np.float64)
+        lvl = {k: rows[i * (nz + 1):(i + 1) * (nz + 1)] for i, k in enumerate(("ir_fup_n", "ir_fdn_n", "sol_fup_n", "sol_fdn_n"))}
+    else:
+        w_ir, w_sol = rad.wrk_ir, rad.wrk_sol    # with a communicator: the reduced rows, the same on every rank
+        lvl = {"ir_fup_n": w_ir.fup_n, "ir_fdn_n": w_ir.fdn_n, "sol_fup_n": w_sol.fup_n, "sol_fdn_n": w_sol.fdn_n}
+    olr = -float(lvl["ir_fdn_n"][nz] - lvl["ir_fup_n"][nz])
+    isr = float(lvl["sol_fdn_n"][nz] - lvl["sol_fup_n"][nz])
+    if args.dump_outputs and rank == 0:
+        outputs = dict(lvl, f_total=rad.f_total)
+        if not dist_on:
+            outputs.update(rad.spectra_all(do_solar=True))
+            outputs = {k: np.array(v) for k, v in outputs.items()}   # copies: the library's page-locked arrays are released next
+            rad.spectra_release()
+        dump_outputs(args.dump_outputs, outputs)
+
+    def headline(value_is):
+        """The keys every run prints: the figure itself, its unit and what it is."""
+        return {"metric": "radiate() calls/sec", "value": args.steps / dt, "unit": "calls/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
+                "higher_is_better": True, "scaling": "strong" if world > 1 else "weak", "vs_baseline": None,
+                "dtype": "f64", "data": "synthetic",
+                "config": {"workload": what,
+                           "parallelism": ("bins sharded over %d GPUs + 1 all-reduce of %d f64" % (world, 4 * (nz + 1)))
+                           if world > 1 else "1 GPU"},
+                "value_is": value_is, "pipelined_calls_per_s": args.steps / dt,
+                "collective": (("library: ncclAllReduce on the handle's stream (radtran_comm_init_rank)" if not torch_ar else
+                                "torch.distributed all_reduce on an aliased tensor") if dist_on else None),
+                "olr_W_m2": olr / 1e3, "isr_W_m2": isr / 1e3}
+
+    if not args.full:
+        if rank == 0:
+            emit_line(json_fd, headline("pipelined_calls_per_s: one timed loop of the %d steps, resident inputs, calls enqueued back "
+                                        "to back, one synchronise per loop (the driver's contract); per-call latencies, the "
+                                        "roofline and the CPU baseline are measured with --full" % args.steps))
+        if dist_on:
+            dist.barrier()
+            rad.comm_destroy()
+            dist.destroy_process_group()
+        return
 
     # ---- per-call latencies (SURVEY.md 8(d) "Metric"): one host round trip per call
     def _stats(ts, what):
@@ -400,8 +471,6 @@ def main():
         isr = w_sol.fdn_n[nz] - w_sol.fup_n[nz]
 
     if rank == 0:
-        ms_per_step = 1e3 * dt / args.steps
-        value = args.steps / dt
         names = list(KERNELS)
         if rad.fused and kt[2][1] == 0:   # opacity and two-stream work ran as one grid (k_fused), timed as kernel id 1
             names[1] = "fused"
@@ -452,26 +521,17 @@ def main():
                                                           "timed region: each pair drains the queue, so these figures sit a few us above "
                                                           "the profiler's and their sum above ms_per_step -- a breakdown, not a budget" % min(max(args.steps, 1), 50),
                     "whole_call_frac": (b_alg / (dt / args.steps) / 1e9) / HBM_PEAK_GBS}
-        out = {"metric": "radiate() calls/sec", "value": value, "unit": "calls/s", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-               "higher_is_better": True, "scaling": "strong" if world > 1 else "weak", "vs_baseline": None,
-               "dtype": "f64", "data": "synthetic",
-               "config": {"workload": what,
-                          "parallelism": ("bins sharded over %d GPUs + 1 all-reduce of %d f64" % (world, 4 * (nz + 1)))
-                          if world > 1 else "1 GPU"},
-               "value_is": "pipelined_calls_per_s: median of %d repeats of the %d-step loop, resident inputs, calls enqueued back to "
-                           "back, one synchronise per loop (the driver's contract); per-call latencies are in resident_sync / sync_api_c" % (len(dts), args.steps),
-               "pipelined_calls_per_s": value,
-               "collective": (("library: ncclAllReduce on the handle's stream (radtran_comm_init_rank)" if not torch_ar else
-                               "torch.distributed all_reduce on an aliased tensor") if dist_on else None),
+        out = headline("pipelined_calls_per_s: median of %d repeats of the %d-step loop, resident inputs, calls enqueued back to "
+                       "back, one synchronise per loop (the driver's contract); per-call latencies are in resident_sync / sync_api_c" % (len(dts), args.steps))
+        out.update({
                "repeats_calls_per_s": {"n": len(dts), "min": args.steps / max(dts), "p10": args.steps / float(np.percentile(dts, 90)),
                                        "median": args.steps / dt, "p90": args.steps / float(np.percentile(dts, 10)),
                                        "max": args.steps / min(dts), "first": args.steps / dts[0]},
-               "olr_W_m2": olr / 1e3, "isr_W_m2": isr / 1e3, "roofline": roofline,
+               "roofline": roofline,
                "algorithmic": {"N_PT": nodes["N_PT"], "N_PT_table": nodes["N_PT_full"], "N_T": nodes["N_T"],
                                "N_T_table": nodes["N_T_full"], "bytes_distinct_nodes": b_alg,
                                "bytes_whole_tables": b_alg_full,
-                               "frac_whole_tables": (b_alg_full / dur / 1e9) / HBM_PEAK_GBS if dur > 0 else 0.0}}
+                               "frac_whole_tables": (b_alg_full / dur / 1e9) / HBM_PEAK_GBS if dur > 0 else 0.0}})
         if resident_sync is not None:
             out["resident_sync"] = resident_sync
         if sync_api_c is not None:
@@ -488,8 +548,7 @@ def main():
                 out["rce_jacobian_batch"]["cpu_port_ms"] = out["cpu_baseline"]["ir_only_call_ms"] * (nz + 1)
                 out["rce_jacobian_batch"]["cpu_port_what"] = ("%d x one IR-only oracle call on the stored opacities (%d threads, %.1f ms each, "
                                                               "4 timed)" % (nz + 1, out["cpu_baseline"]["cores"], out["cpu_baseline"]["ir_only_call_ms"]))
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
+        emit_line(json_fd, out)
     if dist_on:
         dist.barrier()
         rad.comm_destroy()
@@ -578,7 +637,7 @@ def config4(args, rad, tables, nz, nzen, world, rank, dist_on, dist, torch, json
     from clima_amd import synthetic as S
     cols = S.perturbed_columns(args.ncol, nz=nz, seed=7)
     mine = cols[rank::world] if world > 1 else cols
-    steps, warm = max(1, min(args.steps, 5)), max(1, min(args.warmup, 2))
+    steps, warm = args.steps, args.warmup
     for _ in range(warm):
         isr, olr = rad.TOA_fluxes_batch(mine)
     dts = []
@@ -607,10 +666,25 @@ def config4(args, rad, tables, nz, nzen, world, rank, dist_on, dist, torch, json
                           "parallelism": "%d GPU(s), columns split, no collective" % world},
                "us_per_column": 1e6 * dt / args.ncol * world, "value_is": "median of %d batches" % steps,
                "olr_W_m2_mean": float(np.mean(olr)) / 1e3, "fused_fallbacks": rad.fused_fallbacks}
-        sys.stdout.flush()
-        os.write(json_fd, (json.dumps(out) + "\n").encode())
+        if args.dump_outputs:   # this rank's columns (all of them with one rank)
+            dump_outputs(args.dump_outputs, {"isr": isr, "olr": olr})
+        emit_line(json_fd, out)
     if dist_on:
         dist.destroy_process_group()
+
+
+def emit_line(json_fd, out):
+    """The one JSON result line, on the real stdout."""
+    sys.stdout.flush()
+    os.write(json_fd, (json.dumps(out) + "\n").encode())
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: every array as <path>/<name>.npy in float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def physical_cores():

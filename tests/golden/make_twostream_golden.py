@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/twostream_golden.npz from the REFERENCE two-stream solver.
+"""Generate tests/golden/twostream_golden_<i>.npz from the REFERENCE two-stream solver.
 
 Runs only in the build container: it calls oracle/_ref/libclima_twostream_ref.so, which
 oracle/Makefile compiles with amdflang, unmodified, from
@@ -150,9 +150,29 @@ def main():
             out.update({r + "c%d_k" % j: np.array(ks), r + "c%d_b" % j: bp2[ks], r + "c%d_fup" % j: fup2, r + "c%d_fdn" % j: fdn2})
         m += 1
     out["nresp"] = np.array([m])
-    path = os.path.join(HERE, "twostream_golden.npz")
-    np.savez_compressed(path, **out)
-    print("wrote", path, n, "cases", os.path.getsize(path), "bytes")
+    for i, part in enumerate(split_parts(out)):
+        path = os.path.join(HERE, "twostream_golden_%d.npz" % i)
+        np.savez_compressed(path, **part)
+        print("wrote", path, len(part), "arrays", os.path.getsize(path), "bytes")
+    print(n, "cases")
+
+
+PART_BYTES = 800_000
+
+
+def split_parts(out):
+    """The arrays in key order, cut into parts of at most PART_BYTES uncompressed, so that every
+    archive stays well under the 1 MiB a committed file may have."""
+    parts, cur, size = [], {}, 0
+    for k, v in out.items():
+        v = np.asarray(v)
+        if cur and size + v.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += v.nbytes
+    parts.append(cur)
+    return parts
 
 
 if __name__ == "__main__":

@@ -7,7 +7,8 @@ import pytest
 
 from clima_amd import synthetic as S
 
-REF_TEMPLATE = "/root/reference/templates/ModernEarth/atmosphere.txt"
+# the reference's templates/ModernEarth/atmosphere.txt, stored as a fixture
+REF_TEMPLATE = os.path.join(os.path.dirname(__file__), "golden", "ModernEarth_atmosphere.txt")
 
 
 def _write_atmosphere(path, drop=None, rename=None):
@@ -41,7 +42,6 @@ def test_file_column_equals_fixture_column(tmp_path):
         assert col["T_surface"] == ref["T_surface"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TEMPLATE), reason="reference templates not present")
 def test_reference_template_parses_to_the_fixture():
     from clima_amd.atmosphere import column_from_atmosphere
     col = column_from_atmosphere(REF_TEMPLATE, S.MODERN_EARTH_SPECIES, n_particles=1)

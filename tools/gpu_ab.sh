@@ -3,7 +3,7 @@
 # A build that fails to load or to run shows its stderr and a FAILED line instead of a JSON traceback.
 for round in 1 2 3; do
   for lib in "$@"; do
-    out=$(CLIMA_HIP_LIB=$PWD/$lib python3 bench.py --steps 400 --warmup 200 --repeats 3 --no-cpu-baseline $AB_ARGS)
+    out=$(CLIMA_HIP_LIB=$PWD/$lib python3 bench.py --full --steps 400 --warmup 200 --repeats 3 --no-cpu-baseline $AB_ARGS)
     rc=$?
     if [ $rc -ne 0 ] || [ -z "$out" ]; then echo "$lib round $round FAILED (exit $rc)"; continue; fi
     echo "$out" | python3 -c "

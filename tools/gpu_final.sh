@@ -14,27 +14,27 @@ mkdir -p $o
 run() { name=$1; shift; echo "== $name: $*"; "$@" > $o/${tag}_$name 2> $o/${tag}_$name.err || { echo "FAILED: $name"; tail -5 $o/${tag}_$name.err; return 1; }; }
 if want lines; then
 # ---- bench lines: the driver's own command, the default command, configs 3 / 4 / 5
-run bench_line_steps20.json python3 bench.py --gpus 1 --steps 20 --warmup 5 || exit 1
-run bench_line_default.json python3 bench.py || exit 1
-run bench_line_config3.json python3 bench.py --config 3 --no-cpu-baseline || exit 1
-run bench_line_config4.json python3 bench.py --config 4 --no-cpu-baseline || exit 1
-run bench_line_config5.json python3 bench.py --config 5 --no-cpu-baseline || exit 1
+run bench_line_steps20.json python3 bench.py --gpus 1 --steps 20 --warmup 5 --full || exit 1
+run bench_line_default.json python3 bench.py --full || exit 1
+run bench_line_config3.json python3 bench.py --full --config 3 --no-cpu-baseline || exit 1
+run bench_line_config4.json python3 bench.py --full --config 4 --steps 5 --warmup 2 --no-cpu-baseline || exit 1
+run bench_line_config5.json python3 bench.py --full --config 5 --no-cpu-baseline || exit 1
 # ---- one rank's share of an N-GPU step rehearsed on one GPU, through the LIBRARY's own RCCL step (one-rank
 #      communicator + the bin shard (0, N)): configs 2 and 5
 for n in 2 4 8; do
-  CLIMA_BENCH_FORCE_DIST=1 CLIMA_BENCH_FAKE_SHARD=0,$n run bench_line_fake_shard_0_of_$n.json python3 bench.py --no-cpu-baseline || exit 1
-  CLIMA_BENCH_FORCE_DIST=1 CLIMA_BENCH_FAKE_SHARD=0,$n run bench_line_config5_fake_shard_0_of_$n.json python3 bench.py --config 5 --no-cpu-baseline || exit 1
+  CLIMA_BENCH_FORCE_DIST=1 CLIMA_BENCH_FAKE_SHARD=0,$n run bench_line_fake_shard_0_of_$n.json python3 bench.py --full --no-cpu-baseline || exit 1
+  CLIMA_BENCH_FORCE_DIST=1 CLIMA_BENCH_FAKE_SHARD=0,$n run bench_line_config5_fake_shard_0_of_$n.json python3 bench.py --full --config 5 --no-cpu-baseline || exit 1
 done
-CLIMA_BENCH_FORCE_DIST=1 run bench_line_one_rank_comm.json python3 bench.py --no-cpu-baseline || exit 1
-CLIMA_BENCH_FORCE_DIST=1 CLIMA_BENCH_TORCH_ALLREDUCE=1 run bench_line_one_rank_torch.json python3 bench.py --no-cpu-baseline || exit 1
+CLIMA_BENCH_FORCE_DIST=1 run bench_line_one_rank_comm.json python3 bench.py --full --no-cpu-baseline || exit 1
+CLIMA_BENCH_FORCE_DIST=1 CLIMA_BENCH_TORCH_ALLREDUCE=1 run bench_line_one_rank_torch.json python3 bench.py --full --no-cpu-baseline || exit 1
 run bench_line_gpus2_refused.txt bash -c 'python3 bench.py --gpus 2 --steps 2 --warmup 1; echo "exit code $?"'   # one GPU here: the launcher's one-line refusal
 fi
 if want profile; then
 # ---- kernel statistics + PMC passes of the default workload
 bash tools/gpu_profile.sh $tag || exit 1
 # ... and of configs 3 and 5 (their bench lines take traffic and issue fraction from the same JSON record)
-PMC_EXTRA="--config 3" bash tools/gpu_profile.sh ${tag}c3 --config 3 --steps 100 --warmup 20 --no-cpu-baseline || exit 1
-PMC_EXTRA="--config 5" bash tools/gpu_profile.sh ${tag}c5 --config 5 --steps 100 --warmup 20 --no-cpu-baseline || exit 1
+PMC_EXTRA="--config 3" bash tools/gpu_profile.sh ${tag}c3 --full --config 3 --steps 100 --warmup 20 --no-cpu-baseline || exit 1
+PMC_EXTRA="--config 5" bash tools/gpu_profile.sh ${tag}c5 --full --config 5 --steps 100 --warmup 20 --no-cpu-baseline || exit 1
 fi
 if want sweeps1; then
 # ---- sweeps

@@ -4,7 +4,7 @@
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 [ -f gpurun_out/counters_avail.txt ] || rocprofv3 -L > gpurun_out/counters_avail.txt 2>&1
-pargs="--steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-jacobian ${PMC_EXTRA}"
+pargs="--full --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline --no-jacobian ${PMC_EXTRA}"
 for lib in "$@"; do
   name=$(basename $lib .so)
   export CLIMA_HIP_LIB=$PWD/$lib

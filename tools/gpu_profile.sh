@@ -5,10 +5,10 @@
 #   tools/gpu_profile.sh <tag> [bench args...]
 set -o pipefail
 tag=${1:-r02}; shift
-args=${@:---steps 100 --warmup 20 --no-cpu-baseline}
+args=${@:---full --steps 100 --warmup 20 --no-cpu-baseline}
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_stats -o run -- python3 bench.py $args > gpurun_out/${tag}_stats.log 2>&1 || exit 1
-pargs="--steps 10 --warmup 2 --repeats 1 --no-cpu-baseline ${PMC_EXTRA}"
+pargs="--full --steps 10 --warmup 2 --repeats 1 --no-cpu-baseline ${PMC_EXTRA}"
 for set in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE" \
            "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS" \
            "FETCH_SIZE" "WRITE_SIZE"; do
