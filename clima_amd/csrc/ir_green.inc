@@ -23,7 +23,9 @@
 //
 // Kernels: k_green_factor (wave per q: elimination, z, running products, level factors), k_green_unit (thread per (k, q):
 // unit responses), k_green_local (level factors relative to their block's reference level), k_green_db (Planck
-// differences), k_green_accum_far / k_green_accum_mixed (the sums), k_green_combine (columns).
+// differences), k_green_accum_far / k_green_accum_mixed (the sums), k_green_combine (columns).  The exact Jacobian
+// (radtran_ir_jacobian) is the limit of a step to 0: k_green_dbdt (Planck derivatives) in place of k_green_db, every
+// level one deviation, k_green_jacobian (the matrices) in place of k_green_combine.
 // Layouts: q = (bin - ir_lo) * ng + g, NQ of them; every array is q-major.  Levels, layers and k are TOA-first as in
 // the kernels above (k = nz is the surface); the result rows are ground-first like every level row of the library.
 
@@ -427,6 +429,27 @@ __global__ __launch_bounds__(256) void k_green_db(GreenParams p) {
   p.DB[(size_t)bi * p.ndev_pad + dev] = v;
 }
 
+// 6'. the exact Jacobian's amplitudes (radtran_ir_jacobian): the Planck DERIVATIVES at the deviations' base temperatures,
+//     times the bin's width -- the limit of k_green_db's differences over the step.  With x = h nu / k T and e = exp(-x),
+//     dB/dT = K (x / T) e^x / (e^x - 1)^2 = K (x / expm1(-x)) (e / expm1(-x)) / T: large x takes e to 0 (no overflow, no
+//     NaN), small x keeps its digits through expm1.  DB[bin][dev]
+__global__ __launch_bounds__(256) void k_green_dbdt(GreenParams p) {
+  const int dev = blockIdx.x * blockDim.x + threadIdx.x, bi = blockIdx.y;
+  if (dev >= p.ndev_pad) return;
+  double v = 0.0;
+  if (dev < p.ndev) {
+    const int l = p.ir_start + p.ir_lo + bi, ll = p.ir_lo + bi;
+    const double avg_freq = 0.5 * (p.freq[l] + p.freq[l + 1]);
+    const double T = p.base_T[p.dev_k[dev]];
+    const double x = ((PLANK * avg_freq) / K_BOLTZ_SI) / T;
+    const double K = 1.0e3 * ((2.0 * PLANK * (avg_freq * avg_freq * avg_freq)) / (C_LIGHT * C_LIGHT));
+    const double e = exp(-x), em = expm1(-x);
+    v = K * ((x / em) * (e / em)) / T;
+    v *= p.ir_freq[ll] - p.ir_freq[ll + 1];
+  }
+  p.DB[(size_t)bi * p.ndev_pad + dev] = v;
+}
+
 // 7a. accumulation, far form: one wave = 64 deviations x one level block x one bin split.  A lane forms its deviation's
 //     amplitude once per (bin, g-point) -- one exponential -- and adds it, times the block's 2 x 16 level factors, onto
 //     its 32 sums; the level factors are the same for every lane: scalar loads, SGPR operands of the FMAs.
@@ -571,7 +594,8 @@ __device__ __forceinline__ void green_far_pass_mfma(const GreenParams &p, const 
     constexpr bool TAIL = decltype(tail)::value;
     int q = q_lo + kq + 4 * s;
     if constexpr (TAIL) q = min(q, q_hi - 1);
-    const int b = (int)__umulhi((unsigned)q, ng_inv);    // q / ng (q < 65536, radtran_api.hip's guard on NQ)
+    // q / ng (q < 65536, radtran_api.hip's guard on NQ; one g-point: ng_inv wraps to 0, q is the bin itself)
+    const int b = ng == 1 ? q : (int)__umulhi((unsigned)q, ng_inv);
     const double *row = pdb + (size_t)b * p.ndev_pad;
 #pragma unroll
     for (int i = 0; i < 4; i++) db.v[i] = row[16 * i];
@@ -821,6 +845,30 @@ __global__ __launch_bounds__(64) void k_green_accum_mixed(GreenParams p) {
   }
 }
 
+// the response of level lv to deviation dev, its bin splits' partial sums added onto (up, dn) in split order (bitwise
+// repeatable).  A level's sums sit where the kernel that formed them put them: far form or the mixed blocks' own splits.
+__device__ __forceinline__ void green_split_sum(const GreenParams &p, int dev, int lv, double &up, double &dn) {
+  const int nl = p.nz + 1;
+  const bool mixed = green_block_class(p.dev_k[dev], lv / GREEN_LB, p.nz) == 2;
+  const double *base = mixed ? p.partial_m : p.partial;
+  const int ns = mixed ? p.msplit : p.qsplit;
+  // eight splits' loads at a time, added in split order (one after the other each waited for the one before it:
+  // 16 + 27 memory round trips per value)
+  const size_t stride = (size_t)p.ndev_pad * 2 * nl;
+  const double *pp0 = base + ((size_t)dev * 2) * nl + lv;
+  for (int s0 = 0; s0 < ns; s0 += 8) {
+    double u8[8], d8[8];
+#pragma unroll
+    for (int s = 0; s < 8; s++) {
+      const double *pp = pp0 + (size_t)min(s0 + s, ns - 1) * stride;
+      u8[s] = pp[0]; d8[s] = pp[nl];
+    }
+#pragma unroll
+    for (int s = 0; s < 8; s++)
+      if (s0 + s < ns) { up = up + u8[s]; dn = dn + d8[s]; }
+  }
+}
+
 // 8. the columns: base rows + the responses of the column's deviations (splits in order), reversed to ground-first
 //    (radiate.f90:140-154); f_total with the solar rows of the handle's last solar call (clima_radtran.f90:287).
 //    A column that went through the general kernel (col_src >= 0) is copied.  out / gen_out: three arrays
@@ -837,31 +885,35 @@ __global__ __launch_bounds__(256) void k_green_combine(GreenParams p) {
     }
     const int lv = p.nz - i;
     double up = p.gen_out[i], dn = p.gen_out[p.gen_arr + i];    // column 0 of the general sub-batch is the base
-    for (int j = p.col_ptr[c]; j < p.col_ptr[c + 1]; j++) {
-      const int dev = p.col_dev[j];
-      // (a level's sums sit where the kernel that formed them put them: far form or the mixed blocks' own splits)
-      const bool mixed = green_block_class(p.dev_k[dev], lv / GREEN_LB, p.nz) == 2;
-      const double *base = mixed ? p.partial_m : p.partial;
-      const int ns = mixed ? p.msplit : p.qsplit;
-      // eight splits' loads at a time, added in split order (one after the other each waited for the one before it:
-      // 16 + 27 memory round trips per value)
-      const size_t stride = (size_t)p.ndev_pad * 2 * nl;
-      const double *pp0 = base + ((size_t)dev * 2) * nl + lv;
-      for (int s0 = 0; s0 < ns; s0 += 8) {
-        double u8[8], d8[8];
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-          const double *pp = pp0 + (size_t)min(s0 + s, ns - 1) * stride;
-          u8[s] = pp[0]; d8[s] = pp[nl];
-        }
-#pragma unroll
-        for (int s = 0; s < 8; s++)
-          if (s0 + s < ns) { up = up + u8[s]; dn = dn + d8[s]; }
-      }
-    }
+    for (int j = p.col_ptr[c]; j < p.col_ptr[c + 1]; j++) green_split_sum(p, p.col_dev[j], lv, up, dn);
     o[i] = up; o[p.out_arr + i] = dn;
     o[2 * p.out_arr + i] = (p.flux_n[3 * nl + i] - p.flux_n[2 * nl + i]) + (dn - up);
   }
+}
+
+// 8'. the exact Jacobian (radtran_ir_jacobian): every level k = 0..nz is one deviation (dev_k sorted, one each), and its
+//     responses to the Planck derivatives (k_green_dbdt) are the matrix's column j = nz - k (k TOA-first, the column of
+//     x(1) = T_surface first), row i = nz - lv ground-first.  No base rows, no solar rows: the derivative of
+//     f_total = (solar) + (dn - up) at fixed opacities is dn - up.  out: three (nz+1) x (nz+1) arrays column-major
+//     (up, down, total), out_arr elements apart.  Block per deviation, thread per level.
+__global__ __launch_bounds__(256) void k_green_jacobian(GreenParams p) {
+  const int dev = blockIdx.x, nl = p.nz + 1;
+  double *o = p.out + (size_t)(p.nz - p.dev_k[dev]) * nl;
+  for (int i = threadIdx.x; i < nl; i += blockDim.x) {
+    double up = 0.0, dn = 0.0;
+    green_split_sum(p, dev, p.nz - i, up, dn);
+    o[i] = up; o[p.out_arr + i] = dn; o[2 * p.out_arr + i] = dn - up;
+  }
+}
+
+// total = dn - up of a communicator handle's reduced Jacobian (radtran_ir_jacobian; a rank without IR bins runs this
+// and no k_green_* kernel).  jac: three arrays of n doubles (up, down, total), arr elements apart.
+__global__ __launch_bounds__(256) void k_jacobian_total(double *jac, size_t arr, size_t n) {
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x)
+    jac[2 * arr + t] = jac[arr + t] - jac[t];
+}
+void launch_jacobian_total(double *jac, size_t arr, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_jacobian_total, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, s, jac, arr, n);
 }
 
 // f_total of a batch's columns from their (reduced) IR rows and the handle's solar rows (clima_radtran.f90:287): what a
@@ -927,4 +979,10 @@ void launch_green_columns(const GreenParams &p, int ncol, hipStream_t s) {
     launch_green_accumulate(p, s);
   }
   hipLaunchKernelGGL(k_green_combine, dim3(ncol), dim3(256), 0, s, p);
+}
+// the exact Jacobian from the opacity-only part: Planck derivatives, the two accumulations, the matrices (ndev = nz + 1)
+void launch_green_jacobian(const GreenParams &p, hipStream_t s) {
+  hipLaunchKernelGGL(k_green_dbdt, dim3((p.ndev_pad + 255) / 256, p.n_ir), dim3(256), 0, s, p);
+  launch_green_accumulate(p, s);
+  hipLaunchKernelGGL(k_green_jacobian, dim3(p.ndev), dim3(256), 0, s, p);
 }

@@ -1636,33 +1636,76 @@ static void green_factor_part(Radtran *r, GreenParams &g) {
   HIPCHK(hipGetLastError());
 }
 
+// What the response form's two callers (ir_batch_green, radtran_ir_jacobian) share.
+// The level blocks around a deviation's own levels (green_block_class == 2), deviations sorted by k: the pairs of
+// k_green_accum_mixed
+static void green_mixed_list(const std::vector<int> &dev_k, int nz, std::vector<int> &mdev, std::vector<int> &mblk) {
+  const int nl = nz + 1;
+  for (int d = 0; d < (int)dev_k.size(); d++)
+    for (int blk = std::max(0, (dev_k[d] - 1) / 16 - 1); blk < (nl + 15) / 16; blk++) {
+      const int cls = green_block_class(dev_k[d], blk, nz);
+      if (cls == 2) { mdev.push_back(d); mblk.push_back(blk); }
+      if (cls == 1) break;
+    }
+}
+// bin splits of the two accumulation kernels for ndev deviations (the mixed blocks' from a lower bound of their
+// number when nmix < 0: one per deviation)
+static void green_splits(const Radtran *r, int ndev, int nmix, int &qsplit, int &msplit) {
+  const int nl = r->nz + 1, n_ir = r->ir_n;
+  // bin splits: the accumulation's waves should fill the machine ONCE (green_far_resident_waves): a few waves more
+  // than that and the kernel takes two rounds
+  qsplit = green_far_splits(n_ir, green_far_waves(ndev, nl));
+  // the mixed blocks: few pairs, finer splits
+  msplit = std::max(qsplit, std::min(n_ir, 4096 / std::max(((nmix < 0 ? ndev : nmix) + 3) / 4, 1)));
+}
+// bytes of the response form's work arrays for ndev deviations (~150 KB per (bin, g-point) at 500 layers, and the
+// partial sums of the two accumulation kernels: their bin splits x deviations x 2 x levels)
+static double green_work_bytes(const Radtran *r, int ndev) {
+  const int nz = r->nz, nl = nz + 1;
+  int qs, ms;
+  green_splits(r, ndev, -1, qs, ms);
+  return ((double)r->ir_n * r->ng * (13.0 * nl + 14.0 * nz + 4.3 * nl) + (double)(qs + ms) * ((double)ndev + 64.0) * 2.0 * nl) * 8.0;
+}
+// the handle's pinned staging block, at least `bytes` long
+static char *green_stage(Radtran *r, size_t bytes) {
+  if (r->h_green_n < bytes) {
+    if (r->h_green) (void)hipHostFree(r->h_green);
+    r->h_green = nullptr; r->h_green_n = 0;
+    HIPCHK(hipHostMalloc((void **)&r->h_green, bytes + bytes / 2, hipHostMallocDefault));
+    r->h_green_n = bytes + bytes / 2;
+  }
+  return r->h_green;
+}
+// the accumulation's arrays (Planck factors, the partial sums of both kernels) and split counts; the deviation and
+// mixed-pair lists are the caller's
+static void green_accum_arrays(Radtran *r, GreenParams &g, int ndev, int ndev_pad, int nmix) {
+  const int nl = r->nz + 1, n_ir = r->ir_n;
+  int qsplit, msplit;
+  green_splits(r, ndev, nmix, qsplit, msplit);
+  const size_t need = (size_t)n_ir * ndev_pad + 64 + (size_t)(qsplit + msplit) * ndev_pad * 2 * nl;
+  if (r->d_green_acc.n < need) r->d_green_acc.alloc(need);
+  double *w = r->d_green_acc.p;
+  auto take = [&](size_t cnt) { double *p0 = w; w += cnt; return p0; };
+  g.DB = take((size_t)n_ir * ndev_pad + 64); g.partial = take((size_t)qsplit * ndev_pad * 2 * nl);
+  g.msplit = msplit; g.partial_m = take((size_t)msplit * ndev_pad * 2 * nl);
+  g.ndev = ndev; g.ndev_pad = ndev_pad; g.qsplit = qsplit; g.nmix = nmix;
+}
+
 // `pre`: the opacity-only part has been issued already (green_factor_part's parameter block)
 static void ir_batch_green(Radtran *r, const GreenPlan &pl, const double *T, const double *Ts, int n, double *d_out, const GreenParams *pre) {
-  const int nz = r->nz, nl = nz + 1, n_ir = r->ir_n;
+  const int nz = r->nz, nl = nz + 1;
   auto ensure = [](DevBuf<double> &b, size_t count) { if (b.n < count) b.alloc(count); };
   // 1. the base profile and the dense columns through the general kernel
   const int ngen = 1 + (int)pl.dense.size();
   const int ndev = (int)pl.dev_k.size(), ndev_pad = std::max(16, (ndev + 15) / 16 * 16);
-  std::vector<int> mdev, mblk;           // the level blocks around a deviation's own levels (green_block_class == 2)
-  for (int d = 0; d < ndev; d++)
-    for (int blk = std::max(0, (pl.dev_k[d] - 1) / 16 - 1); blk < (nl + 15) / 16; blk++) {
-      const int cls = green_block_class(pl.dev_k[d], blk, nz);
-      if (cls == 2) { mdev.push_back(d); mblk.push_back(blk); }
-      if (cls == 1) break;
-    }
+  std::vector<int> mdev, mblk;
+  green_mixed_list(pl.dev_k, nz, mdev, mblk);
   const int nmix = (int)mdev.size();
   // everything the host hands over goes through ONE pinned block (no pageable copies, no synchronise before the
   // kernels): doubles T [ngen][nz] | Ts [ngen] | dev_T [ndev_pad] | base_T by level k [nl], then ints
   // dev_k [ndev_pad] | col_src [n] | col_ptr [n+1] | col_dev [ndev] | mix_dev [nmix] | mix_blk [nmix]
   const size_t nd = (size_t)ngen * nz + ngen + ndev_pad + nl, ni = (size_t)ndev_pad + n + (n + 1) + ndev + 2 * (size_t)nmix;
-  const size_t stage_bytes = sizeof(double) * nd + sizeof(int) * ni;
-  if (r->h_green_n < stage_bytes) {
-    if (r->h_green) (void)hipHostFree(r->h_green);
-    r->h_green = nullptr; r->h_green_n = 0;
-    HIPCHK(hipHostMalloc((void **)&r->h_green, stage_bytes + stage_bytes / 2, hipHostMallocDefault));
-    r->h_green_n = stage_bytes + stage_bytes / 2;
-  }
-  double *hd = reinterpret_cast<double *>(r->h_green);
+  double *hd = reinterpret_cast<double *>(green_stage(r, sizeof(double) * nd + sizeof(int) * ni));
   int *hi = reinterpret_cast<int *>(hd + nd);
   {
     double *hT = hd, *hTs = hd + (size_t)ngen * nz, *hdev = hTs + ngen, *hbase = hdev + ndev_pad;
@@ -1693,24 +1736,44 @@ static void ir_batch_green(Radtran *r, const GreenPlan &pl, const double *T, con
   GreenParams g;
   if (pre) g = *pre;
   else green_factor_part(r, g);
-  const int waves = green_far_waves(ndev, nl);    // of the far-form accumulation, per bin split
-  // bin splits: the accumulation's waves should fill the machine ONCE (green_far_resident_waves): a few waves more
-  // than that and the kernel takes two rounds
-  const int qsplit = green_far_splits(n_ir, waves);
-  const int msplit = std::max(qsplit, std::min(n_ir, 4096 / std::max((nmix + 3) / 4, 1)));   // the mixed blocks: few pairs, finer splits
-  ensure(r->d_green_acc, (size_t)n_ir * ndev_pad + 64 + (size_t)(qsplit + msplit) * ndev_pad * 2 * nl);
-  double *w = r->d_green_acc.p;
-  auto take = [&](size_t cnt) { double *p0 = w; w += cnt; return p0; };
-  g.DB = take((size_t)n_ir * ndev_pad + 64); g.partial = take((size_t)qsplit * ndev_pad * 2 * nl);
-  g.msplit = msplit; g.partial_m = take((size_t)msplit * ndev_pad * 2 * nl);
-  g.ndev = ndev; g.ndev_pad = ndev_pad; g.qsplit = qsplit;
+  green_accum_arrays(r, g, ndev, ndev_pad, nmix);
   g.dev_k = r->d_green_idx.p; g.col_src = g.dev_k + ndev_pad; g.col_ptr = g.col_src + n; g.col_dev = g.col_ptr + n + 1;
-  g.nmix = nmix; g.mix_dev = g.col_dev + ndev; g.mix_blk = g.mix_dev + nmix;
+  g.mix_dev = g.col_dev + ndev; g.mix_blk = g.mix_dev + nmix;
   g.dev_T = d_Ts + ngen; g.base_T = g.dev_T + ndev_pad;
   g.gen_out = r->d_gen_out.p; g.gen_arr = (size_t)ngen * nl; g.flux_n = r->d_flux_n.p; g.out = d_out; g.out_arr = (size_t)n * nl;
   launch_green_columns(g, n, r->stream);
   HIPCHK(hipGetLastError());
   r->ir_green_batches++;
+}
+
+// Three result arrays of `arr` doubles each, back to back in d_bout, into the caller's outs[0..2] through the handle's
+// pinned block in pieces, the host copying piece i out while piece i + 1 is still on the link (one copy and then one
+// memcpy of the whole took 95 + 140 us of a 0.93 ms batch call at 403 columns x 403 levels).  Returns when all are there.
+static void bout_to_host(Radtran *r, double *const outs[3], size_t arr) {
+  if (r->h_bout_n < 3 * arr) {
+    if (r->h_bout) (void)hipHostFree(r->h_bout);
+    r->h_bout = nullptr; r->h_bout_n = 0;
+    HIPCHK(hipHostMalloc((void **)&r->h_bout, sizeof(double) * 3 * arr, hipHostMallocDefault));
+    r->h_bout_n = 3 * arr;
+  }
+  constexpr int NPIECE = 6;
+  const size_t total = 3 * arr, piece = (total + NPIECE - 1) / NPIECE;
+  for (auto &e : r->bout_ev)
+    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (int k = 0; k < NPIECE; k++) {
+    const size_t lo = std::min(total, (size_t)k * piece), hi = std::min(total, lo + piece);
+    if (hi > lo) HIPCHK(hipMemcpyAsync(r->h_bout + lo, r->d_bout.p + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(hipEventRecord(r->bout_ev[k], r->stream));
+  }
+  for (int k = 0; k < NPIECE; k++) {
+    const size_t lo = std::min(total, (size_t)k * piece), hi = std::min(total, lo + piece);
+    HIPCHK(hipEventSynchronize(r->bout_ev[k]));
+    for (size_t x = lo; x < hi;) {      // (a piece may straddle two of the three arrays)
+      const size_t i = x / arr, n_here = std::min(hi, (i + 1) * arr) - x;
+      std::memcpy(outs[i] + (x - i * arr), r->h_bout + x, sizeof(double) * n_here);
+      x += n_here;
+    }
+  }
 }
 
 static void register_host(Radtran *r, void *p, size_t bytes);
@@ -1762,15 +1825,7 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
     // not with a base that is not a number anywhere (every column would "deviate" there and inherit it), nor when the
     // work arrays (~150 KB per (bin, g-point) at 500 layers) would take more than 16 GB
     for (double v : pl.base) if (!std::isfinite(v)) green = false;
-    // (the partial sums of the two accumulation kernels are part of that: their bin splits x deviations x 2 x levels, with
-    // ir_batch_green's split counts -- the mixed blocks' from a lower bound of their number, one per deviation)
-    {
-      const int ndev = (int)pl.dev_k.size();
-      const int qs = green_far_splits(r->ir_n, green_far_waves(ndev, nl));
-      const int ms = std::max(qs, std::min(r->ir_n, 4096 / std::max((ndev + 3) / 4, 1)));
-      if (((double)r->ir_n * r->ng * (13.0 * nl + 14.0 * nz + 4.3 * nl) +
-           (double)(qs + ms) * ((double)ndev + 64.0) * 2.0 * nl) * 8.0 > 16.0e9) green = false;
-    }
+    if (green_work_bytes(r, (int)pl.dev_k.size()) > 16.0e9) green = false;
     if (!fits) green = false;
     if (green) ir_batch_green(r, pl, T, T_surface, n, r->d_bout.p, pre ? &gpre : nullptr);
     r->green_last_n = green ? n : -1;
@@ -1789,13 +1844,6 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
     r->comm_reduces++;
     launch_batch_ftotal(r->d_bout.p, arr, n, nz, r->d_flux_n.p, r->stream);
     HIPCHK(hipGetLastError());
-  }
-  // the three result arrays come back through the handle's pinned block
-  if (r->h_bout_n < 3 * arr) {
-    if (r->h_bout) (void)hipHostFree(r->h_bout);
-    r->h_bout = nullptr; r->h_bout_n = 0;
-    HIPCHK(hipHostMalloc((void **)&r->h_bout, sizeof(double) * 3 * arr, hipHostMallocDefault));
-    r->h_bout_n = 3 * arr;
   }
   const double t_enq = times ? since() : 0.0;
   if (times) HIPCHK(hipStreamSynchronize(r->stream));
@@ -1824,29 +1872,86 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
     HIPCHK(hipStreamSynchronize(r->stream));
     t_d2h = times ? since() : 0.0;
   } else {
-    constexpr int NPIECE = 6;
-    const size_t total = 3 * arr, piece = (total + NPIECE - 1) / NPIECE;
-    for (auto &e : r->bout_ev)
-      if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (int k = 0; k < NPIECE; k++) {
-      const size_t lo = std::min(total, (size_t)k * piece), hi = std::min(total, lo + piece);
-      if (hi > lo) HIPCHK(hipMemcpyAsync(r->h_bout + lo, r->d_bout.p + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
-      HIPCHK(hipEventRecord(r->bout_ev[k], r->stream));
-    }
-    for (int k = 0; k < NPIECE; k++) {
-      const size_t lo = std::min(total, (size_t)k * piece), hi = std::min(total, lo + piece);
-      HIPCHK(hipEventSynchronize(r->bout_ev[k]));
-      for (size_t x = lo; x < hi;) {      // (a piece may straddle two of the three arrays)
-        const size_t i = x / arr, n_here = std::min(hi, (i + 1) * arr) - x;
-        std::memcpy(outs[i] + (x - i * arr), r->h_bout + x, sizeof(double) * n_here);
-        x += n_here;
-      }
-    }
+    bout_to_host(r, outs, arr);
     t_d2h = times ? since() : 0.0;
   }
   if (times)
     fprintf(stderr, "radiate_ir_batch: %d columns%s: plan + enqueue %.0f us, kernels done at %.0f, results with the caller at %.0f%s\n",
             n, green ? " (response form)" : "", t_enq, t_kern, t_d2h, direct ? " (its arrays page-locked)" : " (through the pinned block, six pieces)");
+  CATCH(err)
+}
+
+// The exact IR temperature Jacobian of the level fluxes: the limit of the batch's response form as the step goes to 0.
+// Every level k = 0..nz is one deviation with the Planck derivative at its base temperature as amplitude, so the
+// matrices come from the opacity-only part and one accumulation alone -- no base-profile solve, no plan, no step.
+// jac_*(i, j) column-major (nz+1) x (nz+1): i the level ground-first, x(1) = T_surface, x(1 + m) = T(m).
+void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, const double *T,
+                         const int *dim1, const int *dim2, double *jac_up, double *jac_dn, double *jac_total, char *err) {
+  clear_err(err);
+  GUARD(r, ptr, err);
+  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  const int nz = r->nz, nl = nz + 1;
+  if (*dim_T != nz) { set_err(err, "\"T\" has the wrong input dimension."); return; }
+  if (*dim1 != nl || *dim2 != nl) { set_err(err, "jac has the wrong dimension"); return; }
+  for (int j = 0; j <= nz; j++) {
+    const double v = j < nz ? T[j] : *T_surface;
+    if (!(std::isfinite(v) && v > 0.0)) { set_err(err, "ir_jacobian: temperatures must be finite and positive"); return; }
+  }
+  if (r->shard_world != 1 && !r->comm) { set_err(err, "ir_jacobian is not available on a bin-sharded handle"); return; }
+  // the response form's range (that of radtran_radiate_ir_batch's): no other solver stands behind it
+  if (nz < 4 || nz > 512) { set_err(err, "ir_jacobian: the response form takes 4 <= nz <= 512 (nz = " + std::to_string(nz) + ")"); return; }
+  if ((long)r->ir_n * r->ng > 65535) {     // (k_green_unit / k_green_local: one (bin, g-point) pair per blockIdx.y)
+    set_err(err, "ir_jacobian: the response form takes at most 65535 (bin, g-point) pairs (" + std::to_string((long)r->ir_n * r->ng) + ")");
+    return;
+  }
+  if (green_work_bytes(r, nl) > 16.0e9) { set_err(err, "ir_jacobian: the response form's work arrays would take more than 16 GB"); return; }
+  if (!r->opr_valid) { set_err(err, "ir_jacobian needs opacities: call radiate with compute_opacity first"); return; }
+  TRY
+  settle(r);
+  upload_fields(r);
+  ensure_w0(r);
+  const size_t arr = (size_t)nl * nl;
+  if (r->d_bout.n < 3 * arr) r->d_bout.alloc(3 * arr);
+  if (r->ir_n > 0) {
+    // deviations: every level k, sorted (dev_k[d] = d); the mixed pairs as the batch builds them
+    const int ndev = nl, ndev_pad = (ndev + 15) / 16 * 16;
+    std::vector<int> dev_k(ndev), mdev, mblk;
+    for (int k = 0; k < ndev; k++) dev_k[k] = k;
+    green_mixed_list(dev_k, nz, mdev, mblk);
+    const int nmix = (int)mdev.size();
+    // through the handle's pinned block: doubles base_T by level k [nl], then ints dev_k [ndev_pad] | mix_dev | mix_blk
+    const size_t ni = (size_t)ndev_pad + 2 * (size_t)nmix;
+    double *hd = reinterpret_cast<double *>(green_stage(r, sizeof(double) * nl + sizeof(int) * ni));
+    int *hi = reinterpret_cast<int *>(hd + nl);
+    for (int k = 0; k < nz; k++) hd[k] = T[nz - 1 - k];     // (radiate.f90:65-69: level k is layer nz-1-k)
+    hd[nz] = *T_surface;
+    for (int d = 0; d < ndev_pad; d++) hi[d] = d < ndev ? d : 0;
+    std::copy(mblk.begin(), mblk.end(), std::copy(mdev.begin(), mdev.end(), hi + ndev_pad));
+    if (r->d_green_in.n < (size_t)nl) r->d_green_in.alloc(nl);
+    if (r->d_green_idx.n < ni) r->d_green_idx.alloc(ni);
+    HIPCHK(hipMemcpyAsync(r->d_green_in.p, hd, sizeof(double) * nl, hipMemcpyHostToDevice, r->stream));
+    HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * ni, hipMemcpyHostToDevice, r->stream));
+    GreenParams g;
+    green_factor_part(r, g);
+    green_accum_arrays(r, g, ndev, ndev_pad, nmix);
+    g.dev_k = r->d_green_idx.p; g.mix_dev = g.dev_k + ndev_pad; g.mix_blk = g.mix_dev + nmix;
+    g.base_T = r->d_green_in.p;
+    g.out = r->d_bout.p; g.out_arr = arr;
+    launch_green_jacobian(g, r->stream);
+    HIPCHK(hipGetLastError());
+  } else {
+    // a shard without IR bins: no k_green_* kernel (their grids would be empty), zeros into the all-reduce
+    HIPCHK(hipMemsetAsync(r->d_bout.p, 0, sizeof(double) * 3 * arr, r->stream));
+  }
+  if (r->comm) {
+    // every rank worked on its bins: one all-reduce of the up / down matrices, the total from the reduced ones
+    NCCLCHK(ncclAllReduce(r->d_bout.p, r->d_bout.p, 2 * arr, ncclDouble, ncclSum, r->comm, r->stream));
+    r->comm_reduces++;
+    launch_jacobian_total(r->d_bout.p, arr, arr, r->stream);
+    HIPCHK(hipGetLastError());
+  }
+  double *const outs[3] = {jac_up, jac_dn, jac_total};
+  bout_to_host(r, outs, arr);
   CATCH(err)
 }
 

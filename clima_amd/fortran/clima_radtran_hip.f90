@@ -81,6 +81,7 @@ module clima_radtran_hip
     procedure :: equilibrium_temperature => Radtran_equilibrium_temperature
     procedure :: apply_radiation_enhancement => Radtran_apply_radiation_enhancement
     procedure :: radiate_ir_batch => Radtran_radiate_ir_batch
+    procedure :: ir_jacobian => Radtran_ir_jacobian
     procedure :: TOA_fluxes_batch => Radtran_TOA_fluxes_batch
     procedure :: opacities2yaml => Radtran_opacities2yaml
     procedure :: set_names => Radtran_set_names
@@ -182,6 +183,14 @@ module clima_radtran_hip
       integer(c_int), intent(in) :: ncol, dim1_T, dim2_T
       real(c_double), intent(in) :: T_surface(*), T(*)
       real(c_double), intent(out) :: fup_n(*), fdn_n(*), f_total(*)
+      character(c_char), intent(out) :: err(*)
+    end subroutine
+    subroutine c_radtran_ir_jacobian(ptr, T_surface, dim_T, T, dim1, dim2, jac_up, jac_dn, jac_total, err) &
+                                     bind(c, name="radtran_ir_jacobian")
+      import; type(c_ptr), value :: ptr
+      integer(c_int), intent(in) :: dim_T, dim1, dim2
+      real(c_double), intent(in) :: T_surface, T(*)
+      real(c_double), intent(out) :: jac_up(*), jac_dn(*), jac_total(*)
       character(c_char), intent(out) :: err(*)
     end subroutine
     subroutine c_radtran_opacities2yaml_wrapper_1(ptr, out_len, out_cp) bind(c, name="radtran_opacities2yaml_wrapper_1")
@@ -800,6 +809,27 @@ contains
     endif
     call c_radtran_batch_pin_results_set(self%handle, merge(1_c_int, 0_c_int, self%pin_batch_results))
     call c_radtran_radiate_ir_batch(self%handle, ncol, T_surface, size(T,1), size(T,2), T, fup_n, fdn_n, f_total, err_c)
+    call take_err(err_c, err)
+  end subroutine
+
+  !> The exact IR temperature Jacobian of the level fluxes at the opacities of the last compute_opacity call: what the
+  !> RCE Jacobian's one-sided differences (src/adiabat/clima_adiabat_solve.f90:768-822) tend to as the step goes to 0.
+  !> jac_up(i,j) = d self%wrk_ir%fup_n(i) / d x(j), jac_dn the same of fdn_n, jac_total = jac_dn - jac_up, with
+  !> x(1) = T_surface, x(1+m) = T(m) and i the level, ground-first (mW m-2 K-1).  self%wrk_ir and self%f_total stay as
+  !> they are.
+  subroutine Radtran_ir_jacobian(self, T_surface, T, jac_up, jac_dn, jac_total, err)
+    class(Radtran), intent(inout) :: self
+    real(dp), intent(in) :: T_surface
+    real(dp), intent(in), contiguous :: T(:)                                           !! (nz)
+    real(dp), intent(out), contiguous :: jac_up(:,:), jac_dn(:,:), jac_total(:,:)   !! (nz+1, nz+1)
+    character(:), allocatable, intent(out) :: err
+    character(c_char) :: err_c(err_len+1)
+    if (any(shape(jac_dn) /= shape(jac_up)) .or. any(shape(jac_total) /= shape(jac_up))) then
+      err = 'jac has the wrong dimension'
+      return
+    endif
+    call c_radtran_ir_jacobian(self%handle, T_surface, size(T), T, size(jac_up,1), size(jac_up,2), &
+                               jac_up, jac_dn, jac_total, err_c)
     call take_err(err_c, err)
   end subroutine
 

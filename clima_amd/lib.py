@@ -59,6 +59,7 @@ SIGNATURES = {
     "radtran_names_get": [_vp, _ip, C.c_char_p, C.c_char_p],
     "radtran_toa_fluxes_batch": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _err],
     "radtran_radiate_ir_batch": [_vp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _err],
+    "radtran_ir_jacobian": [_vp, _dp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _err],
     "radtran_upload_column": [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _err],
     "radtran_radiate_resident": [_vp, _ip, _ip, _err],
     "radtran_synchronize": [_vp, _err],

@@ -353,6 +353,21 @@ class Radtran:
         self._check()
         return tuple(out)
 
+    def ir_jacobian(self, T_surface, T):
+        """The exact IR temperature Jacobian of the level fluxes at the resident opacities (radtran_ir_jacobian):
+        (jac_up, jac_dn, jac_total), each (nz+1, nz+1) Fortran-ordered, [i, j] = d flux(level i, ground-first) / d x(j)
+        with x(0) = T_surface, x(1 + m) = T[m]; mW m^-2 K^-1.  The limit of the RCE Jacobian's one-sided differences
+        (src/adiabat/clima_adiabat_solve.f90:768-822) as the step goes to 0."""
+        T, Ts = _c(np.atleast_1d(T)), _c(np.atleast_1d(T_surface))
+        if T.ndim != 1 or Ts.shape != (1,):
+            raise ClimaException('"T" has the wrong input dimension.')
+        nl = self.nz + 1
+        out = [np.empty((nl, nl), order="F") for _ in range(3)]
+        self._L.radtran_ir_jacobian(self._ptr, _d(Ts), _i(len(T)), _d(T), _i(nl), _i(nl),
+                                    _d(out[0]), _d(out[1]), _d(out[2]), self._err)
+        self._check()
+        return tuple(out)
+
     # ---- HBM-resident form (bench / batched callers)
     def upload_column(self, T_surface, T, P, densities, dz, pdensities=None, radii=None):
         T, P, dz, densities = _c(T), _c(P), _c(dz), _fo(densities)

@@ -190,6 +190,25 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
 void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surface, const int *dim1_T,
                               const int *dim2_T, const double *T, double *fup_n, double *fdn_n,
                               double *f_total, char *err);
+/* The exact IR temperature Jacobian of the level fluxes at fixed opacities: the limit, as the step goes to 0, of what
+ * the RCE Jacobian's one-sided differences compute (src/adiabat/clima_adiabat_solve.f90:768-822), in one call.  For the
+ * base profile T_surface, T (dim_T = nz) and the opacities of the last compute_opacity call, jac_up, jac_dn and
+ * jac_total are (nz+1, nz+1) column-major (dim1 = dim2 = nz+1):
+ *   jac_up(i, j) = d wrk_ir%fup_n(i) / d x(j),  jac_dn(i, j) = d wrk_ir%fdn_n(i) / d x(j),  jac_total = jac_dn - jac_up
+ * with x(1) = T_surface, x(1+m) = T(m) (the reference's T_in order) and i the level, ground-first; mW m^-2 K^-1.  Each
+ * column is the derivative of radiate(..., compute_solar = .false., compute_opacity = .false.) (clima_radtran.f90:221-318),
+ * both surface forms, per-bin emissivity and thin layers (ir_tau_min) included; solar terms do not depend on T at
+ * fixed opacity.  Built on radtran_radiate_ir_batch's response form (two_stream_ir is linear in the Planck values):
+ * the opacity-only part, then every level one deviation whose amplitude is dnu dB/dT at its base temperature -- no
+ * base solve, no step.  A convective zone's column is the sum of its levels' columns.  The handle's wrk_ir, wrk_sol,
+ * f_total and spectra are left untouched.  Refused (err): a handle that is not constructed or has no opacities yet,
+ * wrong extents ("jac has the wrong dimension"), a temperature that is not finite and positive, a bin shard without a
+ * communicator, and shapes outside the response form's range -- 4 <= nz <= 512, at most 65535 (bin, g-point) pairs,
+ * work arrays of at most 16 GB.  On a handle with a communicator (radtran_comm_init_rank) every rank passes the same
+ * profile and works on its bins (a rank without IR bins contributes zeros); one all-reduce of the up and down matrices
+ * (2 (nz+1)^2 doubles) precedes jac_total, and every rank receives the whole result. */
+void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, const double *T,
+                         const int *dim1, const int *dim2, double *jac_up, double *jac_dn, double *jac_total, char *err);
 /* clima/fortran/Radtran.f90:41-75 (same names and argument lists): the YAML text of
  * OpticalProperties_opacities2yaml (src/radtran/clima_radtran_types.f90:328-430).  _1 allocates
  * the string and returns its length, _2 copies it into out_c (out_len + 1 chars) and frees it.

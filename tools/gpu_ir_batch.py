@@ -3,7 +3,9 @@
 (src/adiabat/clima_adiabat_solve.f90:768-822: nz_r + 1 IR-only calls on unchanged opacities; nz_r = 2 nz + 2,
 src/adiabat/clima_adiabat.f90:729-773) through radtran_radiate_ir_batch, config 2's tables, host arrays in / out.
 Usage: gpu_ir_batch.py [nz ...] (AdiabatClimate nz).  CLIMA_HIP_BATCH_SHARED=0 times the per-column form;
-CLIMA_BATCH_PIN=0 leaves the result arrays pageable (radtran_batch_pin_results_set)."""
+CLIMA_BATCH_PIN=0 leaves the result arrays pageable (radtran_batch_pin_results_set).
+gpu_ir_batch.py jacobian [nz ...]: the exact Jacobian (radtran_ir_jacobian) against the equivalent batch of nz_r + 1
+one-level columns, on one handle, the two calls alternating, both on the default (unpinned) result path: medians."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
@@ -12,6 +14,43 @@ from clima_amd.atmosphere import copy_atm_to_radiative_grid
 from clima_amd.radtran import Radtran
 PIN = os.environ.get("CLIMA_BATCH_PIN", "1") != "0"    # the caller's result arrays page-locked (the default here: a caller that keeps them); 0: through the pinned block
 tb = S.modern_earth_tables()
+
+
+def jacobian_leg(nzs, warm=5, reps=25):
+    for nz in nzs:
+        col = S.Column(copy_atm_to_radiative_grid(S.modern_earth_column(nz)))
+        nzr = len(col["T"])
+        r = Radtran(tb, nzr, 4, 0.15)
+        r.radiate(*col.args())
+        ncol = nzr + 1
+        x = np.concatenate([[float(col["T_surface"])], np.asarray(col["T"], float)])
+        dT = 1.0e-4 * x                      # the reference's one-sided step, relative (clima_adiabat_solve.f90:798-812)
+        X = np.repeat(x[:, None], ncol, axis=1)
+        X[np.arange(ncol), np.arange(ncol)] += dT
+        tj, tbt = [], []
+        for rep in range(warm + reps):
+            t0 = time.perf_counter()
+            jac = r.ir_jacobian(x[0], x[1:])
+            t1 = time.perf_counter()
+            out = r.radiate_ir_batch(X[0], X[1:])
+            t2 = time.perf_counter()
+            if rep >= warm:
+                tj.append(t1 - t0); tbt.append(t2 - t1)
+        r.ir_green = 0
+        base = r.radiate_ir_batch(x[:1], x[1:, None])
+        fd = (out[2] - base[2]) / dT[None, :]
+        dev = float(np.max(np.abs(fd - jac[2])) / np.max(np.abs(jac[2])))
+        mj, mb = float(np.median(tj)) * 1e3, float(np.median(tbt)) * 1e3
+        print("AdiabatClimate nz %3d -> %3d layers: ir_jacobian median %.3f ms (min %.3f), %3d-column radiate_ir_batch median %.3f ms "
+              "(min %.3f)%s, ratio %.2f over %d alternating calls; one-sided difference at dT = 1e-4 T vs exact: %.1e of the "
+              "largest |entry|" % (nz, nzr, mj, min(tj) * 1e3, ncol, mb, min(tbt) * 1e3,
+                                  " [response form]" if r.ir_green_batches > 0 else "", mj / mb, reps, dev), flush=True)
+        del r
+
+
+if sys.argv[1:2] == ["jacobian"]:
+    jacobian_leg([int(a) for a in sys.argv[2:]] or [200, 100])
+    sys.exit(0)
 for nz in [int(a) for a in sys.argv[1:]] or [50, 100, 200]:
     col = S.Column(copy_atm_to_radiative_grid(S.modern_earth_column(nz)))
     nzr = len(col["T"])
