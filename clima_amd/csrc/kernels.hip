@@ -1614,33 +1614,33 @@ static void launch_coop(const OpacityParams &p, hipStream_t s) {
   else hipLaunchKernelGGL((k_opacity_coop<NG, false>), dim3(grid), dim3(OP_THREADS), 0, s, p);
 }
 
-bool launch_opacity(const OpacityParams &p, hipStream_t s) {
-  long total = (long)p.nbins * p.nz;
-  // every g-point count but the tuned 8 goes to the group-of-lanes kernel with the next power of two of lanes per item
-  // (OpacityParams::generic, CLIMA_HIP_GENERIC=1 when the handle is made: the wave-per-item generic kernel instead --
-  // the same arithmetic order as the reference, kept as a cross-check)
-  if (p.ng >= 1 && p.ng <= 32 && (p.ng != 8 ? !p.generic : p.coop != 0) && (long)p.nbins * p.nsrc > 0) {
-    if (p.ng <= 8) launch_coop<8>(p, s);
-    else if (p.ng <= 16) launch_coop<16>(p, s);
+// the plan's opacity kernel: every g-point count but the tuned 8 goes to the group-of-lanes kernel with the next power of
+// two of lanes per item (OP_GENERIC, CLIMA_HIP_GENERIC=1 when the handle is made: the wave-per-item generic kernel
+// instead -- the same arithmetic order as the reference, kept as a cross-check)
+bool launch_opacity(const OpacityParams &p, const LaunchPlan &pl, hipStream_t s) {
+  const long items = (long)p.nbins * p.nsrc;  // (bin, source layer)
+  if (pl.opacity == OP_COOP) {
+    if (items <= 0) return true;
+    if (pl.coop_ng == 8) launch_coop<8>(p, s);
+    else if (pl.coop_ng == 16) launch_coop<16>(p, s);
     else launch_coop<32>(p, s);
-    return true;
-  }
-  if (p.ng != 8) {
-    if (p.ng < 1 || p.ng > OPG_MAX_NG) return false;
+  } else if (pl.opacity == OP_GENERIC) {
+    const long total = (long)p.nbins * p.nz;
     if (total <= 0) return true;
     int N2 = 2;
     while (N2 < p.ng * p.ng) N2 <<= 1;
     const size_t lds = sizeof(double) * ((size_t)N2 + 2 * p.ng * p.ng + 1 + 3 * p.ng) + sizeof(int) * (size_t)N2;
     hipLaunchKernelGGL(k_opacity_generic, dim3((unsigned)total), dim3(64), lds, s, p, N2);
-    return true;
+  } else if (pl.opacity == OP_TILE) {
+    if (items <= 0) return true;
+    const int grid = (int)((items + OP_THREADS - 1) / OP_THREADS);  // one lane per item
+    using Kern = void (*)(OpacityParams);
+    static const Kern kern[2][3] = {{k_opacity8<0, false>, k_opacity8<1, false>, k_opacity8<2, false>},
+                                    {k_opacity8<0, true>, k_opacity8<1, true>, k_opacity8<2, true>}};
+    hipLaunchKernelGGL(kern[p.cust.on ? 1 : 0][p.rebin_mode], dim3(grid), dim3(OP_THREADS), 0, s, p);
+  } else {
+    return false;
   }
-  total = (long)p.nbins * p.nsrc;  // one lane per (bin, source layer)
-  if (total <= 0) return true;
-  const int grid = (int)((total + OP_THREADS - 1) / OP_THREADS);
-  using Kern = void (*)(OpacityParams);
-  static const Kern kern[2][3] = {{k_opacity8<0, false>, k_opacity8<1, false>, k_opacity8<2, false>},
-                                  {k_opacity8<0, true>, k_opacity8<1, true>, k_opacity8<2, true>}};
-  hipLaunchKernelGGL(kern[p.cust.on ? 1 : 0][p.rebin_mode], dim3(grid), dim3(OP_THREADS), 0, s, p);
   return true;
 }
 
@@ -2134,47 +2134,49 @@ static size_t ts_lds_bytes(int nz, int nc, int S) {
   return sizeof(double) * ((size_t)6 * nz * nc + (nz + 1) + 3 * nc + (size_t)((nz + 7) / 8) * nc + (size_t)6 * S * nc + (size_t)(nz + 2) / 2 + 1);
 }
 
-bool launch_twostream(TwoStreamParams &p, hipStream_t s, size_t *lds_bytes) {
+// the workgroup-per-bin form's geometry for the planner: TS_NONE when the column does not fit
+static TsPlan plan_block(int nz, int ng, int ncols_env) {
+  TsPlan b{};
   // columns per block: all g-points when the LDS image fits, else split the g-points over
   // gridDim.y groups (outputs are then accumulated with atomics into zeroed arrays)
-  int nc = p.ncols;
+  int nc = ncols_env;
   if (nc <= 0) {
     // prefer an LDS image small enough for 3 workgroups per CU (latency hiding), but never
     // more than two g-point groups per bin: two partial sums added into a zeroed output
     // are order-independent, so results stay bitwise reproducible
-    nc = p.ng;
-    if (ts_lds_bytes(p.nz, nc, 64 / nc) > 53 * 1024 && p.ng % 2 == 0) nc = p.ng / 2;
+    nc = ng;
+    if (ts_lds_bytes(nz, nc, 64 / nc) > 53 * 1024 && ng % 2 == 0) nc = ng / 2;
   }
-  while (nc > 1 && (ts_lds_bytes(p.nz, nc, 64 / nc > 16 ? 16 : 64 / nc) > 150 * 1024 || p.ng % nc != 0 || nc > 64)) nc--;
-  if (p.ng % nc != 0) return false;
-  int S = 64 / nc;
-  if (S > 16) S = 16;
-  if (S > p.nz) S = p.nz;
-  if (S < 1) S = 1;
-  p.ncols = nc;
-  p.nchunks = S;
-  p.nc_shift = -1;
-  for (int b = 0; b < 7; b++) if ((1 << b) == nc) p.nc_shift = b;
-  const size_t lds = ts_lds_bytes(p.nz, nc, S);
-  if (lds_bytes) *lds_bytes = lds;
-  if (lds > 160 * 1024) return false;
-  const int npairs = p.nz * nc;
-  const int nseg = (p.nz + 7) / 8;
-  int threads = (npairs + TS_MAXP - 1) / TS_MAXP;
-  threads = ((threads + 63) / 64) * 64;
-  if (threads < 64) threads = 64;
+  while (nc > 1 && (ts_lds_bytes(nz, nc, 64 / nc > 16 ? 16 : 64 / nc) > 150 * 1024 || ng % nc != 0 || nc > 64)) nc--;
+  if (ng % nc != 0) return b;
+  const int S = std::max(1, std::min({64 / nc, 16, nz}));
+  const int nseg = (nz + 7) / 8;
+  int threads = (nz * nc + TS_MAXP - 1) / TS_MAXP;
+  threads = std::max(64, ((threads + 63) / 64) * 64);
   if (threads < nseg * nc) threads = ((nseg * nc + 63) / 64) * 64;
-  if (threads > 1024) return false;
+  b.lds = ts_lds_bytes(nz, nc, S);
+  if (b.lds > 160 * 1024 || threads > 1024) return b;
+  b.form = TS_BLOCK; b.slots = S; b.cols = nc; b.groups = b.per_launch = ng / nc; b.threads = threads;
+  b.zero_launch = b.groups > 1;
+  return b;
+}
+
+bool launch_twostream(TwoStreamParams &p, const TsPlan &t, hipStream_t s) {
+  if (t.form != TS_BLOCK) return false;
+  p.ncols = t.cols;
+  p.nchunks = t.slots;
+  p.nc_shift = -1;
+  for (int b = 0; b < 7; b++) if ((1 << b) == t.cols) p.nc_shift = b;
   const int grid = p.n_sol + p.n_ir;
   if (grid <= 0) return true;
-  const dim3 g(grid, p.ng / nc);
-  if (g.y > 1) ts_zero_outputs(p, s);
-  if (threads <= 512) {
+  const dim3 g(grid, t.groups);
+  if (t.zero_launch) ts_zero_outputs(p, s);
+  if (t.threads <= 512) {
     if (!ensure_max_lds((const void *)k_twostream<512, 4>)) return false;
-    hipLaunchKernelGGL((k_twostream<512, 4>), g, dim3(threads), lds, s, p);
+    hipLaunchKernelGGL((k_twostream<512, 4>), g, dim3(t.threads), t.lds, s, p);
   } else {
     if (!ensure_max_lds((const void *)k_twostream<1024, 4>)) return false;
-    hipLaunchKernelGGL((k_twostream<1024, 4>), g, dim3(threads), lds, s, p);
+    hipLaunchKernelGGL((k_twostream<1024, 4>), g, dim3(t.threads), t.lds, s, p);
   }
   return true;
 }
@@ -2830,90 +2832,52 @@ __global__ __launch_bounds__(64 * TSW_COLS, 2) void k_twostream_h(TwoStreamParam
   else twostream_p_body<L, false, 0, false, false, false, true>(p, (int)blockIdx.x - p.n_sol, lds, (int)blockIdx.y, (int)blockIdx.z);
 }
 
-static void ts_zero_outputs(const TwoStreamParams &p, hipStream_t s) {
-  // partial sums over g-point groups accumulate into zeroed outputs: one launch
+int ts_clear_ranges(const TwoStreamParams &p, double *ptr[6], size_t count[6]) {
   const size_t nl = (size_t)p.nz + 1;
-  ZeroParams z;
-  z.n = 0;
+  int n = 0;
   if (p.n_ir > 0) {
-    z.ptr[z.n] = p.ir_fup_a + (size_t)p.ir_lo * nl; z.count[z.n++] = nl * p.n_ir;
-    z.ptr[z.n] = p.ir_fdn_a + (size_t)p.ir_lo * nl; z.count[z.n++] = nl * p.n_ir;
+    ptr[n] = p.ir_fup_a + (size_t)p.ir_lo * nl; count[n++] = nl * p.n_ir;
+    ptr[n] = p.ir_fdn_a + (size_t)p.ir_lo * nl; count[n++] = nl * p.n_ir;
   }
   if (p.n_sol > 0) {
-    z.ptr[z.n] = p.sol_fup_a + (size_t)p.sol_lo * nl; z.count[z.n++] = nl * p.n_sol;
-    z.ptr[z.n] = p.sol_fdn_a + (size_t)p.sol_lo * nl; z.count[z.n++] = nl * p.n_sol;
-    z.ptr[z.n] = p.sol_amean + (size_t)p.sol_lo * nl; z.count[z.n++] = nl * p.n_sol;
+    ptr[n] = p.sol_fup_a + (size_t)p.sol_lo * nl; count[n++] = nl * p.n_sol;
+    ptr[n] = p.sol_fdn_a + (size_t)p.sol_lo * nl; count[n++] = nl * p.n_sol;
+    ptr[n] = p.sol_amean + (size_t)p.sol_lo * nl; count[n++] = nl * p.n_sol;
   }
+  return n;
+}
+static void ts_zero_outputs(const TwoStreamParams &p, hipStream_t s) {
+  // partial sums over g-point groups accumulate into zeroed outputs: one launch
+  ZeroParams z;
+  z.n = ts_clear_ranges(p, z.ptr, z.count);
   if (z.n > 0) hipLaunchKernelGGL(k_zero, dim3(128, z.n), dim3(256), 0, s, z);
 }
 
-// wave-per-column launcher; false when nz needs more than 8 layers per lane
-int twostream_w_groups(int ng) { return (ng + TSW_COLS - 1) / TSW_COLS; }
-
-// slots per lane (3..7) when launch_twostream_w() will take the half-wave kernel k_twostream_h for this call, else 0.
-// With 8 g-points that kernel stores every output value itself: the caller need not clear the outputs first.
-int twostream_w_half_slots(const TwoStreamParams &p) {
-  static const bool off = [] { const char *e = getenv("CLIMA_HIP_NO_HALF"); return e && e[0] == '1'; }();
-  const int hs = (p.nz + 31) / 32;
-  if (off || p.ng < 8 || p.ng % 8 != 0 || hs < 3 || hs > 7 || p.force_slots != 0 || p.nzen > MAX_ZEN) return 0;
-  if (sizeof(double) * (3 * 2 * TSW_COLS + 1) * ((size_t)p.nz + 1) > 64 * 1024) return 0;
-  // 8 g-points: its blocks are half as many and nearly twice as long as the whole-wave kernel's, which pays when the
-  // launch is throughput-bound or when it saves the clearing launch -- IR-only calls on stored opacities (102 / 202
-  // layers: 19.3 -> 16.7, 26.1 -> 22.3 us per call) -- and loses when a few bins' blocks are the whole launch (a rank's
-  // share of 8: 12.9 -> 15.2 us); profiles/r03_coop_ab.txt
-  if (p.ng == 8 && p.n_sol > 0 && p.n_sol + p.n_ir < 512) return 0;
-  return hs;
-}
-
-bool launch_twostream_w(TwoStreamParams &p, hipStream_t s, size_t *lds_bytes, bool zeroed) {
-  const int lmax = std::max((p.nz + 63) / 64, p.force_slots);
-  if (lmax > 8) return false;
-  const int groups = (p.ng + TSW_COLS - 1) / TSW_COLS;
-  const size_t lds = sizeof(double) * (3 * TSW_COLS + 1) * ((size_t)p.nz + 1);  // level values of the columns + the bin's Planck table
-  if (lds_bytes) *lds_bytes = lds;
-  if (lds > 64 * 1024) return false;
+// The wave-per-column launcher: the whole-wave kernel (4 g-point columns per block) or the half-wave one (8: for 8, 16,
+// 24, 32 g-points at 65-224 layers.  With 8 g-points a block holds its bin's whole g-point sum and stores it: nothing to
+// clear first, no adds -- IR-only calls on stored opacities, few-item calls: one launch and ~1/5 of the instructions
+// fewer than the whole-wave kernel with its two groups).
+// Up to two g-point groups go in one launch: two partial sums added into a zeroed output are order-independent.  More
+// groups run as one launch per group on the same stream, each adding a single addend, so results stay bitwise
+// reproducible.
+bool launch_twostream_w(TwoStreamParams &p, const TsPlan &t, hipStream_t s) {
+  if (t.form != TS_WAVE && t.form != TS_HALF) return false;
   const int grid = p.n_sol + p.n_ir;
   if (grid <= 0) return true;
   using Kern = void (*)(TwoStreamParams);
-  if (const int hs = twostream_w_half_slots(p)) {
-    // 8, 16, 24, 32 g-points at 65-224 layers: the half-wave kernel, 8 columns per block.  With 8 g-points a block holds
-    // its bin's whole g-point sum and stores it: nothing to clear first, no adds (IR-only calls on stored opacities,
-    // few-item calls: one launch and ~1/5 of the instructions fewer than the whole-wave kernel with its two groups)
-    static const Kern kh[5] = {k_twostream_h<3>, k_twostream_h<4>, k_twostream_h<5>, k_twostream_h<6>, k_twostream_h<7>};
-    const size_t ldsh = sizeof(double) * (3 * 2 * TSW_COLS + 1) * ((size_t)p.nz + 1);
-    if (ldsh <= 48 * 1024 || ensure_max_lds((const void *)kh[hs - 3], 64 * 1024)) {
-      if (lds_bytes) *lds_bytes = ldsh;
-      const int g8 = p.ng / 8;
-      if (g8 > 1 && !zeroed) ts_zero_outputs(p, s);
-      const int per = g8 <= 2 ? g8 : 1;   // two addends onto zero are order-independent; more go one launch at a time
-      for (int g0 = 0; g0 < g8; g0 += per) {
-        p.col_base = g0 * 2 * TSW_COLS;
-        p.accumulate = g8 > 1 ? 1 : 0;
-        hipLaunchKernelGGL(kh[hs - 3], dim3(grid, per, p.b_ncol > 0 ? p.b_ncol : 1), dim3(64 * TSW_COLS), ldsh, s, p);
-      }
-      return true;
-    }
-  }
-  if (groups > 1 && !zeroed) ts_zero_outputs(p, s);
-  static const Kern kern[8] = {k_twostream_w<1>, k_twostream_w<2>, k_twostream_w<3>, k_twostream_w<4>,
-                               k_twostream_w<5>, k_twostream_w<6>, k_twostream_w<7>, k_twostream_w<8>};
-  if (lds > 48 * 1024 && !ensure_max_lds((const void *)kern[lmax - 1], 64 * 1024)) return false;  // (static LDS on top)
-  // Up to two g-point groups go in one launch: two partial sums added into a zeroed output
-  // are order-independent.  More groups (ng > 8) run as one launch per group on the same
-  // stream, each adding a single addend, so results stay bitwise reproducible.
-  const dim3 blk(64 * TSW_COLS);
-  const int per_launch = groups <= 2 ? groups : 1;
-  for (int g0 = 0; g0 < groups; g0 += per_launch) {
-    p.col_base = g0 * TSW_COLS;
-    p.accumulate = groups > 1 ? 1 : 0;
-    const dim3 g(grid, per_launch, p.b_ncol > 0 ? p.b_ncol : 1);
-    hipLaunchKernelGGL(kern[lmax - 1], g, blk, lds, s, p);  // layer slots per lane = ceil(nz/64)
+  static const Kern kh[5] = {k_twostream_h<3>, k_twostream_h<4>, k_twostream_h<5>, k_twostream_h<6>, k_twostream_h<7>};
+  static const Kern kw[8] = {k_twostream_w<1>, k_twostream_w<2>, k_twostream_w<3>, k_twostream_w<4>,
+                             k_twostream_w<5>, k_twostream_w<6>, k_twostream_w<7>, k_twostream_w<8>};
+  const Kern k = t.form == TS_HALF ? kh[t.slots - 3] : kw[t.slots - 1];
+  if (t.lds > 48 * 1024 && !ensure_max_lds((const void *)k, 64 * 1024)) return false;  // (static LDS on top)
+  if (t.zero_launch) ts_zero_outputs(p, s);
+  for (int g0 = 0; g0 < t.groups; g0 += t.per_launch) {
+    p.col_base = g0 * t.cols;
+    p.accumulate = t.groups > 1 ? 1 : 0;
+    hipLaunchKernelGGL(k, dim3(grid, t.per_launch, p.b_ncol > 0 ? p.b_ncol : 1), dim3(64 * TSW_COLS), t.lds, s, p);
   }
   return true;
 }
-
-
-
 
 __global__ void k_test_wscan(const double *a, const double *b, double *out, int nwaves) {
   // out[0]: inclusive affine scan x_i = a_i + b_i x_{i-1}; out[1]: the same through build + apply;
@@ -3360,7 +3324,7 @@ __global__ __launch_bounds__(OP_THREADS, 2) void k_fused(OpacityParams op, TwoSt
   const TsOfs co{(size_t)cb * fp.bs.opr, (size_t)cb * fp.bs.col, (size_t)cb * fp.bs.res};
   // The number of slots per lane follows the column height (65-128 layers: 2, up to 192: 3, up to
   // 256: 4; 5-8 in the LSEL kernels).  Columns of at most 64 layers are not fused at all
-  // (fused_supported): their opacity tiles do not fill the machine once, so there is no half-empty
+  // (plan_radiate): their opacity tiles do not fill the machine once, so there is no half-empty
   // second round to fill, and the stand-alone one-slot two-stream kernel runs at five waves per SIMD
   // instead of two.
   if constexpr (HALF) {
@@ -3395,85 +3359,120 @@ __global__ __launch_bounds__(OP_THREADS, 2) void k_fused(OpacityParams op, TwoSt
 #endif
 }
 
-// false when the configuration is outside what the fused form covers (the caller then uses the
-// separate launches)
-bool fused_supported(const OpacityParams &op, const TwoStreamParams &ts) {
-  const int slots = (ts.nz + 63) / 64;
-  if (op.ng != 8 || slots < 2 || slots > 8 || ts.nzen > MAX_ZEN) return false;
-  if (slots > 4 && (op.rebin_mode != 0 || op.cust.on)) return false;  // the 5-8 slot kernels exist for the default form only
-  return (long)op.nbins * op.nz > 0 && ts.n_sol + ts.n_ir > 0;
-}
-
 int fused_tiles(const OpacityParams &op) {
   return (int)(((long)op.nbins * op.nsrc + OP_THREADS - 1) / OP_THREADS);
 }
 
+// ------------------------------------------------------------------------------------
+// The launch plan of one radiate call: which kernels run, in which form, and who clears the outputs of a form that adds
+// partial sums.  Plain numbers in, plain numbers out: no HIP call, no environment.
+// ------------------------------------------------------------------------------------
+static size_t wave_lds(int nz, int cols) { return sizeof(double) * (3 * cols + 1) * ((size_t)nz + 1); }  // level values of the columns + the bin's Planck table
+static int wave_groups(int ng) { return (ng + TSW_COLS - 1) / TSW_COLS; }
+
+LaunchPlan plan_radiate(const PlanIn &in) {
+  LaunchPlan pl{};
+  const int slots = (in.nz + 63) / 64, nb = in.n_sol + in.n_ir;
+  const bool plain = in.rebin_mode == 0 && !in.cust_on;   // the 5-8 slot, half-wave and paired kernels exist for the default form only
+  // few (bin, source layer) items -- a bin-sharded rank, a short or all-pairs column: the group-of-lanes kernel (a fifth
+  // of the lane-per-item kernel's dependent chain) and one launch per kernel
+  const bool coop8 = !in.batch && in.ng == 8 && (long)in.op_n * in.nsrc <= in.coop_items;
+  if (in.compute_opacity) {
+    if (in.ng < 1 || in.ng > OPG_MAX_NG) pl.opacity = OP_UNSUPPORTED;
+    else if (in.ng == 8) pl.opacity = coop8 ? OP_COOP : OP_TILE;
+    else pl.opacity = in.generic_opacity ? OP_GENERIC : OP_COOP;
+    pl.coop_ng = in.ng <= 8 ? 8 : in.ng <= 16 ? 16 : 32;
+  }
+
+  // The fused grid: 8 g-points, 65-512 layers.  Columns of at most 64 layers are not fused at all: their opacity tiles do
+  // not fill the machine once, so there is no half-empty second round to fill, and the stand-alone one-slot two-stream
+  // kernel runs at five waves per SIMD instead of two.
+  const bool want_fused = in.compute_opacity && in.fused && in.allow_fused && !coop8 && !in.ts_block_mode;
+  const bool covered = in.ng == 8 && slots >= 2 && slots <= 8 && in.nzen <= MAX_ZEN && (slots <= 4 || plain) &&
+                       (long)in.op_n * in.nz > 0 && nb > 0;
+  if (want_fused && covered) {
+    // 65-224 layers: the half-wave form, 3-7 slots of ceil(nz/32) (225-256 would take 8: the whole-wave form's 4 fill
+    // the lanes as well), also on an all-pairs grid (round 3, measured on AdiabatClimate's doubled grids: 102 layers 66.3
+    // against 69.1 us per call in the paired whole-wave form, 202 layers 78.2 against 80.6); the paired form -- chunks cut
+    // at pair boundaries, twice ceil((nz/2)/64) slots -- takes the all-pairs grids beyond (402 layers: 131 against ~145
+    // unpaired).  A batch's columns are not all pairs.
+    const int hs = (in.nz + 31) / 32, ps = 2 * ((in.nz / 2 + 63) / 64);
+    TsPlan &f = pl.fused;
+    if (!in.no_half && plain && hs >= 3 && hs <= 7) { f.form = TS_HALF; f.slots = hs; }
+    else if (in.ncol <= 1 && in.allow_paired && in.all_pairs && !(in.nz & 1) && plain && ps <= 8) { f.form = TS_PAIRED; f.slots = ps; }
+    else { f.form = TS_WAVE; f.slots = slots; }
+    f.cols = f.form == TS_HALF ? 2 * TSW_COLS : TSW_COLS;   // (a half-wave block holds all 8 g-points of its bin and stores whole values)
+    f.groups = f.per_launch = in.ng / f.cols;
+    f.lds = wave_lds(in.nz, f.cols);
+    // its two-stream part forms w0 from the layers' scattering optical depth itself: the tiles leave the 8 nw nz values
+    // unwritten (26 MB per config-2 call neither stored nor read back; CLIMA_HIP_W0_SCAT=0: always written)
+    pl.write_w0 = !in.w0_from_scat;
+  } else {
+    pl.write_w0 = true;
+  }
+
+  // The stand-alone wave forms: at most 8 layers per lane, zenith angles by value.  The half-wave kernel with 8 g-points:
+  // its blocks are half as many and nearly twice as long as the whole-wave kernel's, which pays when the launch is
+  // throughput-bound or when it saves the clearing launch -- IR-only calls on stored opacities (102 / 202 layers: 19.3 ->
+  // 16.7, 26.1 -> 22.3 us per call) -- and loses when a few bins' blocks are the whole launch (a rank's share of 8: 12.9
+  // -> 15.2 us); profiles/r03_coop_ab.txt.  Its LDS stays below 48 KiB (224 layers: 45 000 bytes).
+  const int lmax = std::max(slots, in.force_slots);
+  if ((in.ir_batch || (!in.ts_block_mode && in.nzen <= MAX_ZEN)) && lmax <= 8 && wave_lds(in.nz, TSW_COLS) <= 64 * 1024) {
+    const int hs = (in.nz + 31) / 32;
+    TsPlan &t = pl.ts;
+    if (!in.no_half && in.ng % 8 == 0 && hs >= 3 && hs <= 7 && in.force_slots == 0 && in.nzen <= MAX_ZEN &&
+        !(in.ng == 8 && in.n_sol > 0 && nb < 512)) { t.form = TS_HALF; t.slots = hs; t.cols = 2 * TSW_COLS; }
+    else { t.form = TS_WAVE; t.slots = lmax; t.cols = TSW_COLS; }
+    t.groups = (in.ng + t.cols - 1) / t.cols;
+    t.per_launch = t.groups <= 2 ? t.groups : 1;
+    t.lds = wave_lds(in.nz, t.cols);
+  }
+  if (!in.ir_batch) pl.block = plan_block(in.nz, in.ng, in.ts_ncols_env);
+
+  // Who clears.  When the wave forms will add two or more g-point groups into their outputs, spare blocks of the prep
+  // launch clear them (saves a launch) -- not when the form the call is headed for stores whole values (7.7 MB of zeros
+  // per config-2 call that nobody reads).  (A call that was headed for the fused grid and is not covered by it is cleared
+  // even if the stand-alone half-wave kernel then stores whole values.)
+  const bool headed_fused = in.fused && in.allow_fused && !coop8;
+  const bool whole_stores = headed_fused ? pl.fused.form == TS_HALF : (pl.ts.form == TS_HALF && pl.ts.groups == 1);
+  pl.prep_clears = in.compute_opacity && !in.ts_block_mode && slots <= 8 && wave_groups(in.ng) >= 2 && !whole_stores;
+  pl.caller_clears = in.ir_batch && wave_groups(in.ng) > 1;   // (decided from the whole-wave form's groups, whichever wave form runs)
+  pl.ts.zero_launch = pl.ts.groups > 1 && !pl.prep_clears && !pl.caller_clears;
+  return pl;
+}
+
 using FusedKern = void (*)(OpacityParams, TwoStreamParams, FusedParams);
-// slots of the paired form: twice the pair slots, ceil((nz/2)/64); 0 when the form does not apply
-static int paired_slots(const OpacityParams &op, const TwoStreamParams &ts) {
-  if (!ts.paired || (ts.nz & 1) || op.rebin_mode != 0 || op.cust.on) return 0;
-  const int s = 2 * ((ts.nz / 2 + 63) / 64);
-  return (s == 2 || s == 4 || s == 6 || s == 8) ? s : 0;
-}
-static FusedKern fused_kernel_paired(int slots) {
-  return slots <= 4 ? (FusedKern)k_fused<0, false, 0, true> : slots == 6 ? (FusedKern)k_fused<0, false, 6, true> : (FusedKern)k_fused<0, false, 8, true>;
-}
-// slots per lane of the half-wave two-stream form, ceil(nz/32); 0 when the form does not apply
-// (CLIMA_HIP_NO_HALF=1 switches it off: the A/B switch of tools/gpu_ab.sh)
-static int half_slots(const OpacityParams &op, const TwoStreamParams &ts) {
-  static const bool off = [] { const char *e = getenv("CLIMA_HIP_NO_HALF"); return e && e[0] == '1'; }();
-  if (off || ts.ng != 8 || op.rebin_mode != 0 || op.cust.on) return 0;
-  const int s = (ts.nz + 31) / 32;   // 65-224 layers: 3-7 slots (225-256 would take 8: the whole-wave form's 4 fill the lanes as well)
-  return (s >= 3 && s <= 7) ? s : 0;
-}
-// slots of the half-wave form when launch_fused() will take it for this call, else 0.  Its blocks hold all 8
-// g-points of a bin and store every output value themselves: the caller need not clear the outputs first.
-int fused_half_form(const OpacityParams &op, const TwoStreamParams &ts, int ncol) {
-  (void)ncol;
-  if (!fused_supported(op, ts)) return 0;
-  return half_slots(op, ts);   // (taken before the paired form wherever both apply: launch_fused)
-}
-static FusedKern fused_kernel_half(int slots) {
-  static const FusedKern k[5] = {k_fused<0, false, 3, false, true>, k_fused<0, false, 4, false, true>, k_fused<0, false, 5, false, true>,
-                                 k_fused<0, false, 6, false, true>, k_fused<0, false, 7, false, true>};
-  return k[slots - 3];
-}
-static FusedKern fused_kernel(const OpacityParams &op, int slots) {
+static FusedKern fused_kernel(const TsPlan &f, int rebin_mode, bool cust_on) {
+  static const FusedKern kp[3] = {k_fused<0, false, 0, true>, k_fused<0, false, 6, true>, k_fused<0, false, 8, true>};   // slots 2 and 4, 6, 8
+  static const FusedKern kh[5] = {k_fused<0, false, 3, false, true>, k_fused<0, false, 4, false, true>, k_fused<0, false, 5, false, true>,
+                                  k_fused<0, false, 6, false, true>, k_fused<0, false, 7, false, true>};
   static const FusedKern k04[2][3] = {{k_fused<0, false, 0>, k_fused<1, false, 0>, k_fused<2, false, 0>},
                                       {k_fused<0, true, 0>, k_fused<1, true, 0>, k_fused<2, true, 0>}};
   static const FusedKern k58[4] = {k_fused<0, false, 5>, k_fused<0, false, 6>, k_fused<0, false, 7>, k_fused<0, false, 8>};
-  return slots <= 4 ? k04[op.cust.on ? 1 : 0][op.rebin_mode] : k58[slots - 5];
+  if (f.form == TS_HALF) return kh[f.slots - 3];
+  if (f.form == TS_PAIRED) return kp[f.slots <= 4 ? 0 : f.slots == 6 ? 1 : 2];
+  return f.slots <= 4 ? k04[cust_on ? 1 : 0][rebin_mode] : k58[f.slots - 5];
 }
 
 // fp.ncol, fp.bs, fp.call_id, fp.max_spins, fp.done, fp.timeout_flag come from the caller.
 // op.nsrc = source layers per column (nz for a batch, where the tile count is an upper bound).
-bool launch_fused(const OpacityParams &op, TwoStreamParams &ts, FusedParams fp, hipStream_t s) {
-  if (!fused_supported(op, ts)) return false;
-  const int nb = ts.n_sol + ts.n_ir;
-  const int groups = (ts.ng + TSW_COLS - 1) / TSW_COLS;  // 2
+bool launch_fused(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, const TsPlan &f, hipStream_t s) {
+  if (f.form == TS_NONE) return false;
   fp.n_op = fused_tiles(op);
-  fp.n_ts = nb * groups;
-  fp.slots = (ts.nz + 63) / 64;  // 2..8 (fused_supported)
-  // 65-224 layers: the half-wave form, also on an all-pairs grid (round 3, measured on AdiabatClimate's doubled grids:
-  // 102 layers 66.3 against 69.1 us per call in the paired whole-wave form, 202 layers 78.2 against 80.6); the paired
-  // form takes the all-pairs grids beyond (402 layers: 131 against ~145 unpaired)
-  const int hs = half_slots(op, ts);
-  const int ps = (!hs && fp.ncol <= 1) ? paired_slots(op, ts) : 0;   // (a batch's columns are not all pairs)
-  if (ps) fp.slots = ps;
-  if (hs) { fp.slots = hs; fp.n_ts = nb; }
+  fp.n_ts = (ts.n_sol + ts.n_ir) * f.groups;
+  fp.slots = f.slots;
   if (fp.ncol < 1) fp.ncol = 1;
   {
     // solar bins (of this shard) whose opacity tiles sit in the first residency round: two blocks per CU
     const long first_round_bins = ((long)2 * device_cus() * OP_THREADS) / std::max(op.nsrc, 1);
     fp.sol_early = (int)std::min<long>(ts.n_sol, std::max<long>(0, first_round_bins - (long)(ts.sol_start + ts.sol_lo - op.bin_lo)));
   }
-  ts.col_base = 0; ts.accumulate = hs ? 0 : 1;   // (a half-wave block holds all 8 g-points of its bin)
+  ts.col_base = 0; ts.accumulate = f.groups > 1 ? 1 : 0;
   ts.scat = op.scat; ts.w0_from_scat = op.write_w0 ? 0 : 1;
-  const size_t lds = sizeof(double) * (3 * TSW_COLS * (hs ? 2 : 1) + 1) * ((size_t)ts.nz + 1);
   const long items = (long)fp.ncol * (fp.n_op + fp.n_ts);
-  const FusedKern k = ps ? fused_kernel_paired(ps) : hs ? fused_kernel_half(hs) : fused_kernel(op, fp.slots);
-  if (lds > 48 * 1024 && !ensure_max_lds((const void *)k, 64 * 1024)) return false;  // (the kernel has static LDS too)
-  hipLaunchKernelGGL(k, dim3((unsigned)items), dim3(OP_THREADS), lds, s, op, ts, fp);
+  const FusedKern k = fused_kernel(f, op.rebin_mode, op.cust.on != 0);
+  if (f.lds > 48 * 1024 && !ensure_max_lds((const void *)k, 64 * 1024)) return false;  // (the kernel has static LDS too)
+  hipLaunchKernelGGL(k, dim3((unsigned)items), dim3(OP_THREADS), f.lds, s, op, ts, fp);
   return true;
 }
 
@@ -3482,7 +3481,12 @@ bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta
   if (half && (paired || slots < 3 || slots > 7 || (ts.nz + 31) / 32 > slots)) return false;
   // the paired form: chunks are cut at pair boundaries, so a lane holds 2 ceil((nz/2)/64) slots at most
   if (paired && ((ts.nz & 1) || (slots & 1) || 2 * ((ts.nz / 2 + 63) / 64) > slots)) return false;
-  ts.paired = paired ? 1 : 0;
+  TsPlan f{};   // filled by hand: the hook forces form and slot count
+  f.form = half ? TS_HALF : paired ? TS_PAIRED : TS_WAVE;
+  f.slots = slots;
+  f.cols = half ? 2 * TSW_COLS : TSW_COLS;
+  f.groups = ts.ng / f.cols;
+  f.lds = wave_lds(ts.nz, f.cols);
   OpacityParams op;
   memset(&op, 0, sizeof(op));
   op.nz = ts.nz;
@@ -3491,14 +3495,13 @@ bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta
   memset(&fp, 0, sizeof(fp));
   fp.ncol = 1;
   fp.n_op = 0;        // no opacity tiles: the two-stream blocks have nothing to wait for
-  fp.n_ts = (ts.n_sol + ts.n_ir) * (half ? 1 : (ts.ng + TSW_COLS - 1) / TSW_COLS);
+  fp.n_ts = (ts.n_sol + ts.n_ir) * f.groups;
   fp.slots = slots;
   fp.sol_early = ts.n_sol;
   ts.col_base = 0; ts.accumulate = half ? 0 : 1;
-  const size_t lds = sizeof(double) * (3 * TSW_COLS * (half ? 2 : 1) + 1) * ((size_t)ts.nz + 1);
-  const FusedKern k = half ? fused_kernel_half(slots) : paired ? fused_kernel_paired(slots) : fused_kernel(op, slots);
-  if (lds > 48 * 1024 && !ensure_max_lds((const void *)k, 64 * 1024)) return false;
-  hipLaunchKernelGGL(k, dim3(fp.n_ts), dim3(OP_THREADS), lds, s, op, ts, fp);
+  const FusedKern k = fused_kernel(f, 0, false);
+  if (f.lds > 48 * 1024 && !ensure_max_lds((const void *)k, 64 * 1024)) return false;
+  hipLaunchKernelGGL(k, dim3(fp.n_ts), dim3(OP_THREADS), f.lds, s, op, ts, fp);
   return true;
 }
 

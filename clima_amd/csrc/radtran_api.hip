@@ -249,7 +249,6 @@ struct Radtran {
   std::vector<hipEvent_t> pool;
   double k_ms[4] = {0, 0, 0, 0};
   int k_n[4] = {0, 0, 0, 0};
-  size_t ts_lds = 0;
 
   ~Radtran() {
     for (auto *x : k) delete x;
@@ -569,8 +568,6 @@ TwoStreamParams make_twostream_params(Radtran *r, const ColumnDev &col, bool com
   const int nz = r->nz;
   std::memset(&ts, 0, sizeof(ts));
   ts.nz = nz; ts.ng = r->ng;
-  if (r->ts_ncols_env) ts.ncols = r->ts_ncols_env;   // (the switches are read once, when the handle is made: a getenv per
-                                                      //  call is a walk through the whole environment)
   ts.n_sol = compute_solar ? r->sol_n : 0; ts.sol_lo = r->sol_lo;
   ts.n_ir = r->ir_n; ts.ir_lo = r->ir_lo;
   ts.sol_start = r->sol.ind_start; ts.ir_start = r->ir.ind_start;
@@ -606,6 +603,28 @@ size_t res_block_count(Radtran *r) {
   return (size_t)r->ir.nw * (2 * nl + nz) + (size_t)r->sol.nw * (3 * nl + nz);
 }
 
+// Switches fixed for the process at their first use (the handle-less test hooks obey them too); the others are read once
+// into the handle when it is made (radtran_create_end) -- a getenv per call is a walk through the whole environment.
+bool sw_no_half() { static const bool v = [] { const char *e = getenv("CLIMA_HIP_NO_HALF"); return e && e[0] == '1'; }(); return v; }
+bool sw_paired() { static const bool v = [] { const char *e = getenv("CLIMA_HIP_PAIRED"); return !(e && e[0] == '0'); }(); return v; }
+bool sw_w0_scat() { static const bool v = [] { const char *e = getenv("CLIMA_HIP_W0_SCAT"); return !(e && e[0] == '0'); }(); return v; }
+
+// what plan_radiate needs to know of a call on this handle; batch_ncol > 0: one launch per kernel for that many columns
+PlanIn plan_input(const Radtran *r, bool compute_solar, bool compute_opacity, bool allow_fused, int batch_ncol) {
+  PlanIn in{};
+  in.nz = r->nz; in.ng = r->ng; in.nzen = (int)r->zenith_u.size();
+  in.n_ir = r->ir_n; in.n_sol = compute_solar ? r->sol_n : 0; in.op_n = r->op_n;
+  in.batch = batch_ncol > 0; in.ncol = in.batch ? batch_ncol : 1;
+  in.nsrc = in.batch ? r->nz : (r->col_override ? r->nsrc_override : r->nsrc);
+  in.rebin_mode = r->rebin_mode; in.cust_on = r->cust_on; in.compute_opacity = compute_opacity;
+  // exact pairs in the column (and this call computes the opacities from it) -> exact pairs in opr
+  in.all_pairs = !in.batch && !r->col_override && compute_opacity && r->all_pairs_exact;
+  in.fused = r->fused; in.allow_fused = allow_fused; in.generic_opacity = r->generic_opacity;
+  in.ts_block_mode = r->ts_block_mode; in.ts_ncols_env = r->ts_ncols_env; in.coop_items = r->coop_items;
+  in.no_half = sw_no_half(); in.allow_paired = sw_paired(); in.w0_from_scat = sw_w0_scat();
+  return in;
+}
+
 // The stored w0 array is current (a fused call's tiles leave it to the two-stream part of the same grid:
 // whoever else wants it -- IR-only calls on the stored opacities, the batched IR kernel, radtran_opr_get --
 // gets it formed from tau and the layers' scattering optical depth first)
@@ -626,8 +645,6 @@ void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool 
   BatchStrides bs;
   std::memset(&bs, 0, sizeof(bs));
   if (bc) bs = bc->bs;
-  const int ncol = bc ? bc->ncol : 1;
-  const int nsrc = bc ? nz : (r->col_override ? r->nsrc_override : r->nsrc);
   // where this call's optical properties and spectra live
   double *o_tau = r->d_tau.p, *o_w0 = r->d_w0.p, *o_g = r->d_g.p, *o_tb = r->d_tau_band.p, *o_sc = r->d_scat.p;
   double *ir_fup = r->wrk_ir.fup_a.p, *ir_fdn = r->wrk_ir.fdn_a.p, *ir_tb = r->wrk_ir.tau_band.p;
@@ -638,21 +655,17 @@ void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool 
     sol_fup = ir_tb + (size_t)r->ir.nw * nz; sol_fdn = sol_fup + r->sol.nw * nl; sol_am = sol_fdn + r->sol.nw * nl;
     sol_tb = sol_am + r->sol.nw * nl;
   }
-  auto ts_params = [&]() {
-    TwoStreamParams ts = make_twostream_params(r, col, compute_solar);
-    ts.tau = o_tau; ts.w0 = o_w0; ts.g = o_g; ts.tau_band = o_tb; ts.scat = o_sc; ts.w0_from_scat = 0;
-    ts.ir_fup_a = ir_fup; ts.ir_fdn_a = ir_fdn; ts.ir_tau_band = ir_tb;
-    ts.sol_fup_a = sol_fup; ts.sol_fdn_a = sol_fdn; ts.sol_amean = sol_am; ts.sol_tau_band = sol_tb;
-    // exact pairs in the column (and this call computes the opacities from it) -> exact pairs in opr
-    static const bool allow_paired = [] { const char *e = getenv("CLIMA_HIP_PAIRED"); return !(e && e[0] == '0'); }();
-    ts.paired = (allow_paired && !bc && !r->col_override && compute_opacity && r->all_pairs_exact) ? 1 : 0;
-    return ts;
-  };
-  bool pre_zeroed = false, fused_done = false, whole_stores = false;
+  TwoStreamParams ts = make_twostream_params(r, col, compute_solar);
+  ts.tau = o_tau; ts.w0 = o_w0; ts.g = o_g; ts.tau_band = o_tb; ts.scat = o_sc; ts.w0_from_scat = 0;
+  ts.ir_fup_a = ir_fup; ts.ir_fdn_a = ir_fdn; ts.ir_tau_band = ir_tb;
+  ts.sol_fup_a = sol_fup; ts.sol_fdn_a = sol_fdn; ts.sol_amean = sol_am; ts.sol_tau_band = sol_tb;
+  const PlanIn in = plan_input(r, compute_solar, compute_opacity, allow_fused, bc ? bc->ncol : 0);
+  const LaunchPlan plan = plan_radiate(in);
+  bool fused_done = false;
   if (compute_opacity) {
     PrepParams pp;
     std::memset(&pp, 0, sizeof(pp));
-    pp.ncol = ncol; pp.bs = bs;
+    pp.ncol = in.ncol; pp.bs = bs;
     pp.nz = nz; pp.nsp = r->nsp; pp.np = r->np; pp.nslots = r->nslots;
     pp.has_cont = r->has_cont; pp.LH2O = r->LH2O;
     for (int s = 0; s < r->nslots; s++) pp.slots[s] = r->slots[s];
@@ -667,47 +680,13 @@ void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool 
     for (int e = 0; e < pp.nabs; e++) { pp.abs_kind[e] = r->abs_entries[e].kind; pp.abs_a[e] = r->abs_entries[e].a; pp.abs_b[e] = r->abs_entries[e].b; }
     pp.col = col;
     pp.call_id = ++r->call_id;
-    {  // when the wave-per-column two-stream kernel will add two g-point groups into its
-       // outputs, let spare blocks of this launch clear them (saves a launch)
-      const bool wave_mode = !r->ts_block_mode && (nz + 63) / 64 <= 8;
-      pre_zeroed = false;
-      // (not when the fused grid will run its half-wave form: those blocks store whole values -- 7.7 MB of
-      // zeros per config-2 call that nobody reads)
-      {
-        OpacityParams oq;
-        std::memset(&oq, 0, sizeof(oq));
-        oq.nz = nz; oq.ng = r->ng; oq.nbins = r->op_n; oq.rebin_mode = r->rebin_mode; oq.cust.on = r->cust_on ? 1 : 0;
-        const bool coop = !bc && r->ng == 8 && (long)r->op_n * nsrc <= r->coop_items;
-        if ((bc || (r->fused && allow_fused && !coop)) && wave_mode && twostream_w_groups(r->ng) >= 2) {
-          const TwoStreamParams tq = ts_params();
-          whole_stores = fused_half_form(oq, tq, ncol) != 0;
-        } else if (!bc && wave_mode && r->ng == 8) {
-          // one launch per kernel: the stand-alone half-wave two-stream kernel stores whole values too
-          const TwoStreamParams tq = ts_params();
-          whole_stores = tq.nzen <= MAX_ZEN && twostream_w_half_slots(tq) != 0;
-        }
-      }
-      if (wave_mode && twostream_w_groups(r->ng) >= 2 && !whole_stores) {
-        int n = 0;
-        if (r->ir_n > 0) {
-          pp.zero_ptr[n] = ir_fup + (size_t)r->ir_lo * nl; pp.zero_count[n++] = nl * r->ir_n;
-          pp.zero_ptr[n] = ir_fdn + (size_t)r->ir_lo * nl; pp.zero_count[n++] = nl * r->ir_n;
-        }
-        if (compute_solar && r->sol_n > 0) {
-          pp.zero_ptr[n] = sol_fup + (size_t)r->sol_lo * nl; pp.zero_count[n++] = nl * r->sol_n;
-          pp.zero_ptr[n] = sol_fdn + (size_t)r->sol_lo * nl; pp.zero_count[n++] = nl * r->sol_n;
-          pp.zero_ptr[n] = sol_am + (size_t)r->sol_lo * nl; pp.zero_count[n++] = nl * r->sol_n;
-        }
-        pp.nzero = n;
-        pre_zeroed = true;
-      }
-    }
+    if (plan.prep_clears) pp.nzero = ts_clear_ranges(ts, pp.zero_ptr, pp.zero_count);
     { KernelTimer t(r, 0); launch_prep(pp, r->stream); HIPCHK(hipGetLastError()); t.stop(); }
 
     OpacityParams op;
     std::memset(&op, 0, sizeof(op));
     op.nz = nz; op.nw = r->nw; op.ng = r->ng; op.nsp = r->nsp; op.np = r->np;
-    op.bin_lo = r->op_lo; op.nbins = r->op_n; op.nsrc = nsrc;
+    op.bin_lo = r->op_lo; op.nbins = r->op_n; op.nsrc = in.nsrc;
     op.nk = (int)r->k.size(); op.nray = (int)r->ray.size(); op.npart = (int)r->part.size();
     for (size_t i = 0; i < r->k.size(); i++)
       op.k[i] = KDev{r->k[i]->d_log10k.p, r->k[i]->sp, r->k[i]->nP, r->k[i]->nT, (int)(2 * i), (int)(2 * i + 1)};
@@ -720,38 +699,27 @@ void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool 
     op.col = col;
     op.cust = CustomDev{r->d_cust_dtau.p, r->d_cust_w0.p, r->d_cust_g0.p, r->cust_nP, r->nslots, r->cust_on ? 1 : 0};
     op.rebin_mode = r->rebin_mode;
-    // few (bin, source layer) items -- a bin-sharded rank, a short or all-pairs column: the group-of-lanes
-    // kernel (a fifth of the lane-per-item kernel's dependent chain) and one launch per kernel
-    op.coop = (!bc && r->ng == 8 && (long)r->op_n * nsrc <= r->coop_items) ? 1 : 0;
-    op.generic = r->generic_opacity ? 1 : 0;
 #ifdef CLIMA_STAMPS
     op.stamps = r->d_stamps.p;
 #endif
-    op.tau = o_tau; op.w0 = o_w0; op.g = o_g; op.tau_band = o_tb; op.scat = o_sc; op.write_w0 = 1;
-    if (bc || (r->fused && allow_fused && (pre_zeroed || whole_stores) && !op.coop)) {
-      TwoStreamParams tsf = ts_params();
-      if (fused_supported(op, tsf) && (pre_zeroed || whole_stores)) {
-        FusedParams fp;
-        std::memset(&fp, 0, sizeof(fp));
-        fp.ncol = ncol; fp.bs = bs;
-        fp.call_id = pp.call_id; fp.max_spins = r->fused_max_spins;
-        fp.done = bc ? bc->done : r->d_done.p; fp.timeout_flag = r->d_err.p + 1;
-        KernelTimer t(r, 1);
-        // the fused grid's two-stream part forms w0 from the layers' scattering optical depth itself: the
-        // tiles leave the 8 nw nz values unwritten (26 MB per config-2 call neither stored nor read back);
-        // ensure_w0() materialises them if something else asks (CLIMA_HIP_W0_SCAT=0: always written)
-        static const bool w0_scat = [] { const char *e = getenv("CLIMA_HIP_W0_SCAT"); return !(e && e[0] == '0'); }();
-        op.write_w0 = w0_scat ? 0 : 1;
-        fused_done = launch_fused(op, tsf, fp, r->stream);
-        HIPCHK(hipGetLastError());
-        t.stop();
-        if (!fused_done) op.write_w0 = 1;
-      }
+    op.tau = o_tau; op.w0 = o_w0; op.g = o_g; op.tau_band = o_tb; op.scat = o_sc; op.write_w0 = plan.write_w0 ? 1 : 0;
+    if (plan.fused.form != TS_NONE) {
+      FusedParams fp;
+      std::memset(&fp, 0, sizeof(fp));
+      fp.ncol = in.ncol; fp.bs = bs;
+      fp.call_id = pp.call_id; fp.max_spins = r->fused_max_spins;
+      fp.done = bc ? bc->done : r->d_done.p; fp.timeout_flag = r->d_err.p + 1;
+      KernelTimer t(r, 1);
+      fused_done = launch_fused(op, ts, fp, plan.fused, r->stream);
+      HIPCHK(hipGetLastError());
+      t.stop();
+      if (!fused_done) op.write_w0 = 1;   // (the runtime refused the grid its LDS: the separate launches, w0 stored; ensure_w0()
+                                          //  materialises an unwritten w0 when something else asks for it)
     }
     if (bc && !fused_done) throw HipFail{"internal: a one-launch batch needs the fused grid"};
     if (!fused_done) {
       KernelTimer t(r, 1);
-      const bool ok = launch_opacity(op, r->stream);
+      const bool ok = launch_opacity(op, plan, r->stream);
       HIPCHK(hipGetLastError());
       if (!ok)
         throw HipFail{"k-distributions with " + std::to_string(r->ng) + " g-points are not supported (1..32)"};
@@ -766,13 +734,11 @@ void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool 
   r->last_cs = compute_solar;
   if (compute_solar) r->solar_id = r->call_id;
 
-  TwoStreamParams ts = ts_params();
   if (!fused_done) {
     KernelTimer t(r, 2);
     // default: wave-per-column kernel; CLIMA_HIP_TS_MODE=block selects the workgroup-per-bin form
-    bool ok = false;
-    if (!r->ts_block_mode && ts.nzen <= MAX_ZEN) ok = launch_twostream_w(ts, r->stream, &r->ts_lds, pre_zeroed);
-    if (!ok) { HIPCHK(hipGetLastError()); ok = launch_twostream(ts, r->stream, &r->ts_lds); }
+    bool ok = launch_twostream_w(ts, plan.ts, r->stream);
+    if (!ok) { HIPCHK(hipGetLastError()); ok = launch_twostream(ts, plan.block, r->stream); }
     HIPCHK(hipGetLastError());
     if (!ok)
       throw HipFail{"nz*ngauss = " + std::to_string(nz * r->ng) + " exceeds what the two-stream kernels can stage"};
@@ -781,7 +747,7 @@ void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool 
 
   IntegrateParams ip;
   std::memset(&ip, 0, sizeof(ip));
-  ip.ncol = ncol; ip.bs = bs;
+  ip.ncol = in.ncol; ip.bs = bs;
   ip.nz = nz; ip.nw_ir = r->ir.nw; ip.nw_sol = r->sol.nw;
   ip.ir_lo = r->ir_lo; ip.ir_n = r->ir_n; ip.sol_lo = r->sol_lo; ip.sol_n = r->sol_n;
   ip.do_solar = compute_solar ? 1 : 0;
@@ -1517,7 +1483,9 @@ static void ir_batch_general(Radtran *r, const double *d_T, const double *d_Ts, 
   TwoStreamParams ts = make_twostream_params(r, col, false);
   ts.ir_fup_a = r->d_bup.p; ts.ir_fdn_a = r->d_bdn.p;
   ts.b_T = nz; ts.b_Ts = 1; ts.b_out = spec;
-  const bool split = twostream_w_groups(r->ng) > 1;
+  PlanIn in = plan_input(r, false, false, false, 0);
+  in.ir_batch = true;
+  const LaunchPlan plan = plan_radiate(in);
   for (int c0 = 0; c0 < n; c0 += CH) {
     const int nc = std::min(CH, n - c0);
     TwoStreamParams tb = ts;
@@ -1531,11 +1499,11 @@ static void ir_batch_general(Radtran *r, const double *d_T, const double *d_Ts, 
     const bool shared_ok = r->batch_shared && !tiny && launch_twostream_ir_batch(tb, nc, r->stream);
     HIPCHK(hipGetLastError());
     if (!shared_ok) {
-      if (split) {  // g-point groups add into zeroed spectra
+      if (plan.caller_clears) {  // g-point groups add into zeroed spectra
         HIPCHK(hipMemsetAsync(r->d_bup.p, 0, sizeof(double) * spec * nc, r->stream));
         HIPCHK(hipMemsetAsync(r->d_bdn.p, 0, sizeof(double) * spec * nc, r->stream));
       }
-      const bool ok = launch_twostream_w(tb, r->stream, &r->ts_lds, true);
+      const bool ok = launch_twostream_w(tb, plan.ts, r->stream);
       HIPCHK(hipGetLastError());
       if (!ok)
         throw HipFail{"radiate_ir_batch: nz = " + std::to_string(nz) + " exceeds what the wave two-stream kernel holds (512)"};
@@ -2003,8 +1971,7 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   // turn, so one column's two-stream tail runs beside the next column's opacity tiles) where the fused
   // form covers the configuration; otherwise the calls of the columns are enqueued back to back.
   const int CH = std::min(n, r->batch_cols_in_flight);
-  bool one_launch = r->fused && r->ng == 8 && !r->ts_block_mode && (nz + 63) / 64 >= 2 && (nz + 63) / 64 <= 8 &&
-                    (int)r->zenith_u.size() <= MAX_ZEN && !((nz + 63) / 64 > 4 && (r->rebin_mode != 0 || r->cust_on)) &&
+  bool one_launch = plan_radiate(plan_input(r, true, true, true, CH)).fused.form != TS_NONE &&
                     integrate_chunks(std::max(r->ir_n, r->sol_n)) * (32 + 16) * sizeof(double) <= 64 * 1024;
   if (const char *e = getenv("CLIMA_HIP_BATCH_ONE_LAUNCH")) one_launch = one_launch && atoi(e) != 0;
   const size_t tiles = ((size_t)r->op_n * nz + 255) / 256;
@@ -2712,9 +2679,12 @@ void clima_test_two_stream(const int *nz_, const int *ng_, const int *form, cons
   ts.ir_fup_a = d_out.p; ts.ir_fdn_a = d_out.p + nl; ts.sol_fup_a = d_out.p + 2 * nl; ts.sol_fdn_a = d_out.p + 3 * nl;
   ts.sol_amean = d_out.p + 4 * nl; ts.ir_tau_band = d_out.p + 5 * nl; ts.sol_tau_band = d_out.p + 6 * nl;
   bool ok = false;
-  size_t lds = 0;
-  if (*form == 0) ok = launch_twostream_w(ts, nullptr, &lds, false);
-  else if (*form == 1) ok = launch_twostream(ts, nullptr, &lds);
+  PlanIn in{};   // a call on stored opacities, no handle: forms 0 and 1 are the plan's stand-alone forms
+  in.nz = nz; in.ng = ng; in.nzen = 1; in.n_ir = ts.n_ir; in.n_sol = ts.n_sol; in.ncol = 1;
+  in.force_slots = *slots; in.no_half = sw_no_half();
+  const LaunchPlan plan = plan_radiate(in);
+  if (*form == 0) ok = launch_twostream_w(ts, plan.ts, nullptr);
+  else if (*form == 1) ok = launch_twostream(ts, plan.block, nullptr);
   else if (*form == 2 || *form == 4 || *form == 5) {   // 4: the half-wave form (two g-point columns per wave), 5: the paired form
     if (*form == 5)
       for (int i = 0; i + 1 < nz; i += 2)

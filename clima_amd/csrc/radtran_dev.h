@@ -127,8 +127,7 @@ struct OpacityParams {
   int nz, nw, ng, nsp, np;
   int bin_lo, nbins;  // opacity bins handled by this launch
   int nsrc;           // source layers of the column (host count, == meta[0]); nz for a batch (upper bound)
-  int coop;           // ng = 8: use the group-of-lanes kernel (k_opacity_coop<8>) -- few items, latency matters
-  int generic;        // ng != 8: the wave-per-item generic kernel instead of the group-of-lanes one (cross-check)
+  int coop, generic;  // unused (the launch plan says which opacity kernel runs); they keep the kernels' argument layout
   int nk, nray, npart;
   KDev k[MAX_K];
   XsDev ray[MAX_XS];
@@ -182,13 +181,11 @@ struct TwoStreamParams {
   const double *wbin;
   const double *freq;                      // opacity grid [nw+1]
   // test hook (clima_test_two_stream): Planck values at the levels given directly [nz+1] TOA-first
-  // instead of computed from T (null in production), and a slot count above ceil(nz/64) (0: none)
+  // instead of computed from T (null in production), and a slot count above ceil(nz/64) (0: none; the batched IR
+  // launcher reads it, the other forms take theirs from the launch plan)
   const double *bplanck;
   int force_slots;
-  // every layer 2m+1 (ground-first) carries exactly the optical properties of layer 2m: pair_reuse marked
-  // all pairs as exact copies (AdiabatClimate's doubled radiative grid); the fused grid then takes the
-  // paired form of the two-stream part
-  int paired;
+  int paired;                              // unused (LaunchPlan::fused says when the paired form runs); keeps the argument layout
   // IR
   const double *T, *T_surface;
   const double *emissivity;                // [nw_ir]
@@ -327,23 +324,64 @@ void green_vector_form_set(int vector_form);   // test hook: the far accumulatio
 int green_far_waves(int ndev, int nl);   // per bin split
 int green_far_splits(int n_ir, int waves);
 
-// launchers (kernels.hip)
+// ---- the launch plan of one radiate call: decided once by plan_radiate (kernels.hip, beside the kernels whose limits
+// it applies), executed by the launchers, which decide nothing ----
+struct PlanIn {
+  // the call
+  int nz, ng, nzen;
+  int n_ir, n_sol, op_n;   // this rank's bins (n_sol = 0: a call without solar fluxes)
+  int nsrc;                // source layers of the column; nz for a batch (upper bound)
+  int ncol;                // columns in the launch
+  bool batch;              // ... of a one-launch batch (radtran_toa_fluxes_batch)
+  bool ir_batch;           // temperature columns on the stored opacities (radiate_ir_batch's general form): the wave forms
+                           // whatever the block-mode switch says, and the caller clears the per-column spectra
+  int rebin_mode;
+  bool cust_on, compute_opacity;
+  bool all_pairs;          // the call computes its opacities from a column of exact pairs (the doubled radiative grid)
+  // the handle's and the process's switches
+  bool fused, allow_fused, generic_opacity, ts_block_mode, no_half, allow_paired, w0_from_scat;
+  long coop_items;
+  int ts_ncols_env;
+  int force_slots;         // test hook: whole-wave slots above ceil(nz/64); rules out the half-wave kernel
+};
+enum { OP_NONE = 0, OP_TILE, OP_COOP, OP_GENERIC, OP_UNSUPPORTED };   // stored opacities | lane per item | group of lanes | wave per item
+enum { TS_NONE = 0, TS_WAVE, TS_HALF, TS_PAIRED, TS_BLOCK };          // whole wave | half wave | exact pairs (fused grid only) | workgroup per bin
+struct TsPlan {
+  int form;
+  int slots;               // layers per lane (TS_BLOCK: chunks per g-point column)
+  int cols;                // g-point columns per workgroup
+  int groups, per_launch;  // g-point groups of a bin (> 1: their partial sums are ADDED into cleared outputs), groups per launch
+  int threads;             // TS_BLOCK
+  size_t lds;              // dynamic LDS bytes
+  bool zero_launch;        // a k_zero launch clears the outputs first
+};
+struct LaunchPlan {
+  int opacity, coop_ng;    // OP_*, lanes per item of the group-of-lanes kernel (8, 16, 32)
+  TsPlan fused;            // TS_NONE: separate launches
+  TsPlan ts;               // the stand-alone wave forms: when no fused grid runs (or the runtime refuses it its LDS); TS_NONE: none applies
+  TsPlan block;            // the workgroup-per-bin form: when no wave form runs; TS_NONE: the column does not fit
+  bool prep_clears;        // spare blocks of the prep launch clear the outputs
+  bool caller_clears;      // ir_batch: the caller clears its per-column spectra
+  bool write_w0;           // the opacity tiles store w0 (false: the fused grid's two-stream part forms it from scat)
+};
+LaunchPlan plan_radiate(const PlanIn &in);
+// the ranges a form that adds partial sums needs cleared: this launch's bins of the five spectra; returns their number
+int ts_clear_ranges(const TwoStreamParams &p, double *ptr[6], size_t count[6]);
+
+// launchers (kernels.hip): they take their part of the plan, pick the kernel, fill the fields marked (launcher) and launch
 void launch_prep(const PrepParams &p, hipStream_t s);
-// returns false when ng is unsupported by the compiled kernels (ng = 8 tuned; 1..32 generic)
-bool launch_opacity(const OpacityParams &p, hipStream_t s);
-bool launch_twostream(TwoStreamParams &p, hipStream_t s, size_t *lds_bytes);
-bool launch_twostream_w(TwoStreamParams &p, hipStream_t s, size_t *lds_bytes, bool zeroed);
+// false: OP_UNSUPPORTED (the compiled kernels cover 1..32 g-points)
+bool launch_opacity(const OpacityParams &p, const LaunchPlan &pl, hipStream_t s);
+// false: the plan has no such form, or the runtime refused the kernel its dynamic LDS (the caller goes on to the next form)
+bool launch_twostream(TwoStreamParams &p, const TsPlan &t, hipStream_t s);
+bool launch_twostream_w(TwoStreamParams &p, const TsPlan &t, hipStream_t s);
 // T + c*b_T, T_surface + c*b_Ts, IR spectra + c*b_out for column c of ncol
 bool launch_twostream_ir_batch(TwoStreamParams &p, int ncol, hipStream_t s, int force_nw = 0);
-bool fused_supported(const OpacityParams &op, const TwoStreamParams &ts);
-int fused_half_form(const OpacityParams &op, const TwoStreamParams &ts, int ncol);
 int fused_tiles(const OpacityParams &op);   // opacity tiles per column (size of a column's done[] slice)
-bool launch_fused(const OpacityParams &op, TwoStreamParams &ts, FusedParams fp, hipStream_t s);
+bool launch_fused(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, const TsPlan &f, hipStream_t s);
 // test hook: the two-stream blocks of the fused grid alone (no opacity blocks), on opacities already in HBM
 // (meta_nsrc: a device int, any value >= 1)
 bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta_nsrc, hipStream_t s, bool half = false, bool paired = false);
-int twostream_w_groups(int ng);
-int twostream_w_half_slots(const TwoStreamParams &p);   // > 0: launch_twostream_w takes k_twostream_h (with 8 g-points: stores whole values)
 void launch_integrate(const IntegrateParams &p, hipStream_t s);
 bool integrate_one_launch(const IntegrateParams &p);
 void launch_integrate_batch(const BatchIntegrateParams &p, int ncol, hipStream_t s);
