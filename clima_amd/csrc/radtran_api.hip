@@ -191,7 +191,7 @@ struct Radtran {
   int fused_max_spins = 400000, checked_timeout = 0, solar_id = 0, fused_fallbacks = 0;
   bool last_cs = true;
   std::vector<double> last_T, last_P, last_radii;  // host copy for byte accounting
-  // opr: one block [tau | w0 | g | tau_band]; the four are views into it
+  // opr: one block [tau | w0 | g | tau_band | scat] (opr_views); the five are views into it
   DevBuf<double> d_opr;
   size_t opr_count = 0;
   DevBuf<double> d_tau, d_w0, d_g, d_tau_band, d_scat;
@@ -208,7 +208,6 @@ struct Radtran {
   hipStream_t copy_streams[3] = {nullptr, nullptr, nullptr}; // radtran_spectra_get_all: the seven copies go out over four queues
   double *h_small = nullptr;  // pinned: flux_n[4*(nz+1)] | f_total[nz+1] | err flag (as double slot)
   double *h_small_dev = nullptr;   // the same block as the device addresses it (null: not mapped)
-  bool want_host_out = false;      // set by the synchronous wrappers around their enqueue_radiate
   bool small_in_host = false;      // the last call's integration stored its rows into h_small itself: no copy to fetch them
   int *h_errflag = nullptr;
   std::vector<double> f_total;
@@ -226,9 +225,7 @@ struct Radtran {
   int op_lo = 0, op_n = 0, ir_lo = 0, ir_n = 0, sol_lo = 0, sol_n = 0;
   // stream + profiling
   hipStream_t stream = nullptr;
-  // column batches (radtran_toa_fluxes_batch): the column / level-flux buffers a call works on
-  double *col_override = nullptr, *flux_override = nullptr, *ftot_override = nullptr;
-  int nsrc_override = 0;
+  // column batches (radtran_toa_fluxes_batch): every column's block, every column's level rows [5][nz+1]
   DevBuf<double> d_cols_arena, d_flux_arena;
   // one-launch batches: per-column prep / opr / spectra blocks for the columns in flight
   DevBuf<double> d_prep_arena, d_opr_arena, d_res_arena;
@@ -499,24 +496,95 @@ size_t prep_block_count(Radtran *r) {
   return nz * (2 + r->nsp + nab + ns) + (ns * nz + 1) / 2;
 }
 
-ColumnDev column_dev_at(Radtran *r, double *col_base, double *prep_base) {
+// Optical-property block [tau | w0 | g | tau_band | scat] laid over `base` (d_opr, or a column's slice of the batch
+// arena); count: doubles in the block.  A null base gives the count alone.
+struct OprViews { double *tau, *w0, *g, *tau_band, *scat; size_t count; };
+OprViews opr_views(const Radtran *r, double *base) {
+  const size_t nwz = (size_t)r->nw * r->nz, nwgz = nwz * r->ng;
+  OprViews v{};
+  auto take = [&](size_t n) { double *p = base ? base + v.count : nullptr; v.count += n; return p; };
+  v.tau = take(nwgz); v.w0 = take(nwgz); v.g = take(nwz); v.tau_band = take(nwz); v.scat = take(nwz);
+  return v;
+}
+
+// Spectra block of one column of a batch, laid over `base` the same way:
+// [ir fup_a | ir fdn_a | ir tau_band | sol fup_a | sol fdn_a | sol amean | sol tau_band]
+struct SpectraViews { double *ir_fup_a, *ir_fdn_a, *ir_tau_band, *sol_fup_a, *sol_fdn_a, *sol_amean, *sol_tau_band; size_t count; };
+SpectraViews spectra_views(const Radtran *r, double *base) {
+  const size_t nl = (size_t)r->nz + 1, nz = r->nz, ni = r->ir.nw, ns = r->sol.nw;
+  SpectraViews v{};
+  auto take = [&](size_t n) { double *p = base ? base + v.count : nullptr; v.count += n; return p; };
+  v.ir_fup_a = take(ni * nl); v.ir_fdn_a = take(ni * nl); v.ir_tau_band = take(ni * nz);
+  v.sol_fup_a = take(ns * nl); v.sol_fdn_a = take(ns * nl); v.sol_amean = take(ns * nl); v.sol_tau_band = take(ns * nz);
+  return v;
+}
+
+// Where one radiate call's data lives.  RESIDENT: the handle's own buffers.  ARENA_COLUMN: one column of a batch
+// (radtran_toa_fluxes_batch), its column block and level rows in the arenas, everything else the handle's.
+// ARENA_CHUNK: `ncol` columns worked on by ONE launch of each kernel, per-column blocks in the arenas, column c of
+// the chunk at base + c * stride.
+enum CallKind { CALL_RESIDENT, CALL_ARENA_COLUMN, CALL_ARENA_CHUNK };
+struct CallBufs {
+  CallKind kind;
+  double *col, *prep;      // column block, prep block
+  int nsrc;                // source layers of the column (a chunk: nz, the bound of its columns')
+  bool all_pairs_exact;    // every layer is half of an exact pair (known of the resident column only)
+  OprViews opr;
+  SpectraViews spec;
+  double *flux_n, *f_total;
+  int *done;               // the fused grid's per-tile flags
+  int ncol;                // columns of this launch; their blocks are bs apart (zero but for a chunk)
+  BatchStrides bs;
+  bool host_out;           // a synchronous wrapper's call: the integration may store into the host's pinned block
+};
+
+CallBufs resident_bufs(Radtran *r, bool host_out = false) {
+  CallBufs b{};
+  b.kind = CALL_RESIDENT; b.ncol = 1; b.host_out = host_out;
+  b.col = r->d_col.p; b.prep = r->d_prep.p;
+  b.nsrc = r->nsrc; b.all_pairs_exact = r->all_pairs_exact;
+  b.opr = OprViews{r->d_tau.p, r->d_w0.p, r->d_g.p, r->d_tau_band.p, r->d_scat.p, r->opr_count};
+  b.spec = SpectraViews{r->wrk_ir.fup_a.p, r->wrk_ir.fdn_a.p, r->wrk_ir.tau_band.p, r->wrk_sol.fup_a.p,
+                        r->wrk_sol.fdn_a.p, r->wrk_sol.amean.p, r->wrk_sol.tau_band.p, 0};   // (seven buffers, no block)
+  b.flux_n = r->d_flux_n.p; b.f_total = r->d_f_total.p; b.done = r->d_done.p;
+  return b;
+}
+// column c of the arena (nsrc: what build_meta returned for it) on the handle's optical-property and spectra buffers
+CallBufs arena_column_bufs(Radtran *r, int c, int nsrc) {
+  CallBufs b = resident_bufs(r);
+  b.kind = CALL_ARENA_COLUMN; b.nsrc = nsrc; b.all_pairs_exact = false;
+  b.col = r->d_cols_arena.p + (size_t)c * r->col_count;
+  b.flux_n = r->d_flux_arena.p + (size_t)c * 5 * (r->nz + 1); b.f_total = b.flux_n + 4 * (r->nz + 1);
+  return b;
+}
+// columns [c0, c0 + ncol) of the arena, their prep / opr / spectra blocks from the start of those arenas
+// (f_total stays the handle's: a chunk's integration is the one-launch form, which leaves it to the host)
+CallBufs arena_chunk_bufs(Radtran *r, int c0, int ncol) {
+  CallBufs b = resident_bufs(r);
+  b.kind = CALL_ARENA_CHUNK; b.ncol = ncol; b.nsrc = r->nz; b.all_pairs_exact = false;
+  b.col = r->d_cols_arena.p + (size_t)c0 * r->col_count; b.prep = r->d_prep_arena.p;
+  b.opr = opr_views(r, r->d_opr_arena.p); b.spec = spectra_views(r, r->d_res_arena.p);
+  b.flux_n = r->d_flux_arena.p + (size_t)c0 * 5 * (r->nz + 1);
+  b.bs = BatchStrides{r->col_count, r->prep_count, b.opr.count, b.spec.count, (size_t)5 * (r->nz + 1),
+                      (int)(((size_t)r->op_n * r->nz + 255) / 256)};
+  return b;
+}
+
+// Column block [T_surface | T | P | dz | dens | pdens | radii | meta] (pack_column writes it on the host)
+ColumnDev column_dev(Radtran *r, const CallBufs &b) {
   ColumnDev c;
   const int nz = r->nz;
-  c.T_surface = col_base;
-  c.T = col_base + 1;
+  c.T_surface = b.col;
+  c.T = b.col + 1;
   c.P = c.T + nz;
   c.dz = c.P + nz;
   c.dens = c.dz + nz;
   c.pdens = c.dens + (size_t)r->nsp * nz;
   c.radii = c.pdens + (size_t)r->np * nz;
-  c.meta = reinterpret_cast<const int *>(col_base + r->meta_ofs);
-  prep_views(r, prep_base, c);
+  c.meta = reinterpret_cast<const int *>(b.col + r->meta_ofs);
+  prep_views(r, b.prep, c);
   c.err_flag = r->d_err.p;
   return c;
-}
-
-ColumnDev column_dev(Radtran *r) {
-  return column_dev_at(r, r->col_override ? r->col_override : r->d_col.p, r->d_prep.p);
 }
 
 // pair_reuse (clima_radtran_types.f90:621-632), decided here once per column so that the grid size
@@ -563,7 +631,39 @@ int build_meta(Radtran *r, const double *T, const double *P, const double *dz, c
   return nsrc;
 }
 
-TwoStreamParams make_twostream_params(Radtran *r, const ColumnDev &col, bool compute_solar) {
+// Packs one column into a host block laid out like d_col (column_dev unpacks it), pair_reuse table included.
+// Returns nsrc.
+int pack_column(Radtran *r, double *h, double T_surface, const double *T, const double *P, const double *dz,
+                const double *dens, const double *pdens, const double *radii) {
+  const size_t nz = r->nz;
+  h[0] = T_surface;
+  std::memcpy(h + 1, T, sizeof(double) * nz);
+  std::memcpy(h + 1 + nz, P, sizeof(double) * nz);
+  std::memcpy(h + 1 + 2 * nz, dz, sizeof(double) * nz);
+  std::memcpy(h + 1 + 3 * nz, dens, sizeof(double) * nz * r->nsp);
+  double *hp = h + 1 + 3 * nz + nz * r->nsp;
+  if (r->np > 0 && pdens && radii) {
+    std::memcpy(hp, pdens, sizeof(double) * nz * r->np);
+    std::memcpy(hp + nz * r->np, radii, sizeof(double) * nz * r->np);
+  }
+  return build_meta(r, T, P, dz, dens, pdens, radii, pdens && radii, reinterpret_cast<int *>(h + r->meta_ofs));
+}
+
+// f_total from the four level rows of a block [ir up | ir down | solar up | solar down | f_total] (clima_radtran.f90:287)
+void f_total_row(double *h, int nl) {
+  for (int i = 0; i < nl; i++) h[4 * nl + i] = (h[3 * nl + i] - h[2 * nl + i]) + (h[1 * nl + i] - h[0 * nl + i]);
+}
+// ... and ISR, OLR: the net solar and IR fluxes at the last level (clima_radtran.f90:339-340)
+void toa_fluxes(const double *h, int nz, double *ISR, double *OLR) {
+  const int nl = nz + 1;
+  *ISR = (h[3 * nl + nz] - h[2 * nl + nz]);
+  *OLR = -(h[1 * nl + nz] - h[0 * nl + nz]);
+}
+
+void invalidate_small(Radtran *r) { r->small_valid = false; r->small_in_host = false; }
+
+// The parameter blocks of a call's launches: each from the handle and the call's buffers
+TwoStreamParams make_twostream_params(Radtran *r, const CallBufs &b, const ColumnDev &col, bool compute_solar) {
   TwoStreamParams ts;
   const int nz = r->nz;
   std::memset(&ts, 0, sizeof(ts));
@@ -571,7 +671,7 @@ TwoStreamParams make_twostream_params(Radtran *r, const ColumnDev &col, bool com
   ts.n_sol = compute_solar ? r->sol_n : 0; ts.sol_lo = r->sol_lo;
   ts.n_ir = r->ir_n; ts.ir_lo = r->ir_lo;
   ts.sol_start = r->sol.ind_start; ts.ir_start = r->ir.ind_start;
-  ts.tau = r->d_tau.p; ts.w0 = r->d_w0.p; ts.g = r->d_g.p; ts.tau_band = r->d_tau_band.p;
+  ts.tau = b.opr.tau; ts.w0 = b.opr.w0; ts.g = b.opr.g; ts.tau_band = b.opr.tau_band; ts.scat = b.opr.scat;
   ts.wbin = r->d_wbin.p; ts.freq = r->d_freq.p;
   ts.T = col.T; ts.T_surface = col.T_surface;
   ts.emissivity = r->d_emis.p; ts.has_hard_surface = r->has_hard_surface ? 1 : 0; ts.ir_tau_min = r->ir_tau_min;
@@ -582,25 +682,90 @@ TwoStreamParams make_twostream_params(Radtran *r, const ColumnDev &col, bool com
   ts.albedo = r->d_albedo.p; ts.photons_sol = r->d_photons.p;
   ts.photon_scale_factor = r->photon_scale_factor; ts.diurnal_fac = r->diurnal_fac;
   ts.am_f1 = r->d_am_f1.p; ts.am_f2 = r->d_am_f2.p; ts.am_dw = r->d_am_dw.p;
-  ts.ir_fup_a = r->wrk_ir.fup_a.p; ts.ir_fdn_a = r->wrk_ir.fdn_a.p; ts.ir_tau_band = r->wrk_ir.tau_band.p;
-  ts.sol_fup_a = r->wrk_sol.fup_a.p; ts.sol_fdn_a = r->wrk_sol.fdn_a.p; ts.sol_amean = r->wrk_sol.amean.p;
-  ts.sol_tau_band = r->wrk_sol.tau_band.p;
+  ts.ir_fup_a = b.spec.ir_fup_a; ts.ir_fdn_a = b.spec.ir_fdn_a; ts.ir_tau_band = b.spec.ir_tau_band;
+  ts.sol_fup_a = b.spec.sol_fup_a; ts.sol_fdn_a = b.spec.sol_fdn_a; ts.sol_amean = b.spec.sol_amean;
+  ts.sol_tau_band = b.spec.sol_tau_band;
   return ts;
 }
 
-// A batch of columns worked on by ONE launch of each kernel (radtran_toa_fluxes_batch): per-column
-// blocks in arenas, column c at base + c * stride.  Null for a single call on the handle's own buffers.
-struct BatchCtx {
-  int ncol;
-  double *col, *prep, *opr, *res, *flux;
-  int *done;
-  BatchStrides bs;
-};
+// clears: the two-stream outputs that spare blocks of the prep launch zero (null: none)
+PrepParams make_prep_params(Radtran *r, const CallBufs &b, const ColumnDev &col, int call_id, const TwoStreamParams *clears) {
+  PrepParams pp;
+  std::memset(&pp, 0, sizeof(pp));
+  pp.ncol = b.ncol; pp.bs = b.bs;
+  pp.nz = r->nz; pp.nsp = r->nsp; pp.np = r->np; pp.nslots = r->nslots;
+  pp.has_cont = r->has_cont; pp.LH2O = r->LH2O;
+  for (int s = 0; s < r->nslots; s++) pp.slots[s] = r->slots[s];
+  if (r->cust_on) {  // evaluated without clamping: the end intervals extrapolate (linear_interpolation_module.F90:348-350)
+    SlotDev cs;
+    cs.axis = r->d_cust_axis.p; cs.n = r->cust_nP; cs.source = -1;
+    cs.lo = -std::numeric_limits<double>::infinity(); cs.hi = std::numeric_limits<double>::infinity();
+    cs.flag_clamp = 0;
+    pp.slots[pp.nslots++] = cs;
+  }
+  pp.nabs = (int)r->abs_entries.size();
+  for (int e = 0; e < pp.nabs; e++) { pp.abs_kind[e] = r->abs_entries[e].kind; pp.abs_a[e] = r->abs_entries[e].a; pp.abs_b[e] = r->abs_entries[e].b; }
+  pp.col = col;
+  pp.call_id = call_id;
+  if (clears) pp.nzero = ts_clear_ranges(*clears, pp.zero_ptr, pp.zero_count);
+  return pp;
+}
 
-// spectra block of one column of a batch: [ir fup_a | ir fdn_a | ir tau_band | sol fup_a | sol fdn_a | sol amean | sol tau_band]
-size_t res_block_count(Radtran *r) {
-  const size_t nl = (size_t)r->nz + 1, nz = r->nz;
-  return (size_t)r->ir.nw * (2 * nl + nz) + (size_t)r->sol.nw * (3 * nl + nz);
+OpacityParams make_opacity_params(Radtran *r, const CallBufs &b, const ColumnDev &col, bool write_w0) {
+  OpacityParams op;
+  std::memset(&op, 0, sizeof(op));
+  op.nz = r->nz; op.nw = r->nw; op.ng = r->ng; op.nsp = r->nsp; op.np = r->np;
+  op.bin_lo = r->op_lo; op.nbins = r->op_n; op.nsrc = b.nsrc;
+  op.nk = (int)r->k.size(); op.nray = (int)r->ray.size(); op.npart = (int)r->part.size();
+  for (size_t i = 0; i < r->k.size(); i++)
+    op.k[i] = KDev{r->k[i]->d_log10k.p, r->k[i]->sp, r->k[i]->nP, r->k[i]->nT, (int)(2 * i), (int)(2 * i + 1)};
+  for (size_t i = 0; i < r->ray.size(); i++) op.ray[i] = XsDev{r->ray[i]->d_data.p, 0, r->ray[i]->sp1, -1, 0, -1};
+  op.nabs = (int)r->abs_entries.size();
+  for (int e = 0; e < op.nabs; e++) op.abs[e] = r->abs_entries[e];
+  for (size_t i = 0; i < r->part.size(); i++)
+    op.part[i] = PartDev{r->part[i]->d_w0.p, r->part[i]->d_qext.p, r->part[i]->d_gt.p, r->part[i]->p_ind, r->part[i]->nrad, r->part_slot[i]};
+  op.wbin = r->d_wbin.p; op.wbin_e = r->d_wbin_e.p; op.wxy = r->d_wxy.p; op.wbin_e_pad = r->d_wbin_e_pad.p; op.rorr_tab = r->d_rorr_tab.p;
+  op.col = col;
+  op.cust = CustomDev{r->d_cust_dtau.p, r->d_cust_w0.p, r->d_cust_g0.p, r->cust_nP, r->nslots, r->cust_on ? 1 : 0};
+  op.rebin_mode = r->rebin_mode;
+#ifdef CLIMA_STAMPS
+  op.stamps = r->d_stamps.p;
+#endif
+  op.tau = b.opr.tau; op.w0 = b.opr.w0; op.g = b.opr.g; op.tau_band = b.opr.tau_band; op.scat = b.opr.scat;
+  op.write_w0 = write_w0 ? 1 : 0;
+  return op;
+}
+
+// reduce: the call ends with the handle's all-reduce.  host_out set in the result: the integration stores the level
+// rows and the error words into the host's pinned block as well (a synchronous call on an unsharded handle, which
+// then ends with a stream synchronise -- no copy launch in front of it)
+IntegrateParams make_integrate_params(Radtran *r, const CallBufs &b, bool compute_solar, bool reduce) {
+  IntegrateParams ip;
+  std::memset(&ip, 0, sizeof(ip));
+  ip.ncol = b.ncol; ip.bs = b.bs;
+  ip.nz = r->nz; ip.nw_ir = r->ir.nw; ip.nw_sol = r->sol.nw;
+  ip.ir_lo = r->ir_lo; ip.ir_n = r->ir_n; ip.sol_lo = r->sol_lo; ip.sol_n = r->sol_n;
+  ip.do_solar = compute_solar ? 1 : 0;
+  ip.ir_fup_a = b.spec.ir_fup_a; ip.ir_fdn_a = b.spec.ir_fdn_a;
+  ip.sol_fup_a = b.spec.sol_fup_a; ip.sol_fdn_a = b.spec.sol_fdn_a;
+  ip.ir_freq = r->ir.d_freq.p; ip.sol_freq = r->sol.d_freq.p;
+  ip.flux_n = b.flux_n;
+  ip.flux_part = r->shard_world > 1 ? r->d_flux_part.p : nullptr;
+  ip.f_total = r->shard_world == 1 ? b.f_total : nullptr;
+  ip.nchunk = integrate_chunks(std::max(r->ir_n, r->sol_n));
+  ip.partial = r->d_partial.p;
+  if (b.host_out && r->h_small_dev && b.kind == CALL_RESIDENT && !reduce && r->shard_world == 1 && integrate_one_launch(ip)) {
+    ip.host_out = r->h_small_dev;
+    ip.err_words = r->d_err.p;
+  }
+  if (reduce) {
+    // the status word rides on the all-reduce in the slot behind the four level rows (f_total's first element:
+    // on such a handle f_total is formed on the host from the REDUCED rows, fetch_small)
+    ip.f_total = nullptr;
+    ip.timeout_out = r->d_small.p + 4 * ((size_t)r->nz + 1); ip.timeout_flag = r->d_err.p + 1;
+    ip.id_opr = r->call_id; ip.id_sol = r->solar_id;
+  }
+  return ip;
 }
 
 // Switches fixed for the process at their first use (the handle-less test hooks obey them too); the others are read once
@@ -609,16 +774,16 @@ bool sw_no_half() { static const bool v = [] { const char *e = getenv("CLIMA_HIP
 bool sw_paired() { static const bool v = [] { const char *e = getenv("CLIMA_HIP_PAIRED"); return !(e && e[0] == '0'); }(); return v; }
 bool sw_w0_scat() { static const bool v = [] { const char *e = getenv("CLIMA_HIP_W0_SCAT"); return !(e && e[0] == '0'); }(); return v; }
 
-// what plan_radiate needs to know of a call on this handle; batch_ncol > 0: one launch per kernel for that many columns
-PlanIn plan_input(const Radtran *r, bool compute_solar, bool compute_opacity, bool allow_fused, int batch_ncol) {
+// what plan_radiate needs to know of a call on this handle; a chunk: one launch per kernel for its columns
+PlanIn plan_input(const Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused) {
   PlanIn in{};
   in.nz = r->nz; in.ng = r->ng; in.nzen = (int)r->zenith_u.size();
   in.n_ir = r->ir_n; in.n_sol = compute_solar ? r->sol_n : 0; in.op_n = r->op_n;
-  in.batch = batch_ncol > 0; in.ncol = in.batch ? batch_ncol : 1;
-  in.nsrc = in.batch ? r->nz : (r->col_override ? r->nsrc_override : r->nsrc);
+  in.batch = b.kind == CALL_ARENA_CHUNK; in.ncol = b.ncol;
+  in.nsrc = b.nsrc;
   in.rebin_mode = r->rebin_mode; in.cust_on = r->cust_on; in.compute_opacity = compute_opacity;
   // exact pairs in the column (and this call computes the opacities from it) -> exact pairs in opr
-  in.all_pairs = !in.batch && !r->col_override && compute_opacity && r->all_pairs_exact;
+  in.all_pairs = compute_opacity && b.all_pairs_exact;
   in.fused = r->fused; in.allow_fused = allow_fused; in.generic_opacity = r->generic_opacity;
   in.ts_block_mode = r->ts_block_mode; in.ts_ncols_env = r->ts_ncols_env; in.coop_items = r->coop_items;
   in.no_half = sw_no_half(); in.allow_paired = sw_paired(); in.w0_from_scat = sw_w0_scat();
@@ -635,88 +800,36 @@ void ensure_w0(Radtran *r) {
   r->w0_valid = true;
 }
 
-void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool allow_fused = true,
-                     const BatchCtx *bc = nullptr) {
+// plan -> prep -> opacity (or the fused grid) -> two-stream -> integrate -> reduce, on the buffers `b` names
+void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused = true) {
   r->timer_calls++;
   upload_fields(r);
-  const int nz = r->nz;
-  const size_t nl = (size_t)nz + 1;
-  ColumnDev col = bc ? column_dev_at(r, bc->col, bc->prep) : column_dev(r);
-  BatchStrides bs;
-  std::memset(&bs, 0, sizeof(bs));
-  if (bc) bs = bc->bs;
-  // where this call's optical properties and spectra live
-  double *o_tau = r->d_tau.p, *o_w0 = r->d_w0.p, *o_g = r->d_g.p, *o_tb = r->d_tau_band.p, *o_sc = r->d_scat.p;
-  double *ir_fup = r->wrk_ir.fup_a.p, *ir_fdn = r->wrk_ir.fdn_a.p, *ir_tb = r->wrk_ir.tau_band.p;
-  double *sol_fup = r->wrk_sol.fup_a.p, *sol_fdn = r->wrk_sol.fdn_a.p, *sol_am = r->wrk_sol.amean.p, *sol_tb = r->wrk_sol.tau_band.p;
-  if (bc) {
-    o_tau = bc->opr; o_w0 = o_tau + r->d_tau.n; o_g = o_w0 + r->d_w0.n; o_tb = o_g + r->d_g.n; o_sc = o_tb + r->d_tau_band.n;
-    ir_fup = bc->res; ir_fdn = ir_fup + r->ir.nw * nl; ir_tb = ir_fdn + r->ir.nw * nl;
-    sol_fup = ir_tb + (size_t)r->ir.nw * nz; sol_fdn = sol_fup + r->sol.nw * nl; sol_am = sol_fdn + r->sol.nw * nl;
-    sol_tb = sol_am + r->sol.nw * nl;
-  }
-  TwoStreamParams ts = make_twostream_params(r, col, compute_solar);
-  ts.tau = o_tau; ts.w0 = o_w0; ts.g = o_g; ts.tau_band = o_tb; ts.scat = o_sc; ts.w0_from_scat = 0;
-  ts.ir_fup_a = ir_fup; ts.ir_fdn_a = ir_fdn; ts.ir_tau_band = ir_tb;
-  ts.sol_fup_a = sol_fup; ts.sol_fdn_a = sol_fdn; ts.sol_amean = sol_am; ts.sol_tau_band = sol_tb;
-  const PlanIn in = plan_input(r, compute_solar, compute_opacity, allow_fused, bc ? bc->ncol : 0);
-  const LaunchPlan plan = plan_radiate(in);
+  const bool resident = b.kind == CALL_RESIDENT, chunk = b.kind == CALL_ARENA_CHUNK;
+  const ColumnDev col = column_dev(r, b);
+  TwoStreamParams ts = make_twostream_params(r, b, col, compute_solar);
+  const LaunchPlan plan = plan_radiate(plan_input(r, b, compute_solar, compute_opacity, allow_fused));
   bool fused_done = false;
   if (compute_opacity) {
-    PrepParams pp;
-    std::memset(&pp, 0, sizeof(pp));
-    pp.ncol = in.ncol; pp.bs = bs;
-    pp.nz = nz; pp.nsp = r->nsp; pp.np = r->np; pp.nslots = r->nslots;
-    pp.has_cont = r->has_cont; pp.LH2O = r->LH2O;
-    for (int s = 0; s < r->nslots; s++) pp.slots[s] = r->slots[s];
-    if (r->cust_on) {  // evaluated without clamping: the end intervals extrapolate (linear_interpolation_module.F90:348-350)
-      SlotDev cs;
-      cs.axis = r->d_cust_axis.p; cs.n = r->cust_nP; cs.source = -1;
-      cs.lo = -std::numeric_limits<double>::infinity(); cs.hi = std::numeric_limits<double>::infinity();
-      cs.flag_clamp = 0;
-      pp.slots[pp.nslots++] = cs;
-    }
-    pp.nabs = (int)r->abs_entries.size();
-    for (int e = 0; e < pp.nabs; e++) { pp.abs_kind[e] = r->abs_entries[e].kind; pp.abs_a[e] = r->abs_entries[e].a; pp.abs_b[e] = r->abs_entries[e].b; }
-    pp.col = col;
-    pp.call_id = ++r->call_id;
-    if (plan.prep_clears) pp.nzero = ts_clear_ranges(ts, pp.zero_ptr, pp.zero_count);
+    const int call_id = ++r->call_id;
+    const PrepParams pp = make_prep_params(r, b, col, call_id, plan.prep_clears ? &ts : nullptr);
     { KernelTimer t(r, 0); launch_prep(pp, r->stream); HIPCHK(hipGetLastError()); t.stop(); }
 
-    OpacityParams op;
-    std::memset(&op, 0, sizeof(op));
-    op.nz = nz; op.nw = r->nw; op.ng = r->ng; op.nsp = r->nsp; op.np = r->np;
-    op.bin_lo = r->op_lo; op.nbins = r->op_n; op.nsrc = in.nsrc;
-    op.nk = (int)r->k.size(); op.nray = (int)r->ray.size(); op.npart = (int)r->part.size();
-    for (size_t i = 0; i < r->k.size(); i++)
-      op.k[i] = KDev{r->k[i]->d_log10k.p, r->k[i]->sp, r->k[i]->nP, r->k[i]->nT, (int)(2 * i), (int)(2 * i + 1)};
-    for (size_t i = 0; i < r->ray.size(); i++) op.ray[i] = XsDev{r->ray[i]->d_data.p, 0, r->ray[i]->sp1, -1, 0, -1};
-    op.nabs = (int)r->abs_entries.size();
-    for (int e = 0; e < op.nabs; e++) op.abs[e] = r->abs_entries[e];
-    for (size_t i = 0; i < r->part.size(); i++)
-      op.part[i] = PartDev{r->part[i]->d_w0.p, r->part[i]->d_qext.p, r->part[i]->d_gt.p, r->part[i]->p_ind, r->part[i]->nrad, r->part_slot[i]};
-    op.wbin = r->d_wbin.p; op.wbin_e = r->d_wbin_e.p; op.wxy = r->d_wxy.p; op.wbin_e_pad = r->d_wbin_e_pad.p; op.rorr_tab = r->d_rorr_tab.p;
-    op.col = col;
-    op.cust = CustomDev{r->d_cust_dtau.p, r->d_cust_w0.p, r->d_cust_g0.p, r->cust_nP, r->nslots, r->cust_on ? 1 : 0};
-    op.rebin_mode = r->rebin_mode;
-#ifdef CLIMA_STAMPS
-    op.stamps = r->d_stamps.p;
-#endif
-    op.tau = o_tau; op.w0 = o_w0; op.g = o_g; op.tau_band = o_tb; op.scat = o_sc; op.write_w0 = plan.write_w0 ? 1 : 0;
+    OpacityParams op = make_opacity_params(r, b, col, plan.write_w0);
     if (plan.fused.form != TS_NONE) {
       FusedParams fp;
       std::memset(&fp, 0, sizeof(fp));
-      fp.ncol = in.ncol; fp.bs = bs;
-      fp.call_id = pp.call_id; fp.max_spins = r->fused_max_spins;
-      fp.done = bc ? bc->done : r->d_done.p; fp.timeout_flag = r->d_err.p + 1;
+      fp.ncol = b.ncol; fp.bs = b.bs;
+      fp.call_id = call_id; fp.max_spins = r->fused_max_spins;
+      fp.done = b.done; fp.timeout_flag = r->d_err.p + 1;
       KernelTimer t(r, 1);
       fused_done = launch_fused(op, ts, fp, plan.fused, r->stream);
       HIPCHK(hipGetLastError());
       t.stop();
-      if (!fused_done) op.write_w0 = 1;   // (the runtime refused the grid its LDS: the separate launches, w0 stored; ensure_w0()
-                                          //  materialises an unwritten w0 when something else asks for it)
+      // (the runtime refused the grid its LDS: the separate launches, w0 stored; ensure_w0() materialises an
+      //  unwritten w0 when something else asks for it)
+      if (!fused_done) op = make_opacity_params(r, b, col, true);
     }
-    if (bc && !fused_done) throw HipFail{"internal: a one-launch batch needs the fused grid"};
+    if (chunk && !fused_done) throw HipFail{"internal: a one-launch batch needs the fused grid"};
     if (!fused_done) {
       KernelTimer t(r, 1);
       const bool ok = launch_opacity(op, plan, r->stream);
@@ -726,9 +839,9 @@ void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool 
       t.stop();
     }
     r->opr_valid = true;
-    if (!bc) r->w0_valid = op.write_w0 != 0;
-    if (!bc && !r->col_override) r->opr_upload_id = r->upload_id;
-  } else if (!bc) {
+    if (!chunk) r->w0_valid = op.write_w0 != 0;             // the handle's own optical-property block was written
+    if (resident) r->opr_upload_id = r->upload_id;          // ... from the resident column
+  } else if (!chunk) {
     ensure_w0(r);   // this call's two-stream kernels read the stored optical properties
   }
   r->last_cs = compute_solar;
@@ -741,45 +854,18 @@ void enqueue_radiate(Radtran *r, bool compute_solar, bool compute_opacity, bool 
     if (!ok) { HIPCHK(hipGetLastError()); ok = launch_twostream(ts, plan.block, r->stream); }
     HIPCHK(hipGetLastError());
     if (!ok)
-      throw HipFail{"nz*ngauss = " + std::to_string(nz * r->ng) + " exceeds what the two-stream kernels can stage"};
+      throw HipFail{"nz*ngauss = " + std::to_string(r->nz * r->ng) + " exceeds what the two-stream kernels can stage"};
     t.stop();
   }
 
-  IntegrateParams ip;
-  std::memset(&ip, 0, sizeof(ip));
-  ip.ncol = in.ncol; ip.bs = bs;
-  ip.nz = nz; ip.nw_ir = r->ir.nw; ip.nw_sol = r->sol.nw;
-  ip.ir_lo = r->ir_lo; ip.ir_n = r->ir_n; ip.sol_lo = r->sol_lo; ip.sol_n = r->sol_n;
-  ip.do_solar = compute_solar ? 1 : 0;
-  ip.ir_fup_a = ir_fup; ip.ir_fdn_a = ir_fdn;
-  ip.sol_fup_a = sol_fup; ip.sol_fdn_a = sol_fdn;
-  ip.ir_freq = r->ir.d_freq.p; ip.sol_freq = r->sol.d_freq.p;
-  ip.flux_n = bc ? bc->flux : (r->flux_override ? r->flux_override : r->d_flux_n.p);
-  ip.flux_part = r->shard_world > 1 ? r->d_flux_part.p : nullptr;
-  ip.f_total = r->shard_world == 1 ? (r->ftot_override ? r->ftot_override : r->d_f_total.p) : nullptr;
-  ip.nchunk = integrate_chunks(std::max(r->ir_n, r->sol_n));
-  ip.partial = r->d_partial.p;
-  const bool reduce = r->comm && !bc && !r->col_override;
-  // a synchronous call on an unsharded handle: the integration kernel stores the level rows and the error words into
-  // the host's pinned block as well, and the call ends with a stream synchronise -- no copy launch in front of it
-  r->small_in_host = false;
-  if (r->want_host_out && r->h_small_dev && !bc && !r->col_override && !reduce && r->shard_world == 1 && integrate_one_launch(ip)) {
-    ip.host_out = r->h_small_dev;
-    ip.err_words = r->d_err.p;
-    r->small_in_host = true;
-  }
-  if (reduce) {
-    // the status word rides on the all-reduce in the slot behind the four level rows (f_total's first element:
-    // on such a handle f_total is formed on the host from the REDUCED rows, fetch_small)
-    ip.f_total = nullptr;
-    ip.timeout_out = r->d_small.p + 4 * nl; ip.timeout_flag = r->d_err.p + 1;
-    ip.id_opr = r->call_id; ip.id_sol = r->solar_id;
-  }
+  const bool reduce = r->comm && resident;
+  const IntegrateParams ip = make_integrate_params(r, b, compute_solar, reduce);
+  r->small_in_host = ip.host_out != nullptr;
   { KernelTimer t(r, 3); launch_integrate(ip, r->stream); HIPCHK(hipGetLastError()); t.stop(); }
   if (reduce) {
     // the step's single collective (src/radtran/clima_radtran_radiate.f90:184-192 summed over the bins of all
     // ranks): in place, on the handle's stream, no host round trip
-    NCCLCHK(ncclAllReduce(r->d_small.p, r->d_small.p, 4 * nl + 1, ncclDouble, ncclSum, r->comm, r->stream));
+    NCCLCHK(ncclAllReduce(r->d_small.p, r->d_small.p, 4 * ((size_t)r->nz + 1) + 1, ncclDouble, ncclSum, r->comm, r->stream));
     r->comm_reduces++;
   }
   r->small_valid = false;
@@ -796,12 +882,10 @@ void fetch_small(Radtran *r) {
     HIPCHK(hipStreamSynchronize(r->stream));
     resolve_events(r);
     if (r->comm) r->comm_status = r->h_small[4 * nl];
-    if (r->col_override || !r->column_loaded || !recover_fused_timeout(r)) break;  // re-issued unfused: fetch again
+    if (!r->column_loaded || !recover_fused_timeout(r)) break;  // re-issued unfused: fetch again
   }
-  // f_total from the four level rows (clima_radtran.f90:287); the one-launch integration leaves it
-  // to the host, the other forms computed the same expression on the device
-  double *h = r->h_small;
-  for (int i = 0; i < nl; i++) h[4 * nl + i] = (h[3 * nl + i] - h[2 * nl + i]) + (h[1 * nl + i] - h[0 * nl + i]);
+  // the one-launch integration leaves f_total to the host, the other forms computed the same expression on the device
+  f_total_row(r->h_small, nl);
   r->small_valid = true;
 }
 
@@ -827,25 +911,13 @@ void do_upload(Radtran *r, double T_surface, const double *T, const double *P, c
   double *h = r->h_col;
   // the pinned staging buffer is reused: wait (lazily, here) for the previous upload's copy
   if (r->upload_pending) { HIPCHK(hipEventSynchronize(r->ev_upload)); r->upload_pending = false; }
-  h[0] = T_surface;
-  std::memcpy(h + 1, T, sizeof(double) * nz);
-  std::memcpy(h + 1 + nz, P, sizeof(double) * nz);
-  std::memcpy(h + 1 + 2 * nz, dz, sizeof(double) * nz);
-  std::memcpy(h + 1 + 3 * nz, dens, sizeof(double) * (size_t)nz * r->nsp);
-  double *hp = h + 1 + 3 * nz + (size_t)nz * r->nsp;
-  if (r->np > 0 && pdens && radii) {
-    std::memcpy(hp, pdens, sizeof(double) * (size_t)nz * r->np);
-    std::memcpy(hp + (size_t)nz * r->np, radii, sizeof(double) * (size_t)nz * r->np);
-  }
+  r->nsrc = pack_column(r, h, T_surface, T, P, dz, dens, pdens, radii);
   r->column_has_particles = (pdens && radii);
   r->upload_id++;
-  {
-    int *meta = reinterpret_cast<int *>(h + r->meta_ofs);
-    r->nsrc = build_meta(r, T, P, dz, dens, pdens, radii, r->column_has_particles, meta);
-    bool all = (nz % 2 == 0) && r->nsrc * 2 == nz;
-    for (int m = 0; m < r->nsrc && all; m++) all = (meta[1 + m] & SRC_EXACT) != 0;
-    r->all_pairs_exact = all;
-  }
+  const int *meta = reinterpret_cast<const int *>(h + r->meta_ofs);
+  bool all = (nz % 2 == 0) && r->nsrc * 2 == nz;
+  for (int m = 0; m < r->nsrc && all; m++) all = (meta[1 + m] & SRC_EXACT) != 0;
+  r->all_pairs_exact = all;
   {
     // ~18 KB: a kernel that reads the pinned buffer over PCIe gets the column into HBM 4 us sooner
     // than the copy engine does (CLIMA_HIP_COPY_KERNEL=0 selects hipMemcpyAsync)
@@ -880,7 +952,7 @@ bool recover_fused_timeout(Radtran *r) {
     r->checked_timeout = r->call_id;
     if (std::fmod(st, 1024.0) > 0.0 && r->upload_id != r->opr_upload_id) throw HipFail{REPLACED_MSG};
     r->fused_fallbacks++;
-    enqueue_radiate(r, st >= 1024.0 || r->last_cs, true, false);
+    enqueue_radiate(r, resident_bufs(r), st >= 1024.0 || r->last_cs, true, false);
     return true;
   }
   const int t = r->h_errflag[1];
@@ -896,7 +968,7 @@ bool recover_fused_timeout(Radtran *r) {
   // compute_opacity = .false. pass): computing them again from column B is not what the caller asked for
   if (stale_opr && r->upload_id != r->opr_upload_id) throw HipFail{REPLACED_MSG};
   r->fused_fallbacks++;
-  enqueue_radiate(r, stale_sol || r->last_cs, true, false);
+  enqueue_radiate(r, resident_bufs(r), stale_sol || r->last_cs, true, false);
   return true;
 }
 
@@ -921,7 +993,7 @@ void settle(Radtran *r) {
       HIPCHK(hipMemcpyAsync(&r->comm_status, r->d_small.p + 4 * (r->nz + 1), sizeof(double), hipMemcpyDeviceToHost, r->stream));
     HIPCHK(hipStreamSynchronize(r->stream));
     resolve_events(r);
-    if (r->col_override || !r->column_loaded || !recover_fused_timeout(r)) break;
+    if (!r->column_loaded || !recover_fused_timeout(r)) break;
   }
 }
 
@@ -1282,7 +1354,7 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
   if (r->ir.nw == 0 || r->sol.nw == 0) { set_err(err, "wavelength channels are not set"); return; }
   if (*num_zenith_angles < 1) { set_err(err, "number of zenith angles must be >= 1"); return; }
   TRY
-  const int nz = r->nz, nw = r->nw, ng = r->ng;
+  const int nz = r->nz, nw = r->nw;
   // zenith_angles_and_weights (clima_eqns.f90:26-41) then cos(deg*pi/180) (clima_radtran.f90:165)
   std::vector<double> x, w;
   gauss_legendre(*num_zenith_angles, x, w);
@@ -1406,11 +1478,11 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
 #ifdef CLIMA_STAMPS
   r->d_stamps.alloc(64 + 2 * 8192); r->d_stamps.zero();
 #endif
-  r->opr_count = (size_t)2 * nw * ng * nz + (size_t)3 * nw * nz;
+  r->opr_count = opr_views(r, nullptr).count;
   r->d_opr.alloc(r->opr_count); r->d_opr.zero();
-  r->d_tau.view(r->d_opr.p, (size_t)nw * ng * nz); r->d_w0.view(r->d_tau.p + r->d_tau.n, (size_t)nw * ng * nz);
-  r->d_g.view(r->d_w0.p + r->d_w0.n, (size_t)nw * nz); r->d_tau_band.view(r->d_g.p + r->d_g.n, (size_t)nw * nz);
-  r->d_scat.view(r->d_tau_band.p + r->d_tau_band.n, (size_t)nw * nz);
+  const OprViews o = opr_views(r, r->d_opr.p);
+  r->d_tau.view(o.tau, o.w0 - o.tau); r->d_w0.view(o.w0, o.g - o.w0); r->d_g.view(o.g, o.tau_band - o.g);
+  r->d_tau_band.view(o.tau_band, o.scat - o.tau_band); r->d_scat.view(o.scat, o.tau + o.count - o.scat);
   auto mk = [&](WrkObj &wk, int which, int nwc) {  // clima_radtran.f90:199-214
     wk.parent = r; wk.which = which;
     wk.fup_a.alloc((size_t)(nz + 1) * nwc); wk.fdn_a.alloc((size_t)(nz + 1) * nwc);
@@ -1459,7 +1531,7 @@ void radtran_radiate_resident(void *ptr, const int *compute_solar, const int *co
   if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
   if (!r->column_loaded) { set_err(err, "no column has been uploaded"); return; }
   TRY
-  enqueue_radiate(r, *compute_solar != 0, *compute_opacity != 0);
+  enqueue_radiate(r, resident_bufs(r), *compute_solar != 0, *compute_opacity != 0);
   CATCH(err)
 }
 
@@ -1479,11 +1551,11 @@ static void ir_batch_general(Radtran *r, const double *d_T, const double *d_Ts, 
   const size_t spec = (size_t)nw_ir * nl;
   auto ensure = [](DevBuf<double> &b, size_t count) { if (b.n < count) b.alloc(count); };  // grow-only
   ensure(r->d_bup, spec * CH); ensure(r->d_bdn, spec * CH); ensure(r->d_bpartial, (size_t)CH * 2 * nchunk * nl);
-  ColumnDev col = column_dev(r);
-  TwoStreamParams ts = make_twostream_params(r, col, false);
+  const CallBufs b = resident_bufs(r);
+  TwoStreamParams ts = make_twostream_params(r, b, column_dev(r, b), false);
   ts.ir_fup_a = r->d_bup.p; ts.ir_fdn_a = r->d_bdn.p;
   ts.b_T = nz; ts.b_Ts = 1; ts.b_out = spec;
-  PlanIn in = plan_input(r, false, false, false, 0);
+  PlanIn in = plan_input(r, b, false, false, false);
   in.ir_batch = true;
   const LaunchPlan plan = plan_radiate(in);
   for (int c0 = 0; c0 < n; c0 += CH) {
@@ -1943,24 +2015,13 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return; }
   TRY
   const int nz = r->nz, nl = nz + 1, n = *ncol;
-  const size_t cc = r->col_count;
+  const size_t cc = r->col_count, np_n = (size_t)nz * r->np;
   std::vector<double> h((size_t)n * cc, 0.0);
   std::vector<int> nsrc_h(n);
-  for (int c = 0; c < n; c++) {  // the device layout of one column (do_upload)
-    double *d = h.data() + (size_t)c * cc;
-    d[0] = T_surface[c];
-    std::memcpy(d + 1, T + (size_t)c * nz, sizeof(double) * nz);
-    std::memcpy(d + 1 + nz, P + (size_t)c * nz, sizeof(double) * nz);
-    std::memcpy(d + 1 + 2 * nz, dz + (size_t)c * nz, sizeof(double) * nz);
-    std::memcpy(d + 1 + 3 * nz, densities + (size_t)c * nz * r->nsp, sizeof(double) * (size_t)nz * r->nsp);
-    double *dp = d + 1 + 3 * nz + (size_t)nz * r->nsp;
-    if (r->np > 0) {
-      std::memcpy(dp, pdensities + (size_t)c * nz * r->np, sizeof(double) * (size_t)nz * r->np);
-      std::memcpy(dp + (size_t)nz * r->np, radii + (size_t)c * nz * r->np, sizeof(double) * (size_t)nz * r->np);
-    }
-    nsrc_h[c] = build_meta(r, d + 1, d + 1 + nz, d + 1 + 2 * nz, d + 1 + 3 * nz, r->np > 0 ? dp : nullptr,
-                           r->np > 0 ? dp + (size_t)nz * r->np : nullptr, r->np > 0, reinterpret_cast<int *>(d + r->meta_ofs));
-  }
+  for (int c = 0; c < n; c++)
+    nsrc_h[c] = pack_column(r, h.data() + (size_t)c * cc, T_surface[c], T + (size_t)c * nz, P + (size_t)c * nz, dz + (size_t)c * nz,
+                            densities + (size_t)c * nz * r->nsp, r->np > 0 ? pdensities + c * np_n : nullptr,
+                            r->np > 0 ? radii + c * np_n : nullptr);
   if (r->d_cols_arena.n < h.size()) r->d_cols_arena.alloc(h.size());
   if (r->d_flux_arena.n < (size_t)n * 5 * nl) r->d_flux_arena.alloc((size_t)n * 5 * nl);
   HIPCHK(hipMemcpyAsync(r->d_cols_arena.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, r->stream));
@@ -1971,44 +2032,21 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   // turn, so one column's two-stream tail runs beside the next column's opacity tiles) where the fused
   // form covers the configuration; otherwise the calls of the columns are enqueued back to back.
   const int CH = std::min(n, r->batch_cols_in_flight);
-  bool one_launch = plan_radiate(plan_input(r, true, true, true, CH)).fused.form != TS_NONE &&
+  const CallBufs first = arena_chunk_bufs(r, 0, CH);   // (the arenas it points into are sized below: only its counts are read)
+  bool one_launch = plan_radiate(plan_input(r, first, true, true, true)).fused.form != TS_NONE &&
                     integrate_chunks(std::max(r->ir_n, r->sol_n)) * (32 + 16) * sizeof(double) <= 64 * 1024;
   if (const char *e = getenv("CLIMA_HIP_BATCH_ONE_LAUNCH")) one_launch = one_launch && atoi(e) != 0;
-  const size_t tiles = ((size_t)r->op_n * nz + 255) / 256;
   if (one_launch) {
-    const size_t pc = r->prep_count, oc = r->opr_count, rc = res_block_count(r);
-    if (r->d_prep_arena.n < pc * CH) r->d_prep_arena.alloc(pc * CH);
-    if (r->d_opr_arena.n < oc * CH) r->d_opr_arena.alloc(oc * CH);
-    if (r->d_res_arena.n < rc * CH) { r->d_res_arena.alloc(rc * CH); r->d_res_arena.zero(r->stream); }
-    if (r->d_done.n < tiles * CH + 1) { r->d_done.alloc(tiles * CH + 1); r->d_done.zero(r->stream); }
+    if (r->d_prep_arena.n < first.bs.prep * CH) r->d_prep_arena.alloc(first.bs.prep * CH);
+    if (r->d_opr_arena.n < first.bs.opr * CH) r->d_opr_arena.alloc(first.bs.opr * CH);
+    if (r->d_res_arena.n < first.bs.res * CH) { r->d_res_arena.alloc(first.bs.res * CH); r->d_res_arena.zero(r->stream); }
+    if (r->d_done.n < (size_t)first.bs.done * CH + 1) { r->d_done.alloc((size_t)first.bs.done * CH + 1); r->d_done.zero(r->stream); }
   }
   auto run_all = [&](bool allow_fused) {
-    if (one_launch && allow_fused) {
-      for (int c0 = 0; c0 < n; c0 += CH) {
-        BatchCtx bc;
-        bc.ncol = std::min(CH, n - c0);
-        bc.col = r->d_cols_arena.p + (size_t)c0 * cc;
-        bc.prep = r->d_prep_arena.p; bc.opr = r->d_opr_arena.p; bc.res = r->d_res_arena.p;
-        bc.flux = r->d_flux_arena.p + (size_t)c0 * 5 * nl;
-        bc.done = r->d_done.p;
-        bc.bs = BatchStrides{cc, r->prep_count, r->opr_count, res_block_count(r), (size_t)5 * nl, (int)tiles};
-        enqueue_radiate(r, true, true, true, &bc);
-      }
-    } else {
-      for (int c = 0; c < n; c++) {
-        r->col_override = r->d_cols_arena.p + (size_t)c * cc;
-        r->nsrc_override = nsrc_h[c];
-        r->flux_override = r->d_flux_arena.p + (size_t)c * 5 * nl;
-        r->ftot_override = r->flux_override + 4 * nl;
-        try {
-          enqueue_radiate(r, true, true, allow_fused);
-        } catch (...) {
-          r->col_override = r->flux_override = r->ftot_override = nullptr;
-          throw;
-        }
-      }
-      r->col_override = r->flux_override = r->ftot_override = nullptr;
-    }
+    if (one_launch && allow_fused)
+      for (int c0 = 0; c0 < n; c0 += CH) enqueue_radiate(r, arena_chunk_bufs(r, c0, std::min(CH, n - c0)), true, true);
+    else
+      for (int c = 0; c < n; c++) enqueue_radiate(r, arena_column_bufs(r, c, nsrc_h[c]), true, true, allow_fused);
     HIPCHK(hipMemcpyAsync(out.data(), r->d_flux_arena.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, r->stream));
     HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
     // the handle's own level fluxes = the last column's
@@ -2024,7 +2062,7 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
     fell_back = true;
   }
   r->checked_timeout = r->call_id;
-  r->small_valid = false; r->small_in_host = false;   // (the device rows changed: fetch them)
+  invalidate_small(r);   // (the device rows changed: fetch them)
   r->column_loaded = false;   // d_col does not hold the last column: a resident call needs an upload first
   // What the handle holds afterwards is the LAST column's, like after n single calls: its level rows (copied above),
   // and its spectra / band optical depths -- the one-launch form left those in the batch arena (copied here);
@@ -2033,15 +2071,11 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   const bool in_arena = one_launch && !fell_back;
   r->opr_valid = !in_arena;
   if (in_arena) {
-    const double *res = r->d_res_arena.p + (size_t)((n - 1) % CH) * res_block_count(r);
-    const size_t nli = (size_t)r->ir.nw * nl, nls = (size_t)r->sol.nw * nl, nzi = (size_t)r->ir.nw * nz, nzs = (size_t)r->sol.nw * nz;
-    auto d2d = [&](DevBuf<double> &dst, const double *src, size_t cnt) {
-      HIPCHK(hipMemcpyAsync(dst.p, src, sizeof(double) * cnt, hipMemcpyDeviceToDevice, r->stream));
-    };
-    d2d(r->wrk_ir.fup_a, res, nli); d2d(r->wrk_ir.fdn_a, res + nli, nli); d2d(r->wrk_ir.tau_band, res + 2 * nli, nzi);
-    const double *rs = res + 2 * nli + nzi;
-    d2d(r->wrk_sol.fup_a, rs, nls); d2d(r->wrk_sol.fdn_a, rs + nls, nls); d2d(r->wrk_sol.amean, rs + 2 * nls, nls);
-    d2d(r->wrk_sol.tau_band, rs + 3 * nls, nzs);
+    const SpectraViews src = spectra_views(r, r->d_res_arena.p + (size_t)((n - 1) % CH) * first.bs.res);
+    auto d2d = [&](DevBuf<double> &dst, const double *from) { HIPCHK(hipMemcpyAsync(dst.p, from, sizeof(double) * dst.n, hipMemcpyDeviceToDevice, r->stream)); };
+    d2d(r->wrk_ir.fup_a, src.ir_fup_a); d2d(r->wrk_ir.fdn_a, src.ir_fdn_a); d2d(r->wrk_ir.tau_band, src.ir_tau_band);
+    d2d(r->wrk_sol.fup_a, src.sol_fup_a); d2d(r->wrk_sol.fdn_a, src.sol_fdn_a); d2d(r->wrk_sol.amean, src.sol_amean);
+    d2d(r->wrk_sol.tau_band, src.sol_tau_band);
     HIPCHK(hipStreamSynchronize(r->stream));
   }
   if (*r->h_errflag >= first_call) {
@@ -2052,9 +2086,8 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   r->checked_id = r->call_id;
   for (int c = 0; c < n; c++) {
     double *f = out.data() + (size_t)c * 5 * nl;
-    for (int i = 0; i < nl; i++) f[4 * nl + i] = (f[3 * nl + i] - f[2 * nl + i]) + (f[1 * nl + i] - f[0 * nl + i]);  // :287
-    ISR[c] = f[3 * nl + nz] - f[2 * nl + nz];        // clima_radtran.f90:339-340
-    OLR[c] = -(f[1 * nl + nz] - f[0 * nl + nz]);
+    f_total_row(f, nl);
+    toa_fluxes(f, nz, &ISR[c], &OLR[c]);
     if (fluxes) std::memcpy(fluxes + (size_t)c * 5 * nl, f, sizeof(double) * 5 * nl);
   }
   CATCH(err)
@@ -2099,14 +2132,7 @@ void radtran_radiate_wrapper(void *ptr, const double *T_surface, const int *dim_
 #ifdef CLIMA_TRACE_SYNC
   const double t1 = now();
 #endif
-  r->want_host_out = true;
-  try {
-    enqueue_radiate(r, *compute_solar != 0, *compute_opacity != 0);
-  } catch (...) {
-    r->want_host_out = false;
-    throw;
-  }
-  r->want_host_out = false;
+  enqueue_radiate(r, resident_bufs(r, /*host_out=*/true), *compute_solar != 0, *compute_opacity != 0);
 #ifdef CLIMA_TRACE_SYNC
   const double t2 = now();
 #endif
@@ -2133,12 +2159,7 @@ void radtran_toa_fluxes_wrapper(void *ptr, const double *T_surface, const int *d
                           has_particles, dim1_p, dim2_p, pdensities, dim1_r, dim2_r, radii, compute_solar,
                           compute_opacity, err);
   if (err && err[0]) return;
-  Radtran *r = as_rad(ptr);
-  if (!r) return;
-  const int nl = r->nz + 1, nz = r->nz;
-  // clima_radtran.f90:339-340
-  *ISR = (r->h_small[3 * nl + nz] - r->h_small[2 * nl + nz]);
-  *OLR = -(r->h_small[1 * nl + nz] - r->h_small[0 * nl + nz]);
+  if (Radtran *r = as_rad(ptr)) toa_fluxes(r->h_small, r->nz, ISR, OLR);
 }
 
 // Bench hook: `n` synchronous radtran_toa_fluxes_wrapper calls (host arrays in, ISR / OLR out, one stream
@@ -2197,7 +2218,7 @@ void clima_bench_resident_graph(void *ptr, const int *n, const int *k, double *u
   hipGraphExec_t exec = nullptr;
   HIPCHK(hipStreamBeginCapture(r->stream, hipStreamCaptureModeThreadLocal));
   try {
-    enqueue_radiate(r, true, true);
+    enqueue_radiate(r, resident_bufs(r), true, true);
   } catch (...) {
     // a failure inside the captured section must not leave the handle's stream in capture mode (every later call
     // on it would fail): close the capture, drop what was captured, pass the error on
@@ -2225,7 +2246,7 @@ void clima_bench_resident_graph(void *ptr, const int *n, const int *k, double *u
   }
   (void)hipGraphExecDestroy(exec);
   (void)hipGraphDestroy(graph);
-  r->small_valid = false; r->small_in_host = false; r->opr_valid = false;
+  invalidate_small(r); r->opr_valid = false;
   radtran_radiate_resident(ptr, &one, &one, err);     // leave the handle with a valid call
   if (err && err[0]) return;
   HIPCHK(hipStreamSynchronize(r->stream));
@@ -2246,7 +2267,7 @@ void radtran_apply_radiation_enhancement(void *ptr, const double *rad_enhancemen
     // (with a communicator the slot behind the rows carries the step's status word, and f_total is formed on the host
     // from the rows in any case: fetch_small)
     if (!r->comm) launch_f_total(r->nz, r->d_flux_n.p, r->d_f_total.p, r->stream);
-    r->small_valid = false; r->small_in_host = false;   // (the device rows changed: fetch them)
+    invalidate_small(r);   // (the device rows changed: fetch them)
     fetch_small(r);
     for (int i = 0; i < nl; i++) r->f_total[i] = r->h_small[4 * nl + i];
   } catch (...) {
@@ -2428,7 +2449,7 @@ void radtran_finish_reduced(void *ptr, char *err) {
   // f_total = (sol_dn - sol_up) + (ir_dn - ir_up) of the reduced rows is formed on the host when the
   // results are fetched (fetch_small), like after every call: nothing to launch here, the level
   // rows just have to be read again
-  r->small_valid = false; r->small_in_host = false;   // (the device rows changed: fetch them)
+  invalidate_small(r);   // (the device rows changed: fetch them)
 }
 
 void radtran_stream_get(void *ptr, void **stream) {
