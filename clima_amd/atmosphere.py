@@ -7,6 +7,7 @@ tests/test_radtran.f90 or AdiabatClimate can drive the HIP path from the same in
   vertical_grid             src/clima_eqns.f90:172-184
   column_from_atmosphere    tests/test_radtran.f90:27-67 (densities, dummy particles)
   copy_atm_to_radiative_grid src/adiabat/clima_adiabat.f90:728-771
+  rce_jacobian_map          src/adiabat/clima_adiabat_solve.f90:731-733, 798-809, 824-890 (the solver's unknowns)
 
 Error texts follow the reference (they are API there).  The interpolation used by
 `unpack_atmospherefile` is futils' `interp(ng, n, xg, x, y, yg, ierr)` (v0.1.14, third-party,
@@ -131,3 +132,27 @@ def copy_atm_to_radiative_grid(col, double_radiative_grid=True):
         out["pdensities"] = np.asfortranarray(dbl(col["pdensities"]))
         out["radii"] = np.asfortranarray(dbl(col["radii"]))
     return out
+
+
+def rce_jacobian_map(nz, convecting_with_below=None, double_radiative_grid=True):
+    """The map from the x of `Radtran.ir_jacobian` on AdiabatClimate's radiative grid to the unknowns of its RCE solver,
+    for `Radtran.ir_jacobian_reduced`: (group_of_x, row_level, inds_Tx), all 1-based.
+
+    Over T_in (index 1 the surface, 1 + i layer i of the nz physical layers) T_in(1) opens unknown 1, and T_in(i + 1)
+    joins the unknown of T_in(i) when `convecting_with_below[i - 1]` (it convects with what is below it:
+    AdiabatClimate_set_convecting_zones, clima_adiabat_solve.f90:824-890), else opens the next one; `inds_Tx` lists the
+    opening indices.  A zone so moves with its lower unknown, as the Jacobian's loop moves it (:798-809).  On the doubled
+    grid (clima_adiabat.f90:729-773) radiative x(1) is T_in(1), x(1 + 2i - 1) and x(1 + 2i) are T_in(1 + i), and the
+    two ghost layers x(2 nz + 2), x(2 nz + 3) are T_in(1 + nz); the rows are the levels 2i - 1, i = 1..nz + 1
+    (:731-733).  On the plain grid the map is the groups themselves and the rows are all levels."""
+    conv = np.zeros(nz, dtype=bool) if convecting_with_below is None else np.asarray(convecting_with_below, dtype=bool)
+    if conv.shape != (nz,):
+        raise ClimaException('Input "convecting_with_below" has the wrong dimension')
+    opens = np.concatenate([[True], ~conv])
+    group_of_T_in = np.cumsum(opens).astype(np.int32)
+    inds_Tx = (np.flatnonzero(opens) + 1).astype(np.int32)
+    if not double_radiative_grid:
+        return group_of_T_in, np.arange(1, nz + 2, dtype=np.int32), inds_Tx
+    layers = np.repeat(group_of_T_in[1:], 2)
+    group_of_x = np.concatenate([group_of_T_in[:1], layers, layers[-1:], layers[-1:]]).astype(np.int32)
+    return group_of_x, np.arange(1, 2 * nz + 2, 2, dtype=np.int32), inds_Tx

@@ -906,6 +906,42 @@ __global__ __launch_bounds__(256) void k_green_jacobian(GreenParams p) {
   }
 }
 
+// 8''. the exact Jacobian in the caller's unknowns (radtran_ir_jacobian_reduced): group g's column is the sum of its
+//     members' columns of 8', rows picked.  col_ptr / col_dev: the CSR of a group's deviations, members in ascending
+//     column j (descending k); row_lv: the requested rows as levels, TOA-first.  Each member's entry is formed exactly as
+//     k_green_jacobian forms it (green_split_sum from zero, splits in order) and then added onto the group's running
+//     value, member after member: bitwise the caller's own loop over the full matrices, which are never written -- nor
+//     is any level read that was not asked for.  blockIdx.y = group (at most nz + 1 of them), blockIdx.x = 64 rows;
+//     threadIdx.y = four members whose split sums are in flight together (a zone of 400 levels is otherwise 400
+//     dependent chains of loads, one after the other: with one member row a 201-member group at 402 layers took the
+//     call from 0.89 to 1.27 ms, and the 1-4 member groups of a map without zones gained nothing from it, 0.644
+//     against 0.635), thread row y = 0 adds them in member order.  out: (nrow, ngroup)
+//     column-major -- up, down, total out_arr apart when `parts`, else the total alone.
+constexpr int GREEN_RM = 4;
+__global__ __launch_bounds__(64 * GREEN_RM) void k_green_jacobian_reduced(GreenParams p, const int *__restrict__ row_lv, int nrow, int parts) {
+  const int g = blockIdx.y, a = blockIdx.x * 64 + threadIdx.x, y = threadIdx.y;
+  const int m_lo = p.col_ptr[g], m_hi = p.col_ptr[g + 1];
+  const int lv = a < nrow ? row_lv[a] : 0;
+  __shared__ double su[GREEN_RM][64], sd[GREEN_RM][64];
+  double gu = 0.0, gd = 0.0;
+  for (int m0 = m_lo; m0 < m_hi; m0 += GREEN_RM) {      // (block-uniform bounds: every thread meets every barrier)
+    double up = 0.0, dn = 0.0;
+    if (m0 + y < m_hi && a < nrow) green_split_sum(p, p.col_dev[m0 + y], lv, up, dn);
+    su[y][threadIdx.x] = up; sd[y][threadIdx.x] = dn;
+    __syncthreads();
+    if (y == 0) {
+      const int n = min(GREEN_RM, m_hi - m0);
+      for (int t = 0; t < n; t++) { gu = gu + su[t][threadIdx.x]; gd = gd + sd[t][threadIdx.x]; }
+    }
+    __syncthreads();
+  }
+  if (y == 0 && a < nrow) {
+    double *o = p.out + (size_t)g * nrow + a;
+    if (parts) { o[0] = gu; o[p.out_arr] = gd; o[2 * p.out_arr] = gd - gu; }
+    else o[0] = gd - gu;
+  }
+}
+
 // total = dn - up of a communicator handle's reduced Jacobian (radtran_ir_jacobian; a rank without IR bins runs this
 // and no k_green_* kernel).  jac: three arrays of n doubles (up, down, total), arr elements apart.
 __global__ __launch_bounds__(256) void k_jacobian_total(double *jac, size_t arr, size_t n) {
@@ -985,4 +1021,10 @@ void launch_green_jacobian(const GreenParams &p, hipStream_t s) {
   hipLaunchKernelGGL(k_green_dbdt, dim3((p.ndev_pad + 255) / 256, p.n_ir), dim3(256), 0, s, p);
   launch_green_accumulate(p, s);
   hipLaunchKernelGGL(k_green_jacobian, dim3(p.ndev), dim3(256), 0, s, p);
+}
+// the same in the caller's unknowns: ngroup columns of nrow rows (k_green_jacobian_reduced)
+void launch_green_jacobian_reduced(const GreenParams &p, const int *row_lv, int nrow, int ngroup, bool parts, hipStream_t s) {
+  hipLaunchKernelGGL(k_green_dbdt, dim3((p.ndev_pad + 255) / 256, p.n_ir), dim3(256), 0, s, p);
+  launch_green_accumulate(p, s);
+  hipLaunchKernelGGL(k_green_jacobian_reduced, dim3((nrow + 63) / 64, ngroup), dim3(64, GREEN_RM), 0, s, p, row_lv, nrow, parts ? 1 : 0);
 }

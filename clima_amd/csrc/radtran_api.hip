@@ -1786,23 +1786,26 @@ static void ir_batch_green(Radtran *r, const GreenPlan &pl, const double *T, con
   r->ir_green_batches++;
 }
 
-// Three result arrays of `arr` doubles each, back to back in d_bout, into the caller's outs[0..2] through the handle's
-// pinned block in pieces, the host copying piece i out while piece i + 1 is still on the link (one copy and then one
-// memcpy of the whole took 95 + 140 us of a 0.93 ms batch call at 403 columns x 403 levels).  Returns when all are there.
-static void bout_to_host(Radtran *r, double *const outs[3], size_t arr) {
-  if (r->h_bout_n < 3 * arr) {
+// `narr` result arrays of `arr` doubles each, back to back in d_bout from its first-th array on, into the caller's
+// outs[0..narr-1] through the handle's pinned block in pieces, the host copying piece i out while piece i + 1 is still on
+// the link (one copy and then one memcpy of the whole took 95 + 140 us of a 0.93 ms batch call at 403 columns x 403
+// levels).  Returns when all are there.  (The batch and the full Jacobian: three arrays from the start;
+// radtran_ir_jacobian_reduced's total alone: one.)
+static void bout_to_host(Radtran *r, double *const *outs, size_t arr, int narr = 3, int first = 0) {
+  if (r->h_bout_n < narr * arr) {
     if (r->h_bout) (void)hipHostFree(r->h_bout);
     r->h_bout = nullptr; r->h_bout_n = 0;
-    HIPCHK(hipHostMalloc((void **)&r->h_bout, sizeof(double) * 3 * arr, hipHostMallocDefault));
-    r->h_bout_n = 3 * arr;
+    HIPCHK(hipHostMalloc((void **)&r->h_bout, sizeof(double) * narr * arr, hipHostMallocDefault));
+    r->h_bout_n = narr * arr;
   }
   constexpr int NPIECE = 6;
-  const size_t total = 3 * arr, piece = (total + NPIECE - 1) / NPIECE;
+  const size_t total = narr * arr, piece = (total + NPIECE - 1) / NPIECE;
+  const double *d_src = r->d_bout.p + (size_t)first * arr;
   for (auto &e : r->bout_ev)
     if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (int k = 0; k < NPIECE; k++) {
     const size_t lo = std::min(total, (size_t)k * piece), hi = std::min(total, lo + piece);
-    if (hi > lo) HIPCHK(hipMemcpyAsync(r->h_bout + lo, r->d_bout.p + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
+    if (hi > lo) HIPCHK(hipMemcpyAsync(r->h_bout + lo, d_src + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
     HIPCHK(hipEventRecord(r->bout_ev[k], r->stream));
   }
   for (int k = 0; k < NPIECE; k++) {
@@ -1921,6 +1924,52 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
   CATCH(err)
 }
 
+// What its two entry points (radtran_ir_jacobian, radtran_ir_jacobian_reduced) refuse alike, after their own extents.
+static bool ir_jacobian_refused(const Radtran *r, const double *T_surface, const double *T, char *err) {
+  const int nz = r->nz, nl = nz + 1;
+  for (int j = 0; j <= nz; j++) {
+    const double v = j < nz ? T[j] : *T_surface;
+    if (!(std::isfinite(v) && v > 0.0)) { set_err(err, "ir_jacobian: temperatures must be finite and positive"); return true; }
+  }
+  if (r->shard_world != 1 && !r->comm) { set_err(err, "ir_jacobian is not available on a bin-sharded handle"); return true; }
+  // the response form's range (that of radtran_radiate_ir_batch's): no other solver stands behind it
+  if (nz < 4 || nz > 512) { set_err(err, "ir_jacobian: the response form takes 4 <= nz <= 512 (nz = " + std::to_string(nz) + ")"); return true; }
+  if ((long)r->ir_n * r->ng > 65535) {     // (k_green_unit / k_green_local: one (bin, g-point) pair per blockIdx.y)
+    set_err(err, "ir_jacobian: the response form takes at most 65535 (bin, g-point) pairs (" + std::to_string((long)r->ir_n * r->ng) + ")");
+    return true;
+  }
+  if (green_work_bytes(r, nl) > 16.0e9) { set_err(err, "ir_jacobian: the response form's work arrays would take more than 16 GB"); return true; }
+  if (!r->opr_valid) { set_err(err, "ir_jacobian needs opacities: call radiate with compute_opacity first"); return true; }
+  return false;
+}
+// The opacity-only part and the accumulation's arrays for the Jacobian's deviations: every level k, sorted
+// (dev_k[d] = d).  `extra`: further ints of the caller's, staged behind the lists; returns their place on the device.
+static const int *ir_jacobian_green_part(Radtran *r, const double *T_surface, const double *T, const std::vector<int> &extra, GreenParams &g) {
+  const int nz = r->nz, nl = nz + 1;
+  // the mixed pairs as the batch builds them
+  const int ndev = nl, ndev_pad = (ndev + 15) / 16 * 16;
+  std::vector<int> dev_k(ndev), mdev, mblk;
+  for (int k = 0; k < ndev; k++) dev_k[k] = k;
+  green_mixed_list(dev_k, nz, mdev, mblk);
+  const int nmix = (int)mdev.size();
+  // through the handle's pinned block: doubles base_T by level k [nl], then ints dev_k [ndev_pad] | mix_dev | mix_blk | extra
+  const size_t ni = (size_t)ndev_pad + 2 * (size_t)nmix + extra.size();
+  double *hd = reinterpret_cast<double *>(green_stage(r, sizeof(double) * nl + sizeof(int) * ni));
+  int *hi = reinterpret_cast<int *>(hd + nl);
+  for (int k = 0; k < nz; k++) hd[k] = T[nz - 1 - k];     // (radiate.f90:65-69: level k is layer nz-1-k)
+  hd[nz] = *T_surface;
+  for (int d = 0; d < ndev_pad; d++) hi[d] = d < ndev ? d : 0;
+  std::copy(extra.begin(), extra.end(), std::copy(mblk.begin(), mblk.end(), std::copy(mdev.begin(), mdev.end(), hi + ndev_pad)));
+  if (r->d_green_in.n < (size_t)nl) r->d_green_in.alloc(nl);
+  if (r->d_green_idx.n < ni) r->d_green_idx.alloc(ni);
+  HIPCHK(hipMemcpyAsync(r->d_green_in.p, hd, sizeof(double) * nl, hipMemcpyHostToDevice, r->stream));
+  HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * ni, hipMemcpyHostToDevice, r->stream));
+  green_factor_part(r, g);
+  green_accum_arrays(r, g, ndev, ndev_pad, nmix);
+  g.dev_k = r->d_green_idx.p; g.mix_dev = g.dev_k + ndev_pad; g.mix_blk = g.mix_dev + nmix;
+  g.base_T = r->d_green_in.p;
+  return g.mix_blk + nmix;
+}
 // The exact IR temperature Jacobian of the level fluxes: the limit of the batch's response form as the step goes to 0.
 // Every level k = 0..nz is one deviation with the Planck derivative at its base temperature as amplitude, so the
 // matrices come from the opacity-only part and one accumulation alone -- no base-profile solve, no plan, no step.
@@ -1933,19 +1982,7 @@ void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, c
   const int nz = r->nz, nl = nz + 1;
   if (*dim_T != nz) { set_err(err, "\"T\" has the wrong input dimension."); return; }
   if (*dim1 != nl || *dim2 != nl) { set_err(err, "jac has the wrong dimension"); return; }
-  for (int j = 0; j <= nz; j++) {
-    const double v = j < nz ? T[j] : *T_surface;
-    if (!(std::isfinite(v) && v > 0.0)) { set_err(err, "ir_jacobian: temperatures must be finite and positive"); return; }
-  }
-  if (r->shard_world != 1 && !r->comm) { set_err(err, "ir_jacobian is not available on a bin-sharded handle"); return; }
-  // the response form's range (that of radtran_radiate_ir_batch's): no other solver stands behind it
-  if (nz < 4 || nz > 512) { set_err(err, "ir_jacobian: the response form takes 4 <= nz <= 512 (nz = " + std::to_string(nz) + ")"); return; }
-  if ((long)r->ir_n * r->ng > 65535) {     // (k_green_unit / k_green_local: one (bin, g-point) pair per blockIdx.y)
-    set_err(err, "ir_jacobian: the response form takes at most 65535 (bin, g-point) pairs (" + std::to_string((long)r->ir_n * r->ng) + ")");
-    return;
-  }
-  if (green_work_bytes(r, nl) > 16.0e9) { set_err(err, "ir_jacobian: the response form's work arrays would take more than 16 GB"); return; }
-  if (!r->opr_valid) { set_err(err, "ir_jacobian needs opacities: call radiate with compute_opacity first"); return; }
+  if (ir_jacobian_refused(r, T_surface, T, err)) return;
   TRY
   settle(r);
   upload_fields(r);
@@ -1953,29 +1990,8 @@ void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, c
   const size_t arr = (size_t)nl * nl;
   if (r->d_bout.n < 3 * arr) r->d_bout.alloc(3 * arr);
   if (r->ir_n > 0) {
-    // deviations: every level k, sorted (dev_k[d] = d); the mixed pairs as the batch builds them
-    const int ndev = nl, ndev_pad = (ndev + 15) / 16 * 16;
-    std::vector<int> dev_k(ndev), mdev, mblk;
-    for (int k = 0; k < ndev; k++) dev_k[k] = k;
-    green_mixed_list(dev_k, nz, mdev, mblk);
-    const int nmix = (int)mdev.size();
-    // through the handle's pinned block: doubles base_T by level k [nl], then ints dev_k [ndev_pad] | mix_dev | mix_blk
-    const size_t ni = (size_t)ndev_pad + 2 * (size_t)nmix;
-    double *hd = reinterpret_cast<double *>(green_stage(r, sizeof(double) * nl + sizeof(int) * ni));
-    int *hi = reinterpret_cast<int *>(hd + nl);
-    for (int k = 0; k < nz; k++) hd[k] = T[nz - 1 - k];     // (radiate.f90:65-69: level k is layer nz-1-k)
-    hd[nz] = *T_surface;
-    for (int d = 0; d < ndev_pad; d++) hi[d] = d < ndev ? d : 0;
-    std::copy(mblk.begin(), mblk.end(), std::copy(mdev.begin(), mdev.end(), hi + ndev_pad));
-    if (r->d_green_in.n < (size_t)nl) r->d_green_in.alloc(nl);
-    if (r->d_green_idx.n < ni) r->d_green_idx.alloc(ni);
-    HIPCHK(hipMemcpyAsync(r->d_green_in.p, hd, sizeof(double) * nl, hipMemcpyHostToDevice, r->stream));
-    HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * ni, hipMemcpyHostToDevice, r->stream));
     GreenParams g;
-    green_factor_part(r, g);
-    green_accum_arrays(r, g, ndev, ndev_pad, nmix);
-    g.dev_k = r->d_green_idx.p; g.mix_dev = g.dev_k + ndev_pad; g.mix_blk = g.mix_dev + nmix;
-    g.base_T = r->d_green_in.p;
+    ir_jacobian_green_part(r, T_surface, T, {}, g);
     g.out = r->d_bout.p; g.out_arr = arr;
     launch_green_jacobian(g, r->stream);
     HIPCHK(hipGetLastError());
@@ -1992,6 +2008,98 @@ void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, c
   }
   double *const outs[3] = {jac_up, jac_dn, jac_total};
   bout_to_host(r, outs, arr);
+  CATCH(err)
+}
+
+// The same derivative in the caller's unknowns (the RCE Jacobian's: a pair of the doubled radiative grid, a convective
+// zone and the ghost layers move with ONE unknown, and only some levels are read -- clima_adiabat_solve.f90:731-733,
+// 798-809): jac(a, g) = sum over the x(j) of group g, ascending j, of J(row_level(a), j).  The full matrices are never
+// formed: k_green_jacobian_reduced adds the members' entries as it forms them, and (nrow, ngroup) doubles per requested
+// matrix come back instead of 3 (nz+1)^2.  jac_up and jac_dn may both be NULL: the total alone.
+void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *dim_T, const double *T,
+                                 const int *dim_x, const int *group_of_x, const int *ngroup,
+                                 const int *nrow, const int *row_level,
+                                 const int *dim1, const int *dim2,
+                                 double *jac_up, double *jac_dn, double *jac_total, char *err) {
+  clear_err(err);
+  GUARD(r, ptr, err);
+  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  const int nz = r->nz, nl = nz + 1, ng = *ngroup, nr = *nrow;
+  const std::string pre = "ir_jacobian_reduced: ";
+  if (*dim_T != nz) { set_err(err, "\"T\" has the wrong input dimension."); return; }
+  if (*dim_x != nl) {
+    set_err(err, pre + "\"group_of_x\" has the wrong dimension (dim_x = " + std::to_string(*dim_x) + ", nz + 1 = " + std::to_string(nl) + ")");
+    return;
+  }
+  if (nr < 1) { set_err(err, pre + "nrow must be at least 1 (nrow = " + std::to_string(nr) + ")"); return; }
+  if (ng < 1) { set_err(err, pre + "ngroup must be at least 1 (ngroup = " + std::to_string(ng) + ")"); return; }
+  if (*dim1 != nr || *dim2 != ng) { set_err(err, "jac has the wrong dimension"); return; }
+  if (!jac_total) { set_err(err, pre + "jac_total is required (only jac_up and jac_dn may be absent)"); return; }
+  if ((jac_up == nullptr) != (jac_dn == nullptr)) {
+    set_err(err, pre + "jac_up and jac_dn go together: only " + (jac_up ? "jac_up" : "jac_dn") + " was given");
+    return;
+  }
+  // the map as a CSR of the groups' members (deviation = level k = nz - (j - 1), members in ascending j), then the rows
+  // as levels TOA-first
+  std::vector<int> csr((size_t)ng + 1, 0);
+  for (int j = 0; j < nl; j++) {
+    const int v = group_of_x[j];
+    if (v < 0 || v > ng) {
+      set_err(err, pre + "group_of_x(" + std::to_string(j + 1) + ") = " + std::to_string(v) + " is outside 0.." + std::to_string(ng));
+      return;
+    }
+    if (v > 0) csr[v]++;
+  }
+  for (int v = 1; v <= ng; v++) {
+    // (an empty column is an off-by-one in the caller's map, not a request)
+    if (csr[v] == 0) { set_err(err, pre + "group " + std::to_string(v) + " of " + std::to_string(ng) + " has no member in group_of_x"); return; }
+    csr[v] += csr[v - 1];
+  }
+  const int nmem = csr[ng];
+  std::vector<int> fill(csr.begin(), csr.end() - 1);
+  csr.resize((size_t)ng + 1 + nmem + nr);
+  int *mem = csr.data() + ng + 1, *rows = mem + nmem;
+  for (int j = 0; j < nl; j++)
+    if (group_of_x[j] > 0) mem[fill[group_of_x[j] - 1]++] = nz - j;
+  for (int a = 0; a < nr; a++) {
+    const int v = row_level[a];
+    if (v < 1 || v > nl) {
+      set_err(err, pre + "row_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
+      return;
+    }
+    rows[a] = nz - (v - 1);
+  }
+  if (ir_jacobian_refused(r, T_surface, T, err)) return;
+  TRY
+  settle(r);
+  upload_fields(r);
+  ensure_w0(r);
+  const size_t arr = (size_t)nr * ng;
+  // a communicator handle forms up and down whatever was asked for: they are what is summed over the ranks
+  const bool want_parts = jac_up != nullptr, parts = want_parts || r->comm;
+  const size_t need = (parts ? 3 : 1) * arr;
+  if (r->d_bout.n < need) r->d_bout.alloc(need);
+  if (r->ir_n > 0) {
+    GreenParams g;
+    const int *d_map = ir_jacobian_green_part(r, T_surface, T, csr, g);
+    g.col_ptr = d_map; g.col_dev = d_map + ng + 1;
+    g.out = r->d_bout.p; g.out_arr = arr;
+    launch_green_jacobian_reduced(g, d_map + ng + 1 + nmem, nr, ng, parts, r->stream);
+    HIPCHK(hipGetLastError());
+  } else {
+    // a shard without IR bins: no k_green_* kernel (their grids would be empty), zeros into the all-reduce
+    HIPCHK(hipMemsetAsync(r->d_bout.p, 0, sizeof(double) * need, r->stream));
+  }
+  if (r->comm) {
+    // one all-reduce of the reduced up / down matrices (2 nrow ngroup doubles), the total from the reduced ones
+    NCCLCHK(ncclAllReduce(r->d_bout.p, r->d_bout.p, 2 * arr, ncclDouble, ncclSum, r->comm, r->stream));
+    r->comm_reduces++;
+    launch_jacobian_total(r->d_bout.p, arr, arr, r->stream);
+    HIPCHK(hipGetLastError());
+  }
+  double *const outs[3] = {jac_up, jac_dn, jac_total};
+  if (want_parts) bout_to_host(r, outs, arr);
+  else bout_to_host(r, &jac_total, arr, 1, parts ? 2 : 0);
   CATCH(err)
 }
 

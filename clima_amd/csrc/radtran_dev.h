@@ -318,6 +318,7 @@ void launch_green_columns(const GreenParams &p, int ncol, hipStream_t s);
 void launch_batch_ftotal(double *out, size_t out_arr, int ncol, int nz, const double *flux_n, hipStream_t s);
 void launch_green_accumulate(const GreenParams &p, hipStream_t s);   // the accumulation alone (test hook: DB given)
 void launch_green_jacobian(const GreenParams &p, hipStream_t s);     // Planck derivatives, accumulation, the three matrices
+void launch_green_jacobian_reduced(const GreenParams &p, const int *row_lv, int nrow, int ngroup, bool parts, hipStream_t s);   // ... summed over groups of columns, rows picked
 void launch_jacobian_total(double *jac, size_t arr, size_t n, hipStream_t s);
 int green_far_resident_waves();
 void green_vector_form_set(int vector_form);   // test hook: the far accumulation's vector form (1) or matrix form (0)

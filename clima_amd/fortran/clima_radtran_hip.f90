@@ -82,6 +82,7 @@ module clima_radtran_hip
     procedure :: apply_radiation_enhancement => Radtran_apply_radiation_enhancement
     procedure :: radiate_ir_batch => Radtran_radiate_ir_batch
     procedure :: ir_jacobian => Radtran_ir_jacobian
+    procedure :: ir_jacobian_reduced => Radtran_ir_jacobian_reduced
     procedure :: TOA_fluxes_batch => Radtran_TOA_fluxes_batch
     procedure :: opacities2yaml => Radtran_opacities2yaml
     procedure :: set_names => Radtran_set_names
@@ -191,6 +192,16 @@ module clima_radtran_hip
       integer(c_int), intent(in) :: dim_T, dim1, dim2
       real(c_double), intent(in) :: T_surface, T(*)
       real(c_double), intent(out) :: jac_up(*), jac_dn(*), jac_total(*)
+      character(c_char), intent(out) :: err(*)
+    end subroutine
+    subroutine c_radtran_ir_jacobian_reduced(ptr, T_surface, dim_T, T, dim_x, group_of_x, ngroup, nrow, row_level, &
+                                             dim1, dim2, jac_up, jac_dn, jac_total, err) &
+                                             bind(c, name="radtran_ir_jacobian_reduced")
+      import; type(c_ptr), value :: ptr
+      integer(c_int), intent(in) :: dim_T, dim_x, ngroup, nrow, dim1, dim2, group_of_x(*), row_level(*)
+      real(c_double), intent(in) :: T_surface, T(*)
+      type(c_ptr), value :: jac_up, jac_dn     ! (c_null_ptr: not wanted)
+      real(c_double), intent(out) :: jac_total(*)
       character(c_char), intent(out) :: err(*)
     end subroutine
     subroutine c_radtran_opacities2yaml_wrapper_1(ptr, out_len, out_cp) bind(c, name="radtran_opacities2yaml_wrapper_1")
@@ -830,6 +841,45 @@ contains
     endif
     call c_radtran_ir_jacobian(self%handle, T_surface, size(T), T, size(jac_up,1), size(jac_up,2), &
                                jac_up, jac_dn, jac_total, err_c)
+    call take_err(err_c, err)
+  end subroutine
+
+  !> `ir_jacobian` in the unknowns of the RCE solver (AdiabatClimate_jacobian_from_base,
+  !> src/adiabat/clima_adiabat_solve.f90:768-822): group_of_x(j) (nz+1 entries, one per x of `ir_jacobian`) is 0 for an
+  !> x held fixed or the unknown 1..ngroup it moves with (ngroup = the largest entry); row_level the levels wanted,
+  !> 1..nz+1 ground-first.  jac_total(a,g) = sum over the members j of group g, ascending, of the full
+  !> jac_total(row_level(a), j); jac_up and jac_dn likewise when both are present.  (size(row_level), ngroup) each.
+  subroutine Radtran_ir_jacobian_reduced(self, T_surface, T, group_of_x, row_level, jac_total, err, jac_up, jac_dn)
+    class(Radtran), intent(inout) :: self
+    real(dp), intent(in) :: T_surface
+    real(dp), intent(in), contiguous :: T(:)                                !! (nz)
+    integer, intent(in), contiguous :: group_of_x(:), row_level(:)          !! (nz+1), (nrow)
+    real(dp), intent(out), contiguous :: jac_total(:,:)                     !! (nrow, ngroup)
+    character(:), allocatable, intent(out) :: err
+    real(dp), intent(out), contiguous, optional, target :: jac_up(:,:), jac_dn(:,:)
+    character(c_char) :: err_c(err_len+1)
+    type(c_ptr) :: p_up, p_dn
+    integer(c_int) :: ngroup
+    p_up = c_null_ptr; p_dn = c_null_ptr
+    if (present(jac_up)) then
+      if (any(shape(jac_up) /= shape(jac_total))) then
+        err = 'jac has the wrong dimension'
+        return
+      endif
+      p_up = c_loc(jac_up)
+    endif
+    if (present(jac_dn)) then
+      if (any(shape(jac_dn) /= shape(jac_total))) then
+        err = 'jac has the wrong dimension'
+        return
+      endif
+      p_dn = c_loc(jac_dn)
+    endif
+    ngroup = 0
+    if (size(group_of_x) > 0) ngroup = maxval(group_of_x)
+    call c_radtran_ir_jacobian_reduced(self%handle, T_surface, size(T), T, size(group_of_x), group_of_x, ngroup, &
+                                       size(row_level), row_level, size(jac_total,1), size(jac_total,2), &
+                                       p_up, p_dn, jac_total, err_c)
     call take_err(err_c, err)
   end subroutine
 

@@ -60,6 +60,7 @@ SIGNATURES = {
     "radtran_toa_fluxes_batch": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _err],
     "radtran_radiate_ir_batch": [_vp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _err],
     "radtran_ir_jacobian": [_vp, _dp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _err],
+    "radtran_ir_jacobian_reduced": [_vp, _dp, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _err],
     "radtran_upload_column": [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _err],
     "radtran_radiate_resident": [_vp, _ip, _ip, _err],
     "radtran_synchronize": [_vp, _err],

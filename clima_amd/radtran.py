@@ -368,6 +368,33 @@ class Radtran:
         self._check()
         return tuple(out)
 
+    def ir_jacobian_reduced(self, T_surface, T, group_of_x, rows=None, parts=False):
+        """`ir_jacobian` in the caller's unknowns (radtran_ir_jacobian_reduced): `group_of_x[j]` (nz+1 entries, one per
+        x of `ir_jacobian`) is 0 for an x held fixed or the unknown 1..ngroup it moves with (ngroup = the largest
+        entry); `rows` are the levels wanted, 1..nz+1 ground-first (None: every level).  Returns jac_total
+        (nrow, ngroup), Fortran-ordered: [a, g-1] = sum over the members j of group g, ascending, of
+        jac_total[rows[a]-1, j]; with `parts` (jac_up, jac_dn, jac_total).  `atmosphere.rce_jacobian_map` builds the map
+        of AdiabatClimate's solver (doubled radiative grid, ghost layers, convective zones)."""
+        T, Ts = _c(np.atleast_1d(T)), _c(np.atleast_1d(T_surface))
+        if T.ndim != 1 or Ts.shape != (1,):
+            raise ClimaException('"T" has the wrong input dimension.')
+        grp = np.ascontiguousarray(np.atleast_1d(group_of_x), dtype=np.int32)
+        rows = np.arange(1, self.nz + 2) if rows is None else rows
+        rows = np.ascontiguousarray(np.atleast_1d(rows), dtype=np.int32)
+        if grp.ndim != 1:
+            raise ClimaException('ir_jacobian_reduced: "group_of_x" has the wrong dimension (%d axes, one expected)' % grp.ndim)
+        if rows.ndim != 1:
+            raise ClimaException('ir_jacobian_reduced: "rows" has the wrong dimension (%d axes, one expected)' % rows.ndim)
+        ngroup, nrow = int(grp.max()) if grp.size else 0, len(rows)
+        out = [np.empty((nrow, max(ngroup, 0)), order="F") if (parts or i == 2) else None for i in range(3)]
+        ip = C.POINTER(C.c_int)
+        self._L.radtran_ir_jacobian_reduced(self._ptr, _d(Ts), _i(len(T)), _d(T), _i(len(grp)), grp.ctypes.data_as(ip),
+                                            _i(ngroup), _i(nrow), rows.ctypes.data_as(ip), _i(nrow), _i(ngroup),
+                                            _d(out[0]) if parts else None, _d(out[1]) if parts else None, _d(out[2]),
+                                            self._err)
+        self._check()
+        return tuple(out) if parts else out[2]
+
     # ---- HBM-resident form (bench / batched callers)
     def upload_column(self, T_surface, T, P, densities, dz, pdensities=None, radii=None):
         T, P, dz, densities = _c(T), _c(P), _c(dz), _fo(densities)

@@ -209,6 +209,31 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
  * (2 (nz+1)^2 doubles) precedes jac_total, and every rank receives the whole result. */
 void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, const double *T,
                          const int *dim1, const int *dim2, double *jac_up, double *jac_dn, double *jac_total, char *err);
+/* radtran_ir_jacobian in the unknowns of the RCE solver (AdiabatClimate_jacobian_from_base,
+ * src/adiabat/clima_adiabat_solve.f90:768-822), in one call.  That caller moves several x at once with one unknown --
+ * the two copies of a layer on the doubled radiative grid and the two ghost layers above the top one
+ * (src/adiabat/clima_adiabat.f90:729-773), a whole convective zone with its lower unknown -- reads f_total at some
+ * levels only (every other one on the doubled grid, clima_adiabat_solve.f90:731-733) and needs the net flux alone.
+ *   group_of_x (dim_x = nz+1): one entry per x of radtran_ir_jacobian (x(1) = T_surface, x(1+m) = T(m));
+ *                              0 = held fixed, g in 1..ngroup = moves with unknown g
+ *   row_level (nrow):          levels 1..nz+1, ground-first, in any order, repeats allowed
+ *   jac_up, jac_dn, jac_total: (nrow, ngroup) column-major, dim1 = nrow, dim2 = ngroup; jac_up and jac_dn may both be
+ *                              NULL (the total alone is written and copied), jac_total is required
+ *   jac_up(a, g) = sum over the j with group_of_x(j) = g, in ascending j, of J_up(row_level(a), j), J_up the matrix
+ *   radtran_ir_jacobian returns for the same handle state; jac_dn likewise; jac_total = jac_dn - jac_up.
+ * The sums are formed on the device in exactly that order, entry by entry as radtran_ir_jacobian forms them, so the
+ * result is bit for bit the caller's own loop over the full matrices -- which are never written, copied or reduced:
+ * (nrow, ngroup) doubles per requested matrix come back instead of 3 (nz+1)^2.  The handle's wrk_ir, wrk_sol, f_total
+ * and spectra are left untouched.  Refused (err): everything radtran_ir_jacobian refuses, with its texts; and, each
+ * naming the index and the value, a group_of_x of the wrong dimension, an entry outside 0..ngroup, a group without a
+ * member, a row outside 1..nz+1, nrow or ngroup below 1, only one of jac_up and jac_dn; wrong dim1 or dim2:
+ * "jac has the wrong dimension".  On a handle with a communicator every rank passes the same map; one all-reduce of the
+ * reduced up and down matrices (2 nrow ngroup doubles) precedes jac_total. */
+void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *dim_T, const double *T,
+                                 const int *dim_x, const int *group_of_x, const int *ngroup,
+                                 const int *nrow, const int *row_level,
+                                 const int *dim1, const int *dim2,
+                                 double *jac_up, double *jac_dn, double *jac_total, char *err);
 /* clima/fortran/Radtran.f90:41-75 (same names and argument lists): the YAML text of
  * OpticalProperties_opacities2yaml (src/radtran/clima_radtran_types.f90:328-430).  _1 allocates
  * the string and returns its length, _2 copies it into out_c (out_len + 1 chars) and frees it.

@@ -5,12 +5,15 @@ src/adiabat/clima_adiabat.f90:729-773) through radtran_radiate_ir_batch, config 
 Usage: gpu_ir_batch.py [nz ...] (AdiabatClimate nz).  CLIMA_HIP_BATCH_SHARED=0 times the per-column form;
 CLIMA_BATCH_PIN=0 leaves the result arrays pageable (radtran_batch_pin_results_set).
 gpu_ir_batch.py jacobian [nz ...]: the exact Jacobian (radtran_ir_jacobian) against the equivalent batch of nz_r + 1
-one-level columns, on one handle, the two calls alternating, both on the default (unpinned) result path: medians."""
+one-level columns, on one handle, the two calls alternating, both on the default (unpinned) result path: medians.
+gpu_ir_batch.py reduced [nz ...]: radtran_ir_jacobian_reduced on atmosphere.rce_jacobian_map (no zone; one long zone from
+the ground), total only and with parts, alternating with what a caller does today: ir_jacobian and the reduction of its
+three matrices in numpy.  Medians, minima and the spread (max - min) of each."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 from clima_amd import synthetic as S
-from clima_amd.atmosphere import copy_atm_to_radiative_grid
+from clima_amd.atmosphere import copy_atm_to_radiative_grid, rce_jacobian_map
 from clima_amd.radtran import Radtran
 PIN = os.environ.get("CLIMA_BATCH_PIN", "1") != "0"    # the caller's result arrays page-locked (the default here: a caller that keeps them); 0: through the pinned block
 tb = S.modern_earth_tables()
@@ -48,6 +51,48 @@ def jacobian_leg(nzs, warm=5, reps=25):
         del r
 
 
+def reduced_leg(nzs, warm=5, reps=25):
+    def stats(t):
+        t = np.asarray(t) * 1e3
+        return "median %.3f ms (min %.3f, spread %.3f)" % (np.median(t), t.min(), t.max() - t.min())
+
+    for nz in nzs:
+        col = S.Column(copy_atm_to_radiative_grid(S.modern_earth_column(nz)))
+        nzr = len(col["T"])
+        r = Radtran(tb, nzr, 4, 0.15)
+        r.radiate(*col.args())
+        x = np.concatenate([[float(col["T_surface"])], np.asarray(col["T"], float)])
+        for label, conv in (("no zone", None), ("one zone of %d layers from the ground" % (nz // 2), np.arange(nz) < nz // 2)):
+            group, rows, inds = rce_jacobian_map(nz, conv)
+            C = np.zeros((nzr + 1, len(inds)))
+            C[np.arange(nzr + 1), group - 1] = 1.0
+            pick = rows - 1
+            t_full, t_host, t_tot, t_parts = [], [], [], []
+            for rep in range(warm + reps):
+                t0 = time.perf_counter()
+                jac = r.ir_jacobian(x[0], x[1:])
+                t1 = time.perf_counter()
+                host = jac[2][pick] @ C                       # the caller's reduction of the net matrix
+                t2 = time.perf_counter()
+                tot = r.ir_jacobian_reduced(x[0], x[1:], group, rows)
+                t3 = time.perf_counter()
+                parts = r.ir_jacobian_reduced(x[0], x[1:], group, rows, parts=True)
+                t4 = time.perf_counter()
+                if rep >= warm:
+                    t_full.append(t1 - t0); t_host.append(t2 - t0); t_tot.append(t3 - t2); t_parts.append(t4 - t3)
+            dev = float(np.max(np.abs(host - tot)) / np.max(np.abs(tot)))
+            print("AdiabatClimate nz %3d -> %3d layers, %s (%d unknowns x %d rows), %d alternating calls:\n"
+                  "  ir_jacobian                      %s\n  ir_jacobian + numpy reduction    %s\n"
+                  "  ir_jacobian_reduced, total only  %s\n  ir_jacobian_reduced, parts       %s\n"
+                  "  total only against the host's reduction: %.1e of the largest |entry|; parts' total bitwise equal: %s"
+                  % (nz, nzr, label, len(inds), len(rows), reps, stats(t_full), stats(t_host), stats(t_tot), stats(t_parts),
+                     dev, bool(np.array_equal(parts[2], tot))), flush=True)
+        del r
+
+
+if sys.argv[1:2] == ["reduced"]:
+    reduced_leg([int(a) for a in sys.argv[2:]] or [200, 100])
+    sys.exit(0)
 if sys.argv[1:2] == ["jacobian"]:
     jacobian_leg([int(a) for a in sys.argv[2:]] or [200, 100])
     sys.exit(0)
