@@ -3792,6 +3792,139 @@ void launch_scale(double *a, size_t n, double f, hipStream_t s) {
   hipLaunchKernelGGL(k_scale, dim3(grid), dim3(256), 0, s, a, n, f);
 }
 
+// ------------------------------------------------------------------------------------
+// Column batches out of device arrays (radtran_toa_fluxes_batch_device): the host's pack_column / build_meta and
+// its f_total_row / toa_fluxes as kernels, so that neither the inputs nor the results pass through the host.
+// ------------------------------------------------------------------------------------
+// futils is_close as the host evaluates it (radtran_api.hip is_close): every operation rounded on its own
+__device__ __forceinline__ bool pack_is_close(double a, double b, double tol) {
+  const double fa = fabs(a), fb = fabs(b);
+  const double mx = fa < fb ? fb : fa;                        // std::max
+  return fabs(__dsub_rn(a, b)) <= fabs(__dmul_rn(tol, mx));
+}
+
+constexpr int PACK_THREADS = 256;
+
+// One workgroup per column.  The copy is coalesced (consecutive threads, consecutive elements of a segment).  The
+// pair-reuse table is build_meta's: thread t decides the pair (2t, 2t+1) from the caller's arrays; a pair that is
+// reused takes one entry of the ascending source list, any other two, so pair t's first entry sits at
+// 2t - (reused pairs before t): an exclusive scan of the decisions over the block -- ballot and popcount within a
+// wave, the waves' totals through LDS -- carried from one pass of the block to the next when nz/2 > PACK_THREADS.
+__global__ __launch_bounds__(PACK_THREADS) void k_pack_columns(PackParams p) {
+  const int c = blockIdx.x, tid = threadIdx.x, nz = p.nz, nsp = p.nsp, np = p.np;
+  double *dst = p.blocks + (size_t)c * p.col_count;
+  const double *T = p.T + (size_t)c * nz, *P = p.P + (size_t)c * nz, *dz = p.dz + (size_t)c * nz;
+  const double *dens = p.dens + (size_t)c * nz * nsp;
+  const double *pdens = p.has_particles ? p.pdens + (size_t)c * nz * np : nullptr;
+  const double *radii = p.has_particles ? p.radii + (size_t)c * nz * np : nullptr;
+
+  // [T_surface | T | P | dz | dens | pdens | radii]
+  if (tid == 0) dst[0] = p.T_surface[c];
+  for (int i = tid; i < nz; i += PACK_THREADS) {
+    dst[1 + i] = T[i];
+    dst[1 + nz + i] = P[i];
+    dst[1 + 2 * nz + i] = dz[i];
+  }
+  double *d_dens = dst + 1 + 3 * (size_t)nz;
+  for (int i = tid; i < nz * nsp; i += PACK_THREADS) d_dens[i] = dens[i];
+  double *d_pd = d_dens + (size_t)nz * nsp, *d_ra = d_pd + (size_t)nz * np;
+  for (int i = tid; i < nz * np; i += PACK_THREADS) {
+    // (a handle with particle columns whose batch comes without them is refused before the launch; a block of the
+    //  host's is zero there)
+    d_pd[i] = p.has_particles ? pdens[i] : 0.0;
+    d_ra[i] = p.has_particles ? radii[i] : 0.0;
+  }
+
+  // meta: [0] = nsrc, [1 + m] = m-th source layer | flags, [1 + nz + j] = source of layer j, one int of padding
+  int *meta = reinterpret_cast<int *>(dst + p.meta_ofs);
+  int *srcl = meta + 1, *src = meta + 1 + nz;
+  __shared__ int s_tot[PACK_THREADS / 64];
+  const double tol = 1.0e-12;
+  const int lane = tid & 63, w = tid >> 6;
+  int reused = 0;   // reused pairs in the passes so far (uniform)
+  if ((nz & 1) == 0) {
+    const int npairs = nz / 2;
+    for (int t0 = 0; t0 < npairs; t0 += PACK_THREADS) {
+      const int t = t0 + tid, j = 2 * t + 1;
+      const bool valid = t < npairs;
+      bool reuse = false, exact = false;
+      if (valid) {
+        reuse = pack_is_close(P[j], P[j - 1], tol) && pack_is_close(T[j], T[j - 1], tol);
+        exact = P[j] == P[j - 1] && T[j] == T[j - 1] && dz[j] == dz[j - 1];
+        const double dzb = dz[j], dza = dz[j - 1];
+        for (int i = 0; i < nsp && reuse; i++) {
+          const double nb = dens[(size_t)i * nz + j], na = dens[(size_t)i * nz + j - 1];
+          reuse = pack_is_close(__dmul_rn(nb, dzb), __dmul_rn(na, dza), tol);   // opw%cols: stored (rounded) products
+          exact = exact && nb == na;
+        }
+        if (p.use_radii)
+          for (int i = 0; i < np && reuse; i++) reuse = pack_is_close(radii[(size_t)i * nz + j], radii[(size_t)i * nz + j - 1], tol);
+        if (reuse && np > 0 && p.has_particles)
+          for (int i = 0; i < np; i++)
+            exact = exact && pdens[(size_t)i * nz + j] == pdens[(size_t)i * nz + j - 1] &&
+                    radii[(size_t)i * nz + j] == radii[(size_t)i * nz + j - 1];
+        exact = exact && reuse;
+      }
+      const unsigned long long m = __ballot(reuse);
+      if (lane == 0) s_tot[w] = __popcll(m);
+      __syncthreads();
+      int before = reused + __popcll(m & ((1ull << lane) - 1ull)), total = 0;
+      for (int k = 0; k < PACK_THREADS / 64; k++) {
+        const int n = s_tot[k];
+        if (k < w) before += n;
+        total += n;
+      }
+      if (valid) {
+        const int pos = 2 * t - before;
+        src[j - 1] = j - 1;
+        if (reuse) {
+          srcl[pos] = (j - 1) | SRC_PAIR | (exact ? SRC_EXACT : 0);
+          src[j] = j - 1;
+        } else {
+          srcl[pos] = j - 1;
+          srcl[pos + 1] = j;
+          src[j] = j;
+        }
+      }
+      reused += total;
+      __syncthreads();   // s_tot is rewritten by the next pass
+    }
+  } else {
+    for (int j = tid; j < nz; j += PACK_THREADS) { srcl[j] = j; src[j] = j; }
+  }
+  const int nsrc = nz - reused;
+  for (int m = nsrc + tid; m < nz; m += PACK_THREADS) srcl[m] = nz - 1;
+  if (tid == 0) {
+    meta[0] = nsrc;
+    meta[2 * nz + 1] = 0;
+    if (p.nsrc) p.nsrc[c] = nsrc;
+  }
+}
+void launch_pack_columns(const PackParams &p, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_columns, dim3(p.ncol), dim3(PACK_THREADS), 0, s, p);
+}
+
+// One workgroup per column: f_total in the order of the host's f_total_row, ISR / OLR as its toa_fluxes forms them
+// (clima_radtran.f90:287, :339-340) -- differences and one sum, no product anywhere -- and the five rows out.
+__global__ __launch_bounds__(256) void k_batch_finish(BatchFinishParams p) {
+  const int c = blockIdx.x, nl = p.nz + 1;
+  double *h = p.flux + (size_t)c * 5 * nl;
+  double *out = p.fluxes ? p.fluxes + (size_t)c * 5 * nl : nullptr;
+  for (int i = threadIdx.x; i < nl; i += blockDim.x) {
+    const double iu = h[i], id = h[nl + i], su = h[2 * nl + i], sd = h[3 * nl + i];
+    const double sol = sd - su, ir = id - iu;
+    const double ft = sol + ir;
+    h[4 * nl + i] = ft;
+    if (out) {
+      out[i] = iu; out[nl + i] = id; out[2 * nl + i] = su; out[3 * nl + i] = sd; out[4 * nl + i] = ft;
+    }
+    if (i == p.nz) { p.ISR[c] = sol; p.OLR[c] = -ir; }
+  }
+}
+void launch_batch_finish(const BatchFinishParams &p, hipStream_t s) {
+  hipLaunchKernelGGL(k_batch_finish, dim3(p.ncol), dim3(256), 0, s, p);
+}
+
 #include "ir_green.inc"
 
 }  // namespace clima

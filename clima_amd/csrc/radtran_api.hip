@@ -230,6 +230,18 @@ struct Radtran {
   // one-launch batches: per-column prep / opr / spectra blocks for the columns in flight
   DevBuf<double> d_prep_arena, d_opr_arena, d_res_arena;
   int batch_cols_in_flight = 64;
+  // A batch out of device arrays (radtran_toa_fluxes_batch_device) returns with its work enqueued; what the host
+  // batch does after its synchronise -- the look at the two error words, the repeat through the separate launches
+  // when a fused hand-off wait expired -- is due at the next settle_device_batch().  The repeat reads the column
+  // blocks still in d_cols_arena and writes the caller's same result arrays.
+  struct DeviceBatch {
+    bool pending = false, one_launch = false;
+    int n = 0, first_call = 0;
+    double *ISR = nullptr, *OLR = nullptr, *fluxes = nullptr;
+  } dev_batch;
+  DevBuf<int> d_batch_nsrc;        // every column's source-layer count, as k_pack_columns found it
+  std::vector<int> batch_nsrc;     // ... on the host (fetched only for one call per column: those launches are sized by it)
+  hipEvent_t ev_producer = nullptr;   // orders the handle's stream behind the stream that wrote a device batch's inputs
   bool batch_shared = true;        // radiate_ir_batch: temperature-independent work shared by the columns (CLIMA_HIP_BATCH_SHARED=0: one full solve per column)
   int rebin_mode = 1;              // 0 window form, 1 streaming, 2 streaming multi-edge (rebin_mode_for)
   long coop_items = 34816;         // ng = 8: at most this many (bin, source layer) items go to k_opacity_coop<8> (CLIMA_HIP_COOP_ITEMS)
@@ -263,6 +275,7 @@ struct Radtran {
     if (h_bout) (void)hipHostFree(h_bout);
     if (h_green) (void)hipHostFree(h_green);
     if (ev_upload) (void)hipEventDestroy(ev_upload);
+    if (ev_producer) (void)hipEventDestroy(ev_producer);
     if (comm) (void)ncclCommDestroy(comm);
     if (stream) (void)hipStreamDestroy(stream);
     magic = 0;
@@ -872,8 +885,10 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
 }
 
 bool recover_fused_timeout(Radtran *r);
+void settle_device_batch(Radtran *r);
 
 void fetch_small(Radtran *r) {
+  settle_device_batch(r);
   if (r->small_valid) return;
   const int nl = r->nz + 1;
   for (int pass = 0; pass < 2; pass++) {
@@ -909,6 +924,7 @@ void do_upload(Radtran *r, double T_surface, const double *T, const double *P, c
                const double *dz, const double *pdens, const double *radii) {
   const int nz = r->nz;
   double *h = r->h_col;
+  settle_device_batch(r);
   // the pinned staging buffer is reused: wait (lazily, here) for the previous upload's copy
   if (r->upload_pending) { HIPCHK(hipEventSynchronize(r->ev_upload)); r->upload_pending = false; }
   r->nsrc = pack_column(r, h, T_surface, T, P, dz, dens, pdens, radii);
@@ -987,6 +1003,7 @@ bool surface_device_error(Radtran *r, char *err) {
 // device buffers hold the call's results (what fetch_small does for the level rows; the per-bin spectra and the
 // optical properties are read out after this)
 void settle(Radtran *r) {
+  settle_device_batch(r);
   for (int pass = 0; pass < 2; pass++) {
     HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
     if (r->comm && !r->small_valid)   // the reduced status word (the rows themselves are fetched when they are read)
@@ -999,6 +1016,105 @@ void settle(Radtran *r) {
 
 void defer_err(Radtran *r, const std::string &msg) {
   if (r && r->deferred_err.empty()) r->deferred_err = msg;
+}
+
+// The launch form of a batch of n columns (radtran_toa_fluxes_batch and its device-array form decide it here, once):
+// one launch of each kernel per chunk of CH columns (the fused grid takes the columns' work items in turn, so one
+// column's two-stream tail runs beside the next column's opacity tiles) where the fused form covers the
+// configuration -- the per-column arenas of a chunk are sized here --, otherwise the columns' calls back to back.
+struct BatchForm {
+  int CH;
+  bool one_launch;
+  CallBufs first;   // the first chunk (only its counts are read)
+};
+BatchForm batch_form(Radtran *r, int n) {
+  BatchForm f{std::min(n, r->batch_cols_in_flight), false, CallBufs{}};
+  f.first = arena_chunk_bufs(r, 0, f.CH);
+  f.one_launch = plan_radiate(plan_input(r, f.first, true, true, true)).fused.form != TS_NONE &&
+                 integrate_chunks(std::max(r->ir_n, r->sol_n)) * (32 + 16) * sizeof(double) <= 64 * 1024;
+  if (const char *e = getenv("CLIMA_HIP_BATCH_ONE_LAUNCH")) f.one_launch = f.one_launch && atoi(e) != 0;
+  if (f.one_launch) {
+    const BatchStrides &bs = f.first.bs;
+    if (r->d_prep_arena.n < bs.prep * f.CH) r->d_prep_arena.alloc(bs.prep * f.CH);
+    if (r->d_opr_arena.n < bs.opr * f.CH) r->d_opr_arena.alloc(bs.opr * f.CH);
+    if (r->d_res_arena.n < bs.res * f.CH) { r->d_res_arena.alloc(bs.res * f.CH); r->d_res_arena.zero(r->stream); }
+    if (r->d_done.n < (size_t)bs.done * f.CH + 1) { r->d_done.alloc((size_t)bs.done * f.CH + 1); r->d_done.zero(r->stream); }
+  }
+  return f;
+}
+// The handle's spectra and band optical depths = the last column's, which a one-launch batch left in the arena
+void batch_keep_last_spectra(Radtran *r, int n, const BatchForm &f) {
+  const SpectraViews src = spectra_views(r, r->d_res_arena.p + (size_t)((n - 1) % f.CH) * f.first.bs.res);
+  auto d2d = [&](DevBuf<double> &dst, const double *from) { HIPCHK(hipMemcpyAsync(dst.p, from, sizeof(double) * dst.n, hipMemcpyDeviceToDevice, r->stream)); };
+  d2d(r->wrk_ir.fup_a, src.ir_fup_a); d2d(r->wrk_ir.fdn_a, src.ir_fdn_a); d2d(r->wrk_ir.tau_band, src.ir_tau_band);
+  d2d(r->wrk_sol.fup_a, src.sol_fup_a); d2d(r->wrk_sol.fdn_a, src.sol_fdn_a); d2d(r->wrk_sol.amean, src.sol_amean);
+  d2d(r->wrk_sol.tau_band, src.sol_tau_band);
+}
+
+// ---- batches out of device arrays (radtran_toa_fluxes_batch_device) ----
+PackParams make_pack_params(Radtran *r, int n, const double *T_surface, const double *T, const double *P, const double *dens,
+                            const double *dz, const double *pdens, const double *radii, double *blocks, int *nsrc) {
+  PackParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.ncol = n; p.nz = r->nz; p.nsp = r->nsp; p.np = r->np;
+  p.has_particles = r->np > 0 && pdens && radii;
+  p.use_radii = p.has_particles && !r->part.empty();
+  p.col_count = r->col_count; p.meta_ofs = r->meta_ofs;
+  p.T_surface = T_surface; p.T = T; p.P = P; p.dz = dz; p.dens = dens; p.pdens = pdens; p.radii = radii;
+  p.blocks = blocks; p.nsrc = nsrc;
+  return p;
+}
+// the columns' source-layer counts (4 bytes each): the launches of one call per column are sized by them
+void fetch_batch_nsrc(Radtran *r, int n) {
+  r->batch_nsrc.resize(n);
+  HIPCHK(hipMemcpyAsync(r->batch_nsrc.data(), r->d_batch_nsrc.p, sizeof(int) * n, hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipStreamSynchronize(r->stream));
+}
+// The batch whose column blocks are in d_cols_arena, start to end: the chunks (or the columns' calls), f_total / ISR /
+// OLR and the rows out to the caller's arrays, the handle's own level rows = the last column's.  Nothing waits.
+void enqueue_device_batch(Radtran *r, const Radtran::DeviceBatch &b, bool allow_fused) {
+  const int n = b.n, nl = r->nz + 1, CH = std::min(n, r->batch_cols_in_flight);
+  if (b.one_launch && allow_fused)
+    for (int c0 = 0; c0 < n; c0 += CH) enqueue_radiate(r, arena_chunk_bufs(r, c0, std::min(CH, n - c0)), true, true);
+  else
+    for (int c = 0; c < n; c++) enqueue_radiate(r, arena_column_bufs(r, c, r->batch_nsrc[c]), true, true, allow_fused);
+  launch_batch_finish(BatchFinishParams{n, r->nz, r->d_flux_arena.p, b.ISR, b.OLR, b.fluxes}, r->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(r->d_flux_n.p, r->d_flux_arena.p + (size_t)(n - 1) * 5 * nl, sizeof(double) * 4 * nl, hipMemcpyDeviceToDevice, r->stream));
+}
+// What the host batch does behind its synchronise, for a device batch still pending: wait, look at the two error
+// words, repeat the batch through the separate launches if a fused hand-off wait of one of its calls expired
+// (the column blocks are still in the arena, the results go to the caller's same arrays), keep an opacity failure
+// for the next call that reports errors.
+void settle_device_batch(Radtran *r) {
+  if (!r->dev_batch.pending) return;
+  const Radtran::DeviceBatch b = r->dev_batch;
+  r->dev_batch.pending = false;
+  auto wait = [&] {
+    HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(hipStreamSynchronize(r->stream));
+    resolve_events(r);
+  };
+  wait();
+  if (r->h_errflag[1] >= b.first_call) {
+    r->fused_fallbacks++;
+    if (b.one_launch) fetch_batch_nsrc(r, b.n);
+    enqueue_device_batch(r, b, false);
+    wait();
+    r->opr_valid = true;   // one call per column works in the handle's own buffers: they hold the last column's
+  }
+  r->checked_timeout = r->call_id;
+  r->checked_id = r->call_id;
+  invalidate_small(r);
+  if (*r->h_errflag >= b.first_call) defer_err(r, "Opacity computation failed in one or more wavelength bins.");  // clima_radtran_types.f90:773-776
+}
+// device memory of the handle's device?  (an address the runtime does not know -- pageable host memory -- is an
+// error return on some runtimes and "unregistered" on others)
+bool on_handle_device(const Radtran *r, const void *p) {
+  hipPointerAttribute_t a;
+  std::memset(&a, 0, sizeof(a));
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return a.type == hipMemoryTypeDevice && a.device == r->device;
 }
 
 void get2d(WrkObj *w, DevBuf<double> &buf, int dim1, int dim2, double *arr) {
@@ -2122,6 +2238,7 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   const int hp = has_particles ? *has_particles : 0;
   if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return; }
   TRY
+  settle_device_batch(r);
   const int nz = r->nz, nl = nz + 1, n = *ncol;
   const size_t cc = r->col_count, np_n = (size_t)nz * r->np;
   std::vector<double> h((size_t)n * cc, 0.0);
@@ -2139,17 +2256,9 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   // One launch of each kernel per chunk of columns (the fused grid takes the columns' work items in
   // turn, so one column's two-stream tail runs beside the next column's opacity tiles) where the fused
   // form covers the configuration; otherwise the calls of the columns are enqueued back to back.
-  const int CH = std::min(n, r->batch_cols_in_flight);
-  const CallBufs first = arena_chunk_bufs(r, 0, CH);   // (the arenas it points into are sized below: only its counts are read)
-  bool one_launch = plan_radiate(plan_input(r, first, true, true, true)).fused.form != TS_NONE &&
-                    integrate_chunks(std::max(r->ir_n, r->sol_n)) * (32 + 16) * sizeof(double) <= 64 * 1024;
-  if (const char *e = getenv("CLIMA_HIP_BATCH_ONE_LAUNCH")) one_launch = one_launch && atoi(e) != 0;
-  if (one_launch) {
-    if (r->d_prep_arena.n < first.bs.prep * CH) r->d_prep_arena.alloc(first.bs.prep * CH);
-    if (r->d_opr_arena.n < first.bs.opr * CH) r->d_opr_arena.alloc(first.bs.opr * CH);
-    if (r->d_res_arena.n < first.bs.res * CH) { r->d_res_arena.alloc(first.bs.res * CH); r->d_res_arena.zero(r->stream); }
-    if (r->d_done.n < (size_t)first.bs.done * CH + 1) { r->d_done.alloc((size_t)first.bs.done * CH + 1); r->d_done.zero(r->stream); }
-  }
+  const BatchForm form = batch_form(r, n);
+  const int CH = form.CH;
+  const bool one_launch = form.one_launch;
   auto run_all = [&](bool allow_fused) {
     if (one_launch && allow_fused)
       for (int c0 = 0; c0 < n; c0 += CH) enqueue_radiate(r, arena_chunk_bufs(r, c0, std::min(CH, n - c0)), true, true);
@@ -2179,11 +2288,7 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   const bool in_arena = one_launch && !fell_back;
   r->opr_valid = !in_arena;
   if (in_arena) {
-    const SpectraViews src = spectra_views(r, r->d_res_arena.p + (size_t)((n - 1) % CH) * first.bs.res);
-    auto d2d = [&](DevBuf<double> &dst, const double *from) { HIPCHK(hipMemcpyAsync(dst.p, from, sizeof(double) * dst.n, hipMemcpyDeviceToDevice, r->stream)); };
-    d2d(r->wrk_ir.fup_a, src.ir_fup_a); d2d(r->wrk_ir.fdn_a, src.ir_fdn_a); d2d(r->wrk_ir.tau_band, src.ir_tau_band);
-    d2d(r->wrk_sol.fup_a, src.sol_fup_a); d2d(r->wrk_sol.fdn_a, src.sol_fdn_a); d2d(r->wrk_sol.amean, src.sol_amean);
-    d2d(r->wrk_sol.tau_band, src.sol_tau_band);
+    batch_keep_last_spectra(r, n, form);
     HIPCHK(hipStreamSynchronize(r->stream));
   }
   if (*r->h_errflag >= first_call) {
@@ -2199,6 +2304,118 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
     if (fluxes) std::memcpy(fluxes + (size_t)c * 5 * nl, f, sizeof(double) * 5 * nl);
   }
   CATCH(err)
+}
+
+// The same batch with every array in device memory (the f64 tensors of a GPU-resident ensemble): the column blocks
+// are built on the device (k_pack_columns), the chunks run as in the host batch, f_total / ISR / OLR are formed and
+// stored on the device (k_batch_finish).  The call returns with the work enqueued on the handle's stream, behind the
+// caller's writes of the inputs on `producer_stream` (NULL: they are complete); the results are final when the next
+// radtran_synchronize returns with `err` empty (settle_device_batch).  The host stages nothing and waits for
+// nothing -- but for a configuration that runs one call per column (the fused grid does not cover it, or
+// CLIMA_HIP_BATCH_ONE_LAUNCH=0): plan_radiate picks the opacity kernel and sizes the grids of such a call from the
+// column's own source-layer count, and the kernels it chooses between round differently, so the bound nsrc = nz
+// would not be the host batch's computation; the ncol counts (4 bytes each) are fetched in one copy first.
+void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
+                                     const double *d_P, const double *d_densities, const double *d_dz,
+                                     const int *has_particles, const double *d_pdensities, const double *d_radii,
+                                     double *d_ISR, double *d_OLR, double *d_fluxes, const void *producer_stream,
+                                     char *err) {
+  clear_err(err);
+  GUARD(r, ptr, err);
+  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return; }
+  if (r->shard_world != 1) { set_err(err, "toa_fluxes_batch is not available on a bin-sharded handle"); return; }
+  const int hp = has_particles ? *has_particles : 0;
+  if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return; }
+  TRY
+  const bool part = r->np > 0;
+  enum { UNUSED, REQUIRED, OPTIONAL };   // (the particle arrays of a handle without particle columns are not read)
+  const struct { const char *name; const void *p; int use; } args[] = {
+      {"T_surface", d_T_surface, REQUIRED}, {"T", d_T, REQUIRED}, {"P", d_P, REQUIRED}, {"densities", d_densities, REQUIRED},
+      {"dz", d_dz, REQUIRED}, {"pdensities", d_pdensities, part ? REQUIRED : UNUSED}, {"radii", d_radii, part ? REQUIRED : UNUSED},
+      {"ISR", d_ISR, REQUIRED}, {"OLR", d_OLR, REQUIRED}, {"fluxes", d_fluxes, OPTIONAL}};
+  for (const auto &a : args) {
+    if (a.use == UNUSED || (a.use == OPTIONAL && !a.p)) continue;
+    if (!a.p) { set_err(err, std::string("toa_fluxes_batch_device: \"") + a.name + "\" is a required argument"); return; }
+    if (!on_handle_device(r, a.p)) {
+      set_err(err, std::string("toa_fluxes_batch_device: \"") + a.name + "\" is not device memory of this handle's device");
+      return;
+    }
+  }
+  settle_device_batch(r);   // an earlier batch's checks (and its repeat, which reads the arena this one overwrites)
+  const int nz = r->nz, nl = nz + 1, n = *ncol;
+  if (r->d_cols_arena.n < (size_t)n * r->col_count) r->d_cols_arena.alloc((size_t)n * r->col_count);
+  if (r->d_flux_arena.n < (size_t)n * 5 * nl) r->d_flux_arena.alloc((size_t)n * 5 * nl);
+  if (r->d_batch_nsrc.n < (size_t)n) r->d_batch_nsrc.alloc(n);
+  if (producer_stream) {
+    if (!r->ev_producer) HIPCHK(hipEventCreateWithFlags(&r->ev_producer, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(r->ev_producer, reinterpret_cast<hipStream_t>(const_cast<void *>(producer_stream))));
+    HIPCHK(hipStreamWaitEvent(r->stream, r->ev_producer, 0));
+  }
+  launch_pack_columns(make_pack_params(r, n, d_T_surface, d_T, d_P, d_densities, d_dz, part ? d_pdensities : nullptr,
+                                       part ? d_radii : nullptr, r->d_cols_arena.p, r->d_batch_nsrc.p), r->stream);
+  HIPCHK(hipGetLastError());
+  r->column_has_particles = part;
+  Radtran::DeviceBatch b;
+  b.n = n; b.first_call = r->call_id + 1;
+  b.ISR = d_ISR; b.OLR = d_OLR; b.fluxes = d_fluxes;
+  const BatchForm form = batch_form(r, n);
+  b.one_launch = form.one_launch;
+  if (!b.one_launch) fetch_batch_nsrc(r, n);
+  enqueue_device_batch(r, b, true);
+  // the handle afterwards: the last column's level rows (copied above), spectra and band optical depths; its optical
+  // properties stay in the arena after a one-launch batch (opr_valid false), as after the host batch
+  invalidate_small(r);
+  r->column_loaded = false;
+  r->opr_valid = !b.one_launch;
+  if (b.one_launch) batch_keep_last_spectra(r, n, form);
+  b.pending = true;
+  r->dev_batch = b;
+  CATCH(err)
+}
+
+/* test hooks: the column blocks of a batch (ncol * col_count doubles, host arrays as radtran_toa_fluxes_batch) as
+ * k_pack_columns builds them on the device, and as the host's pack_column does */
+void clima_test_pack_columns(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                             const double *densities, const double *dz, const int *has_particles, const double *pdensities,
+                             const double *radii, double *blocks, int *col_count, char *err) {
+  clear_err(err);
+  GUARD(r, ptr, err);
+  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  const int hp = has_particles ? *has_particles : 0;
+  if (*ncol < 1 || (r->np > 0 && !(hp && pdensities && radii))) { set_err(err, "clima_test_pack_columns: bad arguments"); return; }
+  *col_count = (int)r->col_count;
+  if (!blocks) return;
+  TRY
+  const size_t n = *ncol, nz = r->nz;
+  DevBuf<double> ts, t, p, de, z, pd, ra, out;
+  DevBuf<int> ns;
+  auto up = [&](DevBuf<double> &d, const double *h, size_t count) { d.upload(std::vector<double>(h, h + count)); };
+  up(ts, T_surface, n); up(t, T, n * nz); up(p, P, n * nz); up(de, densities, n * nz * r->nsp); up(z, dz, n * nz);
+  if (r->np > 0) { up(pd, pdensities, n * nz * r->np); up(ra, radii, n * nz * r->np); }
+  out.alloc(n * r->col_count);
+  ns.alloc(n);
+  launch_pack_columns(make_pack_params(r, (int)n, ts.p, t.p, p.p, de.p, z.p, pd.p, ra.p, out.p, ns.p), r->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(blocks, out.p, sizeof(double) * out.n, hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipStreamSynchronize(r->stream));
+  CATCH(err)
+}
+void clima_test_pack_columns_host(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                                  const double *densities, const double *dz, const int *has_particles,
+                                  const double *pdensities, const double *radii, double *blocks, int *col_count, char *err) {
+  clear_err(err);
+  GUARD(r, ptr, err);
+  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  const int hp = has_particles ? *has_particles : 0;
+  if (*ncol < 1 || (r->np > 0 && !(hp && pdensities && radii))) { set_err(err, "clima_test_pack_columns: bad arguments"); return; }
+  *col_count = (int)r->col_count;
+  if (!blocks) return;
+  const size_t nz = r->nz, np_n = nz * r->np;
+  std::memset(blocks, 0, sizeof(double) * (size_t)*ncol * r->col_count);
+  for (size_t c = 0; c < (size_t)*ncol; c++)
+    pack_column(r, blocks + c * r->col_count, T_surface[c], T + c * nz, P + c * nz, dz + c * nz, densities + c * nz * r->nsp,
+                r->np > 0 ? pdensities + c * np_n : nullptr, r->np > 0 ? radii + c * np_n : nullptr);
 }
 
 void radtran_synchronize(void *ptr, char *err) {

@@ -259,7 +259,29 @@ struct BatchIntegrateParams {
   size_t out_arr;
 };
 
-constexpr int GREEN_LB = 16;                 // levels per block of the far form (ir_green.inc)
+// Column batches whose inputs are device arrays (radtran_toa_fluxes_batch_device): k_pack_columns builds column c's block
+// (the layout column_dev unpacks, pair-reuse table included) at blocks + c * col_count out of the caller's arrays, which
+// carry the column as their last dimension.
+struct PackParams {
+  int ncol, nz, nsp, np;
+  int has_particles;         // pdens and radii are given (np > 0)
+  int use_radii;             // ... and the handle has particle opacities: the radii take part in the pair decision
+  size_t col_count, meta_ofs;
+  const double *T_surface, *T, *P, *dz, *dens, *pdens, *radii;
+  double *blocks;
+  int *nsrc;                 // [ncol] every column's source-layer count once more, contiguous (null: not wanted)
+};
+// ... and k_batch_finish ends the batch on the device: f_total into row 4 of every column's level rows [5][nz+1]
+// (flux, 5 (nz+1) apart), ISR / OLR (ncol), and the five rows into fluxes (nz+1, 5, ncol) when that is given.
+struct BatchFinishParams {
+  int ncol, nz;
+  double *flux;
+  double *ISR, *OLR, *fluxes;
+};
+void launch_pack_columns(const PackParams &p, hipStream_t s);
+void launch_batch_finish(const BatchFinishParams &p, hipStream_t s);
+
+constexpr int GREEN_LB = 16;                // levels per block of the far form (ir_green.inc)
 // Which form a level takes for a deviation at k.  A unit change of bplanck[k] reaches the source terms of layers k-1 and
 // k, i.e. the rows 2k-3 .. 2k+2 of E (those that exist); the levels k and k+1 (the bottoms of these two layers) and, for
 // k <= 1, level 0 are evaluated explicitly; the levels above take the above form, those below the below form.

@@ -329,6 +329,62 @@ class Radtran:
             return isr, olr, np.transpose(fl, (2, 1, 0))
         return isr, olr
 
+    def TOA_fluxes_batch_tensors(self, T_surface, T, P, densities, dz, pdensities=None, radii=None, return_fluxes=False,
+                                 sync=True):
+        """`TOA_fluxes_batch` for columns that live in device memory (radtran_toa_fluxes_batch_device): torch CUDA
+        float64 tensors, C-contiguous, T_surface (ncol,); T, P, dz (ncol, nz); densities (ncol, nsp, nz);
+        pdensities / radii (ncol, np, nz).  Nothing passes through the host.  Returns fresh tensors on the same
+        device: ISR, OLR (ncol,), plus the level fluxes (ncol, 5, nz+1) = ir up, ir down, solar up, solar down,
+        f_total when `return_fluxes` -- bit for bit what `TOA_fluxes_batch` gives for the same columns.
+
+        The library's work is ordered behind what torch's current stream has enqueued.  With `sync=True` the call
+        ends with `synchronize()`.  With `sync=False` it returns at once, torch's current stream ordered behind the
+        handle's: the tensors are FINAL ONLY AFTER `synchronize()` -- that is where a fused hand-off wait that
+        expired in the batch is found, and the batch is then computed again, unfused, into the same tensors
+        (`fused_fallbacks` + 1), and where an opacity failure is raised.  Keep inputs and outputs alive until then."""
+        import torch
+        nz, hp = self.nz, self.np > 0
+        if hp and (pdensities is None or radii is None):
+            raise ClimaException('"pdensities" and "radii" are required arguments.')
+        n = int(T_surface.shape[0]) if isinstance(T_surface, torch.Tensor) and T_surface.dim() == 1 else -1
+        want = [("T_surface", T_surface, (n,)), ("T", T, (n, nz)), ("P", P, (n, nz)), ("densities", densities, (n, self.ng, nz)),
+                ("dz", dz, (n, nz))]
+        if hp:
+            want += [("pdensities", pdensities, (n, self.np, nz)), ("radii", radii, (n, self.np, nz))]
+        for name, t, shape in want:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+                raise ClimaException('toa_fluxes_batch_device: "%s" is not a float64 torch tensor' % name)
+            if tuple(t.shape) != shape:
+                raise ClimaException('"%s" has the wrong input dimension.' % name)
+            if not t.is_contiguous():   # (no silent copy: the caller decides where a transposed view is materialised)
+                raise ClimaException('toa_fluxes_batch_device: "%s" is not C-contiguous' % name)
+        # (a tensor that is not on the handle's device is refused by the library, which names it)
+        dev = next((t.device for _, t, _ in want if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+        isr, olr = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+        fl = torch.empty((n, 5, nz + 1), dtype=torch.float64, device=dev) if return_fluxes else None
+
+        def addr(t):
+            return t.data_ptr() if t is not None else None
+
+        cur = torch.cuda.current_stream(dev)
+        mine = torch.cuda.ExternalStream(self.stream(), device=dev)
+        producer = cur.cuda_stream
+        if not producer:
+            # the legacy default stream: NULL tells the library that the inputs are complete, so the order is made here
+            mine.wait_stream(cur)
+        self._L.radtran_toa_fluxes_batch_device(self._ptr, _i(n), addr(T_surface), addr(T), addr(P), addr(densities), addr(dz),
+                                                _i(1 if hp else 0), addr(pdensities) if hp else None,
+                                                addr(radii) if hp else None, addr(isr), addr(olr), addr(fl), producer or None,
+                                                self._err)
+        self._check()
+        if sync:
+            self.synchronize()
+        else:
+            ev = torch.cuda.Event()
+            ev.record(mine)
+            cur.wait_event(ev)
+        return (isr, olr, fl) if return_fluxes else (isr, olr)
+
     def radiate_ir_batch(self, T_surface, T, out=None, pin=False):
         """ncol IR-only calls with the resident opacities in one go: column c is
         `radiate(T_surface[c], T[:, c], ..., compute_solar=False, compute_opacity=False)`

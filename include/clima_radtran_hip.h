@@ -173,6 +173,34 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
                               const double *densities, const double *dz, const int *has_particles,
                               const double *pdensities, const double *radii, double *ISR, double *OLR,
                               double *fluxes, char *err);
+/* The same batch with every array in device memory of the handle's device (f64, dense, same shapes and order):
+ * nothing is staged on the host -- the column blocks and the pair-reuse tables are built, and f_total / ISR / OLR
+ * formed, by kernels -- and the call RETURNS WITHOUT WAITING for the device.  d_fluxes may be NULL.
+ * producer_stream: the HIP stream on which the caller's writes of the inputs were enqueued (the library records an
+ * event on it and makes the handle's stream, radtran_stream_get, wait for that event; the host is not
+ * synchronised), or NULL when the inputs are complete.
+ * The results are final when the next radtran_synchronize returns with `err` empty; inputs and outputs must stay
+ * allocated until then: a fused hand-off wait that expired in the batch is found there, and the batch is then
+ * computed again through the separate launches into the SAME output arrays (radtran_fused_fallbacks_get + 1); an
+ * opacity failure is reported there with the reference's text.  Any later call on the handle that enqueues work or
+ * reads results settles a pending batch first.  Bit for bit radtran_toa_fluxes_batch on the same columns; the handle
+ * holds the last column afterwards, as there.  Refused with nothing enqueued: what the host batch refuses, a NULL
+ * required array, an array that is not device memory of the handle's device (`"T" is not device memory ...`).
+ * Configurations that run one call per column (at most 64 layers, g-point counts other than 8, ...) fetch the
+ * columns' source-layer counts (4 bytes each) before enqueuing, which waits for the inputs. */
+void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
+                                     const double *d_P, const double *d_densities, const double *d_dz,
+                                     const int *has_particles, const double *d_pdensities, const double *d_radii,
+                                     double *d_ISR, double *d_OLR, double *d_fluxes, const void *producer_stream,
+                                     char *err);
+/* test hooks: the column blocks (ncol * col_count doubles; blocks NULL: col_count alone) of a batch given as host
+ * arrays, built by the device batch's kernel and by the host batch's pack_column */
+void clima_test_pack_columns(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                             const double *densities, const double *dz, const int *has_particles, const double *pdensities,
+                             const double *radii, double *blocks, int *col_count, char *err);
+void clima_test_pack_columns_host(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                                  const double *densities, const double *dz, const int *has_particles,
+                                  const double *pdensities, const double *radii, double *blocks, int *col_count, char *err);
 /* Batched shared-opacity IR calls: what the RCE Jacobian does one call at a time
  * (src/adiabat/clima_adiabat_solve.f90:798-812 -> clima_radtran.f90:221-318 with
  * compute_solar = compute_opacity = .false.).  T is (nz, ncol) column-major, T_surface (ncol);
