@@ -4,7 +4,13 @@ inputs.  Floating-point path: tolerances are stated here.
 north_star tolerance: OLR within 1e-4 relative of the reference.  What is enforced:
   * OLR / ISR ............................ 1e-9 relative
   * level fluxes fup_n, fdn_n, f_total .... 1e-9 of the channel's profile maximum (up and down together)
-  * per-bin spectra fup_a, fdn_a, amean ... 1e-8 of the array maximum (fup_a, fdn_a together)
+  * per-bin spectra fup_a, fdn_a, amean ... 1e-8 of the array maximum (fup_a, fdn_a together), AND every bin on its own
+    scale (the larger of the bin's fup_a and fdn_a maxima; the bin's own amean maximum) to 1e-9: a bin that carries
+    less than 1e-8 of the peak -- every solar bin below ~200 nm, the short-wave end of the IR channel -- is otherwise
+    not compared at all.  The oracle's two compilations differ per bin by at most 1.2e-11 (IR) and 8.2e-13 (solar)
+    over the 160 seeds of test_gpu_fuzz.py wherever ir_tau_min >= 1e-6; below that by up to 1.5e-8, which is why
+    the fuzz file scales this bound with its yardstick (`bin_tol_scale`).  A bin that is identically zero in the
+    oracle must be identically zero here.
   * opr tau, w0, g, tau_band .............. 1e-11 relative (k-table exp() argument rounding
     bounds this at ~3e-14; measured 2.8e-14)
 Differences come from device exp/log10 (<=1 ulp), FMA contraction, reciprocal-multiply in
@@ -52,24 +58,35 @@ def _pair(O, tables, nz, nzen, albedo, **scalars):
     return r, o
 
 
-def _compare(r, o, col, flux_tol_scale=1.0, **kw):
+def per_bin_difference(up, dn, up_ref, dn_ref):
+    """Every bin (column) on its own scale: the largest difference of the two spectra over the larger of the reference's
+    two maxima in that bin.  -> array [nw]; inf for a bin that is identically zero in the reference and not in `up`, `dn`."""
+    up, dn, up_ref, dn_ref = (np.asarray(a) for a in (up, dn, up_ref, dn_ref))
+    scale = np.maximum(np.max(np.abs(up_ref), axis=0), np.max(np.abs(dn_ref), axis=0))
+    err = np.maximum(np.max(np.abs(up - up_ref), axis=0), np.max(np.abs(dn - dn_ref), axis=0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(scale > 0, err / scale, np.where(err > 0, np.inf, 0.0))
+
+
+def _compare(r, o, col, flux_tol_scale=1.0, bin_tol_scale=1.0, **kw):
     """HIP against the oracle.  With 8 g-points a call of few (bin, layer) items runs the group-of-lanes
     opacity kernel (k_opacity_coop<8>) and one launch per kernel, a larger one the lane-per-item kernel
     inside the fused grid: a small test case is therefore compared TWICE, once in each form."""
-    out = _compare_once(r, o, col, flux_tol_scale, **kw)
+    out = _compare_once(r, o, col, flux_tol_scale, bin_tol_scale, **kw)
     items = r.coop_items
     if r.ngauss == 8 and items > 0 and r.nw * r.nz <= items and kw.get("compute_opacity", True):
         r.coop_items = 0
         try:
-            _compare_once(r, o, col, flux_tol_scale, **kw)
+            _compare_once(r, o, col, flux_tol_scale, bin_tol_scale, **kw)
         finally:
             r.coop_items = items
     return out
 
 
-def _compare_once(r, o, col, flux_tol_scale=1.0, **kw):
+def _compare_once(r, o, col, flux_tol_scale=1.0, bin_tol_scale=1.0, **kw):
     """`flux_tol_scale` loosens the flux tolerances for deliberately ill-conditioned settings
-    (see test_gpu_fuzz.py); the opacity tolerances never move."""
+    (see test_gpu_fuzz.py), `bin_tol_scale` the per-bin one in the same way (10 x the largest per-bin difference of
+    the oracle's two compilations over TOL_LEVEL, never below 1); the opacity tolerances never move."""
     f = flux_tol_scale
     isr, olr = r.TOA_fluxes(*col.args(), **kw)
     isr_o, olr_o = o.TOA_fluxes(*col.args(), **kw)
@@ -88,6 +105,11 @@ def _compare_once(r, o, col, flux_tol_scale=1.0, **kw):
         assert float(np.max(np.abs(np.asarray(wg.fup_a) - np.asarray(wo.fup_a)))) <= f * TOL_SPEC * a_scale
         assert float(np.max(np.abs(np.asarray(wg.fdn_a) - np.asarray(wo.fdn_a)))) <= f * TOL_SPEC * a_scale
         assert _scaled(wg.amean, wo.amean) <= f * TOL_SPEC
+        # every bin on its own scale (a zero bin of the oracle gives 0 or inf: it must be zero here too)
+        e_bin = float(np.max(per_bin_difference(wg.fup_a, wg.fdn_a, wo.fup_a, wo.fdn_a)))
+        assert e_bin <= bin_tol_scale * TOL_LEVEL, ("per bin, fup_a / fdn_a", e_bin, bin_tol_scale)
+        e_bin = float(np.max(per_bin_difference(wg.amean, wg.amean, wo.amean, wo.amean)))
+        assert e_bin <= bin_tol_scale * TOL_LEVEL, ("per bin, amean", e_bin, bin_tol_scale)
         assert _rel(wg.tau_band, wo.tau_band) <= RTOL_OPR
     assert _scaled(r.f_total, o.f_total) <= f * TOL_LEVEL
     for a, b in zip(r.opr(), o.opr()):
