@@ -22,8 +22,9 @@ Bounds -- none of them taken from what the kernels give:
     the difference of the oracle's two compilations as the yardstick: max(1e-9, 10 x yardstick) for the response form,
     5 x that for the general kernel
 
-The closed forms take tau[nz][ng][nw] from the code under test (closed_forms.py says why); tau itself is held by
-`band_mean` here, by test_gpu_parity._compare's 1e-11 against the oracle and by test_mixing_step_with_every_kind_of_wave.
+The closed forms take tau[nz][ng][nw] from the code under test here; tau itself is held by `band_mean` here and,
+element by element, by `mixing_split` in test_gpu_mixing_split.py, which also runs the pure-absorption cases with no tau
+supplied.
 
 Measured on an MI355X (worst over all cases and launch forms; pytest -s prints each):
   * tau_band 1.7e-13, g 6.2e-15 (margin to 1e-11: 58x); sum_g w_g tau against tau_band 3.0e-16, w0 tau against scat

@@ -908,30 +908,10 @@ def test_mixing_step_with_every_kind_of_wave(O):
     The closed-form rows differ from the sorted path at the 1e-15 level: which is why this is a
     tolerance test and not a bitwise one."""
     from clima_amd import synthetic as S
+    from closed_forms import every_kind_tables
     nz = 70
     for sorted_k in (True, False):
-        tb = S.make_tables(nw=24, seed=77, sorted_k=sorted_k)
-        ng = tb.ng
-        g = np.arange(ng, dtype=float)
-        for bi in range(tb.nw):
-            kind = bi % 4
-            for si, k in enumerate(tb.ktables):
-                a = k["log10k"]                      # [bin][T][P][g]
-                smooth = 0.002 * (k["temp"][:, None] - 300.0) + 0.1 * (k["log10P"][None, :] + 2.0)
-                col_scale = -np.log10({"H2O": 5e22, "CO2": 8e21, "O2": 4.5e24, "O3": 1e19, "CH4": 4e19}[tb.species_names[k["sp_ind"]]])
-                if kind == 0:      # species 0 wide gaps; the others tiny and nearly flat: rows never interleave
-                    base, ramp = (-1.0, 1.0) if si == 0 else (-9.0 - si, 0.004)
-                elif kind == 1:    # species 1 dominant with wide gaps over a narrow mixture: columns never interleave
-                    base, ramp = (-6.0, 0.01) if si == 0 else ((0.0, 1.1) if si == 1 else (-9.0 - si, 0.003))
-                elif kind == 2:    # comparable sizes: everything interleaves
-                    base, ramp = -2.0 + 0.1 * si, 0.35
-                else:              # steep tails: the top rows peel off, the bottom ones interleave
-                    base, ramp = -3.0 + 0.05 * si, 0.0
-                vals = base + ramp * g + (0.0 if kind != 3 else 0.02 * g + 0.9 * np.maximum(g - 4.0, 0.0) ** 1.5)
-                a[bi] = col_scale - 2.0 + smooth[:, :, None] + vals[None, None, :]
-            if not sorted_k:
-                for k in tb.ktables:
-                    k["log10k"][bi] = k["log10k"][bi][..., ::-1] if bi % 2 else np.roll(k["log10k"][bi], 3, axis=-1)
+        tb = every_kind_tables(24, sorted_k)
         r, o = _pair(O, tb, nz, 2, 0.2)
         r.coop_items = 0          # the lane-per-item tile (the assembly block) whatever the item count
         _compare_once(r, o, S.modern_earth_column(nz))
