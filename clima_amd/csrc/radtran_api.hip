@@ -116,6 +116,17 @@ struct WrkObj {  // ClimaRadtranWrk, clima_radtran.f90:11-25
   DevBuf<double> fup_a, fdn_a, amean, tau_band;
 };
 
+// A column batch in flight (radtran_toa_fluxes_batch and its device-array form): the launch form batch_form decided
+// for its n columns, once -- one launch of each kernel per chunk of CH columns, or the columns' calls back to back --,
+// the id of its first call, and its sink: the caller's device arrays (k_batch_finish forms f_total / ISR / OLR
+// there), or `rows`, n blocks [5][nz+1] on the host (which forms them itself).
+struct BatchRun {
+  int n = 0, first_call = 0, CH = 0;
+  bool one_launch = false, pending = false;
+  double *ISR = nullptr, *OLR = nullptr, *fluxes = nullptr;
+  double *rows = nullptr;
+};
+
 struct Radtran {
   unsigned magic = MAGIC;
   int state = 0;  // 0 allocated, 1 begun, 2 finalized
@@ -230,17 +241,12 @@ struct Radtran {
   // one-launch batches: per-column prep / opr / spectra blocks for the columns in flight
   DevBuf<double> d_prep_arena, d_opr_arena, d_res_arena;
   int batch_cols_in_flight = 64;
-  // A batch out of device arrays (radtran_toa_fluxes_batch_device) returns with its work enqueued; what the host
-  // batch does after its synchronise -- the look at the two error words, the repeat through the separate launches
-  // when a fused hand-off wait expired -- is due at the next settle_device_batch().  The repeat reads the column
-  // blocks still in d_cols_arena and writes the caller's same result arrays.
-  struct DeviceBatch {
-    bool pending = false, one_launch = false;
-    int n = 0, first_call = 0;
-    double *ISR = nullptr, *OLR = nullptr, *fluxes = nullptr;
-  } dev_batch;
+  // A batch out of device arrays (radtran_toa_fluxes_batch_device) returns with its work enqueued: its settle_batch
+  // is due at the next settle_device_batch().  A repeat reads the column blocks still in d_cols_arena and writes the
+  // caller's same result arrays.
+  BatchRun dev_batch;
   DevBuf<int> d_batch_nsrc;        // every column's source-layer count, as k_pack_columns found it
-  std::vector<int> batch_nsrc;     // ... on the host (fetched only for one call per column: those launches are sized by it)
+  std::vector<int> batch_nsrc;     // ... on the host: pack_column's, or fetched (only before one call per column: those launches are sized by it)
   hipEvent_t ev_producer = nullptr;   // orders the handle's stream behind the stream that wrote a device batch's inputs
   bool batch_shared = true;        // radiate_ir_batch: temperature-independent work shared by the columns (CLIMA_HIP_BATCH_SHARED=0: one full solve per column)
   int rebin_mode = 1;              // 0 window form, 1 streaming, 2 streaming multi-edge (rebin_mode_for)
@@ -988,15 +994,20 @@ bool recover_fused_timeout(Radtran *r) {
   return true;
 }
 
+constexpr const char *OPACITY_FAILED_MSG = "Opacity computation failed in one or more wavelength bins.";  // clima_radtran_types.f90:773-776
 bool surface_device_error(Radtran *r, char *err) {
   const bool failed = *r->h_errflag > r->checked_id;  // a call since the last check flagged
   r->checked_id = r->call_id;
-  if (failed) {
-    // clima_radtran_types.f90:773-776
-    set_err(err, "Opacity computation failed in one or more wavelength bins.");
-    return true;
-  }
-  return false;
+  if (failed) set_err(err, OPACITY_FAILED_MSG);
+  return failed;
+}
+
+// The two error words (opacity failure, expired fused hand-off wait: the ids of the last calls that flagged them) as
+// they stand once everything enqueued so far has run
+void wait_error_words(Radtran *r) {
+  HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipStreamSynchronize(r->stream));
+  resolve_events(r);
 }
 
 // Everything enqueued so far has run, and a fused hand-off that timed out has been repaired: after this the
@@ -1005,11 +1016,9 @@ bool surface_device_error(Radtran *r, char *err) {
 void settle(Radtran *r) {
   settle_device_batch(r);
   for (int pass = 0; pass < 2; pass++) {
-    HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
     if (r->comm && !r->small_valid)   // the reduced status word (the rows themselves are fetched when they are read)
       HIPCHK(hipMemcpyAsync(&r->comm_status, r->d_small.p + 4 * (r->nz + 1), sizeof(double), hipMemcpyDeviceToHost, r->stream));
-    HIPCHK(hipStreamSynchronize(r->stream));
-    resolve_events(r);
+    wait_error_words(r);
     if (!r->column_loaded || !recover_fused_timeout(r)) break;
   }
 }
@@ -1018,23 +1027,29 @@ void defer_err(Radtran *r, const std::string &msg) {
   if (r && r->deferred_err.empty()) r->deferred_err = msg;
 }
 
-// The launch form of a batch of n columns (radtran_toa_fluxes_batch and its device-array form decide it here, once):
-// one launch of each kernel per chunk of CH columns (the fused grid takes the columns' work items in turn, so one
-// column's two-stream tail runs beside the next column's opacity tiles) where the fused form covers the
-// configuration -- the per-column arenas of a chunk are sized here --, otherwise the columns' calls back to back.
-struct BatchForm {
-  int CH;
-  bool one_launch;
-  CallBufs first;   // the first chunk (only its counts are read)
-};
-BatchForm batch_form(Radtran *r, int n) {
-  BatchForm f{std::min(n, r->batch_cols_in_flight), false, CallBufs{}};
-  f.first = arena_chunk_bufs(r, 0, f.CH);
-  f.one_launch = plan_radiate(plan_input(r, f.first, true, true, true)).fused.form != TS_NONE &&
+// ---- column batches (radtran_toa_fluxes_batch, radtran_toa_fluxes_batch_device): one path, two sinks ----
+// An earlier batch's checks (and its repeat, which reads the arena this one overwrites), then room for n columns'
+// blocks and level rows (and their source-layer counts, where the device finds them)
+void begin_batch(Radtran *r, int n, bool nsrc_on_device) {
+  settle_device_batch(r);
+  const size_t rows = (size_t)n * 5 * (r->nz + 1);
+  if (r->d_cols_arena.n < (size_t)n * r->col_count) r->d_cols_arena.alloc((size_t)n * r->col_count);
+  if (r->d_flux_arena.n < rows) r->d_flux_arena.alloc(rows);
+  if (nsrc_on_device && r->d_batch_nsrc.n < (size_t)n) r->d_batch_nsrc.alloc(n);
+}
+// The launch form of a batch of n columns, decided here, once: one launch of each kernel per chunk of CH columns
+// (the fused grid takes the columns' work items in turn, so one column's two-stream tail runs beside the next
+// column's opacity tiles) where the fused form covers the configuration -- the per-column arenas of a chunk are
+// sized here --, otherwise the columns' calls back to back.
+BatchRun batch_form(Radtran *r, int n) {
+  BatchRun f;
+  f.n = n; f.first_call = r->call_id + 1; f.CH = std::min(n, r->batch_cols_in_flight);
+  const CallBufs first = arena_chunk_bufs(r, 0, f.CH);   // the first chunk (only its counts are read)
+  f.one_launch = plan_radiate(plan_input(r, first, true, true, true)).fused.form != TS_NONE &&
                  integrate_chunks(std::max(r->ir_n, r->sol_n)) * (32 + 16) * sizeof(double) <= 64 * 1024;
   if (const char *e = getenv("CLIMA_HIP_BATCH_ONE_LAUNCH")) f.one_launch = f.one_launch && atoi(e) != 0;
   if (f.one_launch) {
-    const BatchStrides &bs = f.first.bs;
+    const BatchStrides &bs = first.bs;
     if (r->d_prep_arena.n < bs.prep * f.CH) r->d_prep_arena.alloc(bs.prep * f.CH);
     if (r->d_opr_arena.n < bs.opr * f.CH) r->d_opr_arena.alloc(bs.opr * f.CH);
     if (r->d_res_arena.n < bs.res * f.CH) { r->d_res_arena.alloc(bs.res * f.CH); r->d_res_arena.zero(r->stream); }
@@ -1042,16 +1057,66 @@ BatchForm batch_form(Radtran *r, int n) {
   }
   return f;
 }
-// The handle's spectra and band optical depths = the last column's, which a one-launch batch left in the arena
-void batch_keep_last_spectra(Radtran *r, int n, const BatchForm &f) {
-  const SpectraViews src = spectra_views(r, r->d_res_arena.p + (size_t)((n - 1) % f.CH) * f.first.bs.res);
+// the columns' source-layer counts as k_pack_columns found them (4 bytes each): the launches of one call per column are sized by them
+void fetch_batch_nsrc(Radtran *r, int n) {
+  r->batch_nsrc.resize(n);
+  HIPCHK(hipMemcpyAsync(r->batch_nsrc.data(), r->d_batch_nsrc.p, sizeof(int) * n, hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipStreamSynchronize(r->stream));
+}
+// The batch whose column blocks are in d_cols_arena and whose source-layer counts are in batch_nsrc, start to end: the
+// chunks (or the columns' calls), the rows out to the sink, the handle's own level rows = the last column's.  Nothing waits.
+void enqueue_batch(Radtran *r, const BatchRun &b, bool allow_fused) {
+  const int n = b.n, nl = r->nz + 1;
+  if (b.one_launch && allow_fused)
+    for (int c0 = 0; c0 < n; c0 += b.CH) enqueue_radiate(r, arena_chunk_bufs(r, c0, std::min(b.CH, n - c0)), true, true);
+  else
+    for (int c = 0; c < n; c++) enqueue_radiate(r, arena_column_bufs(r, c, r->batch_nsrc[c]), true, true, allow_fused);
+  if (b.rows) {
+    HIPCHK(hipMemcpyAsync(b.rows, r->d_flux_arena.p, sizeof(double) * n * 5 * nl, hipMemcpyDeviceToHost, r->stream));
+  } else {
+    launch_batch_finish(BatchFinishParams{n, r->nz, r->d_flux_arena.p, b.ISR, b.OLR, b.fluxes}, r->stream);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipMemcpyAsync(r->d_flux_n.p, r->d_flux_arena.p + (size_t)(n - 1) * 5 * nl, sizeof(double) * 4 * nl, hipMemcpyDeviceToDevice, r->stream));
+}
+// What the handle holds after a batch is the LAST column's, like after n single calls: its level rows (enqueue_batch),
+// and its spectra / band optical depths -- the one-launch form left those in the batch arena (copied here); its optical
+// properties stay in the arena (opr_valid false: an IR-only call needs a compute_opacity call first).  One call per
+// column works in the handle's own buffers; so does a repeat (settle_batch), which overwrites what is copied here.
+void batch_leaves_handle(Radtran *r, const BatchRun &b) {
+  r->column_loaded = false;   // d_col does not hold the last column: a resident call needs an upload first
+  r->column_has_particles = r->np > 0;
+  r->opr_valid = !b.one_launch;
+  if (!b.one_launch) return;
+  const SpectraViews src = spectra_views(r, r->d_res_arena.p + (size_t)((b.n - 1) % b.CH) * spectra_views(r, nullptr).count);
   auto d2d = [&](DevBuf<double> &dst, const double *from) { HIPCHK(hipMemcpyAsync(dst.p, from, sizeof(double) * dst.n, hipMemcpyDeviceToDevice, r->stream)); };
   d2d(r->wrk_ir.fup_a, src.ir_fup_a); d2d(r->wrk_ir.fdn_a, src.ir_fdn_a); d2d(r->wrk_ir.tau_band, src.ir_tau_band);
   d2d(r->wrk_sol.fup_a, src.sol_fup_a); d2d(r->wrk_sol.fdn_a, src.sol_fdn_a); d2d(r->wrk_sol.amean, src.sol_amean);
   d2d(r->wrk_sol.tau_band, src.sol_tau_band);
 }
-
-// ---- batches out of device arrays (radtran_toa_fluxes_batch_device) ----
+// Everything the batch enqueued has run, and a fused hand-off wait that expired in one of its calls has been repaired:
+// the whole batch again through the separate launches (the column blocks are still in the arena, the results go to the
+// same sink).  Returns whether one of its calls flagged an opacity failure.
+bool settle_batch(Radtran *r, const BatchRun &b) {
+  wait_error_words(r);
+  if (r->h_errflag[1] >= b.first_call) {
+    r->fused_fallbacks++;
+    if (b.one_launch && !b.rows) fetch_batch_nsrc(r, b.n);   // (the host's pack_column returned them)
+    enqueue_batch(r, b, false);
+    wait_error_words(r);
+    r->opr_valid = true;   // one call per column works in the handle's own buffers: they hold the last column's
+  }
+  r->checked_timeout = r->checked_id = r->call_id;
+  invalidate_small(r);   // (the device rows changed: fetch them)
+  return *r->h_errflag >= b.first_call;
+}
+// a device batch still pending: its checks now, an opacity failure kept for the next call that reports errors
+void settle_device_batch(Radtran *r) {
+  if (!r->dev_batch.pending) return;
+  r->dev_batch.pending = false;
+  if (settle_batch(r, r->dev_batch)) defer_err(r, OPACITY_FAILED_MSG);
+}
+// the parameter block of k_pack_columns: the column blocks of a batch built on the device
 PackParams make_pack_params(Radtran *r, int n, const double *T_surface, const double *T, const double *P, const double *dens,
                             const double *dz, const double *pdens, const double *radii, double *blocks, int *nsrc) {
   PackParams p;
@@ -1063,50 +1128,6 @@ PackParams make_pack_params(Radtran *r, int n, const double *T_surface, const do
   p.T_surface = T_surface; p.T = T; p.P = P; p.dz = dz; p.dens = dens; p.pdens = pdens; p.radii = radii;
   p.blocks = blocks; p.nsrc = nsrc;
   return p;
-}
-// the columns' source-layer counts (4 bytes each): the launches of one call per column are sized by them
-void fetch_batch_nsrc(Radtran *r, int n) {
-  r->batch_nsrc.resize(n);
-  HIPCHK(hipMemcpyAsync(r->batch_nsrc.data(), r->d_batch_nsrc.p, sizeof(int) * n, hipMemcpyDeviceToHost, r->stream));
-  HIPCHK(hipStreamSynchronize(r->stream));
-}
-// The batch whose column blocks are in d_cols_arena, start to end: the chunks (or the columns' calls), f_total / ISR /
-// OLR and the rows out to the caller's arrays, the handle's own level rows = the last column's.  Nothing waits.
-void enqueue_device_batch(Radtran *r, const Radtran::DeviceBatch &b, bool allow_fused) {
-  const int n = b.n, nl = r->nz + 1, CH = std::min(n, r->batch_cols_in_flight);
-  if (b.one_launch && allow_fused)
-    for (int c0 = 0; c0 < n; c0 += CH) enqueue_radiate(r, arena_chunk_bufs(r, c0, std::min(CH, n - c0)), true, true);
-  else
-    for (int c = 0; c < n; c++) enqueue_radiate(r, arena_column_bufs(r, c, r->batch_nsrc[c]), true, true, allow_fused);
-  launch_batch_finish(BatchFinishParams{n, r->nz, r->d_flux_arena.p, b.ISR, b.OLR, b.fluxes}, r->stream);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(r->d_flux_n.p, r->d_flux_arena.p + (size_t)(n - 1) * 5 * nl, sizeof(double) * 4 * nl, hipMemcpyDeviceToDevice, r->stream));
-}
-// What the host batch does behind its synchronise, for a device batch still pending: wait, look at the two error
-// words, repeat the batch through the separate launches if a fused hand-off wait of one of its calls expired
-// (the column blocks are still in the arena, the results go to the caller's same arrays), keep an opacity failure
-// for the next call that reports errors.
-void settle_device_batch(Radtran *r) {
-  if (!r->dev_batch.pending) return;
-  const Radtran::DeviceBatch b = r->dev_batch;
-  r->dev_batch.pending = false;
-  auto wait = [&] {
-    HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
-    HIPCHK(hipStreamSynchronize(r->stream));
-    resolve_events(r);
-  };
-  wait();
-  if (r->h_errflag[1] >= b.first_call) {
-    r->fused_fallbacks++;
-    if (b.one_launch) fetch_batch_nsrc(r, b.n);
-    enqueue_device_batch(r, b, false);
-    wait();
-    r->opr_valid = true;   // one call per column works in the handle's own buffers: they hold the last column's
-  }
-  r->checked_timeout = r->call_id;
-  r->checked_id = r->call_id;
-  invalidate_small(r);
-  if (*r->h_errflag >= b.first_call) defer_err(r, "Opacity computation failed in one or more wavelength bins.");  // clima_radtran_types.f90:773-776
 }
 // device memory of the handle's device?  (an address the runtime does not know -- pageable host memory -- is an
 // error return on some runtimes and "unregistered" on others)
@@ -2238,65 +2259,21 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   const int hp = has_particles ? *has_particles : 0;
   if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return; }
   TRY
-  settle_device_batch(r);
   const int nz = r->nz, nl = nz + 1, n = *ncol;
   const size_t cc = r->col_count, np_n = (size_t)nz * r->np;
-  std::vector<double> h((size_t)n * cc, 0.0);
-  std::vector<int> nsrc_h(n);
+  begin_batch(r, n, false);
+  std::vector<double> h((size_t)n * cc, 0.0), out((size_t)n * 5 * nl);
+  r->batch_nsrc.resize(n);
   for (int c = 0; c < n; c++)
-    nsrc_h[c] = pack_column(r, h.data() + (size_t)c * cc, T_surface[c], T + (size_t)c * nz, P + (size_t)c * nz, dz + (size_t)c * nz,
-                            densities + (size_t)c * nz * r->nsp, r->np > 0 ? pdensities + c * np_n : nullptr,
-                            r->np > 0 ? radii + c * np_n : nullptr);
-  if (r->d_cols_arena.n < h.size()) r->d_cols_arena.alloc(h.size());
-  if (r->d_flux_arena.n < (size_t)n * 5 * nl) r->d_flux_arena.alloc((size_t)n * 5 * nl);
+    r->batch_nsrc[c] = pack_column(r, h.data() + (size_t)c * cc, T_surface[c], T + (size_t)c * nz, P + (size_t)c * nz, dz + (size_t)c * nz,
+                                   densities + (size_t)c * nz * r->nsp, r->np > 0 ? pdensities + c * np_n : nullptr,
+                                   r->np > 0 ? radii + c * np_n : nullptr);
   HIPCHK(hipMemcpyAsync(r->d_cols_arena.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, r->stream));
-  r->column_has_particles = r->np > 0;
-  const int first_call = r->call_id + 1;
-  std::vector<double> out((size_t)n * 5 * nl);
-  // One launch of each kernel per chunk of columns (the fused grid takes the columns' work items in
-  // turn, so one column's two-stream tail runs beside the next column's opacity tiles) where the fused
-  // form covers the configuration; otherwise the calls of the columns are enqueued back to back.
-  const BatchForm form = batch_form(r, n);
-  const int CH = form.CH;
-  const bool one_launch = form.one_launch;
-  auto run_all = [&](bool allow_fused) {
-    if (one_launch && allow_fused)
-      for (int c0 = 0; c0 < n; c0 += CH) enqueue_radiate(r, arena_chunk_bufs(r, c0, std::min(CH, n - c0)), true, true);
-    else
-      for (int c = 0; c < n; c++) enqueue_radiate(r, arena_column_bufs(r, c, nsrc_h[c]), true, true, allow_fused);
-    HIPCHK(hipMemcpyAsync(out.data(), r->d_flux_arena.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, r->stream));
-    HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
-    // the handle's own level fluxes = the last column's
-    HIPCHK(hipMemcpyAsync(r->d_flux_n.p, r->d_flux_arena.p + (size_t)(n - 1) * 5 * nl, sizeof(double) * 4 * nl, hipMemcpyDeviceToDevice, r->stream));
-    HIPCHK(hipStreamSynchronize(r->stream));
-    resolve_events(r);
-  };
-  run_all(true);
-  bool fell_back = false;
-  if (r->h_errflag[1] >= first_call) {  // a fused hand-off wait expired in some column: the batch again, unfused
-    r->fused_fallbacks++;
-    run_all(false);
-    fell_back = true;
-  }
-  r->checked_timeout = r->call_id;
-  invalidate_small(r);   // (the device rows changed: fetch them)
-  r->column_loaded = false;   // d_col does not hold the last column: a resident call needs an upload first
-  // What the handle holds afterwards is the LAST column's, like after n single calls: its level rows (copied above),
-  // and its spectra / band optical depths -- the one-launch form left those in the batch arena (copied here);
-  // its optical properties stay in the arena (opr_valid false: an IR-only call needs a compute_opacity call first),
-  // unless the batch fell back to one call per column, which works in the handle's own buffers.
-  const bool in_arena = one_launch && !fell_back;
-  r->opr_valid = !in_arena;
-  if (in_arena) {
-    batch_keep_last_spectra(r, n, form);
-    HIPCHK(hipStreamSynchronize(r->stream));
-  }
-  if (*r->h_errflag >= first_call) {
-    r->checked_id = r->call_id;
-    set_err(err, "Opacity computation failed in one or more wavelength bins.");  // clima_radtran_types.f90:773-776
-    return;
-  }
-  r->checked_id = r->call_id;
+  BatchRun run = batch_form(r, n);
+  run.rows = out.data();
+  enqueue_batch(r, run, true);
+  batch_leaves_handle(r, run);
+  if (settle_batch(r, run)) { set_err(err, OPACITY_FAILED_MSG); return; }
   for (int c = 0; c < n; c++) {
     double *f = out.data() + (size_t)c * 5 * nl;
     f_total_row(f, nl);
@@ -2342,11 +2319,8 @@ void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d
       return;
     }
   }
-  settle_device_batch(r);   // an earlier batch's checks (and its repeat, which reads the arena this one overwrites)
-  const int nz = r->nz, nl = nz + 1, n = *ncol;
-  if (r->d_cols_arena.n < (size_t)n * r->col_count) r->d_cols_arena.alloc((size_t)n * r->col_count);
-  if (r->d_flux_arena.n < (size_t)n * 5 * nl) r->d_flux_arena.alloc((size_t)n * 5 * nl);
-  if (r->d_batch_nsrc.n < (size_t)n) r->d_batch_nsrc.alloc(n);
+  const int n = *ncol;
+  begin_batch(r, n, true);
   if (producer_stream) {
     if (!r->ev_producer) HIPCHK(hipEventCreateWithFlags(&r->ev_producer, hipEventDisableTiming));
     HIPCHK(hipEventRecord(r->ev_producer, reinterpret_cast<hipStream_t>(const_cast<void *>(producer_stream))));
@@ -2355,22 +2329,13 @@ void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d
   launch_pack_columns(make_pack_params(r, n, d_T_surface, d_T, d_P, d_densities, d_dz, part ? d_pdensities : nullptr,
                                        part ? d_radii : nullptr, r->d_cols_arena.p, r->d_batch_nsrc.p), r->stream);
   HIPCHK(hipGetLastError());
-  r->column_has_particles = part;
-  Radtran::DeviceBatch b;
-  b.n = n; b.first_call = r->call_id + 1;
-  b.ISR = d_ISR; b.OLR = d_OLR; b.fluxes = d_fluxes;
-  const BatchForm form = batch_form(r, n);
-  b.one_launch = form.one_launch;
-  if (!b.one_launch) fetch_batch_nsrc(r, n);
-  enqueue_device_batch(r, b, true);
-  // the handle afterwards: the last column's level rows (copied above), spectra and band optical depths; its optical
-  // properties stay in the arena after a one-launch batch (opr_valid false), as after the host batch
-  invalidate_small(r);
-  r->column_loaded = false;
-  r->opr_valid = !b.one_launch;
-  if (b.one_launch) batch_keep_last_spectra(r, n, form);
-  b.pending = true;
-  r->dev_batch = b;
+  BatchRun run = batch_form(r, n);
+  run.ISR = d_ISR; run.OLR = d_OLR; run.fluxes = d_fluxes;
+  if (!run.one_launch) fetch_batch_nsrc(r, n);
+  enqueue_batch(r, run, true);
+  batch_leaves_handle(r, run);
+  run.pending = true;
+  r->dev_batch = run;
   CATCH(err)
 }
 

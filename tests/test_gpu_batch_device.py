@@ -299,11 +299,56 @@ def test_expired_handoff_is_repaired_at_synchronize():
     r.synchronize()                          # settled: nothing is repeated twice
     assert r.fused_fallbacks == n0 + 1
     np.testing.assert_array_equal(np.array(r.f_total), want[2][:, 4, -1])
+    left = handle_state(r) + r.opr()         # what the repaired device batch left in the handle's own buffers
     n1 = r.fused_fallbacks
     host = r.TOA_fluxes_batch(cols, return_fluxes=True)      # the host batch on this handle repeats itself the same way
     assert r.fused_fallbacks == n1 + 1
     for g, h, name in zip(got, host, names):
         np.testing.assert_array_equal(g, h, err_msg=name)
+    # ... and leaves the handle holding the same: the last column's rows, spectra and optical properties
+    for g, w, name in zip(handle_state(r) + r.opr(), left, ("f_total", "wrk_ir.fup_a", "wrk_sol.tau_band", "tau", "w0", "g", "tau_band")):
+        np.testing.assert_array_equal(g, w, err_msg=name)
+
+
+OPACITY_FAILED = "Opacity computation failed in one or more wavelength bins."
+
+
+@pytest.mark.parametrize("form", ["per_column", "one_launch"])
+def test_opacity_failure_inside_a_batch(small_tables, form):
+    """The middle column of three has particle radii outside the Mie grid (the reference's own ierr path, as in
+    test_error_behaviour_matches_reference): the host batch reports it in its own call, the device batch at the next
+    synchronize() -- once --, no route mistakes it for an expired hand-off wait, and the handle computes the good
+    columns afterwards as a fresh handle does.  50 layers run one call per column, the 102 doubled ones one launch
+    per chunk."""
+    from clima_amd import synthetic as S
+    from clima_amd.radtran import ClimaException, Radtran
+    good = S.perturbed_columns(3, 50) if form == "per_column" else doubled(50, 3)
+    bad = list(good)
+    bad[1] = S.Column(good[1])
+    bad[1]["radii"] = np.asarray(good[1]["radii"]) * 1e6
+    r = Radtran(small_tables, len(good[0]["T"]), NZEN, ALBEDO)
+    assert r.np == 1
+    n0 = r.fused_fallbacks
+    fresh = r.TOA_fluxes_batch(good, return_fluxes=True)
+    # host route
+    with pytest.raises(ClimaException, match=OPACITY_FAILED):
+        r.TOA_fluxes_batch(bad, return_fluxes=True)
+    for g, w, name in zip(r.TOA_fluxes_batch(good, return_fluxes=True), fresh, ("ISR", "OLR", "fluxes")):
+        np.testing.assert_array_equal(g, w, err_msg=name)
+    # device route, sync=False: reported at synchronize(), once
+    t = tensors(bad, r.np)
+    out = r.TOA_fluxes_batch_tensors(**t, return_fluxes=True, sync=False)
+    with pytest.raises(ClimaException, match=OPACITY_FAILED):
+        r.synchronize()
+    r.synchronize()
+    del out
+    for g, w, name in zip(assert_same_batch(r, good), fresh, ("ISR", "OLR", "fluxes")):
+        np.testing.assert_array_equal(g, w, err_msg=name)
+    # device route, sync=True
+    with pytest.raises(ClimaException, match=OPACITY_FAILED):
+        r.TOA_fluxes_batch_tensors(**t, return_fluxes=True)
+    assert_same_batch(r, good, sync=False)
+    assert r.fused_fallbacks == n0
 
 
 def test_inputs_written_on_another_torch_stream(small_tables):
