@@ -378,13 +378,13 @@ __device__ __forceinline__ ColumnDev column_at(const ColumnDev &c0, const BatchS
   return c;
 }
 
-__global__ __launch_bounds__(256) void k_prep(PrepParams p) {
+// the body of block `bx` of column `cb` (k_prep; k_prep_integrate runs it in the blocks behind its integration blocks)
+__device__ __forceinline__ void prep_block(const PrepParams &p, const int bx, const int cb) {
   __shared__ double s_axis[PREP_AXIS_MAX];
   const int nz = p.nz;
-  const int cb = blockIdx.y;
   const ColumnDev c = column_at(p.col, p.bs, cb);
   const int *src = c.meta + 1 + nz;  // source layer of every layer (pair_reuse, decided on the host)
-  if (blockIdx.x == 0) {
+  if (bx == 0) {
     for (int j = threadIdx.x; j < nz; j += blockDim.x) {
       const double Pj = c.P[j], dzj = c.dz[j];
       double fc = 0.0;
@@ -407,18 +407,18 @@ __global__ __launch_bounds__(256) void k_prep(PrepParams p) {
     }
     return;
   }
-  if ((int)blockIdx.x > p.nslots + p.nabs) {
+  if (bx > p.nslots + p.nabs) {
     // spare blocks clear the output spectra that the two-stream kernel accumulates into
-    const int zb = (int)blockIdx.x - (p.nslots + p.nabs + 1);
+    const int zb = bx - (p.nslots + p.nabs + 1);
     const int arr = zb / PREP_ZERO_BLOCKS, part = zb - arr * PREP_ZERO_BLOCKS;
     double *dst = p.zero_ptr[arr] + (size_t)cb * p.bs.res;
     const size_t n = p.zero_count[arr];
     for (size_t i = (size_t)part * blockDim.x + threadIdx.x; i < n; i += (size_t)PREP_ZERO_BLOCKS * blockDim.x) dst[i] = 0.0;
     return;
   }
-  if ((int)blockIdx.x > p.nslots) {
+  if (bx > p.nslots) {
     // bin-independent weight of one continuum term for every layer (types.f90:696-723)
-    const int e = (int)blockIdx.x - p.nslots - 1;
+    const int e = bx - p.nslots - 1;
     const int a = p.abs_a[e], b = p.abs_b[e], kind = p.abs_kind[e];
     for (int j = threadIdx.x; j < nz; j += blockDim.x) {
       double w;
@@ -439,7 +439,7 @@ __global__ __launch_bounds__(256) void k_prep(PrepParams p) {
   // interpolation bracket and weight of one slot for every layer; reuse layers take their
   // source layer's inputs, which is what copying its interpolated value amounts to
   // (:652-653, :907-908, :933-935, :963-968)
-  const int s = blockIdx.x - 1;
+  const int s = bx - 1;
   const SlotDev &sl = p.slots[s];
   const bool in_lds = sl.n <= PREP_AXIS_MAX;
   // this thread's first layer: its input goes out together with the axis (and, for a layer that is its own source -- all of
@@ -469,6 +469,8 @@ __global__ __launch_bounds__(256) void k_prep(PrepParams p) {
     c.q[s * nz + j] = (x - axis[i]) / (axis[i + 1] - axis[i]);  // linear_interpolation_module.F90:256, :319-320
   }
 }
+
+__global__ __launch_bounds__(256) void k_prep(PrepParams p) { prep_block(p, blockIdx.x, blockIdx.y); }
 
 void launch_prep(const PrepParams &p, hipStream_t s) {
   hipLaunchKernelGGL(k_prep, dim3(1 + p.nslots + p.nabs + p.nzero * PREP_ZERO_BLOCKS, p.ncol > 0 ? p.ncol : 1), dim3(256), 0, s, p);
@@ -3641,18 +3643,17 @@ int integrate_chunks(int nbins) { return nbins <= 0 ? 1 : (nbins + INT_CHUNK - 1
 constexpr int INT_LV = CLIMA_INT_LV;   // levels per block: 13 x 4 blocks at nz = 200
 constexpr int INT_CG = CLIMA_INT_CG;   // chunk groups: threads = INT_LV * INT_CG = 512
 
-__global__ __launch_bounds__(INT_LV * INT_CG) void k_integrate_one(IntegrateParams p) {
-  extern __shared__ __align__(16) double s_int[];  // widths [nchunk*INT_CHUNK], then partial [nchunk][INT_LV]
-  const int a = blockIdx.y;
+// the body of block (level group `bx`, array `a`, column `cb`); s_int: widths [nchunk*INT_CHUNK], then partial [nchunk][INT_LV]
+__device__ __forceinline__ void integrate_block(const IntegrateParams &p, const int bx, const int a, const int cb, double *s_int) {
   const bool sol = a >= 2;
   const int nl = p.nz + 1;
   const int lv = threadIdx.x % INT_LV, cg = threadIdx.x / INT_LV;
-  const int i = blockIdx.x * INT_LV + lv;
-  if (p.timeout_out && a == 0 && blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) {
+  const int i = bx * INT_LV + lv;
+  if (p.timeout_out && a == 0 && bx == 0 && cb == 0 && threadIdx.x == 0) {
     const int t = *p.timeout_flag;   // the fused grid of this call has drained: the word is final
     *p.timeout_out = (t == p.id_opr ? 1.0 : 0.0) + (t == p.id_sol ? 1024.0 : 0.0);
   }
-  if (p.host_out && a == 0 && blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x < 2)   // the error words ride along
+  if (p.host_out && a == 0 && bx == 0 && cb == 0 && threadIdx.x < 2)   // the error words ride along
     reinterpret_cast<int *>(p.host_out + 5 * nl)[threadIdx.x] = p.err_words[threadIdx.x];
   if (sol && !p.do_solar) {
     // solar rows keep the last solar call's values (clima_radtran.f90:286-289).  On a bin-sharded
@@ -3662,7 +3663,6 @@ __global__ __launch_bounds__(INT_LV * INT_CG) void k_integrate_one(IntegratePara
     if (p.host_out && cg == 0 && i < nl) p.host_out[a * nl + i] = p.flux_n[a * nl + i];
     return;
   }
-  const int cb = blockIdx.z;  // column of a batch
   const double *src = (a == 0 ? p.ir_fup_a : a == 1 ? p.ir_fdn_a : a == 2 ? p.sol_fup_a : p.sol_fdn_a) + (size_t)cb * p.bs.res;
   double *const flux_n = p.flux_n + (size_t)cb * p.bs.flux;
   const double *freq = sol ? p.sol_freq : p.ir_freq;
@@ -3703,9 +3703,42 @@ __global__ __launch_bounds__(INT_LV * INT_CG) void k_integrate_one(IntegratePara
   }
 }
 
+__global__ __launch_bounds__(INT_LV * INT_CG) void k_integrate_one(IntegrateParams p) {
+  extern __shared__ __align__(16) double s_int[];
+  integrate_block(p, blockIdx.x, blockIdx.y, blockIdx.z, s_int);
+}
+
+// One call's integration and the NEXT call's prep pass in one grid (a pipelined sequence of resident calls: the two are
+// adjacent on the stream and independent -- the integration reads the finished call's spectra and writes the level rows,
+// the prep pass reads the column and writes brackets, weights and columns).  Blocks [0, 4 * level groups) are
+// k_integrate_one's, array-major like its grid, dispatched first because they run longer; the blocks behind them are
+// k_prep's.  Nothing passes between the two kinds.  Single calls only, and a prep pass that clears nothing (it would
+// clear the spectra being integrated): prep_integrate_merges().
+static_assert(sizeof(PrepParams) + sizeof(IntegrateParams) <= 4096, "k_prep_integrate: the two parameter blocks share the 4 KiB kernel-argument segment");
+__global__ __launch_bounds__(INT_LV * INT_CG) void k_prep_integrate(PrepParams pp, IntegrateParams ip) {
+  extern __shared__ __align__(16) double s_int[];
+  const int nlb = (ip.nz + 1 + INT_LV - 1) / INT_LV;
+  const int b = blockIdx.x;
+  if (b < 4 * nlb) integrate_block(ip, b % nlb, b / nlb, 0, s_int);
+  else prep_block(pp, b - 4 * nlb, 0);
+}
+
 // true when launch_integrate() takes the one-launch kernel (the form that can store into the host's block)
 bool integrate_one_launch(const IntegrateParams &p) {
   return sizeof(double) * (size_t)p.nchunk * (INT_CHUNK + INT_LV) <= 64 * 1024;
+}
+
+// true when k_prep_integrate can stand for launch_integrate(ip) followed by launch_prep(pp)
+bool prep_integrate_merges(const PrepParams &pp, const IntegrateParams &ip) {
+  const size_t lds = sizeof(double) * ((size_t)ip.nchunk * (INT_CHUNK + INT_LV) + PREP_AXIS_MAX);   // dynamic + prep_block's axis
+  return pp.ncol <= 1 && ip.ncol <= 1 && pp.nzero == 0 && pp.nz == ip.nz && !ip.host_out && !ip.timeout_out &&
+         integrate_one_launch(ip) && lds <= 48 * 1024;
+}
+
+void launch_prep_integrate(const PrepParams &pp, const IntegrateParams &ip, hipStream_t s) {
+  const int nlb = (ip.nz + 1 + INT_LV - 1) / INT_LV;
+  const size_t lds = sizeof(double) * (size_t)ip.nchunk * (INT_CHUNK + INT_LV);
+  hipLaunchKernelGGL(k_prep_integrate, dim3(4 * nlb + 1 + pp.nslots + pp.nabs), dim3(INT_LV * INT_CG), lds, s, pp, ip);
 }
 
 void launch_integrate(const IntegrateParams &p, hipStream_t s) {

@@ -256,6 +256,14 @@ struct Radtran {
   bool ts_block_mode = false;      // CLIMA_HIP_TS_MODE=block when the handle was made: the workgroup-per-bin two-stream kernel
   int ts_ncols_env = 0;            // CLIMA_HIP_TS_NCOLS (that kernel's columns per block), 0: its own choice
   DevBuf<int> d_done;              // per opacity block: call id of its last completed run
+  // A resident call that returns with nobody reading its results keeps its frequency integration back (pending_ip): the
+  // next compute_opacity call launches it in one grid with its own prep pass (k_prep_integrate), anything else launches
+  // it first as it is (resolve_pending_integration).
+  bool defer_integration = true;   // radtran_defer_integration_set
+  bool flux_ptr_taken = false;     // radtran_flux_device_ptr was called: its caller reads d_small in stream order, unannounced
+  bool int_pending = false;
+  IntegrateParams pending_ip;
+  long merged_integrations = 0, standalone_integrations = 0;   // pending integrations resolved either way (radtran_merged_integrations_get)
   int profile = 0;   // 0 off, 1 HIP events around every kernel, 2 around the dominant kernel (id 1) only
   long timer_calls = 0;
   int profile_stride = 1;   // events on every profile_stride-th call only (bounds the cost of measuring)
@@ -283,6 +291,7 @@ struct Radtran {
     if (ev_upload) (void)hipEventDestroy(ev_upload);
     if (ev_producer) (void)hipEventDestroy(ev_producer);
     if (comm) (void)ncclCommDestroy(comm);
+    // (an integration still pending is dropped: nobody is left to read its rows)
     if (stream) (void)hipStreamDestroy(stream);
     magic = 0;
   }
@@ -819,8 +828,44 @@ void ensure_w0(Radtran *r) {
   r->w0_valid = true;
 }
 
+// May a resident call on this handle keep its integration back?  Not on a bin-sharded handle or one with a communicator
+// (the all-reduce follows the integration), not with per-kernel events (they need the four kernels apart), not while the
+// stream is being captured (a graph holds whole calls), not once the flux device pointer is out, not with the switch off.
+bool defer_allowed(bool switch_on, int shard_world, bool has_comm, int profile, bool capturing, bool flux_ptr_taken) {
+  return switch_on && shard_world == 1 && !has_comm && profile != 1 && !capturing && !flux_ptr_taken;
+}
+bool defer_allowed_but_for_capture(const Radtran *r) {
+  return defer_allowed(r->defer_integration, r->shard_world, r->comm != nullptr, r->profile, false, r->flux_ptr_taken);
+}
+bool stream_capturing(Radtran *r) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  HIPCHK(hipStreamIsCapturing(r->stream, &st));
+  return st != hipStreamCaptureStatusNone;
+}
+bool defer_eligible(Radtran *r) {
+  return defer_allowed_but_for_capture(r) && !stream_capturing(r);   // (the runtime is asked only where the answer decides)
+}
+// THE place where a pending integration is resolved.  With the prep parameters of a compute_opacity call that is about
+// to launch its prep pass (and clears nothing there): both in one grid where k_prep_integrate covers them -- returns
+// true, the prep pass is launched.  Otherwise (prep null: everything else that enqueues work or reads results, through
+// settle_device_batch) the integration alone, with the parameters stored when its call was enqueued -- returns false.
+bool resolve_pending_integration(Radtran *r, const PrepParams *prep = nullptr) {
+  if (!r->int_pending) return false;
+  r->int_pending = false;
+  if (prep && r->profile != 1 && prep_integrate_merges(*prep, r->pending_ip) && !stream_capturing(r)) {
+    launch_prep_integrate(*prep, r->pending_ip, r->stream);
+    HIPCHK(hipGetLastError());
+    r->merged_integrations++;
+    return true;
+  }
+  { KernelTimer t(r, 3); launch_integrate(r->pending_ip, r->stream); HIPCHK(hipGetLastError()); t.stop(); }
+  r->standalone_integrations++;
+  return false;
+}
+
 // plan -> prep -> opacity (or the fused grid) -> two-stream -> integrate -> reduce, on the buffers `b` names
-void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused = true) {
+// defer: the caller returns without anyone reading a result, so the integration may wait for the next call's prep launch
+void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused = true, bool defer = false) {
   r->timer_calls++;
   upload_fields(r);
   const bool resident = b.kind == CALL_RESIDENT, chunk = b.kind == CALL_ARENA_CHUNK;
@@ -831,7 +876,10 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
   if (compute_opacity) {
     const int call_id = ++r->call_id;
     const PrepParams pp = make_prep_params(r, b, col, call_id, plan.prep_clears ? &ts : nullptr);
-    { KernelTimer t(r, 0); launch_prep(pp, r->stream); HIPCHK(hipGetLastError()); t.stop(); }
+    // (a prep pass that clears would zero the very spectra a pending integration reads: that one goes first, alone)
+    if (!resolve_pending_integration(r, resident && !plan.prep_clears ? &pp : nullptr)) {
+      KernelTimer t(r, 0); launch_prep(pp, r->stream); HIPCHK(hipGetLastError()); t.stop();
+    }
 
     OpacityParams op = make_opacity_params(r, b, col, plan.write_w0);
     if (plan.fused.form != TS_NONE) {
@@ -860,8 +908,9 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
     r->opr_valid = true;
     if (!chunk) r->w0_valid = op.write_w0 != 0;             // the handle's own optical-property block was written
     if (resident) r->opr_upload_id = r->upload_id;          // ... from the resident column
-  } else if (!chunk) {
-    ensure_w0(r);   // this call's two-stream kernels read the stored optical properties
+  } else {
+    resolve_pending_integration(r);   // (an IR-only call's solar rows are the last solar call's)
+    if (!chunk) ensure_w0(r);   // this call's two-stream kernels read the stored optical properties
   }
   r->last_cs = compute_solar;
   if (compute_solar) r->solar_id = r->call_id;
@@ -880,7 +929,12 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
   const bool reduce = r->comm && resident;
   const IntegrateParams ip = make_integrate_params(r, b, compute_solar, reduce);
   r->small_in_host = ip.host_out != nullptr;
-  { KernelTimer t(r, 3); launch_integrate(ip, r->stream); HIPCHK(hipGetLastError()); t.stop(); }
+  if (defer && resident && !reduce && !ip.host_out && integrate_one_launch(ip) && defer_eligible(r)) {
+    r->pending_ip = ip;
+    r->int_pending = true;
+  } else {
+    KernelTimer t(r, 3); launch_integrate(ip, r->stream); HIPCHK(hipGetLastError()); t.stop();
+  }
   if (reduce) {
     // the step's single collective (src/radtran/clima_radtran_radiate.f90:184-192 summed over the bins of all
     // ranks): in place, on the handle's stream, no host round trip
@@ -892,6 +946,7 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
 
 bool recover_fused_timeout(Radtran *r);
 void settle_device_batch(Radtran *r);
+void settle_pending_batch(Radtran *r);
 
 void fetch_small(Radtran *r) {
   settle_device_batch(r);
@@ -930,7 +985,7 @@ void do_upload(Radtran *r, double T_surface, const double *T, const double *P, c
                const double *dz, const double *pdens, const double *radii) {
   const int nz = r->nz;
   double *h = r->h_col;
-  settle_device_batch(r);
+  settle_pending_batch(r);   // (a pending integration stays: it does not read the column)
   // the pinned staging buffer is reused: wait (lazily, here) for the previous upload's copy
   if (r->upload_pending) { HIPCHK(hipEventSynchronize(r->ev_upload)); r->upload_pending = false; }
   r->nsrc = pack_column(r, h, T_surface, T, P, dz, dens, pdens, radii);
@@ -1110,8 +1165,13 @@ bool settle_batch(Radtran *r, const BatchRun &b) {
   invalidate_small(r);   // (the device rows changed: fetch them)
   return *r->h_errflag >= b.first_call;
 }
-// a device batch still pending: its checks now, an opacity failure kept for the next call that reports errors
+// What the handle still owes before anything else is enqueued or read: a resident call's integration that was kept
+// back (alone, now) and a device batch's checks (an opacity failure kept for the next call that reports errors)
 void settle_device_batch(Radtran *r) {
+  resolve_pending_integration(r);
+  settle_pending_batch(r);
+}
+void settle_pending_batch(Radtran *r) {
   if (!r->dev_batch.pending) return;
   r->dev_batch.pending = false;
   if (settle_batch(r, r->dev_batch)) defer_err(r, OPACITY_FAILED_MSG);
@@ -1476,6 +1536,23 @@ void radtran_fused_fallbacks_get(void *ptr, int *count) {
   Radtran *r = as_rad(ptr);
   *count = r ? r->fused_fallbacks : 0;
 }
+void radtran_defer_integration_set(void *ptr, const int *enable) {
+  Radtran *r = as_rad(ptr);
+  if (r) r->defer_integration = (*enable != 0);
+}
+void radtran_defer_integration_get(void *ptr, int *enabled) {
+  Radtran *r = as_rad(ptr);
+  *enabled = (r && r->defer_integration) ? 1 : 0;
+}
+void clima_test_defer_allowed(const int *switch_on, const int *shard_world, const int *has_comm, const int *profile,
+                              const int *capturing, const int *flux_ptr_taken, int *allowed) {
+  *allowed = defer_allowed(*switch_on != 0, *shard_world, *has_comm != 0, *profile, *capturing != 0, *flux_ptr_taken != 0) ? 1 : 0;
+}
+void radtran_merged_integrations_get(void *ptr, int *merged, int *standalone) {
+  Radtran *r = as_rad(ptr);
+  *merged = r ? (int)std::min<long>(r->merged_integrations, 2147483647L) : 0;
+  *standalone = r ? (int)std::min<long>(r->standalone_integrations, 2147483647L) : 0;
+}
 
 // clima/fortran/Radtran.f90:109-118
 void radtran_unset_custom_optical_properties(void *ptr) {
@@ -1668,7 +1745,7 @@ void radtran_radiate_resident(void *ptr, const int *compute_solar, const int *co
   if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
   if (!r->column_loaded) { set_err(err, "no column has been uploaded"); return; }
   TRY
-  enqueue_radiate(r, resident_bufs(r), *compute_solar != 0, *compute_opacity != 0);
+  enqueue_radiate(r, resident_bufs(r), *compute_solar != 0, *compute_opacity != 0, true, /*defer=*/true);
   CATCH(err)
 }
 
@@ -2500,6 +2577,7 @@ void clima_bench_resident_graph(void *ptr, const int *n, const int *k, double *u
   const int one = 1;
   radtran_radiate_resident(ptr, &one, &one, err);     // steady state: buffers allocated, fields uploaded
   if (err && err[0]) return;
+  settle_device_batch(r);   // (the capture holds one whole call: no integration of the call above in it)
   HIPCHK(hipStreamSynchronize(r->stream));
   // (nothing that synchronises or allocates may run inside the capture: stale fields are uploaded by the call above;
   // per-kernel event profiling records events of its own)
@@ -2568,6 +2646,11 @@ void radtran_flux_device_ptr(void *ptr, void **dptr, int *count) {
   Radtran *r = as_rad(ptr);
   *dptr = r ? (void *)r->d_flux_n.p : nullptr;
   *count = r ? 4 * (r->nz + 1) : 0;
+  if (!r) return;
+  // whoever holds the pointer reads the rows in stream order without telling the library: every call of this handle
+  // integrates at once from here on, and what is pending goes out now
+  r->flux_ptr_taken = true;
+  try { settle_device_batch(r); } catch (const HipFail &f) { defer_err(r, f.msg); }
 }
 
 void radtran_set_bin_shard(void *ptr, const int *rank, const int *world, char *err) {
@@ -2582,6 +2665,7 @@ void radtran_set_bin_shard(void *ptr, const int *rank, const int *world, char *e
     return;
   }
   TRY
+  settle_device_batch(r);
   HIPCHK(hipStreamSynchronize(r->stream));
   r->shard_rank = *rank; r->shard_world = *world;
   compute_shard(r);
@@ -2625,6 +2709,7 @@ void radtran_comm_unique_id(char *id, char *err) {
 
 static void comm_attach(Radtran *r, int nranks, int rank, const char *id) {
   if (r->comm) throw HipFail{"this handle already has a communicator"};
+  settle_device_batch(r);
   HIPCHK(hipSetDevice(r->device));
   ncclUniqueId u;
   std::memcpy(&u, id, sizeof(u));
@@ -2739,6 +2824,9 @@ void radtran_finish_reduced(void *ptr, char *err) {
   // f_total = (sol_dn - sol_up) + (ir_dn - ir_up) of the reduced rows is formed on the host when the
   // results are fetched (fetch_small), like after every call: nothing to launch here, the level
   // rows just have to be read again
+  TRY
+  settle_device_batch(r);
+  CATCH(err)
   invalidate_small(r);   // (the device rows changed: fetch them)
 }
 

@@ -407,6 +407,9 @@ bool launch_fused(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, c
 bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta_nsrc, hipStream_t s, bool half = false, bool paired = false);
 void launch_integrate(const IntegrateParams &p, hipStream_t s);
 bool integrate_one_launch(const IntegrateParams &p);
+// one call's integration and the next call's prep pass as ONE grid (k_prep_integrate), where prep_integrate_merges() holds
+bool prep_integrate_merges(const PrepParams &pp, const IntegrateParams &ip);
+void launch_prep_integrate(const PrepParams &pp, const IntegrateParams &ip, hipStream_t s);
 void launch_integrate_batch(const BatchIntegrateParams &p, int ncol, hipStream_t s);
 int integrate_chunks(int nbins);
 void launch_f_total(int nz, const double *flux_n, double *f_total, hipStream_t s);

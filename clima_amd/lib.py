@@ -44,6 +44,10 @@ SIGNATURES = {
     "radtran_fused_set": [_vp, _ip],
     "radtran_fused_get": [_vp, _ip],
     "radtran_fused_fallbacks_get": [_vp, _ip],
+    "radtran_defer_integration_set": [_vp, _ip],
+    "radtran_defer_integration_get": [_vp, _ip],
+    "radtran_merged_integrations_get": [_vp, _ip, _ip],
+    "clima_test_defer_allowed": [_ip, _ip, _ip, _ip, _ip, _ip, _ip],
     "radtran_ir_green_set": [_vp, _ip],
     "radtran_ir_green_get": [_vp, _ip, _ip],
     "radtran_coop_items_set": [_vp, _ip],

@@ -608,6 +608,25 @@ class Radtran:
         self._L.radtran_fused_fallbacks_get(self._ptr, C.byref(v))
         return v.value
 
+    @property
+    def defer_integration(self):
+        """True (default): a `radiate_resident` call keeps its frequency integration back for the next call's prep
+        launch (one grid for both); anything that reads results launches it first.  Same results bit for bit."""
+        v = C.c_int()
+        self._L.radtran_defer_integration_get(self._ptr, C.byref(v))
+        return bool(v.value)
+
+    @defer_integration.setter
+    def defer_integration(self, on):
+        self._L.radtran_defer_integration_set(self._ptr, _i(1 if on else 0))
+
+    @property
+    def merged_integrations(self):
+        """(merged, standalone): integrations kept back that went out in the next call's prep launch / on their own."""
+        m, s = C.c_int(), C.c_int()
+        self._L.radtran_merged_integrations_get(self._ptr, C.byref(m), C.byref(s))
+        return m.value, s.value
+
     def flux_tensor(self):
         """The packed level fluxes [ir_up, ir_dn, sol_up, sol_dn][nz+1] as a torch CUDA tensor
         aliasing the library's buffer (the RCCL all-reduce payload of a bin-sharded run)."""

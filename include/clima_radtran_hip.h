@@ -334,6 +334,21 @@ void radtran_ir_green_get(void *ptr, int *mode, int *batches);
  * launches before results are handed out.  This counts such re-issues on the handle (0 in normal
  * operation; CLIMA_HIP_FUSED_SPINS=0 forces them, for tests). */
 void radtran_fused_fallbacks_get(void *ptr, int *count);
+/* radtran_radiate_resident returns without anyone reading a result, so on a handle where this is on (the default) it
+ * keeps the call's frequency integration back: the next compute_opacity call on the handle launches it in ONE grid with
+ * its own prep pass (k_prep_integrate; the two are independent and each far too small to fill the device), and anything
+ * else that enqueues work or reads results -- radtran_synchronize, every getter, an IR-only call, the batches, the
+ * Jacobians, a call whose prep pass clears the spectra (columns of at most 64 layers, the whole-wave forms) -- launches
+ * it first, alone, exactly as the call itself would have.  Results are bitwise the same either way.  Never on a
+ * bin-sharded handle or one with a communicator, with radtran_profile_set(1), while the handle's stream is being
+ * captured, or once radtran_flux_device_ptr has been called (its caller reads the rows in stream order, unannounced).
+ * merged_integrations_get: pending integrations that went out with the next prep pass / alone. */
+void radtran_defer_integration_set(void *ptr, const int *enable);
+void radtran_defer_integration_get(void *ptr, int *enabled);
+void radtran_merged_integrations_get(void *ptr, int *merged, int *standalone);
+/* test hook: the rule above as a function of its inputs (no handle, no device) */
+void clima_test_defer_allowed(const int *switch_on, const int *shard_world, const int *has_comm, const int *profile,
+                              const int *capturing, const int *flux_ptr_taken, int *allowed);
 /* HIP stream the handle launches on (for callers that order other work against it) */
 void radtran_stream_get(void *ptr, void **stream);
 /* per-kernel device time (HIP events on the handle's stream).  enable = 1 records events
