@@ -973,13 +973,9 @@ void launch_green_factor(const GreenParams &p, hipStream_t s) {
   const int nblk = (nl + GREEN_LB - 1) / GREEN_LB;
   hipLaunchKernelGGL(k_green_local, dim3((nblk * GREEN_LB + 255) / 256, NQ), dim3(256), 0, s, p);
 }
-// CLIMA_HIP_GREEN_MFMA=0: the vector form of the far accumulation (the A/B switch of tools/gpu_ir_batch.py and of the
-// parity test of the two)
-static int g_green_vector_form = -1;     // -1: not decided yet (the environment decides), 0 matrix form, 1 vector form
-static bool green_vector_form() {
-  if (g_green_vector_form < 0) { const char *e = getenv("CLIMA_HIP_GREEN_MFMA"); g_green_vector_form = (e && e[0] == '0') ? 1 : 0; }
-  return g_green_vector_form != 0;
-}
+// the far accumulation's form: 0 the matrix form, 1 the vector form it replaced (the test hook of the parity test of the two)
+static int g_green_vector_form = 0;
+static bool green_vector_form() { return g_green_vector_form != 0; }
 void green_vector_form_set(int vector_form) { g_green_vector_form = vector_form ? 1 : 0; }
 // waves of the far accumulation that are resident at a time (the host cuts the bins into so many splits that the kernel's
 // waves fill the machine once): 1024 SIMDs x 2 waves of <= 256 registers in the matrix form, x 3 of 152 in the vector form

@@ -10,8 +10,6 @@
 //   k_opacity_coop     NG = 8, 16 or 32 lanes per (bin, source layer): the sort across the group (DPP / ds_swizzle);
 //                      few-item calls (a bin-sharded rank) and EVERY g-point count other than 8 (1..32: the lanes
 //                      beyond ng are padded).
-//   k_opacity_generic  any g-point count 1..32, one wave per item, LDS bitonic sort in the reference's arithmetic
-//                      order: a cross-check (CLIMA_HIP_GENERIC=1), on no default path.
 //   k_twostream_w      one WAVE per (channel, bin, g-point) -- twostream_p_body: lane q owns a chunk of layers in
 //                      registers, per-lane elimination with flux boundary conditions, the chunks joined by DPP wave
 //                      scans (3x3 projective suffix scan + affine prefix scan); half-wave (two columns per wave) and
@@ -183,13 +181,7 @@ struct ExpK {
   }
 };
 __device__ __forceinline__ double fma3(double a, double b, double c) {
-#ifdef CLIMA_FMA3_ASM
-  double d;
-  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-#else
   return __builtin_fma(a, b, c);
-#endif
 }
 __device__ __forceinline__ double fast_exp(double x, const ExpK &K) {
   const double k = __builtin_rint(x * K.l2e);
@@ -633,10 +625,6 @@ __device__ __forceinline__ void rebin_window(const double (&key)[64], const bool
 }
 
 #include "rorr_xys_asm.inc"
-#ifndef CLIMA_RORR_ASM
-#define CLIMA_RORR_ASM 1
-#endif
-constexpr bool RORR_ASM = CLIMA_RORR_ASM != 0;   // (0: the compiler-scheduled step of rounds 1-3, for A/B timing)
 
 template <int RM>
 __device__ __forceinline__ void rorr_mix8(const double (&x)[8], const double (&y)[8],
@@ -653,7 +641,7 @@ __device__ __forceinline__ void rorr_mix8(const double (&x)[8], const double (&y
     xsorted = xsorted && (x[j] <= x[j + 1]);
   }
   const bool ys = __all(ysorted), xys = ys && __all(xsorted);
-  if constexpr (RM == 0 && RORR_ASM) {
+  if constexpr (RM == 0) {
     // x and y ascending (the normal case: k-coefficients ascend in g, and so does a rebinned mixture) with the
     // window-form rebin: the whole step is one block of generated assembly (rorr_xys_asm.inc,
     // tools/gen_rorr_asm.py) that leaves out the merges and the rebin rows the wave's operands make unnecessary.
@@ -868,10 +856,6 @@ __device__ __forceinline__ void opacity8_body(const OpacityParams &p, const int 
   // is in this load-latency-bound part while the other is in the VALU-bound sort/rebin, instead of
   // both stalling on memory at the same time.
   auto layer_terms = [&](const int jl, LayerTerms &o) {
-#ifdef CLIMA_EXP_NOTERMS   // timing experiment only (WRONG results): what the tile costs without its layer terms
-    o.tausg = 1e-3; o.taua = 1e-3; o.tauc = TINY; o.tausc = TINY * TINY; o.taup = 0.0; o.tausp = 0.0; o.gt = 0.0;
-    if (jl >= 0) return;
-#endif
     const double dzj = c.dz[oc + jl];
     // ---- Rayleigh (:686-693)
     double tausg = 0.0;
@@ -898,11 +882,7 @@ __device__ __forceinline__ void opacity8_body(const OpacityParams &p, const int 
   #pragma unroll
       for (int u = 0; u < AB; u++) {
         const AbsEntry &x = p.abs[e0 + u];
-#ifdef CLIMA_EXP_NODEP   // timing experiment only (WRONG results): the table loads do not wait for the bracket index
-        const double *base = x.data + (x.nT ? (size_t)l * x.nT : (size_t)l);
-#else
         const double *base = x.data + (x.nT ? (size_t)l * x.nT + ixx[u] : (size_t)l);
-#endif
         v0[u] = base[0];
         v1[u] = base[x.nT ? 1 : 0];
       }
@@ -956,7 +936,7 @@ __device__ __forceinline__ void opacity8_body(const OpacityParams &p, const int 
   __shared__ double s_lt[7][OP_THREADS];
   if (terms_first) {
     layer_terms(j, lt);
-    if constexpr (RM == 0 && RORR_ASM) {
+    if constexpr (RM == 0) {
       s_lt[0][tid] = lt.tausg; s_lt[1][tid] = lt.taua; s_lt[2][tid] = lt.tauc; s_lt[3][tid] = lt.tausc;
       s_lt[4][tid] = lt.taup; s_lt[5][tid] = lt.tausp; s_lt[6][tid] = lt.gt;
     }
@@ -996,7 +976,7 @@ __device__ __forceinline__ void opacity8_body(const OpacityParams &p, const int 
     // once before the loop -- hoisted, they are 64-bit values that have to live across the mixing step's assembly
     // block (192 named registers), and the ones that do not fit are spilled and reloaded every iteration
     int jv = j;
-    if constexpr (RM == 0 && RORR_ASM) asm volatile("" : "+v"(jv));
+    if constexpr (RM == 0) asm volatile("" : "+v"(jv));
     if (s + 1 < p.nk) {
       const KDev &kn = p.k[s + 1];
       iP_n = c.ix[2 * opf + kn.slotP * nz + jv]; iT_n = c.ix[2 * opf + kn.slotT * nz + jv];
@@ -1021,7 +1001,7 @@ __device__ __forceinline__ void opacity8_body(const OpacityParams &p, const int 
   }
   if (!terms_first) {
     layer_terms(j, lt);
-  } else if constexpr (RM == 0 && RORR_ASM) {
+  } else if constexpr (RM == 0) {
     lt.tausg = s_lt[0][tid]; lt.taua = s_lt[1][tid]; lt.tauc = s_lt[2][tid]; lt.tausc = s_lt[3][tid];
     lt.taup = s_lt[4][tid]; lt.tausp = s_lt[5][tid]; lt.gt = s_lt[6][tid];
   }
@@ -1089,187 +1069,6 @@ __global__ __launch_bounds__(OP_THREADS, 2) void k_opacity8(OpacityParams p) {
 }
 
 // ------------------------------------------------------------------------------------
-// k_opacity_generic: any g-point count ng <= OPG_MAX_NG (the k-distribution settings allow
-// `new_num_k_bins` other than 8).  One wave per (bin, layer); the ng*ng sums of the
-// random-overlap step live in LDS and are sorted by a wave-cooperative bitonic network on
-// (value, pair index) -- lexicographic, i.e. exactly the stable rank of mrgrnk
-// (types.f90:840) -- then weights_to_bins (clima_eqns.f90:43-54) runs serially in rank
-// order and every output g-point is rebinned by its own lane with the overlap sum of the
-// futils rebin (types.f90:847).  Same arithmetic order as the reference; this is the
-// completeness path, k_opacity8 is the tuned one.
-// ------------------------------------------------------------------------------------
-constexpr int OPG_MAX_NG = 32;
-
-__global__ __launch_bounds__(64) void k_opacity_generic(OpacityParams p, int N2) {
-  extern __shared__ __align__(16) double sm[];
-  const int ng = p.ng, n2 = ng * ng, nz = p.nz;
-  double *s_key = sm;                 // [N2]
-  double *s_cum = s_key + N2;         // [n2 + 1] cumulative sorted weights
-  double *s_tk = s_cum + (n2 + 1);    // [ng] running mixture
-  double *s_kc = s_tk + ng;           // [ng] new species
-  double *s_out = s_kc + ng;          // [ng]
-  double *s_wxy = s_out + ng;         // [n2] weights of the pairs
-  int *s_idx = (int *)(s_wxy + n2);   // [N2]
-  const int lane = threadIdx.x;
-  for (int m = lane; m < n2; m += 64) s_wxy[m] = p.wxy[m];
-  const ColumnDev &c = p.col;
-  const long t = blockIdx.x;
-  const int l = p.bin_lo + (int)(t / nz);
-  const int j = (int)(t % nz);   // ground-first layer
-  const int n = nz - 1 - j;      // TOA-first index
-  const double dzj = c.dz[j];
-  // the second layer of a reused pair takes the rebinned mixture of the first (:833-834);
-  // with nk >= 2 its final mixture depends on the first layer's inputs only
-  const int jk = (p.nk >= 2) ? c.meta[1 + nz + j] : j;
-
-  // ---- wave-uniform terms (same statements as k_opacity8)
-  double tausg = 0.0;
-  for (int i = 0; i < p.nray; i++) tausg = tausg + p.ray[i].data[l] * c.cols[p.ray[i].sp1 * nz + j];
-  double taua = 0.0;
-  for (int e = 0; e < p.nabs; e++) {
-    const AbsEntry &x = p.abs[e];
-    double sgm;
-    if (x.nT) {
-      const int ix = c.ix[x.slot * nz + j];
-      const double q = c.q[x.slot * nz + j];
-      const double *base = x.data + (size_t)l * x.nT + ix;
-      sgm = ten2power((1.0 - q) * base[0] + q * base[1]);
-    } else {
-      sgm = x.data[l];
-    }
-    taua = taua + sgm * c.absw[e * nz + j];
-  }
-  double tauc = TINY, tausc = TINY * TINY, g0c = TINY;
-  if (p.cust.on) {
-    const int ix = c.ix[p.cust.slot * nz + j];
-    const double q = c.q[p.cust.slot * nz + j];
-    const size_t o = (size_t)l * p.cust.nP;
-    tauc = lerp1(p.cust.dtau + o, ix, q) * dzj;
-    const double w0c = lerp1(p.cust.w0 + o, ix, q);
-    g0c = lerp1(p.cust.g0 + o, ix, q);
-    tausc = w0c * tauc;
-  }
-  double tausp = 0.0, taup = 0.0;
-  double tausp_1[MAX_PART], gtp[MAX_PART];
-  for (int i = 0; i < p.npart; i++) {
-    const PartDev &pt = p.part[i];
-    const int ix = c.ix[pt.slot * nz + j];
-    const double q = c.q[pt.slot * nz + j];
-    const double w0p = lerp1(pt.w0 + (size_t)l * pt.nrad, ix, q);
-    const double qext = lerp1(pt.qext + (size_t)l * pt.nrad, ix, q);
-    gtp[i] = lerp1(pt.gt + (size_t)l * pt.nrad, ix, q);
-    const double rr = c.radii[pt.p_ind * nz + j];
-    const double taup_1 = qext * PI * (rr * rr) * c.pdens[pt.p_ind * nz + j] * dzj;
-    taup = taup + taup_1;
-    tausp_1[i] = w0p * taup_1;
-    tausp = tausp + tausp_1[i];
-  }
-  double gt = 0.0;
-  for (int i = 0; i < p.npart; i++) gt = gt + gtp[i] * tausp_1[i] / fmax(TAU_MIN, (tausp + tausg + tausc));
-  gt = gt + g0c * tausc / fmax(TAU_MIN, (tausp + tausg + tausc));
-  gt = fmin(gt, MAX_GT);
-
-  // ---- k-distributions and random-overlap mixing
-  for (int s = 0; s < p.nk; s++) {
-    const KDev &kd = p.k[s];
-    if (lane < ng) {
-      const int iP = c.ix[kd.slotP * nz + jk], iT = c.ix[kd.slotT * nz + jk];
-      const double q1 = c.q[kd.slotP * nz + jk], q2 = c.q[kd.slotT * nz + jk];
-      const double p1 = 1.0 - q1, p2 = 1.0 - q2;
-      const double *f11 = kd.log10k + (size_t)l * kd.nT * kd.nP * ng + ((size_t)iT * kd.nP + iP) * ng;
-      const double *f21 = f11 + ng, *f12 = f11 + (size_t)kd.nP * ng, *f22 = f12 + ng;
-      const double fx1 = p1 * f11[lane] + q1 * f21[lane];
-      const double fx2 = p1 * f12[lane] + q1 * f22[lane];
-      const double v = ten2power(p2 * fx1 + q2 * fx2) * c.cols[kd.sp * nz + jk];
-      if (s == 0) s_tk[lane] = v;
-      else s_kc[lane] = v;
-    }
-    __syncthreads();
-    if (s == 0) continue;
-    for (int m = lane; m < N2; m += 64) {
-      double v = __longlong_as_double(0x7ff0000000000000LL);  // +inf padding sorts last
-      if (m < n2) v = s_tk[m / ng] + s_kc[m % ng];            // tau_xy(:, j+(i-1)*ng), :828
-      s_key[m] = v;
-      s_idx[m] = m;
-    }
-    __syncthreads();
-    for (int k = 2; k <= N2; k <<= 1) {
-      for (int d = k >> 1; d > 0; d >>= 1) {
-        for (int u = lane; u < (N2 >> 1); u += 64) {
-          const int i = ((u & ~(d - 1)) << 1) | (u & (d - 1));
-          const int x = i + d;
-          const bool up = (i & k) == 0;
-          const double ka = s_key[i], kb = s_key[x];
-          const int ia = s_idx[i], ib = s_idx[x];
-          const bool gtr = (ka > kb) || (ka == kb && ia > ib);
-          if (gtr == up) { s_key[i] = kb; s_key[x] = ka; s_idx[i] = ib; s_idx[x] = ia; }
-        }
-        __syncthreads();
-      }
-    }
-    {
-      // weights_to_bins (clima_eqns.f90:43-54): cumulative weights in rank order.  Every lane sums a
-      // run of consecutive ranks, an exclusive wave scan of the run totals gives its offset (a
-      // serial sum over all ng^2 ranks by one lane was 95 % of this kernel's time at ng = 16)
-      const int seg = (N2 + 63) / 64;
-      double tot = 0.0;
-      for (int q = 0; q < seg; q++) {
-        const int m = lane * seg + q;
-        if (m < n2) tot = tot + s_wxy[s_idx[m]];
-      }
-      double incl = tot;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const double nb = __shfl_up(incl, d);
-        if (lane >= d) incl = incl + nb;
-      }
-      double cum = incl - tot;
-      if (lane == 0) { cum = 0.0; s_cum[0] = 0.0; }
-      for (int q = 0; q < seg; q++) {
-        const int m = lane * seg + q;
-        if (m < n2) { cum = cum + s_wxy[s_idx[m]]; s_cum[m + 1] = cum; }
-      }
-    }
-    __syncthreads();
-    if (lane < ng) {
-      const double b0 = p.wbin_e[lane], b1 = p.wbin_e[lane + 1];
-      int lo = 0, hi = n2;  // first old bin whose upper edge is above b0
-      while (lo < hi) { const int mid = (lo + hi) >> 1; if (s_cum[mid + 1] <= b0) lo = mid + 1; else hi = mid; }
-      double acc = 0.0;
-      for (int m = lo; m < n2; m++) {
-        const double e0 = s_cum[m], e1 = s_cum[m + 1];
-        if (e0 >= b1) break;
-        const double a = e0 > b0 ? e0 : b0, b = e1 < b1 ? e1 : b1;
-        if (b > a) acc = acc + (b - a) * s_key[m];
-      }
-      s_out[lane] = acc / (b1 - b0);
-    }
-    __syncthreads();
-    if (lane < ng) s_tk[lane] = s_out[lane];
-    __syncthreads();
-  }
-
-  // ---- totals (:856-886)
-  if (lane < ng) {
-    const double tau = tausg + taua + taup + s_tk[lane] + tauc;
-    double w0;
-    if (tau <= TAU_MIN) w0 = 0.0;
-    else w0 = fmin(MAX_W0, (tausg + tausp + tausc) / tau);
-    const size_t o = ((size_t)l * ng + lane) * nz + n;
-    p.tau[o] = tau;
-    p.w0[o] = w0;
-    s_out[lane] = tau;
-  }
-  __syncthreads();
-  if (lane == 0) {
-    double tb = 0.0;
-    for (int g = 0; g < ng; g++) tb = tb + s_out[g] * p.wbin[g];
-    p.tau_band[(size_t)l * nz + n] = tb;
-    p.g[(size_t)l * nz + n] = gt;
-  }
-}
-
-// ------------------------------------------------------------------------------------
 // k_opacity_coop<NG>: NG lanes per (bin, source layer), NG = 8, 16 or 32 g-points.  Lane g of a
 // group owns g-point g: it interpolates that g-point's k-coefficient, and in a mixing step it holds
 // row g of the NG x NG sums (x_g + y_r, r = 0..NG-1) in registers.  The NG*NG keys are sorted ACROSS
@@ -1318,16 +1117,8 @@ __device__ __forceinline__ double group_sum(double v) {
 // (measured, profiles/r03_coop_ab.txt: 16 g-points at three waves per SIMD instead of two -- 168 registers, 14-22
 // scratch accesses outside the sort -- 610 -> 541 us; 8 g-points forced from three to four: slower, left alone;
 // 32 g-points at two instead of one: 4.67 -> 2.92 ms)
-#ifndef COOP_WAVES_8
-#define COOP_WAVES_8 1
-#endif
-#ifndef COOP_WAVES_16
-#define COOP_WAVES_16 3
-#endif
-#ifndef COOP_WAVES_32
-#define COOP_WAVES_32 2
-#endif
-#define COOP_MIN_WAVES(NG) ((NG) == 8 ? COOP_WAVES_8 : (NG) == 16 ? COOP_WAVES_16 : COOP_WAVES_32)
+constexpr int COOP_WAVES_8 = 1, COOP_WAVES_16 = 3, COOP_WAVES_32 = 2;
+constexpr int coop_min_waves(int ng) { return ng == 8 ? COOP_WAVES_8 : ng == 16 ? COOP_WAVES_16 : COOP_WAVES_32; }
 template <int NG>
 struct CoopSort {
   // one step with partner position pos ^ X restricted to partners in another lane: lane ^ LM, register
@@ -1384,15 +1175,14 @@ struct CoopSort {
 };
 
 template <int NG, bool CUSTOM>
-__global__ __launch_bounds__(OP_THREADS, COOP_MIN_WAVES(NG)) void k_opacity_coop(OpacityParams p) {
+__global__ __launch_bounds__(OP_THREADS, coop_min_waves(NG)) void k_opacity_coop(OpacityParams p) {
   constexpr int N2 = NG * NG, GROUPS = OP_THREADS / NG;
   constexpr unsigned long long IDX_MASK = (unsigned long long)(N2 - 1);
   __shared__ double s_wxy[N2];
   __shared__ double s_E[NG + 1];
   __shared__ double sIe[GROUPS][NG + 1];
   const int tid = threadIdx.x;
-  // ng <= NG g-points (round 3: 12 runs in the 16-lane kernel, 4 and 6 in the 8-lane one, 20-28 in the 32-lane one
-  // instead of the wave-per-item generic kernel): the lanes g >= ng of a group carry coefficients of PAD_K -- finite, far
+  // ng <= NG g-points (12 runs in the 16-lane kernel, 4 and 6 in the 8-lane one, 20-28 in the 32-lane one): the lanes g >= ng of a group carry coefficients of PAD_K -- finite, far
   // above any optical depth -- and pair weights of 0, so their sums sort behind the real ones, add nothing to the running
   // weight or integral, and every output edge k <= ng is crossed inside the real data; they store nothing.
   const int ng = p.ng;
@@ -1617,8 +1407,7 @@ static void launch_coop(const OpacityParams &p, hipStream_t s) {
 }
 
 // the plan's opacity kernel: every g-point count but the tuned 8 goes to the group-of-lanes kernel with the next power of
-// two of lanes per item (OP_GENERIC, CLIMA_HIP_GENERIC=1 when the handle is made: the wave-per-item generic kernel
-// instead -- the same arithmetic order as the reference, kept as a cross-check)
+// two of lanes per item
 bool launch_opacity(const OpacityParams &p, const LaunchPlan &pl, hipStream_t s) {
   const long items = (long)p.nbins * p.nsrc;  // (bin, source layer)
   if (pl.opacity == OP_COOP) {
@@ -1626,13 +1415,6 @@ bool launch_opacity(const OpacityParams &p, const LaunchPlan &pl, hipStream_t s)
     if (pl.coop_ng == 8) launch_coop<8>(p, s);
     else if (pl.coop_ng == 16) launch_coop<16>(p, s);
     else launch_coop<32>(p, s);
-  } else if (pl.opacity == OP_GENERIC) {
-    const long total = (long)p.nbins * p.nz;
-    if (total <= 0) return true;
-    int N2 = 2;
-    while (N2 < p.ng * p.ng) N2 <<= 1;
-    const size_t lds = sizeof(double) * ((size_t)N2 + 2 * p.ng * p.ng + 1 + 3 * p.ng) + sizeof(int) * (size_t)N2;
-    hipLaunchKernelGGL(k_opacity_generic, dim3((unsigned)total), dim3(64), lds, s, p, N2);
   } else if (pl.opacity == OP_TILE) {
     if (items <= 0) return true;
     const int grid = (int)((items + OP_THREADS - 1) / OP_THREADS);  // one lane per item
@@ -2137,18 +1919,15 @@ static size_t ts_lds_bytes(int nz, int nc, int S) {
 }
 
 // the workgroup-per-bin form's geometry for the planner: TS_NONE when the column does not fit
-static TsPlan plan_block(int nz, int ng, int ncols_env) {
+static TsPlan plan_block(int nz, int ng) {
   TsPlan b{};
   // columns per block: all g-points when the LDS image fits, else split the g-points over
-  // gridDim.y groups (outputs are then accumulated with atomics into zeroed arrays)
-  int nc = ncols_env;
-  if (nc <= 0) {
-    // prefer an LDS image small enough for 3 workgroups per CU (latency hiding), but never
-    // more than two g-point groups per bin: two partial sums added into a zeroed output
-    // are order-independent, so results stay bitwise reproducible
-    nc = ng;
-    if (ts_lds_bytes(nz, nc, 64 / nc) > 53 * 1024 && ng % 2 == 0) nc = ng / 2;
-  }
+  // gridDim.y groups (outputs are then accumulated with atomics into zeroed arrays).
+  // Prefer an LDS image small enough for 3 workgroups per CU (latency hiding), but never
+  // more than two g-point groups per bin: two partial sums added into a zeroed output
+  // are order-independent, so results stay bitwise reproducible
+  int nc = ng;
+  if (ts_lds_bytes(nz, nc, 64 / nc) > 53 * 1024 && ng % 2 == 0) nc = ng / 2;
   while (nc > 1 && (ts_lds_bytes(nz, nc, 64 / nc > 16 ? 16 : 64 / nc) > 150 * 1024 || ng % nc != 0 || nc > 64)) nc--;
   if (ng % nc != 0) return b;
   const int S = std::max(1, std::min({64 / nc, 16, nz}));
@@ -2371,11 +2150,6 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
   // fused grid, 256 per wave); the stand-alone kernels keep their higher occupancy instead
   ExpK K;
   if constexpr (RESK) K.load();
-  auto fexp = [&](double x) {
-    if constexpr (RESK) return fast_exp(x, K);
-    else return fast_exp(x);
-  };
-  (void)fexp;   // (only the CLIMA_ZEN_EXP_POLY build still uses the polynomial exp here)
   auto planck = [&](double nu, double T) {
     if constexpr (RESK) return planck_fcn(nu, T, K);
     else return planck_fcn(nu, T);
@@ -2523,20 +2297,12 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
       dir0 = dir0 + wz * u0;
       const double iu2 = iu * iu, wzu = wz * u0;
       const double kz = -iu * EXP2_PER_E;   // exp(-tau'/u0) = 2^(tau' kz / 256)
-#ifdef CLIMA_ZEN_EXP_POLY
-      double et = fexp(-tauc0 * iu);
-#else
       double et = exp_tab_any(tauc0, kz, s_e2);
-#endif
       double ex = 0.0, R = 0.0, sR = 0.0;  // attenuation and source factors of the current layer (pair)
 #pragma unroll
       for (int t = 0; t < L; t++) {
         if (!(PAIRED && (t & 1))) {
-#ifdef CLIMA_ZEN_EXP_POLY
-          ex = fexp(-taup[t] * iu);  // :79
-#else
           ex = exp_tab_any(taup[t], kz, s_e2);  // :79
-#endif
           R = wz * rcp_n1(__builtin_fma(lam[t], lam[t], -iu2));   // w_z / denom (:80)
           sR = __builtin_fma(-zB[t], u0, iu) * R;                   // s w_z / denom
         }
@@ -3212,9 +2978,7 @@ bool launch_twostream_ir_batch(TwoStreamParams &p, int ncol, hipStream_t s, int 
 }
 
 // ------------------------------------------------------------------------------------
-#ifndef FUSED_NZMAX
-#define FUSED_NZMAX 8
-#endif
+constexpr int FUSED_NZMAX = 8;
 // k_fused: opacity and two-stream work of one call -- or of a batch of columns -- in ONE grid, one
 // workgroup per work item.  The items of column c are the blocks [c*(n_op+n_ts), (c+1)*(n_op+n_ts)):
 // first its n_op opacity tiles, then its n_ts two-stream items (one per (bin, g-point group), ordered
@@ -3369,6 +3133,7 @@ int fused_tiles(const OpacityParams &op) {
 // The launch plan of one radiate call: which kernels run, in which form, and who clears the outputs of a form that adds
 // partial sums.  Plain numbers in, plain numbers out: no HIP call, no environment.
 // ------------------------------------------------------------------------------------
+constexpr int OPG_MAX_NG = 32;   // g-points per bin the opacity kernels cover (k_opacity_coop<32> pads up to it)
 static size_t wave_lds(int nz, int cols) { return sizeof(double) * (3 * cols + 1) * ((size_t)nz + 1); }  // level values of the columns + the bin's Planck table
 static int wave_groups(int ng) { return (ng + TSW_COLS - 1) / TSW_COLS; }
 
@@ -3382,7 +3147,7 @@ LaunchPlan plan_radiate(const PlanIn &in) {
   if (in.compute_opacity) {
     if (in.ng < 1 || in.ng > OPG_MAX_NG) pl.opacity = OP_UNSUPPORTED;
     else if (in.ng == 8) pl.opacity = coop8 ? OP_COOP : OP_TILE;
-    else pl.opacity = in.generic_opacity ? OP_GENERIC : OP_COOP;
+    else pl.opacity = OP_COOP;
     pl.coop_ng = in.ng <= 8 ? 8 : in.ng <= 16 ? 16 : 32;
   }
 
@@ -3401,14 +3166,14 @@ LaunchPlan plan_radiate(const PlanIn &in) {
     const int hs = (in.nz + 31) / 32, ps = 2 * ((in.nz / 2 + 63) / 64);
     TsPlan &f = pl.fused;
     if (!in.no_half && plain && hs >= 3 && hs <= 7) { f.form = TS_HALF; f.slots = hs; }
-    else if (in.ncol <= 1 && in.allow_paired && in.all_pairs && !(in.nz & 1) && plain && ps <= 8) { f.form = TS_PAIRED; f.slots = ps; }
+    else if (in.ncol <= 1 && in.all_pairs && !(in.nz & 1) && plain && ps <= 8) { f.form = TS_PAIRED; f.slots = ps; }
     else { f.form = TS_WAVE; f.slots = slots; }
     f.cols = f.form == TS_HALF ? 2 * TSW_COLS : TSW_COLS;   // (a half-wave block holds all 8 g-points of its bin and stores whole values)
     f.groups = f.per_launch = in.ng / f.cols;
     f.lds = wave_lds(in.nz, f.cols);
     // its two-stream part forms w0 from the layers' scattering optical depth itself: the tiles leave the 8 nw nz values
-    // unwritten (26 MB per config-2 call neither stored nor read back; CLIMA_HIP_W0_SCAT=0: always written)
-    pl.write_w0 = !in.w0_from_scat;
+    // unwritten (26 MB per config-2 call neither stored nor read back)
+    pl.write_w0 = false;
   } else {
     pl.write_w0 = true;
   }
@@ -3429,7 +3194,7 @@ LaunchPlan plan_radiate(const PlanIn &in) {
     t.per_launch = t.groups <= 2 ? t.groups : 1;
     t.lds = wave_lds(in.nz, t.cols);
   }
-  if (!in.ir_batch) pl.block = plan_block(in.nz, in.ng, in.ts_ncols_env);
+  if (!in.ir_batch) pl.block = plan_block(in.nz, in.ng);
 
   // Who clears.  When the wave forms will add two or more g-point groups into their outputs, spare blocks of the prep
   // launch clear them (saves a launch) -- not when the form the call is headed for stores whole values (7.7 MB of zeros
@@ -3512,10 +3277,7 @@ bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta
 // in two deterministic stages (chunks of INT_CHUNK bins in bin order, then the chunk
 // sums in order), then f_total (clima_radtran.f90:316)
 // ------------------------------------------------------------------------------------
-#ifndef CLIMA_INT_CHUNK
-#define CLIMA_INT_CHUNK 32
-#endif
-constexpr int INT_CHUNK = CLIMA_INT_CHUNK;
+constexpr int INT_CHUNK = 32;
 
 __global__ __launch_bounds__(256) void k_integrate_partial(IntegrateParams p) {
   const int nl = p.nz + 1;
@@ -3634,14 +3396,8 @@ int integrate_chunks(int nbins) { return nbins <= 0 ? 1 : (nbins + INT_CHUNK - 1
 // forms it from the four rows it fetches anyway (fetch_small), with the same expression.
 // The earlier form (4 levels x 4 arrays per block) spent its time in the L1's tag lookups:
 // every wave load touched 16 lines for 32 bytes each, and the widths were re-read per lane.
-#ifndef CLIMA_INT_LV
-#define CLIMA_INT_LV 16
-#endif
-#ifndef CLIMA_INT_CG
-#define CLIMA_INT_CG 32
-#endif
-constexpr int INT_LV = CLIMA_INT_LV;   // levels per block: 13 x 4 blocks at nz = 200
-constexpr int INT_CG = CLIMA_INT_CG;   // chunk groups: threads = INT_LV * INT_CG = 512
+constexpr int INT_LV = 16;   // levels per block: 13 x 4 blocks at nz = 200
+constexpr int INT_CG = 32;   // chunk groups: threads = INT_LV * INT_CG = 512
 
 // the body of block (level group `bx`, array `a`, column `cb`); s_int: widths [nchunk*INT_CHUNK], then partial [nchunk][INT_LV]
 __device__ __forceinline__ void integrate_block(const IntegrateParams &p, const int bx, const int a, const int cb, double *s_int) {

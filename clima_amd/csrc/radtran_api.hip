@@ -213,7 +213,7 @@ struct Radtran {
   std::vector<std::pair<void *, size_t>> host_registered;   // caller arrays page-locked by radtran_spectra_get_all / radtran_radiate_ir_batch
   double *batch_out[3] = {nullptr, nullptr, nullptr};       // the result arrays of the last radtran_radiate_ir_batch call
   size_t batch_out_n = 0;
-  int batch_shared_min = 2;                                 // CLIMA_HIP_BATCH_SHARED_MIN: batches of at most so many columns take the per-column kernel
+  static constexpr int batch_shared_min = 2;                // batches of at most so many columns take the per-column kernel
   bool batch_pin_results = false;                           // radtran_batch_pin_results_set
   hipEvent_t bout_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // the batch's result pieces
   hipStream_t copy_streams[3] = {nullptr, nullptr, nullptr}; // radtran_spectra_get_all: the seven copies go out over four queues
@@ -250,11 +250,10 @@ struct Radtran {
   hipEvent_t ev_producer = nullptr;   // orders the handle's stream behind the stream that wrote a device batch's inputs
   bool batch_shared = true;        // radiate_ir_batch: temperature-independent work shared by the columns (CLIMA_HIP_BATCH_SHARED=0: one full solve per column)
   int rebin_mode = 1;              // 0 window form, 1 streaming, 2 streaming multi-edge (rebin_mode_for)
+  bool rebin_stream = false;       // CLIMA_HIP_REBIN=stream when the handle was made: never the window form
   long coop_items = 34816;         // ng = 8: at most this many (bin, source layer) items go to k_opacity_coop<8> (CLIMA_HIP_COOP_ITEMS)
   bool fused = true;               // opacity + two-stream in one grid (k_fused); CLIMA_HIP_FUSED=0 or radtran_fused_set turns it off
-  bool generic_opacity = false;    // g-point counts other than 8: k_opacity_generic instead of the group-of-lanes kernel (CLIMA_HIP_GENERIC=1)
   bool ts_block_mode = false;      // CLIMA_HIP_TS_MODE=block when the handle was made: the workgroup-per-bin two-stream kernel
-  int ts_ncols_env = 0;            // CLIMA_HIP_TS_NCOLS (that kernel's columns per block), 0: its own choice
   DevBuf<int> d_done;              // per opacity block: call id of its last completed run
   // A resident call that returns with nobody reading its results keeps its frequency integration back (pending_ip): the
   // next compute_opacity call launches it in one grid with its own prep pass (k_prep_integrate), anything else launches
@@ -387,11 +386,10 @@ void upload_fields(Radtran *r) {
 // that crosses E_k (C_{j*-1} < E_k <= C_{j*}) must be among them WHATEVER order the sort produces.
 // C_j is bounded by the sums of the j+1 smallest / largest pair weights, so
 //   j* >= first j with (sum of the j+1 largest)  >= E_k,   j* <= first j with (sum of the j+1 smallest) >= E_k.
-// Both bounds are taken with a relative slack far above the rounding of a 64-term sum.
-int rebin_mode_for(const std::vector<double> &wbin, const std::vector<double> &wbin_e, const std::vector<double> &wxy) {
+// Both bounds are taken with a relative slack far above the rounding of a 64-term sum.  `stream`: never the window form.
+int rebin_mode_for(const std::vector<double> &wbin, const std::vector<double> &wbin_e, const std::vector<double> &wxy, bool stream) {
   const int multi = (*std::max_element(wxy.begin(), wxy.end()) > *std::min_element(wbin.begin(), wbin.end())) ? 2 : 1;
-  if (wbin.size() != 8) return multi;
-  if (const char *e = getenv("CLIMA_HIP_REBIN")) { if (std::strcmp(e, "stream") == 0) return multi; }
+  if (wbin.size() != 8 || stream) return multi;
   std::vector<double> s(wxy);
   std::sort(s.begin(), s.end());
   if (s[0] <= 0.0) return multi;
@@ -436,12 +434,10 @@ void compute_shard(Radtran *r) {
   const int nw = r->nw, W = r->shard_world, R = r->shard_rank;
   std::vector<double> cost(nw + 1, 0.0);
   const int nzen = (int)r->zenith_u.size();
-  double w_op = SHARD_W_OP, w_ir = SHARD_W_IR, w_s0 = SHARD_W_SOL0, w_sz = SHARD_W_SOLZ;
-  if (const char *e = getenv("CLIMA_HIP_SHARD_COST")) (void)sscanf(e, "%lf,%lf,%lf,%lf", &w_op, &w_ir, &w_s0, &w_sz);  // tuning aid
   for (int l = 0; l < nw; l++) {
-    double c = w_op;
-    if (l >= r->ir.ind_start && l <= r->ir.ind_end) c += w_ir;
-    if (l >= r->sol.ind_start && l <= r->sol.ind_end) c += w_s0 + w_sz * nzen;
+    double c = SHARD_W_OP;
+    if (l >= r->ir.ind_start && l <= r->ir.ind_end) c += SHARD_W_IR;
+    if (l >= r->sol.ind_start && l <= r->sol.ind_end) c += SHARD_W_SOL0 + SHARD_W_SOLZ * nzen;
     cost[l + 1] = cost[l] + c;
   }
   auto cut = [&](int k) {
@@ -796,11 +792,9 @@ IntegrateParams make_integrate_params(Radtran *r, const CallBufs &b, bool comput
   return ip;
 }
 
-// Switches fixed for the process at their first use (the handle-less test hooks obey them too); the others are read once
-// into the handle when it is made (radtran_create_end) -- a getenv per call is a walk through the whole environment.
+// The one switch fixed for the process at its first use (the handle-less test hooks obey it too); the others are read
+// once into the handle when it is made (read_handle_switches) -- a look into the environment per call is a walk through the whole of it.
 bool sw_no_half() { static const bool v = [] { const char *e = getenv("CLIMA_HIP_NO_HALF"); return e && e[0] == '1'; }(); return v; }
-bool sw_paired() { static const bool v = [] { const char *e = getenv("CLIMA_HIP_PAIRED"); return !(e && e[0] == '0'); }(); return v; }
-bool sw_w0_scat() { static const bool v = [] { const char *e = getenv("CLIMA_HIP_W0_SCAT"); return !(e && e[0] == '0'); }(); return v; }
 
 // what plan_radiate needs to know of a call on this handle; a chunk: one launch per kernel for its columns
 PlanIn plan_input(const Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused) {
@@ -812,9 +806,9 @@ PlanIn plan_input(const Radtran *r, const CallBufs &b, bool compute_solar, bool 
   in.rebin_mode = r->rebin_mode; in.cust_on = r->cust_on; in.compute_opacity = compute_opacity;
   // exact pairs in the column (and this call computes the opacities from it) -> exact pairs in opr
   in.all_pairs = compute_opacity && b.all_pairs_exact;
-  in.fused = r->fused; in.allow_fused = allow_fused; in.generic_opacity = r->generic_opacity;
-  in.ts_block_mode = r->ts_block_mode; in.ts_ncols_env = r->ts_ncols_env; in.coop_items = r->coop_items;
-  in.no_half = sw_no_half(); in.allow_paired = sw_paired(); in.w0_from_scat = sw_w0_scat();
+  in.fused = r->fused; in.allow_fused = allow_fused;
+  in.ts_block_mode = r->ts_block_mode; in.coop_items = r->coop_items;
+  in.no_half = sw_no_half();
   return in;
 }
 
@@ -995,13 +989,10 @@ void do_upload(Radtran *r, double T_surface, const double *T, const double *P, c
   bool all = (nz % 2 == 0) && r->nsrc * 2 == nz;
   for (int m = 0; m < r->nsrc && all; m++) all = (meta[1 + m] & SRC_EXACT) != 0;
   r->all_pairs_exact = all;
-  {
-    // ~18 KB: a kernel that reads the pinned buffer over PCIe gets the column into HBM 4 us sooner
-    // than the copy engine does (CLIMA_HIP_COPY_KERNEL=0 selects hipMemcpyAsync)
-    static const bool kcopy = [] { const char *e = getenv("CLIMA_HIP_COPY_KERNEL"); return !(e && e[0] == '0'); }();
-    if (kcopy && r->h_col_dev) launch_copy(r->d_col.p, r->h_col_dev, r->col_count, r->stream);
-    else HIPCHK(hipMemcpyAsync(r->d_col.p, h, sizeof(double) * r->col_count, hipMemcpyHostToDevice, r->stream));
-  }
+  // ~18 KB: a kernel that reads the pinned buffer over PCIe gets the column into HBM 4 us sooner
+  // than the copy engine does (which takes over where the runtime did not map the buffer)
+  if (r->h_col_dev) launch_copy(r->d_col.p, r->h_col_dev, r->col_count, r->stream);
+  else HIPCHK(hipMemcpyAsync(r->d_col.p, h, sizeof(double) * r->col_count, hipMemcpyHostToDevice, r->stream));
   HIPCHK(hipEventRecord(r->ev_upload, r->stream));
   r->upload_pending = true;
   r->last_T.assign(T, T + nz);
@@ -1213,6 +1204,19 @@ void get2d(WrkObj *w, DevBuf<double> &buf, int dim1, int dim2, double *arr) {
 #define TRY try {
 #define CATCH(err) } catch (const HipFail &f) { set_err(err, f.msg); } catch (const std::exception &e) { set_err(err, e.what()); }
 
+// The environment's say in how a handle runs, read once while the handle is made (radtran_create_begin), before the
+// first use of any of it.  INTEGRATION.md lists every name the library reads.
+static void read_handle_switches(Radtran *r) {
+  if (const char *f = getenv("CLIMA_HIP_FUSED")) r->fused = atoi(f) != 0;
+  if (const char *f = getenv("CLIMA_HIP_TS_MODE")) r->ts_block_mode = std::strcmp(f, "block") == 0;
+  if (const char *f = getenv("CLIMA_HIP_BATCH_SHARED")) r->batch_shared = atoi(f) != 0;
+  if (const char *f = getenv("CLIMA_HIP_IR_GREEN")) r->ir_green_mode = std::max(0, std::min(2, atoi(f)));
+  if (const char *f = getenv("CLIMA_HIP_FUSED_SPINS")) r->fused_max_spins = std::max(0, atoi(f));  // test aid: 0 makes waits expire
+  if (const char *f = getenv("CLIMA_HIP_BATCH_COLS")) r->batch_cols_in_flight = std::max(1, atoi(f));
+  if (const char *f = getenv("CLIMA_HIP_COOP_ITEMS")) r->coop_items = atol(f);
+  if (const char *f = getenv("CLIMA_HIP_REBIN")) r->rebin_stream = std::strcmp(f, "stream") == 0;
+}
+
 extern "C" {
 
 void allocate_radtran(void **ptr) { *ptr = new Radtran(); }
@@ -1232,6 +1236,7 @@ void radtran_create_begin(void *ptr, const int *nz, const int *nsp, const int *n
   r->wavl.assign(wavl, wavl + *nw + 1);
   r->freq.resize(*nw + 1);
   for (int i = 0; i < *nw + 1; i++) r->freq[i] = C_LIGHT / (wavl[i] * 1.0e-9);  // types_create.f90:361
+  read_handle_switches(r);
   r->state = 1;
 }
 
@@ -1259,7 +1264,7 @@ void radtran_add_ktable(void *ptr, const int *sp_ind, const int *ngauss, const d
     r->wxy.assign((size_t)r->ng * r->ng, 0.0);
     for (int i = 0; i < r->ng; i++)
       for (int j = 0; j < r->ng; j++) r->wxy[j + (size_t)i * r->ng] = r->wbin[i] * r->wbin[j];
-    r->rebin_mode = rebin_mode_for(r->wbin, r->wbin_e, r->wxy);
+    r->rebin_mode = rebin_mode_for(r->wbin, r->wbin_e, r->wxy, r->rebin_stream);
   }
   r->k.push_back(k);
 }
@@ -1590,14 +1595,6 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
   HIPCHK(hipGetDevice(&r->device));
   HIPCHK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
   HIPCHK(hipEventCreateWithFlags(&r->ev_upload, hipEventDisableTiming));
-  if (const char *f = getenv("CLIMA_HIP_FUSED")) r->fused = atoi(f) != 0;
-  if (const char *f = getenv("CLIMA_HIP_GENERIC")) r->generic_opacity = atoi(f) != 0;
-  if (const char *f = getenv("CLIMA_HIP_TS_MODE")) r->ts_block_mode = std::strcmp(f, "block") == 0;
-  if (const char *f = getenv("CLIMA_HIP_TS_NCOLS")) r->ts_ncols_env = atoi(f);
-  if (const char *f = getenv("CLIMA_HIP_BATCH_SHARED")) r->batch_shared = atoi(f) != 0;
-  if (const char *f = getenv("CLIMA_HIP_IR_GREEN")) r->ir_green_mode = std::max(0, std::min(2, atoi(f)));
-  if (const char *f = getenv("CLIMA_HIP_BATCH_SHARED_MIN")) r->batch_shared_min = std::max(0, atoi(f));
-  if (const char *f = getenv("CLIMA_HIP_FUSED_SPINS")) r->fused_max_spins = std::max(0, atoi(f));  // test aid: 0 makes waits expire
 
   // ---- tables to HBM + interpolation slots
   r->slots.clear();
@@ -1687,8 +1684,6 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
   r->prep_count = prep_block_count(r);
   r->d_prep.alloc(r->prep_count); r->d_prep.zero();
   r->d_done.alloc(((size_t)nw * nz + 255) / 256 + 1); r->d_done.zero();
-  if (const char *f = getenv("CLIMA_HIP_BATCH_COLS")) r->batch_cols_in_flight = std::max(1, atoi(f));
-  if (const char *f = getenv("CLIMA_HIP_COOP_ITEMS")) r->coop_items = atol(f);
 #ifdef CLIMA_STAMPS
   r->d_stamps.alloc(64 + 2 * 8192); r->d_stamps.zero();
 #endif
@@ -1713,10 +1708,7 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
   r->d_f_total.view(r->d_small.p + (size_t)4 * (nz + 1), nz + 1);
   HIPCHK(hipHostMalloc((void **)&r->h_small, sizeof(double) * (5 * (nz + 1) + 1), hipHostMallocMapped));
   std::memset(r->h_small, 0, sizeof(double) * (5 * (nz + 1) + 1));
-  {
-    static const bool direct = [] { const char *e = getenv("CLIMA_HIP_HOST_OUT"); return !(e && e[0] == '0'); }();
-    if (!direct || hipHostGetDevicePointer((void **)&r->h_small_dev, r->h_small, 0) != hipSuccess) { r->h_small_dev = nullptr; (void)hipGetLastError(); }
-  }
+  if (hipHostGetDevicePointer((void **)&r->h_small_dev, r->h_small, 0) != hipSuccess) { r->h_small_dev = nullptr; (void)hipGetLastError(); }
   r->h_errflag = reinterpret_cast<int *>(r->h_small + 5 * (nz + 1));
   r->f_total.assign(nz + 1, 0.0);
   HIPCHK(hipDeviceSynchronize());
@@ -2489,26 +2481,9 @@ void radtran_radiate_wrapper(void *ptr, const double *T_surface, const int *dim_
                   dim1_r ? *dim1_r : 0, dim2_r ? *dim2_r : 0, hp ? pdensities : nullptr, hp ? radii : nullptr, err))
     return;
   TRY
-#ifdef CLIMA_TRACE_SYNC
-  static double acc[4] = {0, 0, 0, 0};
-  static long ncalls = 0;
-  auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
-#endif
   do_upload(r, *T_surface, T, P, densities, dz, hp ? pdensities : nullptr, hp ? radii : nullptr);
-#ifdef CLIMA_TRACE_SYNC
-  const double t1 = now();
-#endif
   enqueue_radiate(r, resident_bufs(r, /*host_out=*/true), *compute_solar != 0, *compute_opacity != 0);
-#ifdef CLIMA_TRACE_SYNC
-  const double t2 = now();
-#endif
   fetch_small(r);
-#ifdef CLIMA_TRACE_SYNC
-  const double t3 = now();
-  acc[0] += t1 - t0; acc[1] += t2 - t1; acc[2] += t3 - t2; ncalls++;
-  if (ncalls % 100 == 0) { fprintf(stderr, "sync trace over 100 calls: upload %.1f us, enqueue %.1f us, fetch+sync %.1f us\n", acc[0] / 100, acc[1] / 100, acc[2] / 100); acc[0] = acc[1] = acc[2] = 0; }
-#endif
   if (surface_device_error(r, err)) return;
   const int nl = r->nz + 1;
   for (int i = 0; i < nl; i++) r->f_total[i] = r->h_small[4 * nl + i];
@@ -3166,7 +3141,7 @@ void clima_test_ir_response(const int *nz_, const int *ng_, const double *tau, c
 }
 
 // which form of the response form's far accumulation the process uses from here on: 0 the matrix-core kernel
-// (k_green_accum_far_mfma, the default), 1 the vector kernel (k_green_accum_far; CLIMA_HIP_GREEN_MFMA=0 selects it too)
+// (k_green_accum_far_mfma, the default), 1 the vector kernel (k_green_accum_far)
 void clima_test_green_far_form_set(const int *vector_form) { green_vector_form_set(*vector_form); }
 
 // ---- reference-named getters / setters (clima/fortran/Radtran.f90) -------------------

@@ -362,12 +362,11 @@ struct PlanIn {
   bool cust_on, compute_opacity;
   bool all_pairs;          // the call computes its opacities from a column of exact pairs (the doubled radiative grid)
   // the handle's and the process's switches
-  bool fused, allow_fused, generic_opacity, ts_block_mode, no_half, allow_paired, w0_from_scat;
+  bool fused, allow_fused, ts_block_mode, no_half;
   long coop_items;
-  int ts_ncols_env;
   int force_slots;         // test hook: whole-wave slots above ceil(nz/64); rules out the half-wave kernel
 };
-enum { OP_NONE = 0, OP_TILE, OP_COOP, OP_GENERIC, OP_UNSUPPORTED };   // stored opacities | lane per item | group of lanes | wave per item
+enum { OP_NONE = 0, OP_TILE, OP_COOP, OP_UNSUPPORTED };   // stored opacities | lane per item | group of lanes
 enum { TS_NONE = 0, TS_WAVE, TS_HALF, TS_PAIRED, TS_BLOCK };          // whole wave | half wave | exact pairs (fused grid only) | workgroup per bin
 struct TsPlan {
   int form;

@@ -423,7 +423,7 @@ void clima_test_ir_response(const int *nz, const int *ng, const double *tau, con
                             const double *dev_db, double *resp_up, double *resp_dn, char *err);
 
 /* The far accumulation of the response form has two kernels: 0 (default) the matrix-core one (v_mfma_f64_16x16x4_f64),
- * 1 the vector one it replaced (also CLIMA_HIP_GREEN_MFMA=0).  Process-wide; tests hold the two against each other. */
+ * 1 the vector one it replaced.  Process-wide; tests hold the two against each other. */
 void clima_test_green_far_form_set(const int *vector_form);
 
 /* OpticalPropertiesResult (clima_radtran_types.f90:242-247), for parity checks:

@@ -70,3 +70,31 @@ def test_hot_kernels_have_no_scratch_traffic(assembly):
 
 def test_build_flags_keep_parameter_blocks_in_the_kernarg_segment():
     assert any("instcombine-max-copied-from-constant-users" in f for f in B.FLAGS)
+
+
+def _environment_table():
+    """The names in the first column of INTEGRATION.md's table of environment variables."""
+    text = open(os.path.join(os.path.dirname(B.CSRC), "..", "INTEGRATION.md")).read()
+    rows = text[text.index("Environment variables."):].split("\n| name |", 1)[1].split("\n\n", 1)[0].splitlines()[2:]
+    return {re.match(r"\| `(\w+)` \|", row).group(1) for row in rows}
+
+
+def test_every_environment_variable_the_library_reads_is_documented():
+    """The string literals passed to getenv( under clima_amd/csrc, with the CLIMA_* names the Python package reads, are
+    exactly the rows of INTEGRATION.md's table; the kernels' file and what it includes read no environment at all."""
+    read = set()
+    for name in sorted(os.listdir(B.CSRC)):
+        if not name.endswith((".hip", ".inc", ".h")):
+            continue
+        src = open(os.path.join(B.CSRC, name)).read()
+        found = re.findall(r'getenv\(\s*"(\w+)"', src)
+        assert len(found) == src.count("getenv"), "%s: a getenv whose argument is no string literal (or a comment's)" % name
+        if name == "kernels.hip" or name.endswith(".inc"):
+            assert "getenv" not in src, "%s reads the environment" % name
+        read |= set(found)
+    assert len(read) >= 10, read
+    pkg = os.path.dirname(B.CSRC)
+    for name in os.listdir(pkg):
+        if name.endswith(".py"):
+            read |= set(re.findall(r'environ(?:\.get\(|\[)\s*"(CLIMA_\w+)"', open(os.path.join(pkg, name)).read()))
+    assert read == _environment_table(), sorted(read ^ _environment_table())

@@ -10,7 +10,7 @@ Every form the step can take is run:
     with the window rebin (scrambled ones), `k_opacity_coop`, the paired form (doubled columns);
   * CLIMA_HIP_REBIN=stream around the handle's construction: the streaming rebin, single-edge, and multi-edge with
     W_MULTI_EDGE; W_SINGLE_EDGE takes the streaming single-edge form by itself (the window tables refuse it);
-  * CLIMA_HIP_GENERIC 0 and 1 for the other g-point counts: the padded group-of-lanes form and the bitonic kernel;
+  * the other g-point counts: the padded group-of-lanes form;
   * TOA_fluxes_batch and TOA_fluxes_batch_tensors on three columns, the case's last: `opr()` then holds that column
     (where the batch runs one call per column; test_split_after_a_column_batch says what is compared otherwise);
   * a handle with set_bin_shard(1, 3), compared on the rank's own opacity bins (`bin_shard()`): wave-mates change there.
@@ -29,7 +29,7 @@ No test here reads the reference's tree or needs oracle/_ref.
 
 Measured on an MI355X (worst over the cases; pytest -s prints each):
   * every case but the ill-conditioned one, tau and w0 alike: group-of-lanes kernel 2.3e-13, lane-per-item tile
-    6.2e-13 (fused or not), streaming rebin 2.3e-13 / 6.3e-13, other g-point counts 3.8e-13 padded and 7.5e-14 bitonic,
+    6.2e-13 (fused or not), streaming rebin 2.3e-13 / 6.3e-13, other g-point counts 3.8e-13 (padded),
     batches 3.8e-13 (host and device route the same), bin shard 3.4e-13.  Largest share of a bin's bound 0.063
     (steep-rows-2-decades, streaming, lane-per-item); the floor ruled in every one (margin to 1e-11: 16x)
   * ill-conditioned-steep-rows, where the oracle is 3.99e-12 from exact and 10 x that rules: the lane-per-item tile
@@ -109,19 +109,16 @@ def test_split_with_the_streaming_rebin(O, hip_lib, name, form, monkeypatch):
     hold(name, "stream " + form, parts, dist[0], tau, w0)
 
 
-@pytest.mark.parametrize("generic", [0, 1])
-@pytest.mark.parametrize("name", OTHER_G)
-def test_split_at_other_g_point_counts(O, hip_lib, name, generic, monkeypatch):
-    """generic = 0: the group-of-lanes kernel with the next power of two of lanes per item, the lanes beyond ng padded;
-    generic = 1 (CLIMA_HIP_GENERIC, read when the handle is made): the wave-per-item bitonic kernel."""
+# (the ids end in -0 so that the cases keep the names under which earlier results are filed)
+@pytest.mark.parametrize("name", OTHER_G, ids=[n + "-0" for n in OTHER_G])
+def test_split_at_other_g_point_counts(O, hip_lib, name):
+    """The group-of-lanes kernel with the next power of two of lanes per item, the lanes beyond ng padded."""
     tables, column, custom, parts, dist = oracle_split(O, name)
-    monkeypatch.setenv("CLIMA_HIP_GENERIC", str(generic))
     r = _handle(tables, len(column["T"]), 1, "coop-fused", custom=custom)
-    monkeypatch.delenv("CLIMA_HIP_GENERIC")
     r.radiate(*column.args())
     print()
     tau, w0 = r.opr()[:2]
-    hold(name, "generic=%d" % generic, parts, dist[0], tau, w0)
+    hold(name, "padded", parts, dist[0], tau, w0)
 
 
 def _three_columns(column):

@@ -314,19 +314,17 @@ def test_uneven_g_weights_multi_edge_rebin(O):
     _compare(r, o, S.modern_earth_column(33))
 
 
-@pytest.mark.parametrize("generic", [0, 1])
-@pytest.mark.parametrize("ng,sorted_k", [(1, True), (4, True), (6, True), (12, False), (12, True), (16, True), (20, True), (24, False),
-                                         (32, True)])
-def test_other_g_point_counts(O, ng, sorted_k, generic, monkeypatch):
-    # `new_num_k_bins` need not be 8.  generic = 0: the group-of-lanes kernel with the next power of two of lanes per
-    # item, the lanes beyond ng padded (round 3: 12 g-points 4.2 ms -> 0.66 ms at config 2's size); generic = 1
-    # (CLIMA_HIP_GENERIC): the wave-per-item resort-rebin kernel (bitonic sort on (value, index) in LDS, the
-    # reference's arithmetic order) kept as a cross-check.  Both with the per-group two-stream launches.
+OTHER_G_COUNTS = [(1, True), (4, True), (6, True), (12, False), (12, True), (16, True), (20, True), (24, False), (32, True)]
+
+
+# (the ids end in -0 so that the cases keep the names under which earlier results are filed)
+@pytest.mark.parametrize("ng,sorted_k", OTHER_G_COUNTS, ids=["%d-%s-0" % c for c in OTHER_G_COUNTS])
+def test_other_g_point_counts(O, ng, sorted_k):
+    # `new_num_k_bins` need not be 8: the group-of-lanes kernel with the next power of two of lanes per item, the lanes
+    # beyond ng padded (round 3: 12 g-points 4.2 ms -> 0.66 ms at config 2's size), with the per-group two-stream launches.
     from clima_amd import synthetic as S
     tb = S.modern_earth_tables(nw=12, ng=ng, sorted_k=sorted_k, seed=5 + ng)
-    monkeypatch.setenv("CLIMA_HIP_GENERIC", str(generic))
     r, o = _pair(O, tb, 22, 2, 0.25)
-    monkeypatch.delenv("CLIMA_HIP_GENERIC")
     _compare(r, o, S.doubled_column(S.modern_earth_column(11)))
 
 

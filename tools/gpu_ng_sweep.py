@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Developer diagnostic: per-call time against the number of g-points (config 2's shape: nz = 200,
 1000 bins, 5 k-species), ng = 8 (lane-per-item kernel in the fused grid), 16 and 32
-(k_opacity_coop<16/32>), others (k_opacity_generic)."""
+(k_opacity_coop<16/32>), others (the same kernels, the lanes beyond ng padded)."""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from clima_amd import synthetic as S
