@@ -31,11 +31,9 @@
 
 constexpr double GREEN_TINY = 1.0e-300;
 constexpr int GREEN_NF = 3;       // explicit levels per deviation: level k, level k+1, level 0 (k <= 1)
-constexpr int GREEN_DS = 4 + 2 * 2;          // per (q, k): above amplitude, its log, below amplitude, its log, explicit values of the levels k and k + 1
-                                             // (level 0's, for k <= 1 only, sit in D0[q][k][up, down]: as two more rows of every k they were a fifth of what k_green_unit writes)
-constexpr int GREEN_RW = 7;       // per (q, row): c', 1/den, z, running products of phi and of -c' (mantissa, exponent each)
+// (the work arrays' per-q extents GREEN_RW / IS / FS / DS / D0: radtran_dev.h.  Level 0's explicit values, for k <= 1
+// only, sit in D0[q][k][up, down]: as two more rows of DS for every k they were a fifth of what k_green_unit writes)
 constexpr int GREEN_TILE = 16;
-constexpr int GREEN_FS = 2 * GREEN_LB + 2;   // per (q, form, level block): reference log, pad, 16 (up factor, down factor) pairs
 
 // gamma1 + gamma2 and the e's of one layer (:195-211).  The first and the last row of the system are the interface rows
 // of two VIRTUAL layers: above layer 0 one with e = (1, ., 0, 0), below layer nz-1 one with e = (0, 1, 0, Rsfc) whose
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(64) void k_green_factor(GreenParams p) {
   const double Rsfc = p.has_hard_surface ? 1.0 - p.emissivity[p.ir_lo + bi] : 0.0;
   const double w = p.wbin[g];
   double *rw = p.RW + (size_t)q * GREEN_RW * N;
-  double *is = p.IS + (size_t)q * 6 * nl;
+  double *is = p.IS + (size_t)q * GREEN_IS * nl;
   // ---- downwards: c', 1/den, phi (kept in z's place until the way back), the running products
   double c_in = 0.0;
   GreenX PLc = {1.0, 0.0}, QLc = {1.0, 0.0};      // products over the rows before the segment
@@ -388,7 +386,7 @@ __global__ __launch_bounds__(256) void k_green_local(GreenParams p) {
     fa[2 + 2 * j] = 0.0; fa[3 + 2 * j] = 0.0; fb[2 + 2 * j] = 0.0; fb[3 + 2 * j] = 0.0;
     return;
   }
-  const double *is = p.IS + (size_t)q * 6 * nl;
+  const double *is = p.IS + (size_t)q * GREEN_IS * nl;
   const int ref_a = min(blk * GREEN_LB + GREEN_LB - 1, nz), ref_b = max(blk * GREEN_LB, 1);
   // (every load before the first store: IS and FS are plain pointers of one parameter block, so a load written behind a
   // store stays behind it -- four memory round trips one after the other)
@@ -797,7 +795,7 @@ __global__ __launch_bounds__(64) void k_green_accum_mixed(GreenParams p) {
   if (on) cls = green_class(lv, k, slot);
   const int per = (p.n_ir + p.msplit - 1) / p.msplit;      // (its own, finer bin splits: few pairs, a long dependent loop each)
   const int b_lo = (int)blockIdx.y * per, b_hi = min(p.n_ir, b_lo + per);
-  const size_t is_q = (size_t)6 * nl, ds_q = (size_t)GREEN_DS * nl;
+  const size_t is_q = (size_t)GREEN_IS * nl, ds_q = (size_t)GREEN_DS * nl;
   // one branch-free body for the three classes (so that the loads of several g-points go out together): a far-form
   // level reads (log, up, down) of the level and (amplitude, log) of the deviation; an explicit level reads its two
   // values in place of the level factors and takes the amplitude as 1
@@ -887,7 +885,7 @@ __global__ __launch_bounds__(256) void k_green_combine(GreenParams p) {
     double up = p.gen_out[i], dn = p.gen_out[p.gen_arr + i];    // column 0 of the general sub-batch is the base
     for (int j = p.col_ptr[c]; j < p.col_ptr[c + 1]; j++) green_split_sum(p, p.col_dev[j], lv, up, dn);
     o[i] = up; o[p.out_arr + i] = dn;
-    o[2 * p.out_arr + i] = (p.flux_n[3 * nl + i] - p.flux_n[2 * nl + i]) + (dn - up);
+    o[2 * p.out_arr + i] = f_total_level(up, dn, p.flux_n[2 * nl + i], p.flux_n[3 * nl + i]);
   }
 }
 
@@ -958,7 +956,7 @@ __global__ __launch_bounds__(256) void k_batch_ftotal(double *out, size_t out_ar
   const size_t n = (size_t)ncol * nl;
   for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
     const int i = (int)(t % nl);
-    out[2 * out_arr + t] = (flux_n[3 * nl + i] - flux_n[2 * nl + i]) + (out[out_arr + t] - out[t]);
+    out[2 * out_arr + t] = f_total_level(out[t], out[out_arr + t], flux_n[2 * nl + i], flux_n[3 * nl + i]);
   }
 }
 void launch_batch_ftotal(double *out, size_t out_arr, int ncol, int nz, const double *flux_n, hipStream_t s) {

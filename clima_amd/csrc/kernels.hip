@@ -333,11 +333,6 @@ __device__ __forceinline__ double row_shr(double old, double x) { return dpp_mov
 template <int D>
 __device__ __forceinline__ double row_shl(double old, double x) { return dpp_mov<DPP_ROW_SHL + D, 0xf, 0xf>(old, x); }
 
-// futils is_close (fortran-stdlib form): |a-b| <= tol*max(|a|,|b|)
-__device__ __forceinline__ bool is_close(double a, double b, double tol) {
-  return fabs(a - b) <= fabs(tol * fmax(fabs(a), fabs(b)));
-}
-
 // dintrv bracketing, linear_interpolation_module.F90:348-350 (stateless form)
 __device__ __forceinline__ int bracket(const double *xt, int n, double x) {
   if (x < xt[0]) return 0;
@@ -3277,8 +3272,6 @@ bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta
 // in two deterministic stages (chunks of INT_CHUNK bins in bin order, then the chunk
 // sums in order), then f_total (clima_radtran.f90:316)
 // ------------------------------------------------------------------------------------
-constexpr int INT_CHUNK = 32;
-
 __global__ __launch_bounds__(256) void k_integrate_partial(IntegrateParams p) {
   const int nl = p.nz + 1;
   const int a = blockIdx.y;
@@ -3324,7 +3317,7 @@ __global__ __launch_bounds__(1024) void k_integrate_final(IntegrateParams p) {
   __syncthreads();
   if (p.f_total)
     for (int i = threadIdx.x; i < nl; i += blockDim.x)
-      p.f_total[i] = (p.flux_n[3 * nl + i] - p.flux_n[2 * nl + i]) + (p.flux_n[1 * nl + i] - p.flux_n[0 * nl + i]);
+      p.f_total[i] = f_total_level(p.flux_n[i], p.flux_n[nl + i], p.flux_n[2 * nl + i], p.flux_n[3 * nl + i]);
 }
 
 // Batched IR form (shared opacity, ncol temperature columns): the same two deterministic
@@ -3377,7 +3370,7 @@ __global__ __launch_bounds__(256) void k_integrate_final_b(BatchIntegrateParams 
     double *o = p.out + (size_t)(p.col0 + col) * nl;
     o[i] = up;
     o[p.out_arr + i] = dn;
-    o[2 * p.out_arr + i] = (p.flux_n[3 * nl + i] - p.flux_n[2 * nl + i]) + (dn - up);  // clima_radtran.f90:287
+    o[2 * p.out_arr + i] = f_total_level(up, dn, p.flux_n[2 * nl + i], p.flux_n[3 * nl + i]);
   }
 }
 
@@ -3386,17 +3379,15 @@ void launch_integrate_batch(const BatchIntegrateParams &p, int ncol, hipStream_t
   hipLaunchKernelGGL(k_integrate_final_b, dim3(ncol), dim3(256), 0, s, p);
 }
 
-int integrate_chunks(int nbins) { return nbins <= 0 ? 1 : (nbins + INT_CHUNK - 1) / INT_CHUNK; }
-
 // Both stages in one launch: block (level group, array) owns INT_LV = 16 consecutive levels
 // (one 128-byte line per bin) of ONE of the four arrays; thread (level, chunk group) forms the
 // chunk sums exactly as k_integrate_partial does, with the frequency widths staged in LDS once
 // per block; the chunk sums meet in LDS and are added in chunk order.  Same association as the
 // two-launch form.  f_total is NOT formed here (its four operands sit in four blocks): the host
-// forms it from the four rows it fetches anyway (fetch_small), with the same expression.
+// forms it from the four rows it fetches anyway (fetch_small).
 // The earlier form (4 levels x 4 arrays per block) spent its time in the L1's tag lookups:
 // every wave load touched 16 lines for 32 bytes each, and the widths were re-read per lane.
-constexpr int INT_LV = 16;   // levels per block: 13 x 4 blocks at nz = 200
+// (INT_LV = 16 levels per block: 13 x 4 blocks at nz = 200)
 constexpr int INT_CG = 32;   // chunk groups: threads = INT_LV * INT_CG = 512
 
 // the body of block (level group `bx`, array `a`, column `cb`); s_int: widths [nchunk*INT_CHUNK], then partial [nchunk][INT_LV]
@@ -3479,29 +3470,22 @@ __global__ __launch_bounds__(INT_LV * INT_CG) void k_prep_integrate(PrepParams p
   else prep_block(pp, b - 4 * nlb, 0);
 }
 
-// true when launch_integrate() takes the one-launch kernel (the form that can store into the host's block)
-bool integrate_one_launch(const IntegrateParams &p) {
-  return sizeof(double) * (size_t)p.nchunk * (INT_CHUNK + INT_LV) <= 64 * 1024;
-}
-
 // true when k_prep_integrate can stand for launch_integrate(ip) followed by launch_prep(pp)
 bool prep_integrate_merges(const PrepParams &pp, const IntegrateParams &ip) {
-  const size_t lds = sizeof(double) * ((size_t)ip.nchunk * (INT_CHUNK + INT_LV) + PREP_AXIS_MAX);   // dynamic + prep_block's axis
+  const size_t lds = integrate_lds_bytes(ip.nchunk) + sizeof(double) * PREP_AXIS_MAX;   // dynamic + prep_block's axis
   return pp.ncol <= 1 && ip.ncol <= 1 && pp.nzero == 0 && pp.nz == ip.nz && !ip.host_out && !ip.timeout_out &&
-         integrate_one_launch(ip) && lds <= 48 * 1024;
+         integrate_fits_one_launch(ip.nchunk) && lds <= 48 * 1024;
 }
 
 void launch_prep_integrate(const PrepParams &pp, const IntegrateParams &ip, hipStream_t s) {
   const int nlb = (ip.nz + 1 + INT_LV - 1) / INT_LV;
-  const size_t lds = sizeof(double) * (size_t)ip.nchunk * (INT_CHUNK + INT_LV);
-  hipLaunchKernelGGL(k_prep_integrate, dim3(4 * nlb + 1 + pp.nslots + pp.nabs), dim3(INT_LV * INT_CG), lds, s, pp, ip);
+  hipLaunchKernelGGL(k_prep_integrate, dim3(4 * nlb + 1 + pp.nslots + pp.nabs), dim3(INT_LV * INT_CG), integrate_lds_bytes(ip.nchunk), s, pp, ip);
 }
 
 void launch_integrate(const IntegrateParams &p, hipStream_t s) {
   const int nl = p.nz + 1;
-  const size_t lds = sizeof(double) * (size_t)p.nchunk * (INT_CHUNK + INT_LV);
-  if (lds <= 64 * 1024) {
-    hipLaunchKernelGGL(k_integrate_one, dim3((nl + INT_LV - 1) / INT_LV, 4, p.ncol > 0 ? p.ncol : 1), dim3(INT_LV * INT_CG), lds, s, p);
+  if (integrate_fits_one_launch(p.nchunk)) {
+    hipLaunchKernelGGL(k_integrate_one, dim3((nl + INT_LV - 1) / INT_LV, 4, p.ncol > 0 ? p.ncol : 1), dim3(INT_LV * INT_CG), integrate_lds_bytes(p.nchunk), s, p);
     return;
   }
   hipLaunchKernelGGL(k_integrate_partial, dim3(p.nchunk, 4), dim3(256), 0, s, p);
@@ -3525,7 +3509,7 @@ void launch_w0_from_scat(const double *tau, const double *scat, double *w0, int 
 
 __global__ void k_f_total(int nl, const double *flux_n, double *f_total) {
   for (int i = threadIdx.x; i < nl; i += blockDim.x)
-    f_total[i] = (flux_n[3 * nl + i] - flux_n[2 * nl + i]) + (flux_n[1 * nl + i] - flux_n[0 * nl + i]);
+    f_total[i] = f_total_level(flux_n[i], flux_n[nl + i], flux_n[2 * nl + i], flux_n[3 * nl + i]);
 }
 void launch_f_total(int nz, const double *flux_n, double *f_total, hipStream_t s) {
   hipLaunchKernelGGL(k_f_total, dim3(1), dim3(256), 0, s, nz + 1, flux_n, f_total);
@@ -3583,52 +3567,42 @@ void launch_scale(double *a, size_t n, double f, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------
 // Column batches out of device arrays (radtran_toa_fluxes_batch_device): the host's pack_column / build_meta and
-// its f_total_row / toa_fluxes as kernels, so that neither the inputs nor the results pass through the host.
+// its f_total / ISR / OLR as kernels, so that neither the inputs nor the results pass through the host.
 // ------------------------------------------------------------------------------------
-// futils is_close as the host evaluates it (radtran_api.hip is_close): every operation rounded on its own
-__device__ __forceinline__ bool pack_is_close(double a, double b, double tol) {
-  const double fa = fabs(a), fb = fabs(b);
-  const double mx = fa < fb ? fb : fa;                        // std::max
-  return fabs(__dsub_rn(a, b)) <= fabs(__dmul_rn(tol, mx));
-}
-
 constexpr int PACK_THREADS = 256;
 
 // One workgroup per column.  The copy is coalesced (consecutive threads, consecutive elements of a segment).  The
-// pair-reuse table is build_meta's: thread t decides the pair (2t, 2t+1) from the caller's arrays; a pair that is
-// reused takes one entry of the ascending source list, any other two, so pair t's first entry sits at
+// pair-reuse table is build_meta's: thread t decides the pair (2t, 2t+1) from the caller's arrays (pair_decision); a
+// pair that is reused takes one entry of the ascending source list, any other two, so pair t's first entry sits at
 // 2t - (reused pairs before t): an exclusive scan of the decisions over the block -- ballot and popcount within a
 // wave, the waves' totals through LDS -- carried from one pass of the block to the next when nz/2 > PACK_THREADS.
 __global__ __launch_bounds__(PACK_THREADS) void k_pack_columns(PackParams p) {
   const int c = blockIdx.x, tid = threadIdx.x, nz = p.nz, nsp = p.nsp, np = p.np;
-  double *dst = p.blocks + (size_t)c * p.col_count;
+  const ColumnLayout lay = column_layout(nz, nsp, np);
+  double *dst = p.blocks + (size_t)c * lay.count;
   const double *T = p.T + (size_t)c * nz, *P = p.P + (size_t)c * nz, *dz = p.dz + (size_t)c * nz;
   const double *dens = p.dens + (size_t)c * nz * nsp;
   const double *pdens = p.has_particles ? p.pdens + (size_t)c * nz * np : nullptr;
   const double *radii = p.has_particles ? p.radii + (size_t)c * nz * np : nullptr;
 
-  // [T_surface | T | P | dz | dens | pdens | radii]
   if (tid == 0) dst[0] = p.T_surface[c];
   for (int i = tid; i < nz; i += PACK_THREADS) {
-    dst[1 + i] = T[i];
-    dst[1 + nz + i] = P[i];
-    dst[1 + 2 * nz + i] = dz[i];
+    dst[lay.T + i] = T[i];
+    dst[lay.P + i] = P[i];
+    dst[lay.dz + i] = dz[i];
   }
-  double *d_dens = dst + 1 + 3 * (size_t)nz;
-  for (int i = tid; i < nz * nsp; i += PACK_THREADS) d_dens[i] = dens[i];
-  double *d_pd = d_dens + (size_t)nz * nsp, *d_ra = d_pd + (size_t)nz * np;
+  for (int i = tid; i < nz * nsp; i += PACK_THREADS) dst[lay.dens + i] = dens[i];
   for (int i = tid; i < nz * np; i += PACK_THREADS) {
     // (a handle with particle columns whose batch comes without them is refused before the launch; a block of the
     //  host's is zero there)
-    d_pd[i] = p.has_particles ? pdens[i] : 0.0;
-    d_ra[i] = p.has_particles ? radii[i] : 0.0;
+    dst[lay.pdens + i] = p.has_particles ? pdens[i] : 0.0;
+    dst[lay.radii + i] = p.has_particles ? radii[i] : 0.0;
   }
 
   // meta: [0] = nsrc, [1 + m] = m-th source layer | flags, [1 + nz + j] = source of layer j, one int of padding
-  int *meta = reinterpret_cast<int *>(dst + p.meta_ofs);
+  int *meta = reinterpret_cast<int *>(dst + lay.meta);
   int *srcl = meta + 1, *src = meta + 1 + nz;
   __shared__ int s_tot[PACK_THREADS / 64];
-  const double tol = 1.0e-12;
   const int lane = tid & 63, w = tid >> 6;
   int reused = 0;   // reused pairs in the passes so far (uniform)
   if ((nz & 1) == 0) {
@@ -3636,24 +3610,9 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_columns(PackParams p) {
     for (int t0 = 0; t0 < npairs; t0 += PACK_THREADS) {
       const int t = t0 + tid, j = 2 * t + 1;
       const bool valid = t < npairs;
-      bool reuse = false, exact = false;
-      if (valid) {
-        reuse = pack_is_close(P[j], P[j - 1], tol) && pack_is_close(T[j], T[j - 1], tol);
-        exact = P[j] == P[j - 1] && T[j] == T[j - 1] && dz[j] == dz[j - 1];
-        const double dzb = dz[j], dza = dz[j - 1];
-        for (int i = 0; i < nsp && reuse; i++) {
-          const double nb = dens[(size_t)i * nz + j], na = dens[(size_t)i * nz + j - 1];
-          reuse = pack_is_close(__dmul_rn(nb, dzb), __dmul_rn(na, dza), tol);   // opw%cols: stored (rounded) products
-          exact = exact && nb == na;
-        }
-        if (p.use_radii)
-          for (int i = 0; i < np && reuse; i++) reuse = pack_is_close(radii[(size_t)i * nz + j], radii[(size_t)i * nz + j - 1], tol);
-        if (reuse && np > 0 && p.has_particles)
-          for (int i = 0; i < np; i++)
-            exact = exact && pdens[(size_t)i * nz + j] == pdens[(size_t)i * nz + j - 1] &&
-                    radii[(size_t)i * nz + j] == radii[(size_t)i * nz + j - 1];
-        exact = exact && reuse;
-      }
+      PairDecision d{false, false};
+      if (valid) d = pair_decision(j, nz, nsp, np, T, P, dz, dens, pdens, radii, p.use_radii);
+      const bool reuse = d.reuse, exact = d.exact;
       const unsigned long long m = __ballot(reuse);
       if (lane == 0) s_tot[w] = __popcll(m);
       __syncthreads();
@@ -3693,21 +3652,20 @@ void launch_pack_columns(const PackParams &p, hipStream_t s) {
   hipLaunchKernelGGL(k_pack_columns, dim3(p.ncol), dim3(PACK_THREADS), 0, s, p);
 }
 
-// One workgroup per column: f_total in the order of the host's f_total_row, ISR / OLR as its toa_fluxes forms them
-// (clima_radtran.f90:287, :339-340) -- differences and one sum, no product anywhere -- and the five rows out.
+// One workgroup per column: f_total, ISR / OLR (clima_radtran.f90:287, :339-340) as the host forms them -- differences
+// and one sum, no product anywhere -- and the five rows out.
 __global__ __launch_bounds__(256) void k_batch_finish(BatchFinishParams p) {
   const int c = blockIdx.x, nl = p.nz + 1;
   double *h = p.flux + (size_t)c * 5 * nl;
   double *out = p.fluxes ? p.fluxes + (size_t)c * 5 * nl : nullptr;
   for (int i = threadIdx.x; i < nl; i += blockDim.x) {
     const double iu = h[i], id = h[nl + i], su = h[2 * nl + i], sd = h[3 * nl + i];
-    const double sol = sd - su, ir = id - iu;
-    const double ft = sol + ir;
+    const double ft = f_total_level(iu, id, su, sd);
     h[4 * nl + i] = ft;
     if (out) {
       out[i] = iu; out[nl + i] = id; out[2 * nl + i] = su; out[3 * nl + i] = sd; out[4 * nl + i] = ft;
     }
-    if (i == p.nz) { p.ISR[c] = sol; p.OLR[c] = -ir; }
+    if (i == p.nz) toa_isr_olr(iu, id, su, sd, p.ISR[c], p.OLR[c]);
   }
 }
 void launch_batch_finish(const BatchFinishParams &p, hipStream_t s) {

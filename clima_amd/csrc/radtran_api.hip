@@ -70,6 +70,11 @@ struct DevBuf {
     n = count;
     if (count) HIPCHK(hipMalloc((void **)&p, count * sizeof(T)));
   }
+  bool reserve(size_t count) {  // grow-only; true: a new allocation (its contents undefined)
+    const bool grow = n < count;
+    if (grow) alloc(count);
+    return grow;
+  }
   void upload(const std::vector<T> &v) {
     if (!(p && owned && n == v.size())) alloc(v.size());   // (same size: the allocation is kept)
     if (!v.empty()) HIPCHK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -84,6 +89,23 @@ struct DevBuf {
     owned = true;
   }
   ~DevBuf() { release(); }
+};
+
+// Pinned host memory that only grows: at least `count` elements, `count + spare` when it has to be allocated anew
+template <class T>
+struct PinnedBuf {
+  T *p = nullptr;
+  size_t n = 0;
+  T *reserve(size_t count, size_t spare = 0) {
+    if (n < count) {
+      if (p) (void)hipHostFree(p);
+      p = nullptr; n = 0;
+      HIPCHK(hipHostMalloc((void **)&p, sizeof(T) * (count + spare), hipHostMallocDefault));
+      n = count + spare;
+    }
+    return p;
+  }
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
 };
 
 struct KTabHost {
@@ -168,15 +190,13 @@ struct Radtran {
   // ... and its response form (ir_green.inc): work arrays, deviation lists, the general sub-batch's rows
   DevBuf<double> d_green, d_green_acc, d_green_in, d_gen_out;
   int green_last_n = -1;           // columns of the last batch, when it took the response form (the next one of that size starts its opacity-only part early)
-  double *h_bout = nullptr;        // pinned: the batch's three result arrays on their way to the caller's
-  size_t h_bout_n = 0;
-  char *h_green = nullptr;         // pinned: what the host hands the response form (base profile, deviation lists)
-  size_t h_green_n = 0;
+  PinnedBuf<double> h_bout;        // the batch's three result arrays on their way to the caller's
+  PinnedBuf<char> h_green;         // what the host hands the response form (base profile, deviation lists)
   DevBuf<int> d_green_idx;
   int ir_green_mode = 1;           // CLIMA_HIP_IR_GREEN: 0 never, 1 when enough columns are sparse deviations of one profile, 2 whenever any is
   long ir_green_batches = 0;       // batches that took the response form (radtran_ir_green_batches_get)
-  DevBuf<double> d_col;  // [T_surface | T | P | dz | dens | pdens | radii | meta (ints: nsrc, source list, source of every layer)]
-  size_t meta_ofs = 0;   // doubles before the meta ints in a column block
+  DevBuf<double> d_col;  // one column block
+  ColumnLayout col_layout{};   // ... as column_layout(nz, nsp, np) lays it out
   int nsrc = 0;          // source layers of the resident column (pair_reuse decided at upload)
   bool all_pairs_exact = false;  // ... and every layer is half of an exact pair (the doubled radiative grid)
   DevBuf<double> d_prep;  // one block: [log10P | cols | foreign_col | absw | q | ix (ints)]
@@ -189,7 +209,6 @@ struct Radtran {
 #endif
   double *h_col = nullptr;  // pinned staging
   double *h_col_dev = nullptr;  // the same buffer as the device addresses it (null: not mapped, use the copy engine)
-  size_t col_count = 0;
   bool column_has_particles = false;
   bool column_loaded = false;
   hipEvent_t ev_upload = nullptr;   // marks the end of the last column copy out of the pinned staging buffer
@@ -285,8 +304,6 @@ struct Radtran {
     for (auto &cs : copy_streams) if (cs) (void)hipStreamDestroy(cs);
     for (auto &e : bout_ev) if (e) (void)hipEventDestroy(e);
     if (h_small) (void)hipHostFree(h_small);
-    if (h_bout) (void)hipHostFree(h_bout);
-    if (h_green) (void)hipHostFree(h_green);
     if (ev_upload) (void)hipEventDestroy(ev_upload);
     if (ev_producer) (void)hipEventDestroy(ev_producer);
     if (comm) (void)ncclCommDestroy(comm);
@@ -301,9 +318,6 @@ Radtran *as_rad(void *ptr) {
   if (!r || r->magic != MAGIC) return nullptr;
   return r;
 }
-
-// futils is_close (fortran-stdlib form)
-bool is_close(double a, double b, double tol) { return std::fabs(a - b) <= std::fabs(tol * std::max(std::fabs(a), std::fabs(b))); }
 
 // futils gauss_legendre (setup only, clima_eqns.f90:26-41)
 void gauss_legendre(int n, std::vector<double> &x, std::vector<double> &w) {
@@ -577,7 +591,7 @@ CallBufs resident_bufs(Radtran *r, bool host_out = false) {
 CallBufs arena_column_bufs(Radtran *r, int c, int nsrc) {
   CallBufs b = resident_bufs(r);
   b.kind = CALL_ARENA_COLUMN; b.nsrc = nsrc; b.all_pairs_exact = false;
-  b.col = r->d_cols_arena.p + (size_t)c * r->col_count;
+  b.col = r->d_cols_arena.p + (size_t)c * r->col_layout.count;
   b.flux_n = r->d_flux_arena.p + (size_t)c * 5 * (r->nz + 1); b.f_total = b.flux_n + 4 * (r->nz + 1);
   return b;
 }
@@ -586,64 +600,41 @@ CallBufs arena_column_bufs(Radtran *r, int c, int nsrc) {
 CallBufs arena_chunk_bufs(Radtran *r, int c0, int ncol) {
   CallBufs b = resident_bufs(r);
   b.kind = CALL_ARENA_CHUNK; b.ncol = ncol; b.nsrc = r->nz; b.all_pairs_exact = false;
-  b.col = r->d_cols_arena.p + (size_t)c0 * r->col_count; b.prep = r->d_prep_arena.p;
+  b.col = r->d_cols_arena.p + (size_t)c0 * r->col_layout.count; b.prep = r->d_prep_arena.p;
   b.opr = opr_views(r, r->d_opr_arena.p); b.spec = spectra_views(r, r->d_res_arena.p);
   b.flux_n = r->d_flux_arena.p + (size_t)c0 * 5 * (r->nz + 1);
-  b.bs = BatchStrides{r->col_count, r->prep_count, b.opr.count, b.spec.count, (size_t)5 * (r->nz + 1),
+  b.bs = BatchStrides{r->col_layout.count, r->prep_count, b.opr.count, b.spec.count, (size_t)5 * (r->nz + 1),
                       (int)(((size_t)r->op_n * r->nz + 255) / 256)};
   return b;
 }
 
-// Column block [T_surface | T | P | dz | dens | pdens | radii | meta] (pack_column writes it on the host)
 ColumnDev column_dev(Radtran *r, const CallBufs &b) {
   ColumnDev c;
-  const int nz = r->nz;
+  const ColumnLayout &l = r->col_layout;
   c.T_surface = b.col;
-  c.T = b.col + 1;
-  c.P = c.T + nz;
-  c.dz = c.P + nz;
-  c.dens = c.dz + nz;
-  c.pdens = c.dens + (size_t)r->nsp * nz;
-  c.radii = c.pdens + (size_t)r->np * nz;
-  c.meta = reinterpret_cast<const int *>(b.col + r->meta_ofs);
+  c.T = b.col + l.T; c.P = b.col + l.P; c.dz = b.col + l.dz;
+  c.dens = b.col + l.dens; c.pdens = b.col + l.pdens; c.radii = b.col + l.radii;
+  c.meta = reinterpret_cast<const int *>(b.col + l.meta);
   prep_views(r, b.prep, c);
   c.err_flag = r->d_err.p;
   return c;
 }
 
-// pair_reuse (clima_radtran_types.f90:621-632), decided here once per column so that the grid size
-// and every kernel work from ONE definition: for even nz, layer j (1-based even) reuses layer j-1
-// when P, T, every column densities*dz and (with particles) every radius agree to 1e-12 (is_close).
+// The pair_reuse table of one column (pair_decision, radtran_dev.h, for every pair of an even number of layers), so
+// that the grid size and every kernel work from ONE decision.
 // meta: [0] = nsrc, [1 + m] = m-th source layer (0-based, ascending) | SRC_PAIR | SRC_EXACT,
 // [1 + nz + j] = source layer of layer j.  Returns nsrc.
 int build_meta(Radtran *r, const double *T, const double *P, const double *dz, const double *dens,
-               const double *pdens, const double *radii, bool has_particles, int *meta) {
-#pragma clang fp contract(off)  // the columns are stored products in the reference (opw%cols), never fused into the comparison
-  const int nz = r->nz, nsp = r->nsp, np = r->np;
-  const double tol = 1.0e-12;
-  const bool use_radii = has_particles && radii && !r->part.empty();  // present(radii) .and. self%npart > 0
+               const double *pdens, const double *radii, int *meta) {
+  const int nz = r->nz;
+  const bool use_radii = pdens && radii && !r->part.empty();  // present(radii) .and. self%npart > 0
   int nsrc = 0;
   int *srcl = meta + 1, *src = meta + 1 + nz;
   for (int j = 0; j < nz; j++) {
-    bool reuse = false, exact = false;
-    if ((nz & 1) == 0 && (j & 1) == 1) {
-      reuse = is_close(P[j], P[j - 1], tol) && is_close(T[j], T[j - 1], tol);
-      exact = P[j] == P[j - 1] && T[j] == T[j - 1] && dz[j] == dz[j - 1];
-      for (int i = 0; i < nsp && reuse; i++) {
-        const volatile double ca = dens[(size_t)i * nz + j] * dz[j], cb = dens[(size_t)i * nz + j - 1] * dz[j - 1];  // opw%cols
-        reuse = is_close(ca, cb, tol);
-        exact = exact && dens[(size_t)i * nz + j] == dens[(size_t)i * nz + j - 1];
-      }
-      if (use_radii)
-        for (int i = 0; i < np && reuse; i++) reuse = is_close(radii[(size_t)i * nz + j], radii[(size_t)i * nz + j - 1], tol);
-      if (reuse && np > 0 && has_particles && pdens && radii)
-        for (int i = 0; i < np; i++)
-          exact = exact && pdens[(size_t)i * nz + j] == pdens[(size_t)i * nz + j - 1] &&
-                  radii[(size_t)i * nz + j] == radii[(size_t)i * nz + j - 1];
-      exact = exact && reuse;
-    }
-    if (reuse) {
-      srcl[nsrc - 1] |= SRC_PAIR | (exact ? SRC_EXACT : 0);  // layer j-1 is the entry just written
+    PairDecision d{false, false};
+    if ((nz & 1) == 0 && (j & 1) == 1) d = pair_decision(j, nz, r->nsp, r->np, T, P, dz, dens, pdens, radii, use_radii);
+    if (d.reuse) {
+      srcl[nsrc - 1] |= SRC_PAIR | (d.exact ? SRC_EXACT : 0);  // layer j-1 is the entry just written
       src[j] = j - 1;
     } else {
       srcl[nsrc++] = j;
@@ -655,33 +646,32 @@ int build_meta(Radtran *r, const double *T, const double *P, const double *dz, c
   return nsrc;
 }
 
-// Packs one column into a host block laid out like d_col (column_dev unpacks it), pair_reuse table included.
-// Returns nsrc.
+// Packs one column into a host block (column_layout), pair_reuse table included.  Returns nsrc.
 int pack_column(Radtran *r, double *h, double T_surface, const double *T, const double *P, const double *dz,
                 const double *dens, const double *pdens, const double *radii) {
   const size_t nz = r->nz;
+  const ColumnLayout &l = r->col_layout;
+  if (!(pdens && radii)) pdens = radii = nullptr;   // the particle columns come together or not at all
   h[0] = T_surface;
-  std::memcpy(h + 1, T, sizeof(double) * nz);
-  std::memcpy(h + 1 + nz, P, sizeof(double) * nz);
-  std::memcpy(h + 1 + 2 * nz, dz, sizeof(double) * nz);
-  std::memcpy(h + 1 + 3 * nz, dens, sizeof(double) * nz * r->nsp);
-  double *hp = h + 1 + 3 * nz + nz * r->nsp;
-  if (r->np > 0 && pdens && radii) {
-    std::memcpy(hp, pdens, sizeof(double) * nz * r->np);
-    std::memcpy(hp + nz * r->np, radii, sizeof(double) * nz * r->np);
+  std::memcpy(h + l.T, T, sizeof(double) * nz);
+  std::memcpy(h + l.P, P, sizeof(double) * nz);
+  std::memcpy(h + l.dz, dz, sizeof(double) * nz);
+  std::memcpy(h + l.dens, dens, sizeof(double) * nz * r->nsp);
+  if (pdens) {
+    std::memcpy(h + l.pdens, pdens, sizeof(double) * nz * r->np);
+    std::memcpy(h + l.radii, radii, sizeof(double) * nz * r->np);
   }
-  return build_meta(r, T, P, dz, dens, pdens, radii, pdens && radii, reinterpret_cast<int *>(h + r->meta_ofs));
+  return build_meta(r, T, P, dz, dens, pdens, radii, reinterpret_cast<int *>(h + l.meta));
 }
 
-// f_total from the four level rows of a block [ir up | ir down | solar up | solar down | f_total] (clima_radtran.f90:287)
+// f_total into the fifth row of a block [ir up | ir down | solar up | solar down | f_total]
 void f_total_row(double *h, int nl) {
-  for (int i = 0; i < nl; i++) h[4 * nl + i] = (h[3 * nl + i] - h[2 * nl + i]) + (h[1 * nl + i] - h[0 * nl + i]);
+  for (int i = 0; i < nl; i++) h[4 * nl + i] = f_total_level(h[i], h[nl + i], h[2 * nl + i], h[3 * nl + i]);
 }
-// ... and ISR, OLR: the net solar and IR fluxes at the last level (clima_radtran.f90:339-340)
+// ... and ISR, OLR from its last level
 void toa_fluxes(const double *h, int nz, double *ISR, double *OLR) {
   const int nl = nz + 1;
-  *ISR = (h[3 * nl + nz] - h[2 * nl + nz]);
-  *OLR = -(h[1 * nl + nz] - h[0 * nl + nz]);
+  toa_isr_olr(h[nz], h[nl + nz], h[2 * nl + nz], h[3 * nl + nz], *ISR, *OLR);
 }
 
 void invalidate_small(Radtran *r) { r->small_valid = false; r->small_in_host = false; }
@@ -778,7 +768,7 @@ IntegrateParams make_integrate_params(Radtran *r, const CallBufs &b, bool comput
   ip.f_total = r->shard_world == 1 ? b.f_total : nullptr;
   ip.nchunk = integrate_chunks(std::max(r->ir_n, r->sol_n));
   ip.partial = r->d_partial.p;
-  if (b.host_out && r->h_small_dev && b.kind == CALL_RESIDENT && !reduce && r->shard_world == 1 && integrate_one_launch(ip)) {
+  if (b.host_out && r->h_small_dev && b.kind == CALL_RESIDENT && !reduce && r->shard_world == 1 && integrate_fits_one_launch(ip.nchunk)) {
     ip.host_out = r->h_small_dev;
     ip.err_words = r->d_err.p;
   }
@@ -923,7 +913,7 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
   const bool reduce = r->comm && resident;
   const IntegrateParams ip = make_integrate_params(r, b, compute_solar, reduce);
   r->small_in_host = ip.host_out != nullptr;
-  if (defer && resident && !reduce && !ip.host_out && integrate_one_launch(ip) && defer_eligible(r)) {
+  if (defer && resident && !reduce && !ip.host_out && integrate_fits_one_launch(ip.nchunk) && defer_eligible(r)) {
     r->pending_ip = ip;
     r->int_pending = true;
   } else {
@@ -954,7 +944,7 @@ void fetch_small(Radtran *r) {
     if (r->comm) r->comm_status = r->h_small[4 * nl];
     if (!r->column_loaded || !recover_fused_timeout(r)) break;  // re-issued unfused: fetch again
   }
-  // the one-launch integration leaves f_total to the host, the other forms computed the same expression on the device
+  // the one-launch integration leaves f_total to the host, the other forms called f_total_level on the device
   f_total_row(r->h_small, nl);
   r->small_valid = true;
 }
@@ -985,14 +975,14 @@ void do_upload(Radtran *r, double T_surface, const double *T, const double *P, c
   r->nsrc = pack_column(r, h, T_surface, T, P, dz, dens, pdens, radii);
   r->column_has_particles = (pdens && radii);
   r->upload_id++;
-  const int *meta = reinterpret_cast<const int *>(h + r->meta_ofs);
+  const int *meta = reinterpret_cast<const int *>(h + r->col_layout.meta);
   bool all = (nz % 2 == 0) && r->nsrc * 2 == nz;
   for (int m = 0; m < r->nsrc && all; m++) all = (meta[1 + m] & SRC_EXACT) != 0;
   r->all_pairs_exact = all;
   // ~18 KB: a kernel that reads the pinned buffer over PCIe gets the column into HBM 4 us sooner
   // than the copy engine does (which takes over where the runtime did not map the buffer)
-  if (r->h_col_dev) launch_copy(r->d_col.p, r->h_col_dev, r->col_count, r->stream);
-  else HIPCHK(hipMemcpyAsync(r->d_col.p, h, sizeof(double) * r->col_count, hipMemcpyHostToDevice, r->stream));
+  if (r->h_col_dev) launch_copy(r->d_col.p, r->h_col_dev, r->col_layout.count, r->stream);
+  else HIPCHK(hipMemcpyAsync(r->d_col.p, h, sizeof(double) * r->col_layout.count, hipMemcpyHostToDevice, r->stream));
   HIPCHK(hipEventRecord(r->ev_upload, r->stream));
   r->upload_pending = true;
   r->last_T.assign(T, T + nz);
@@ -1079,9 +1069,9 @@ void defer_err(Radtran *r, const std::string &msg) {
 void begin_batch(Radtran *r, int n, bool nsrc_on_device) {
   settle_device_batch(r);
   const size_t rows = (size_t)n * 5 * (r->nz + 1);
-  if (r->d_cols_arena.n < (size_t)n * r->col_count) r->d_cols_arena.alloc((size_t)n * r->col_count);
-  if (r->d_flux_arena.n < rows) r->d_flux_arena.alloc(rows);
-  if (nsrc_on_device && r->d_batch_nsrc.n < (size_t)n) r->d_batch_nsrc.alloc(n);
+  r->d_cols_arena.reserve((size_t)n * r->col_layout.count);
+  r->d_flux_arena.reserve(rows);
+  if (nsrc_on_device) r->d_batch_nsrc.reserve(n);
 }
 // The launch form of a batch of n columns, decided here, once: one launch of each kernel per chunk of CH columns
 // (the fused grid takes the columns' work items in turn, so one column's two-stream tail runs beside the next
@@ -1092,14 +1082,14 @@ BatchRun batch_form(Radtran *r, int n) {
   f.n = n; f.first_call = r->call_id + 1; f.CH = std::min(n, r->batch_cols_in_flight);
   const CallBufs first = arena_chunk_bufs(r, 0, f.CH);   // the first chunk (only its counts are read)
   f.one_launch = plan_radiate(plan_input(r, first, true, true, true)).fused.form != TS_NONE &&
-                 integrate_chunks(std::max(r->ir_n, r->sol_n)) * (32 + 16) * sizeof(double) <= 64 * 1024;
+                 integrate_fits_one_launch(integrate_chunks(std::max(r->ir_n, r->sol_n)));
   if (const char *e = getenv("CLIMA_HIP_BATCH_ONE_LAUNCH")) f.one_launch = f.one_launch && atoi(e) != 0;
   if (f.one_launch) {
     const BatchStrides &bs = first.bs;
-    if (r->d_prep_arena.n < bs.prep * f.CH) r->d_prep_arena.alloc(bs.prep * f.CH);
-    if (r->d_opr_arena.n < bs.opr * f.CH) r->d_opr_arena.alloc(bs.opr * f.CH);
-    if (r->d_res_arena.n < bs.res * f.CH) { r->d_res_arena.alloc(bs.res * f.CH); r->d_res_arena.zero(r->stream); }
-    if (r->d_done.n < (size_t)bs.done * f.CH + 1) { r->d_done.alloc((size_t)bs.done * f.CH + 1); r->d_done.zero(r->stream); }
+    r->d_prep_arena.reserve(bs.prep * f.CH);
+    r->d_opr_arena.reserve(bs.opr * f.CH);
+    if (r->d_res_arena.reserve(bs.res * f.CH)) r->d_res_arena.zero(r->stream);
+    if (r->d_done.reserve((size_t)bs.done * f.CH + 1)) r->d_done.zero(r->stream);
   }
   return f;
 }
@@ -1175,11 +1165,21 @@ PackParams make_pack_params(Radtran *r, int n, const double *T_surface, const do
   p.ncol = n; p.nz = r->nz; p.nsp = r->nsp; p.np = r->np;
   p.has_particles = r->np > 0 && pdens && radii;
   p.use_radii = p.has_particles && !r->part.empty();
-  p.col_count = r->col_count; p.meta_ofs = r->meta_ofs;
   p.T_surface = T_surface; p.T = T; p.P = P; p.dz = dz; p.dens = dens; p.pdens = pdens; p.radii = radii;
   p.blocks = blocks; p.nsrc = nsrc;
   return p;
 }
+// A communicator handle worked on its share of the bins: ONE all-reduce of the up / down arrays (2 arr doubles from the
+// start of d_bout) over the ranks, then the total from the reduced ones, which `total` launches.
+template <class F>
+void comm_reduce_up_down(Radtran *r, size_t arr, F total) {
+  if (!r->comm) return;
+  NCCLCHK(ncclAllReduce(r->d_bout.p, r->d_bout.p, 2 * arr, ncclDouble, ncclSum, r->comm, r->stream));
+  r->comm_reduces++;
+  total();
+  HIPCHK(hipGetLastError());
+}
+
 // device memory of the handle's device?  (an address the runtime does not know -- pageable host memory -- is an
 // error return on some runtimes and "unregistered" on others)
 bool on_handle_device(const Radtran *r, const void *p) {
@@ -1674,12 +1674,11 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
   r->d_am_f1.upload(f1); r->d_am_f2.upload(f2); r->d_am_dw.upload(dw);
 
   // ---- column, prep, opr, results
-  r->meta_ofs = 1 + (size_t)3 * nz + (size_t)nz * r->nsp + (size_t)2 * nz * r->np;
-  r->col_count = r->meta_ofs + (size_t)nz + 1;   // + (2 nz + 1) ints
-  r->d_col.alloc(r->col_count);
+  r->col_layout = column_layout(nz, r->nsp, r->np);
+  r->d_col.alloc(r->col_layout.count);
   r->d_col.zero();
-  HIPCHK(hipHostMalloc((void **)&r->h_col, sizeof(double) * r->col_count, hipHostMallocMapped));
-  std::memset(r->h_col, 0, sizeof(double) * r->col_count);
+  HIPCHK(hipHostMalloc((void **)&r->h_col, sizeof(double) * r->col_layout.count, hipHostMallocMapped));
+  std::memset(r->h_col, 0, sizeof(double) * r->col_layout.count);
   if (hipHostGetDevicePointer((void **)&r->h_col_dev, r->h_col, 0) != hipSuccess) { r->h_col_dev = nullptr; (void)hipGetLastError(); }
   r->prep_count = prep_block_count(r);
   r->d_prep.alloc(r->prep_count); r->d_prep.zero();
@@ -1755,8 +1754,7 @@ static void ir_batch_general(Radtran *r, const double *d_T, const double *d_Ts, 
   const int CH = std::min(n, 512);
   const int nchunk = integrate_chunks(r->ir_n);
   const size_t spec = (size_t)nw_ir * nl;
-  auto ensure = [](DevBuf<double> &b, size_t count) { if (b.n < count) b.alloc(count); };  // grow-only
-  ensure(r->d_bup, spec * CH); ensure(r->d_bdn, spec * CH); ensure(r->d_bpartial, (size_t)CH * 2 * nchunk * nl);
+  r->d_bup.reserve(spec * CH); r->d_bdn.reserve(spec * CH); r->d_bpartial.reserve((size_t)CH * 2 * nchunk * nl);
   const CallBufs b = resident_bufs(r);
   TwoStreamParams ts = make_twostream_params(r, b, column_dev(r, b), false);
   ts.ir_fup_a = r->d_bup.p; ts.ir_fdn_a = r->d_bdn.p;
@@ -1863,21 +1861,16 @@ static void green_plan(const double *T, const double *Ts, int n, int nz, GreenPl
 // ones.  rocprofv3's kernel trace shows them side by side and each that much slower: the far-form kernel holds 2 x 232
 // registers per SIMD, the general kernel one wave of 512, and the batch took 828-840 us either way.)
 static void green_factor_part(Radtran *r, GreenParams &g) {
-  const int nz = r->nz, nl = nz + 1, N = 2 * nz, ng = r->ng, n_ir = r->ir_n;
+  const int nz = r->nz, ng = r->ng, n_ir = r->ir_n;
   const int NQ = n_ir * ng;
-  const size_t RQ = (size_t)N * NQ, LQ = (size_t)nl * NQ;
-  const size_t FQ = (size_t)2 * ((nl + 15) / 16) * 34 * NQ;    // (GREEN_LB, GREEN_FS of ir_green.inc)
-  const size_t total = 7 * RQ + 6 * LQ + FQ + 8 * LQ + 4 * (size_t)NQ;
-  if (r->d_green.n < total) r->d_green.alloc(total);
+  r->d_green.reserve(green_work_views(nz, NQ, nullptr).count);
   std::memset(&g, 0, sizeof(g));
   g.nz = nz; g.ng = ng; g.n_ir = n_ir; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
   g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
   g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
   g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
-  double *w = r->d_green.p;
-  auto take = [&](size_t cnt) { double *p0 = w; w += cnt; return p0; };
-  g.RW = take(7 * RQ);
-  g.IS = take(6 * LQ); g.FS = take(FQ); g.DS = take(8 * LQ); g.D0 = take(4 * (size_t)NQ);
+  const GreenWork w = green_work_views(nz, NQ, r->d_green.p);
+  g.RW = w.RW; g.IS = w.IS; g.FS = w.FS; g.DS = w.DS; g.D0 = w.D0;
   launch_green_factor(g, r->stream);
   HIPCHK(hipGetLastError());
 }
@@ -1888,7 +1881,7 @@ static void green_factor_part(Radtran *r, GreenParams &g) {
 static void green_mixed_list(const std::vector<int> &dev_k, int nz, std::vector<int> &mdev, std::vector<int> &mblk) {
   const int nl = nz + 1;
   for (int d = 0; d < (int)dev_k.size(); d++)
-    for (int blk = std::max(0, (dev_k[d] - 1) / 16 - 1); blk < (nl + 15) / 16; blk++) {
+    for (int blk = std::max(0, (dev_k[d] - 1) / GREEN_LB - 1); blk < (nl + GREEN_LB - 1) / GREEN_LB; blk++) {
       const int cls = green_block_class(dev_k[d], blk, nz);
       if (cls == 2) { mdev.push_back(d); mblk.push_back(blk); }
       if (cls == 1) break;
@@ -1912,24 +1905,16 @@ static double green_work_bytes(const Radtran *r, int ndev) {
   green_splits(r, ndev, -1, qs, ms);
   return ((double)r->ir_n * r->ng * (13.0 * nl + 14.0 * nz + 4.3 * nl) + (double)(qs + ms) * ((double)ndev + 64.0) * 2.0 * nl) * 8.0;
 }
-// the handle's pinned staging block, at least `bytes` long
-static char *green_stage(Radtran *r, size_t bytes) {
-  if (r->h_green_n < bytes) {
-    if (r->h_green) (void)hipHostFree(r->h_green);
-    r->h_green = nullptr; r->h_green_n = 0;
-    HIPCHK(hipHostMalloc((void **)&r->h_green, bytes + bytes / 2, hipHostMallocDefault));
-    r->h_green_n = bytes + bytes / 2;
-  }
-  return r->h_green;
-}
+// the handle's pinned staging block, at least `bytes` long (half as much again when it has to grow)
+static char *green_stage(Radtran *r, size_t bytes) { return r->h_green.reserve(bytes, bytes / 2); }
 // the accumulation's arrays (Planck factors, the partial sums of both kernels) and split counts; the deviation and
 // mixed-pair lists are the caller's
-static void green_accum_arrays(Radtran *r, GreenParams &g, int ndev, int ndev_pad, int nmix) {
-  const int nl = r->nz + 1, n_ir = r->ir_n;
+static void green_accum_arrays(Radtran *r, GreenParams &g, int ndev, int nmix) {
+  const int nl = r->nz + 1, n_ir = r->ir_n, ndev_pad = green_ndev_pad(ndev);
   int qsplit, msplit;
   green_splits(r, ndev, nmix, qsplit, msplit);
   const size_t need = (size_t)n_ir * ndev_pad + 64 + (size_t)(qsplit + msplit) * ndev_pad * 2 * nl;
-  if (r->d_green_acc.n < need) r->d_green_acc.alloc(need);
+  r->d_green_acc.reserve(need);
   double *w = r->d_green_acc.p;
   auto take = [&](size_t cnt) { double *p0 = w; w += cnt; return p0; };
   g.DB = take((size_t)n_ir * ndev_pad + 64); g.partial = take((size_t)qsplit * ndev_pad * 2 * nl);
@@ -1940,10 +1925,9 @@ static void green_accum_arrays(Radtran *r, GreenParams &g, int ndev, int ndev_pa
 // `pre`: the opacity-only part has been issued already (green_factor_part's parameter block)
 static void ir_batch_green(Radtran *r, const GreenPlan &pl, const double *T, const double *Ts, int n, double *d_out, const GreenParams *pre) {
   const int nz = r->nz, nl = nz + 1;
-  auto ensure = [](DevBuf<double> &b, size_t count) { if (b.n < count) b.alloc(count); };
   // 1. the base profile and the dense columns through the general kernel
   const int ngen = 1 + (int)pl.dense.size();
-  const int ndev = (int)pl.dev_k.size(), ndev_pad = std::max(16, (ndev + 15) / 16 * 16);
+  const int ndev = (int)pl.dev_k.size(), ndev_pad = green_ndev_pad(ndev);
   std::vector<int> mdev, mblk;
   green_mixed_list(pl.dev_k, nz, mdev, mblk);
   const int nmix = (int)mdev.size();
@@ -1972,8 +1956,8 @@ static void ir_batch_green(Radtran *r, const GreenPlan &pl, const double *T, con
     w2 = std::copy(mdev.begin(), mdev.end(), w2);
     w2 = std::copy(mblk.begin(), mblk.end(), w2);
   }
-  ensure(r->d_green_in, nd); ensure(r->d_gen_out, (size_t)ngen * 3 * nl);
-  if (r->d_green_idx.n < ni) r->d_green_idx.alloc(ni);
+  r->d_green_in.reserve(nd); r->d_gen_out.reserve((size_t)ngen * 3 * nl);
+  r->d_green_idx.reserve(ni);
   HIPCHK(hipMemcpyAsync(r->d_green_in.p, hd, sizeof(double) * nd, hipMemcpyHostToDevice, r->stream));
   HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * ni, hipMemcpyHostToDevice, r->stream));
   const double *d_T = r->d_green_in.p, *d_Ts = d_T + (size_t)ngen * nz;
@@ -1982,7 +1966,7 @@ static void ir_batch_green(Radtran *r, const GreenPlan &pl, const double *T, con
   GreenParams g;
   if (pre) g = *pre;
   else green_factor_part(r, g);
-  green_accum_arrays(r, g, ndev, ndev_pad, nmix);
+  green_accum_arrays(r, g, ndev, nmix);
   g.dev_k = r->d_green_idx.p; g.col_src = g.dev_k + ndev_pad; g.col_ptr = g.col_src + n; g.col_dev = g.col_ptr + n + 1;
   g.mix_dev = g.col_dev + ndev; g.mix_blk = g.mix_dev + nmix;
   g.dev_T = d_Ts + ngen; g.base_T = g.dev_T + ndev_pad;
@@ -1998,12 +1982,7 @@ static void ir_batch_green(Radtran *r, const GreenPlan &pl, const double *T, con
 // levels).  Returns when all are there.  (The batch and the full Jacobian: three arrays from the start;
 // radtran_ir_jacobian_reduced's total alone: one.)
 static void bout_to_host(Radtran *r, double *const *outs, size_t arr, int narr = 3, int first = 0) {
-  if (r->h_bout_n < narr * arr) {
-    if (r->h_bout) (void)hipHostFree(r->h_bout);
-    r->h_bout = nullptr; r->h_bout_n = 0;
-    HIPCHK(hipHostMalloc((void **)&r->h_bout, sizeof(double) * narr * arr, hipHostMallocDefault));
-    r->h_bout_n = narr * arr;
-  }
+  double *const h_bout = r->h_bout.reserve(narr * arr);
   constexpr int NPIECE = 6;
   const size_t total = narr * arr, piece = (total + NPIECE - 1) / NPIECE;
   const double *d_src = r->d_bout.p + (size_t)first * arr;
@@ -2011,7 +1990,7 @@ static void bout_to_host(Radtran *r, double *const *outs, size_t arr, int narr =
     if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (int k = 0; k < NPIECE; k++) {
     const size_t lo = std::min(total, (size_t)k * piece), hi = std::min(total, lo + piece);
-    if (hi > lo) HIPCHK(hipMemcpyAsync(r->h_bout + lo, d_src + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
+    if (hi > lo) HIPCHK(hipMemcpyAsync(h_bout + lo, d_src + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
     HIPCHK(hipEventRecord(r->bout_ev[k], r->stream));
   }
   for (int k = 0; k < NPIECE; k++) {
@@ -2019,7 +1998,7 @@ static void bout_to_host(Radtran *r, double *const *outs, size_t arr, int narr =
     HIPCHK(hipEventSynchronize(r->bout_ev[k]));
     for (size_t x = lo; x < hi;) {      // (a piece may straddle two of the three arrays)
       const size_t i = x / arr, n_here = std::min(hi, (i + 1) * arr) - x;
-      std::memcpy(outs[i] + (x - i * arr), r->h_bout + x, sizeof(double) * n_here);
+      std::memcpy(outs[i] + (x - i * arr), h_bout + x, sizeof(double) * n_here);
       x += n_here;
     }
   }
@@ -2045,8 +2024,7 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
   upload_fields(r);
   ensure_w0(r);
   const int nz = r->nz, nl = nz + 1, n = *ncol;
-  auto ensure = [](DevBuf<double> &b, size_t count) { if (b.n < count) b.alloc(count); };  // grow-only
-  ensure(r->d_bout, (size_t)n * 3 * nl);
+  r->d_bout.reserve((size_t)n * 3 * nl);
   bool green = false;
   if (r->ir_green_mode != 0 && r->batch_shared && nz >= 4 && nz <= 512 && r->ir_n > 0) {   // (CLIMA_HIP_BATCH_SHARED=0: one full solve per column, bit for bit the single call)
     // k_green_unit / k_green_local take one (bin, g-point) pair per blockIdx.y: a grid dimension of at most 65535
@@ -2080,20 +2058,14 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
     r->green_last_n = green ? n : -1;
   }
   if (!green) {
-    ensure(r->d_bT, (size_t)n * nz); ensure(r->d_bTs, n);
+    r->d_bT.reserve((size_t)n * nz); r->d_bTs.reserve(n);
     HIPCHK(hipMemcpyAsync(r->d_bT.p, T, sizeof(double) * (size_t)n * nz, hipMemcpyHostToDevice, r->stream));
     HIPCHK(hipMemcpyAsync(r->d_bTs.p, T_surface, sizeof(double) * n, hipMemcpyHostToDevice, r->stream));
     ir_batch_general(r, r->d_bT.p, r->d_bTs.p, n, r->d_bout.p, (size_t)n * nl);
   }
   const size_t arr = (size_t)n * nl;
-  if (r->comm) {
-    // a communicator handle worked on its share of the bins: one all-reduce of the batch's up / down arrays
-    // (src/radtran/clima_radtran_radiate.f90:184-192 summed over the bins of all ranks), f_total from the reduced rows
-    NCCLCHK(ncclAllReduce(r->d_bout.p, r->d_bout.p, 2 * arr, ncclDouble, ncclSum, r->comm, r->stream));
-    r->comm_reduces++;
-    launch_batch_ftotal(r->d_bout.p, arr, n, nz, r->d_flux_n.p, r->stream);
-    HIPCHK(hipGetLastError());
-  }
+  // (src/radtran/clima_radtran_radiate.f90:184-192 summed over the bins of all ranks; f_total from the reduced rows)
+  comm_reduce_up_down(r, arr, [&] { launch_batch_ftotal(r->d_bout.p, arr, n, nz, r->d_flux_n.p, r->stream); });
   const double t_enq = times ? since() : 0.0;
   if (times) HIPCHK(hipStreamSynchronize(r->stream));
   const double t_kern = times ? since() : 0.0;
@@ -2153,7 +2125,7 @@ static bool ir_jacobian_refused(const Radtran *r, const double *T_surface, const
 static const int *ir_jacobian_green_part(Radtran *r, const double *T_surface, const double *T, const std::vector<int> &extra, GreenParams &g) {
   const int nz = r->nz, nl = nz + 1;
   // the mixed pairs as the batch builds them
-  const int ndev = nl, ndev_pad = (ndev + 15) / 16 * 16;
+  const int ndev = nl, ndev_pad = green_ndev_pad(ndev);
   std::vector<int> dev_k(ndev), mdev, mblk;
   for (int k = 0; k < ndev; k++) dev_k[k] = k;
   green_mixed_list(dev_k, nz, mdev, mblk);
@@ -2166,12 +2138,12 @@ static const int *ir_jacobian_green_part(Radtran *r, const double *T_surface, co
   hd[nz] = *T_surface;
   for (int d = 0; d < ndev_pad; d++) hi[d] = d < ndev ? d : 0;
   std::copy(extra.begin(), extra.end(), std::copy(mblk.begin(), mblk.end(), std::copy(mdev.begin(), mdev.end(), hi + ndev_pad)));
-  if (r->d_green_in.n < (size_t)nl) r->d_green_in.alloc(nl);
-  if (r->d_green_idx.n < ni) r->d_green_idx.alloc(ni);
+  r->d_green_in.reserve(nl);
+  r->d_green_idx.reserve(ni);
   HIPCHK(hipMemcpyAsync(r->d_green_in.p, hd, sizeof(double) * nl, hipMemcpyHostToDevice, r->stream));
   HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * ni, hipMemcpyHostToDevice, r->stream));
   green_factor_part(r, g);
-  green_accum_arrays(r, g, ndev, ndev_pad, nmix);
+  green_accum_arrays(r, g, ndev, nmix);
   g.dev_k = r->d_green_idx.p; g.mix_dev = g.dev_k + ndev_pad; g.mix_blk = g.mix_dev + nmix;
   g.base_T = r->d_green_in.p;
   return g.mix_blk + nmix;
@@ -2194,7 +2166,7 @@ void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, c
   upload_fields(r);
   ensure_w0(r);
   const size_t arr = (size_t)nl * nl;
-  if (r->d_bout.n < 3 * arr) r->d_bout.alloc(3 * arr);
+  r->d_bout.reserve(3 * arr);
   if (r->ir_n > 0) {
     GreenParams g;
     ir_jacobian_green_part(r, T_surface, T, {}, g);
@@ -2205,13 +2177,7 @@ void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, c
     // a shard without IR bins: no k_green_* kernel (their grids would be empty), zeros into the all-reduce
     HIPCHK(hipMemsetAsync(r->d_bout.p, 0, sizeof(double) * 3 * arr, r->stream));
   }
-  if (r->comm) {
-    // every rank worked on its bins: one all-reduce of the up / down matrices, the total from the reduced ones
-    NCCLCHK(ncclAllReduce(r->d_bout.p, r->d_bout.p, 2 * arr, ncclDouble, ncclSum, r->comm, r->stream));
-    r->comm_reduces++;
-    launch_jacobian_total(r->d_bout.p, arr, arr, r->stream);
-    HIPCHK(hipGetLastError());
-  }
+  comm_reduce_up_down(r, arr, [&] { launch_jacobian_total(r->d_bout.p, arr, arr, r->stream); });
   double *const outs[3] = {jac_up, jac_dn, jac_total};
   bout_to_host(r, outs, arr);
   CATCH(err)
@@ -2284,7 +2250,7 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
   // a communicator handle forms up and down whatever was asked for: they are what is summed over the ranks
   const bool want_parts = jac_up != nullptr, parts = want_parts || r->comm;
   const size_t need = (parts ? 3 : 1) * arr;
-  if (r->d_bout.n < need) r->d_bout.alloc(need);
+  r->d_bout.reserve(need);
   if (r->ir_n > 0) {
     GreenParams g;
     const int *d_map = ir_jacobian_green_part(r, T_surface, T, csr, g);
@@ -2296,13 +2262,7 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
     // a shard without IR bins: no k_green_* kernel (their grids would be empty), zeros into the all-reduce
     HIPCHK(hipMemsetAsync(r->d_bout.p, 0, sizeof(double) * need, r->stream));
   }
-  if (r->comm) {
-    // one all-reduce of the reduced up / down matrices (2 nrow ngroup doubles), the total from the reduced ones
-    NCCLCHK(ncclAllReduce(r->d_bout.p, r->d_bout.p, 2 * arr, ncclDouble, ncclSum, r->comm, r->stream));
-    r->comm_reduces++;
-    launch_jacobian_total(r->d_bout.p, arr, arr, r->stream);
-    HIPCHK(hipGetLastError());
-  }
+  comm_reduce_up_down(r, arr, [&] { launch_jacobian_total(r->d_bout.p, arr, arr, r->stream); });   // (2 nrow ngroup doubles)
   double *const outs[3] = {jac_up, jac_dn, jac_total};
   if (want_parts) bout_to_host(r, outs, arr);
   else bout_to_host(r, &jac_total, arr, 1, parts ? 2 : 0);
@@ -2329,7 +2289,7 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return; }
   TRY
   const int nz = r->nz, nl = nz + 1, n = *ncol;
-  const size_t cc = r->col_count, np_n = (size_t)nz * r->np;
+  const size_t cc = r->col_layout.count, np_n = (size_t)nz * r->np;
   begin_batch(r, n, false);
   std::vector<double> h((size_t)n * cc, 0.0), out((size_t)n * 5 * nl);
   r->batch_nsrc.resize(n);
@@ -2418,7 +2378,7 @@ void clima_test_pack_columns(void *ptr, const int *ncol, const double *T_surface
   if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
   const int hp = has_particles ? *has_particles : 0;
   if (*ncol < 1 || (r->np > 0 && !(hp && pdensities && radii))) { set_err(err, "clima_test_pack_columns: bad arguments"); return; }
-  *col_count = (int)r->col_count;
+  *col_count = (int)r->col_layout.count;
   if (!blocks) return;
   TRY
   const size_t n = *ncol, nz = r->nz;
@@ -2427,7 +2387,7 @@ void clima_test_pack_columns(void *ptr, const int *ncol, const double *T_surface
   auto up = [&](DevBuf<double> &d, const double *h, size_t count) { d.upload(std::vector<double>(h, h + count)); };
   up(ts, T_surface, n); up(t, T, n * nz); up(p, P, n * nz); up(de, densities, n * nz * r->nsp); up(z, dz, n * nz);
   if (r->np > 0) { up(pd, pdensities, n * nz * r->np); up(ra, radii, n * nz * r->np); }
-  out.alloc(n * r->col_count);
+  out.alloc(n * r->col_layout.count);
   ns.alloc(n);
   launch_pack_columns(make_pack_params(r, (int)n, ts.p, t.p, p.p, de.p, z.p, pd.p, ra.p, out.p, ns.p), r->stream);
   HIPCHK(hipGetLastError());
@@ -2443,12 +2403,12 @@ void clima_test_pack_columns_host(void *ptr, const int *ncol, const double *T_su
   if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
   const int hp = has_particles ? *has_particles : 0;
   if (*ncol < 1 || (r->np > 0 && !(hp && pdensities && radii))) { set_err(err, "clima_test_pack_columns: bad arguments"); return; }
-  *col_count = (int)r->col_count;
+  *col_count = (int)r->col_layout.count;
   if (!blocks) return;
   const size_t nz = r->nz, np_n = nz * r->np;
-  std::memset(blocks, 0, sizeof(double) * (size_t)*ncol * r->col_count);
+  std::memset(blocks, 0, sizeof(double) * (size_t)*ncol * r->col_layout.count);
   for (size_t c = 0; c < (size_t)*ncol; c++)
-    pack_column(r, blocks + c * r->col_count, T_surface[c], T + c * nz, P + c * nz, dz + c * nz, densities + c * nz * r->nsp,
+    pack_column(r, blocks + c * r->col_layout.count, T_surface[c], T + c * nz, P + c * nz, dz + c * nz, densities + c * nz * r->nsp,
                 r->np > 0 ? pdensities + c * np_n : nullptr, r->np > 0 ? radii + c * np_n : nullptr);
 }
 
@@ -2648,7 +2608,7 @@ void radtran_set_bin_shard(void *ptr, const int *rank, const int *world, char *e
   for (WrkObj *w : {&r->wrk_ir, &r->wrk_sol}) { w->fup_a.zero(r->stream); w->fdn_a.zero(r->stream); w->amean.zero(r->stream); w->tau_band.zero(r->stream); }
   r->d_flux_n.zero(r->stream);
   if (*world > 1) {
-    if (r->d_flux_part.n < (size_t)4 * (r->nz + 1)) r->d_flux_part.alloc((size_t)4 * (r->nz + 1));
+    r->d_flux_part.reserve((size_t)4 * (r->nz + 1));
     r->d_flux_part.zero(r->stream);
   }
   HIPCHK(hipStreamSynchronize(r->stream));
@@ -3089,20 +3049,18 @@ void clima_test_ir_response(const int *nz_, const int *ng_, const double *tau, c
                             const double *dev_db, double *resp_up, double *resp_dn, char *err) {
   clear_err(err);
   TRY
-  const int nz = *nz_, ng = *ng_, nl = nz + 1, N = 2 * nz, ndev = *ndev_;
+  const int nz = *nz_, ng = *ng_, nl = nz + 1, ndev = *ndev_;
   if (nz < 4 || ng < 1 || ng > 32 || ndev < 1) throw HipFail{"clima_test_ir_response: bad nz / ng / ndev"};
   std::vector<int> order(ndev);
   for (int i = 0; i < ndev; i++) { order[i] = i; if (dev_k[i] < 0 || dev_k[i] > nz) throw HipFail{"clima_test_ir_response: bad level"}; }
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return dev_k[a] < dev_k[b]; });
-  const int ndev_pad = std::max(16, (ndev + 15) / 16 * 16), nblk = (nl + 15) / 16;
+  const int ndev_pad = green_ndev_pad(ndev);
   std::vector<double> h_tau((size_t)ng * nz), h_w0((size_t)ng * nz), h_db(ndev_pad + 64, 0.0);
   for (int c = 0; c < ng; c++)
     for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau[i]; h_w0[(size_t)c * nz + i] = w0[i]; }
   std::vector<int> hi(ndev_pad, 0), mdev, mblk;
   for (int d = 0; d < ndev; d++) { hi[d] = dev_k[order[d]]; h_db[d] = dev_db[order[d]]; }
-  for (int d = 0; d < ndev; d++)
-    for (int blk = 0; blk < nblk; blk++)
-      if (green_block_class(hi[d], blk, nz) == 2) { mdev.push_back(d); mblk.push_back(blk); }
+  green_mixed_list(std::vector<int>(hi.begin(), hi.begin() + ndev), nz, mdev, mblk);
   const int nmix = (int)mdev.size();
   hi.insert(hi.end(), mdev.begin(), mdev.end());
   hi.insert(hi.end(), mblk.begin(), mblk.end());
@@ -3111,17 +3069,16 @@ void clima_test_ir_response(const int *nz_, const int *ng_, const double *tau, c
   d_tau.upload(h_tau); d_w0.upload(h_w0); d_g.upload(std::vector<double>(g, g + nz));
   d_wbin.upload(std::vector<double>(wbin, wbin + ng)); d_em.upload(std::vector<double>{ir_par[0]});
   d_db.upload(h_db); d_idx.upload(hi);
-  const size_t RQ = (size_t)N * ng, LQ = (size_t)nl * ng, FQ = (size_t)2 * nblk * 34 * ng;
-  d_work.alloc(7 * RQ + 6 * LQ + FQ + 8 * LQ + 4 * (size_t)ng + (size_t)ndev_pad * 2 * nl); d_work.zero();
+  const size_t work = green_work_views(nz, ng, nullptr).count;
+  d_work.alloc(work + (size_t)ndev_pad * 2 * nl); d_work.zero();   // ... and the one array of partial sums behind them
   GreenParams gp;
   std::memset(&gp, 0, sizeof(gp));
   gp.nz = nz; gp.ng = ng; gp.n_ir = 1; gp.ir_lo = 0; gp.ir_start = 0; gp.NQ = ng;
   gp.tau = d_tau.p; gp.w0 = d_w0.p; gp.g = d_g.p; gp.wbin = d_wbin.p; gp.emissivity = d_em.p;
   gp.has_hard_surface = ir_par[1] != 0.0 ? 1 : 0; gp.ir_tau_min = ir_par[2];
-  double *w = d_work.p;
-  auto take = [&](size_t cnt) { double *p0 = w; w += cnt; return p0; };
-  gp.RW = take(7 * RQ); gp.IS = take(6 * LQ); gp.FS = take(FQ); gp.DS = take(8 * LQ); gp.D0 = take(4 * (size_t)ng);
-  gp.partial = take((size_t)ndev_pad * 2 * nl);
+  const GreenWork w = green_work_views(nz, ng, d_work.p);
+  gp.RW = w.RW; gp.IS = w.IS; gp.FS = w.FS; gp.DS = w.DS; gp.D0 = w.D0;
+  gp.partial = d_work.p + work;
   gp.DB = d_db.p;
   gp.ndev = ndev; gp.ndev_pad = ndev_pad; gp.qsplit = 1; gp.msplit = 1; gp.partial_m = gp.partial;   // (disjoint pairs: one array)
   gp.dev_k = d_idx.p; gp.nmix = nmix; gp.mix_dev = gp.dev_k + ndev_pad; gp.mix_blk = gp.mix_dev + nmix;

@@ -21,6 +21,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 namespace clima {
 
 // Crossing windows of the window-form rebin (kernels.hip rb_lo / rb_hi), indexed by the output edge
@@ -94,6 +96,73 @@ constexpr int SRC_PAIR = 1 << 30;    // layer j+1 reuses this layer (pair_reuse,
 constexpr int SRC_EXACT = 1 << 29;   // ... and every input of layer j+1 is bitwise equal to layer j's
 constexpr int SRC_LAYER = 0xffff;
 
+// ---- what the host and the kernels must agree on, each stated once ----
+
+// futils is_close (fortran-stdlib form).  Every operation is rounded on its own, and no product feeds the difference.
+__host__ __device__ inline bool is_close(double a, double b, double tol) {
+#pragma clang fp contract(off)
+  const double fa = fabs(a), fb = fabs(b);
+  return fabs(a - b) <= fabs(tol * (fa < fb ? fb : fa));
+}
+
+// Column block [T_surface | T | P | dz | dens | pdens | radii | meta]: offsets in doubles (T_surface at 0), dens
+// [nsp][nz], pdens / radii [np][nz]; meta is (2 nz + 1) ints (see ColumnDev::meta) and one int of padding.
+struct ColumnLayout { size_t T, P, dz, dens, pdens, radii, meta, count; };
+__host__ __device__ inline ColumnLayout column_layout(int nz, int nsp, int np) {
+  ColumnLayout l;
+  l.T = 1; l.P = l.T + nz; l.dz = l.P + nz; l.dens = l.dz + nz;
+  l.pdens = l.dens + (size_t)nsp * nz; l.radii = l.pdens + (size_t)np * nz; l.meta = l.radii + (size_t)np * nz;
+  l.count = l.meta + nz + 1;
+  return l;
+}
+
+// pair_reuse (clima_radtran_types.f90:621-632) of the pair (j-1, j), j odd (0-based), of a column with an even number
+// of layers: layer j reuses layer j-1 when P, T, every column density * dz and (use_radii: the column comes with
+// particles and the handle has particle opacities) every radius agree to 1e-12 (is_close).  The columns are stored
+// products in the reference (opw%cols): each is rounded before the comparison, never fused into it.  exact: reused,
+// and every input of layer j is bitwise equal to layer j-1's.  pdens / radii: [np][nz], or null (no particles given).
+struct PairDecision { bool reuse, exact; };
+__host__ __device__ inline PairDecision pair_decision(int j, int nz, int nsp, int np, const double *T, const double *P,
+                                                      const double *dz, const double *dens, const double *pdens,
+                                                      const double *radii, bool use_radii) {
+#pragma clang fp contract(off)
+  const double tol = 1.0e-12;
+  bool reuse = is_close(P[j], P[j - 1], tol) && is_close(T[j], T[j - 1], tol);
+  bool exact = P[j] == P[j - 1] && T[j] == T[j - 1] && dz[j] == dz[j - 1];
+  for (int i = 0; i < nsp && reuse; i++) {
+    const double nb = dens[(size_t)i * nz + j], na = dens[(size_t)i * nz + j - 1];
+    const double cb = nb * dz[j], ca = na * dz[j - 1];   // opw%cols
+    reuse = is_close(cb, ca, tol);
+    exact = exact && nb == na;
+  }
+  if (use_radii)
+    for (int i = 0; i < np && reuse; i++) reuse = is_close(radii[(size_t)i * nz + j], radii[(size_t)i * nz + j - 1], tol);
+  if (reuse && pdens && radii)
+    for (int i = 0; i < np; i++)
+      exact = exact && pdens[(size_t)i * nz + j] == pdens[(size_t)i * nz + j - 1] &&
+              radii[(size_t)i * nz + j] == radii[(size_t)i * nz + j - 1];
+  return PairDecision{reuse, exact && reuse};
+}
+
+// f_total of a level from its four fluxes (clima_radtran.f90:287), in this association everywhere: the device batch
+// is held byte for byte to the host batch
+__host__ __device__ inline double f_total_level(double ir_up, double ir_dn, double sol_up, double sol_dn) {
+  return (sol_dn - sol_up) + (ir_dn - ir_up);
+}
+// ... and ISR, OLR: the net solar and IR fluxes of the last level (clima_radtran.f90:339-340)
+__host__ __device__ inline void toa_isr_olr(double ir_up, double ir_dn, double sol_up, double sol_dn, double &ISR, double &OLR) {
+  ISR = sol_dn - sol_up; OLR = -(ir_dn - ir_up);
+}
+
+// Spectral integration (kernels.hip): bins per chunk, levels per block of the one-launch kernel, whose dynamic LDS
+// holds the widths [nchunk * INT_CHUNK] and the chunk sums [nchunk][INT_LV]
+constexpr int INT_CHUNK = 32;
+constexpr int INT_LV = 16;
+inline int integrate_chunks(int nbins) { return nbins <= 0 ? 1 : (nbins + INT_CHUNK - 1) / INT_CHUNK; }
+inline size_t integrate_lds_bytes(int nchunk) { return sizeof(double) * (size_t)nchunk * (INT_CHUNK + INT_LV); }
+// true when launch_integrate() takes the one-launch kernel (the form that can store into the host's block)
+inline bool integrate_fits_one_launch(int nchunk) { return integrate_lds_bytes(nchunk) <= 64 * 1024; }
+
 // Element strides from one column of a batch to the next (0 everywhere for a single call).  Every
 // per-column array of a group lives in ONE block per column with the same internal layout, so a
 // group needs one stride: the column inputs, the prep results, the optical properties, the per-bin
@@ -105,8 +174,8 @@ struct BatchStrides {
 
 struct ColumnDev {
   const double *T, *P, *dz, *dens, *pdens, *radii;  // dens [nsp][nz], pdens/radii [np][nz]
-  // pair_reuse decided on the host when the column is uploaded (one definition of is_close for the
-  // grid size and the kernels): meta[0] = nsrc, meta[1 + m] = source layer m | SRC_* flags
+  // pair_reuse decided when the column block is built (pair_decision, by the host at upload or by
+  // k_pack_columns): meta[0] = nsrc, meta[1 + m] = source layer m | SRC_* flags
   // (ascending), meta[1 + nz + j] = source layer of layer j (j, or j-1 for the second of a pair)
   const int *meta;
   double *log10P, *cols, *foreign_col;
@@ -260,13 +329,12 @@ struct BatchIntegrateParams {
 };
 
 // Column batches whose inputs are device arrays (radtran_toa_fluxes_batch_device): k_pack_columns builds column c's block
-// (the layout column_dev unpacks, pair-reuse table included) at blocks + c * col_count out of the caller's arrays, which
+// (column_layout(nz, nsp, np), pair-reuse table included) at blocks + c * its count out of the caller's arrays, which
 // carry the column as their last dimension.
 struct PackParams {
   int ncol, nz, nsp, np;
   int has_particles;         // pdens and radii are given (np > 0)
   int use_radii;             // ... and the handle has particle opacities: the radii take part in the pair decision
-  size_t col_count, meta_ofs;
   const double *T_surface, *T, *P, *dz, *dens, *pdens, *radii;
   double *blocks;
   int *nsrc;                 // [ncol] every column's source-layer count once more, contiguous (null: not wanted)
@@ -281,7 +349,13 @@ struct BatchFinishParams {
 void launch_pack_columns(const PackParams &p, hipStream_t s);
 void launch_batch_finish(const BatchFinishParams &p, hipStream_t s);
 
-constexpr int GREEN_LB = 16;                // levels per block of the far form (ir_green.inc)
+// The response form's work arrays (ir_green.inc), per (bin, g-point) q
+constexpr int GREEN_LB = 16;                 // levels per block of the far form
+constexpr int GREEN_RW = 7;                  // per (q, row): c', 1/den, z, running products of phi and of -c' (mantissa, exponent each)
+constexpr int GREEN_IS = 6;                  // per (q, level): above form (log, up, down) and below form
+constexpr int GREEN_FS = 2 * GREEN_LB + 2;   // per (q, form, level block): reference log, pad, 16 (up factor, down factor) pairs
+constexpr int GREEN_DS = 4 + 2 * 2;          // per (q, k): above amplitude, its log, below amplitude, its log, explicit values of the levels k and k + 1
+constexpr int GREEN_D0 = 2 * 2;              // per q: level 0's explicit values (up, down) for k = 0, 1
 // Which form a level takes for a deviation at k.  A unit change of bplanck[k] reaches the source terms of layers k-1 and
 // k, i.e. the rows 2k-3 .. 2k+2 of E (those that exist); the levels k and k+1 (the bottoms of these two layers) and, for
 // k <= 1, level 0 are evaluated explicitly; the levels above take the above form, those below the below form.
@@ -335,6 +409,19 @@ struct GreenParams {
   const double *flux_n;                    // the handle's level rows (solar rows of the last solar call)
   double *out;                             // [3][ncol][nz+1] (arrays out_arr apart)
 };
+// RW | IS | FS | DS | D0 of NQ (bin, g-point) pairs laid over `base`; count: doubles in all.  A null base gives the
+// count alone.
+struct GreenWork { double *RW, *IS, *FS, *DS, *D0; size_t count; };
+inline GreenWork green_work_views(int nz, int NQ, double *base) {
+  const size_t nl = (size_t)nz + 1, nblk = (nl + GREEN_LB - 1) / GREEN_LB;
+  GreenWork v{};
+  auto take = [&](size_t n) { double *p = base ? base + v.count : nullptr; v.count += n * NQ; return p; };
+  v.RW = take(GREEN_RW * 2 * (size_t)nz); v.IS = take(GREEN_IS * nl); v.FS = take(2 * nblk * GREEN_FS);
+  v.DS = take(GREEN_DS * nl); v.D0 = take(GREEN_D0);
+  return v;
+}
+// the deviation list's padded length (the accumulation kernels take it in tiles of 16)
+inline int green_ndev_pad(int ndev) { return ndev <= 16 ? 16 : (ndev + 15) / 16 * 16; }
 void launch_green_factor(const GreenParams &p, hipStream_t s);
 void launch_green_columns(const GreenParams &p, int ncol, hipStream_t s);
 void launch_batch_ftotal(double *out, size_t out_arr, int ncol, int nz, const double *flux_n, hipStream_t s);
@@ -405,12 +492,10 @@ bool launch_fused(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, c
 // (meta_nsrc: a device int, any value >= 1)
 bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta_nsrc, hipStream_t s, bool half = false, bool paired = false);
 void launch_integrate(const IntegrateParams &p, hipStream_t s);
-bool integrate_one_launch(const IntegrateParams &p);
 // one call's integration and the next call's prep pass as ONE grid (k_prep_integrate), where prep_integrate_merges() holds
 bool prep_integrate_merges(const PrepParams &pp, const IntegrateParams &ip);
 void launch_prep_integrate(const PrepParams &pp, const IntegrateParams &ip, hipStream_t s);
 void launch_integrate_batch(const BatchIntegrateParams &p, int ncol, hipStream_t s);
-int integrate_chunks(int nbins);
 void launch_f_total(int nz, const double *flux_n, double *f_total, hipStream_t s);
 void launch_scale(double *a, size_t n, double f, hipStream_t s);
 void launch_copy(double *dst, const double *src, size_t n, hipStream_t s);  // src may be pinned host memory

@@ -136,6 +136,47 @@ def check_pair_tables(r, cols, expect):
     assert dev.tobytes() == host.tobytes()    # ... and the device's blocks are the host's, byte for byte
 
 
+def close_products(na, nb, dza, dzb, contracted):
+    """is_close(nb * dzb, na * dza, 1e-12) in float64 (numpy), every operation rounded on its own -- or, `contracted`,
+    with the product nb * dzb fused into the difference: the exact product minus the other column, rounded once"""
+    from fractions import Fraction
+    na, nb, dza, dzb = (np.float64(x) for x in (na, nb, dza, dzb))
+    ca, cb = na * dza, nb * dzb
+    diff = np.float64(float(Fraction(float(nb)) * Fraction(float(dzb)) - Fraction(float(ca)))) if contracted else cb - ca
+    return bool(np.abs(diff) <= np.abs(np.float64(1.0e-12) * max(np.abs(cb), np.abs(ca))))
+
+
+def ulps(x, k):
+    """the float64 k representable numbers above (below: k < 0) the positive x"""
+    return (np.array([x], dtype=np.float64).view(np.int64) + k).view(np.float64)[0]
+
+
+def rounding_cases(n0, dz, walk=400):
+    """Densities (na, nb) of one species in the two layers of a pair of thickness dz for which the decision with rounded
+    products differs from the one with a contracted product: the first found of each direction, keyed by what the
+    rounded decision -- the reference -- says.  na walks upwards from the column's own density n0; for each, nb is
+    bisected to the boundary of the rounded decision above na and the 9 neighbours of the boundary are tried."""
+    found = {}
+    for t in range(walk):
+        na = np.float64(n0) * (1.0 + t / 1024.0 + 1.0e-3)
+        lo, hi = na, na * (1.0 + 3.0e-12)
+        assert close_products(na, lo, dz, dz, False) and not close_products(na, hi, dz, dz, False)
+        while ulps(lo, 1) < hi:
+            mid = lo + 0.5 * (hi - lo)
+            if close_products(na, mid, dz, dz, False):
+                lo = mid
+            else:
+                hi = mid
+        for k in range(-4, 5):
+            nb = ulps(lo, k)
+            want = close_products(na, nb, dz, dz, False)
+            if want != close_products(na, nb, dz, dz, True):
+                found.setdefault(want, (float(na), float(nb)))
+        if len(found) == 2:
+            break
+    return found
+
+
 def child_main():
     """both column sets against the host batch, under whatever launch-form switches the environment carries"""
     from clima_amd import synthetic as S
@@ -224,6 +265,31 @@ def test_pair_table_is_built_on_the_device_as_on_the_host(small_tables, nz_half)
     check_pair_tables(r, cols, expect)
     if nz == 50:
         assert_same_batch(r, cols)
+
+
+def test_pair_decision_rounds_the_column_products(small_tables):
+    """The columns density * dz of the pair decision are rounded before they are compared, on the host and on the
+    device alike: cases, found here in exact arithmetic for the column's own layer thicknesses, whose decision flips
+    when a product is fused into the difference -- one that is reused only with rounded products, one that is split
+    only with them --, in two different pairs of columns of their own.  The reference is the float64 (numpy) decision."""
+    from clima_amd.radtran import Radtran
+    base = doubled(2)[0]
+    nz, sp = len(base["T"]), 1
+    assert nz == 6
+    cols, expect = [], []
+    for reused, pair in ((True, 0), (False, 2)):
+        j = 2 * pair + 1
+        assert base["dz"][j] == base["dz"][j - 1]
+        found = rounding_cases(base["densities"][j, sp], base["dz"][j])
+        print("pair %d, dz %r: rounded and contracted decisions differ at %r" % (pair, float(base["dz"][j]), found))
+        assert set(found) == {True, False}, "no case of each direction for this dz"
+        na, nb = found[reused]
+        c = pair_table_cases(base)[0][0]
+        c["densities"][j - 1, sp], c["densities"][j, sp] = na, nb
+        cols.append(c)
+        expect.append(dict(nsrc=nz // 2, not_exact=(j - 1,), split=()) if reused else dict(nsrc=nz // 2 + 1, not_exact=(), split=(j - 1,)))
+    r = Radtran(small_tables, nz, NZEN, ALBEDO)
+    check_pair_tables(r, cols, expect)
 
 
 def test_pair_table_of_an_odd_column_has_no_reuse(small_tables):
