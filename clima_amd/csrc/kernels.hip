@@ -27,6 +27,8 @@
 //                      tiles of its bin -- write-through hand-off, no cache-wide fence.
 //   k_integrate_one    spectral integration (radiate.f90:184-192); f_total (clima_radtran.f90:316) on the host from
 //                      the four level rows it fetches anyway.
+//   k_pack_columns, k_batch_finish, k_batch_spectra   the ends of a column batch out of device memory (column blocks
+//                      in, f_total / ISR / OLR out) and the gather of the per-bin rows a batch is asked to return.
 //
 // All arithmetic is IEEE binary64.  No MFMA: there is no dense contraction on this path.
 #include "radtran_dev.h"
@@ -3670,6 +3672,31 @@ __global__ __launch_bounds__(256) void k_batch_finish(BatchFinishParams p) {
 }
 void launch_batch_finish(const BatchFinishParams &p, hipStream_t s) {
   hipLaunchKernelGGL(k_batch_finish, dim3(p.ncol), dim3(256), 0, s, p);
+}
+
+// grid (blocks over (bin, selected level), array, column): consecutive threads take consecutive bins of one selected
+// level, so a wave writes 512 contiguous bytes; its reads are nl doubles apart (the arrays carry the level fastest).
+__global__ __launch_bounds__(256) void k_batch_spectra(BatchSpectraParams p) {
+  const int k = blockIdx.y, nw = p.nw[k];
+  const double *src = p.src[k];
+  double *dst = p.dst[k];
+  if (!dst) return;
+  const size_t per_col = (size_t)nw * p.nsel;
+  for (int c = blockIdx.z; c < p.ncol; c += gridDim.z) {
+    const double *s = src + (size_t)c * p.src_stride;
+    double *d = dst + (size_t)c * per_col;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_col; i += (size_t)gridDim.x * blockDim.x) {
+      const int a = (int)(i / nw), l = (int)(i - (size_t)a * nw);
+      d[i] = s[(size_t)l * p.nl + p.level[a]];
+    }
+  }
+}
+void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s) {
+  size_t most = 1;
+  for (int k = 0; k < 4; k++)
+    if (p.dst[k]) most = std::max(most, (size_t)p.nw[k] * p.nsel);
+  const unsigned gx = (unsigned)std::min<size_t>((most + 255) / 256, 4096), gz = (unsigned)std::min(p.ncol, 65535);
+  hipLaunchKernelGGL(k_batch_spectra, dim3(gx, 4, gz), dim3(256), 0, s, p);
 }
 
 #include "ir_green.inc"

@@ -142,11 +142,20 @@ struct WrkObj {  // ClimaRadtranWrk, clima_radtran.f90:11-25
 // for its n columns, once -- one launch of each kernel per chunk of CH columns, or the columns' calls back to back --,
 // the id of its first call, and its sink: the caller's device arrays (k_batch_finish forms f_total / ISR / OLR
 // there), or `rows`, n blocks [5][nz+1] on the host (which forms them itself).
+// The spectral sinks (radtran_toa_fluxes_batch_spectra and its device-array form; nsel = 0: none): the rows
+// spec_level[0 .. nsel) (device, 0-based, ground-first) of every column's ir fup_a / ir fdn_a / sol fup_a / sol fdn_a
+// go to spec[k] (device, (nw, nsel, n); null: not wanted) -- the caller's arrays, or, with `rows`, slices of the
+// handle's staging buffer, whose spec_count doubles come back into spec_host beside the rows.
 struct BatchRun {
   int n = 0, first_call = 0, CH = 0;
   bool one_launch = false, pending = false;
   double *ISR = nullptr, *OLR = nullptr, *fluxes = nullptr;
   double *rows = nullptr;
+  int nsel = 0;
+  const int *spec_level = nullptr;
+  double *spec[4] = {nullptr, nullptr, nullptr, nullptr};
+  double *spec_host = nullptr;
+  size_t spec_count = 0;
 };
 
 struct Radtran {
@@ -264,6 +273,11 @@ struct Radtran {
   // is due at the next settle_device_batch().  A repeat reads the column blocks still in d_cols_arena and writes the
   // caller's same result arrays.
   BatchRun dev_batch;
+  // a batch's spectral sinks: its level list (0-based; staged once per batch), the host form's rows on their way out
+  std::vector<int> spec_level;
+  DevBuf<int> d_spec_level;
+  DevBuf<double> d_spec_stage;
+  PinnedBuf<double> h_spec;
   DevBuf<int> d_batch_nsrc;        // every column's source-layer count, as k_pack_columns found it
   std::vector<int> batch_nsrc;     // ... on the host: pack_column's, or fetched (only before one call per column: those launches are sized by it)
   hipEvent_t ev_producer = nullptr;   // orders the handle's stream behind the stream that wrote a device batch's inputs
@@ -1103,12 +1117,37 @@ void fetch_batch_nsrc(Radtran *r, int n) {
 // chunks (or the columns' calls), the rows out to the sink, the handle's own level rows = the last column's.  Nothing waits.
 void enqueue_batch(Radtran *r, const BatchRun &b, bool allow_fused) {
   const int n = b.n, nl = r->nz + 1;
-  if (b.one_launch && allow_fused)
-    for (int c0 = 0; c0 < n; c0 += b.CH) enqueue_radiate(r, arena_chunk_bufs(r, c0, std::min(b.CH, n - c0)), true, true);
-  else
-    for (int c = 0; c < n; c++) enqueue_radiate(r, arena_column_bufs(r, c, r->batch_nsrc[c]), true, true, allow_fused);
+  // the rows asked for out of the `ncol` columns from c0 on that the launches just enqueued worked on, before the next
+  // ones overwrite their spectra (the arena of a chunk, the handle's own buffers of a column's call)
+  auto gather = [&](const CallBufs &cb, int c0, int ncol) {
+    if (!b.nsel) return;
+    BatchSpectraParams p{};
+    p.ncol = ncol; p.nsel = b.nsel; p.nl = nl; p.level = b.spec_level; p.src_stride = cb.bs.res;
+    const double *const src[4] = {cb.spec.ir_fup_a, cb.spec.ir_fdn_a, cb.spec.sol_fup_a, cb.spec.sol_fdn_a};
+    for (int k = 0; k < 4; k++) {
+      p.nw[k] = k < 2 ? r->ir.nw : r->sol.nw;
+      p.src[k] = src[k];
+      p.dst[k] = b.spec[k] ? b.spec[k] + (size_t)c0 * b.nsel * p.nw[k] : nullptr;
+    }
+    launch_batch_spectra(p, r->stream);
+    HIPCHK(hipGetLastError());
+  };
+  if (b.one_launch && allow_fused) {
+    for (int c0 = 0; c0 < n; c0 += b.CH) {
+      const CallBufs cb = arena_chunk_bufs(r, c0, std::min(b.CH, n - c0));
+      enqueue_radiate(r, cb, true, true);
+      gather(cb, c0, cb.ncol);
+    }
+  } else {
+    for (int c = 0; c < n; c++) {
+      const CallBufs cb = arena_column_bufs(r, c, r->batch_nsrc[c]);
+      enqueue_radiate(r, cb, true, true, allow_fused);
+      gather(cb, c, 1);
+    }
+  }
   if (b.rows) {
     HIPCHK(hipMemcpyAsync(b.rows, r->d_flux_arena.p, sizeof(double) * n * 5 * nl, hipMemcpyDeviceToHost, r->stream));
+    if (b.spec_count) HIPCHK(hipMemcpyAsync(b.spec_host, r->d_spec_stage.p, sizeof(double) * b.spec_count, hipMemcpyDeviceToHost, r->stream));
   } else {
     launch_batch_finish(BatchFinishParams{n, r->nz, r->d_flux_arena.p, b.ISR, b.OLR, b.fluxes}, r->stream);
     HIPCHK(hipGetLastError());
@@ -2269,6 +2308,70 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
   CATCH(err)
 }
 
+// What every column batch refuses before anything else, with the texts of radtran_toa_fluxes_batch
+static bool batch_refused(Radtran *r, const int *ncol, const int *has_particles, char *err) {
+  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return true; }
+  if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return true; }
+  if (r->shard_world != 1) { set_err(err, "toa_fluxes_batch is not available on a bin-sharded handle"); return true; }
+  const int hp = has_particles ? *has_particles : 0;
+  if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return true; }
+  return false;
+}
+// The per-bin rows a spectra batch asks for: levels 1..nz+1 ground-first (row_level's convention in
+// radtran_ir_jacobian_reduced), any order, repeats allowed; out = ir_fup, ir_fdn, sol_fup, sol_fdn, each (nw, nsel, ncol)
+// or NULL.
+struct SpectraAsk { int nsel; const int *level; double *out[4]; };
+constexpr const char *SPECTRA_NAMES[4] = {"ir_fup", "ir_fdn", "sol_fup", "sol_fdn"};
+static bool spectra_refused(Radtran *r, const SpectraAsk &ask, char *err) {
+  const std::string pre = "toa_fluxes_batch_spectra: ";
+  const int nl = r->nz + 1;
+  if (ask.nsel < 1) { set_err(err, pre + "nsel must be at least 1 (nsel = " + std::to_string(ask.nsel) + ")"); return true; }
+  if (!ask.level) { set_err(err, pre + "\"spec_level\" is a required argument"); return true; }
+  for (int a = 0; a < ask.nsel; a++) {
+    const int v = ask.level[a];
+    if (v < 1 || v > nl) {
+      set_err(err, pre + "spec_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
+      return true;
+    }
+  }
+  if (!ask.out[0] && !ask.out[1] && !ask.out[2] && !ask.out[3]) {
+    set_err(err, pre + "none of ir_fup, ir_fdn, sol_fup, sol_fdn was given (radtran_toa_fluxes_batch is the call without spectra)");
+    return true;
+  }
+  return false;
+}
+// The sinks of `ask` into the run, behind begin_batch (an earlier batch is settled by then: the copy of its list out of
+// the handle's vector is done, and so are its gathers): the level list, 0-based, to the device, once; `to_host`: the
+// destinations are slices of the staging buffer, in the order of the arrays given (out_spectra takes them apart the
+// same way)
+static void stage_spectra(Radtran *r, BatchRun &run, const SpectraAsk &ask, bool to_host) {
+  run.nsel = ask.nsel;
+  r->spec_level.resize(ask.nsel);
+  for (int a = 0; a < ask.nsel; a++) r->spec_level[a] = ask.level[a] - 1;
+  r->d_spec_level.reserve(ask.nsel);
+  HIPCHK(hipMemcpyAsync(r->d_spec_level.p, r->spec_level.data(), sizeof(int) * ask.nsel, hipMemcpyHostToDevice, r->stream));
+  run.spec_level = r->d_spec_level.p;
+  if (!to_host) { for (int k = 0; k < 4; k++) run.spec[k] = ask.out[k]; return; }
+  size_t off[4], total = 0;
+  for (int k = 0; k < 4; k++) {
+    off[k] = total;
+    if (ask.out[k]) total += (size_t)(k < 2 ? r->ir.nw : r->sol.nw) * ask.nsel * run.n;
+  }
+  r->d_spec_stage.reserve(total);
+  for (int k = 0; k < 4; k++) run.spec[k] = ask.out[k] ? r->d_spec_stage.p + off[k] : nullptr;
+  run.spec_host = r->h_spec.reserve(total);
+  run.spec_count = total;
+}
+static void out_spectra(Radtran *r, const BatchRun &run, const SpectraAsk &ask) {
+  size_t off = 0;
+  for (int k = 0; k < 4; k++) {
+    if (!ask.out[k]) continue;
+    const size_t cnt = (size_t)(k < 2 ? r->ir.nw : r->sol.nw) * ask.nsel * run.n;
+    std::memcpy(ask.out[k], run.spec_host + off, sizeof(double) * cnt);
+    off += cnt;
+  }
+}
+
 // Config 4 of BASELINE.json (many independent columns): every column is one full
 // Radtran%TOA_fluxes (clima_radtran.f90:320-342), but the batch is moved to HBM in one copy, the
 // calls are enqueued back to back with no host round trip between them, and the level fluxes
@@ -2276,17 +2379,14 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
 // T, P, dz (nz, ncol); densities (nz, nsp, ncol); pdensities, radii (nz, np, ncol).
 // Outputs: ISR, OLR (ncol); fluxes (nz+1, 5, ncol) = ir up, ir down, solar up, solar down, f_total,
 // or NULL.  The handle's own wrk / f_total hold the last column afterwards.
-void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
-                              const double *densities, const double *dz, const int *has_particles,
-                              const double *pdensities, const double *radii, double *ISR, double *OLR,
-                              double *fluxes, char *err) {
+static void toa_fluxes_batch_host(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                                  const double *densities, const double *dz, const int *has_particles,
+                                  const double *pdensities, const double *radii, double *ISR, double *OLR,
+                                  double *fluxes, const SpectraAsk *ask, char *err) {
   clear_err(err);
   GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
-  if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return; }
-  if (r->shard_world != 1) { set_err(err, "toa_fluxes_batch is not available on a bin-sharded handle"); return; }
-  const int hp = has_particles ? *has_particles : 0;
-  if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return; }
+  if (batch_refused(r, ncol, has_particles, err)) return;
+  if (ask && spectra_refused(r, *ask, err)) return;
   TRY
   const int nz = r->nz, nl = nz + 1, n = *ncol;
   const size_t cc = r->col_layout.count, np_n = (size_t)nz * r->np;
@@ -2300,6 +2400,7 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
   HIPCHK(hipMemcpyAsync(r->d_cols_arena.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, r->stream));
   BatchRun run = batch_form(r, n);
   run.rows = out.data();
+  if (ask) stage_spectra(r, run, *ask, true);
   enqueue_batch(r, run, true);
   batch_leaves_handle(r, run);
   if (settle_batch(r, run)) { set_err(err, OPACITY_FAILED_MSG); return; }
@@ -2309,7 +2410,24 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
     toa_fluxes(f, nz, &ISR[c], &OLR[c]);
     if (fluxes) std::memcpy(fluxes + (size_t)c * 5 * nl, f, sizeof(double) * 5 * nl);
   }
+  if (ask) out_spectra(r, run, *ask);
   CATCH(err)
+}
+void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                              const double *densities, const double *dz, const int *has_particles,
+                              const double *pdensities, const double *radii, double *ISR, double *OLR,
+                              double *fluxes, char *err) {
+  toa_fluxes_batch_host(ptr, ncol, T_surface, T, P, densities, dz, has_particles, pdensities, radii, ISR, OLR, fluxes, nullptr, err);
+}
+// ... and with the per-bin rows `spec_level` of every column: what a batch otherwise keeps of the last column only.
+// Copies of the values the batch's own integration sums (k_batch_spectra behind each chunk, enqueue_batch).
+void radtran_toa_fluxes_batch_spectra(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                                      const double *densities, const double *dz, const int *has_particles,
+                                      const double *pdensities, const double *radii, double *ISR, double *OLR,
+                                      double *fluxes, const int *nsel, const int *spec_level, double *ir_fup,
+                                      double *ir_fdn, double *sol_fup, double *sol_fdn, char *err) {
+  const SpectraAsk ask{nsel ? *nsel : 0, spec_level, {ir_fup, ir_fdn, sol_fup, sol_fdn}};
+  toa_fluxes_batch_host(ptr, ncol, T_surface, T, P, densities, dz, has_particles, pdensities, radii, ISR, OLR, fluxes, &ask, err);
 }
 
 // The same batch with every array in device memory (the f64 tensors of a GPU-resident ensemble): the column blocks
@@ -2321,18 +2439,14 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
 // CLIMA_HIP_BATCH_ONE_LAUNCH=0): plan_radiate picks the opacity kernel and sizes the grids of such a call from the
 // column's own source-layer count, and the kernels it chooses between round differently, so the bound nsrc = nz
 // would not be the host batch's computation; the ncol counts (4 bytes each) are fetched in one copy first.
-void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
-                                     const double *d_P, const double *d_densities, const double *d_dz,
-                                     const int *has_particles, const double *d_pdensities, const double *d_radii,
-                                     double *d_ISR, double *d_OLR, double *d_fluxes, const void *producer_stream,
-                                     char *err) {
+static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
+                                 const double *d_P, const double *d_densities, const double *d_dz,
+                                 const int *has_particles, const double *d_pdensities, const double *d_radii,
+                                 double *d_ISR, double *d_OLR, double *d_fluxes, const SpectraAsk *ask,
+                                 const void *producer_stream, char *err) {
   clear_err(err);
   GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
-  if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return; }
-  if (r->shard_world != 1) { set_err(err, "toa_fluxes_batch is not available on a bin-sharded handle"); return; }
-  const int hp = has_particles ? *has_particles : 0;
-  if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return; }
+  if (batch_refused(r, ncol, has_particles, err)) return;
   TRY
   const bool part = r->np > 0;
   enum { UNUSED, REQUIRED, OPTIONAL };   // (the particle arrays of a handle without particle columns are not read)
@@ -2348,6 +2462,14 @@ void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d
       return;
     }
   }
+  if (ask) {
+    if (spectra_refused(r, *ask, err)) return;
+    for (int k = 0; k < 4; k++)
+      if (ask->out[k] && !on_handle_device(r, ask->out[k])) {
+        set_err(err, std::string("toa_fluxes_batch_device: \"") + SPECTRA_NAMES[k] + "\" is not device memory of this handle's device");
+        return;
+      }
+  }
   const int n = *ncol;
   begin_batch(r, n, true);
   if (producer_stream) {
@@ -2360,12 +2482,33 @@ void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d
   HIPCHK(hipGetLastError());
   BatchRun run = batch_form(r, n);
   run.ISR = d_ISR; run.OLR = d_OLR; run.fluxes = d_fluxes;
+  if (ask) stage_spectra(r, run, *ask, false);
   if (!run.one_launch) fetch_batch_nsrc(r, n);
   enqueue_batch(r, run, true);
   batch_leaves_handle(r, run);
   run.pending = true;
   r->dev_batch = run;
   CATCH(err)
+}
+void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
+                                     const double *d_P, const double *d_densities, const double *d_dz,
+                                     const int *has_particles, const double *d_pdensities, const double *d_radii,
+                                     double *d_ISR, double *d_OLR, double *d_fluxes, const void *producer_stream,
+                                     char *err) {
+  toa_fluxes_batch_dev(ptr, ncol, d_T_surface, d_T, d_P, d_densities, d_dz, has_particles, d_pdensities, d_radii, d_ISR, d_OLR,
+                       d_fluxes, nullptr, producer_stream, err);
+}
+// ... and with the per-bin rows (device arrays; spec_level is a HOST array, read before the call returns): final, and
+// after an expired hand-off wait refilled by the repeat, at the same radtran_synchronize as ISR / OLR / fluxes.
+void radtran_toa_fluxes_batch_spectra_device(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
+                                             const double *d_P, const double *d_densities, const double *d_dz,
+                                             const int *has_particles, const double *d_pdensities, const double *d_radii,
+                                             double *d_ISR, double *d_OLR, double *d_fluxes, const int *nsel,
+                                             const int *spec_level, double *d_ir_fup, double *d_ir_fdn, double *d_sol_fup,
+                                             double *d_sol_fdn, const void *producer_stream, char *err) {
+  const SpectraAsk ask{nsel ? *nsel : 0, spec_level, {d_ir_fup, d_ir_fdn, d_sol_fup, d_sol_fdn}};
+  toa_fluxes_batch_dev(ptr, ncol, d_T_surface, d_T, d_P, d_densities, d_dz, has_particles, d_pdensities, d_radii, d_ISR, d_OLR,
+                       d_fluxes, &ask, producer_stream, err);
 }
 
 /* test hooks: the column blocks of a batch (ncol * col_count doubles, host arrays as radtran_toa_fluxes_batch) as

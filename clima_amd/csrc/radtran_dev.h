@@ -346,8 +346,21 @@ struct BatchFinishParams {
   double *flux;
   double *ISR, *OLR, *fluxes;
 };
+// ... and k_batch_spectra takes the per-bin rows a caller asked for (radtran_toa_fluxes_batch_spectra) out of the `ncol`
+// columns of one launch before the next launch overwrites them: of up to four per-column arrays [nw[k]][nl] (src[k],
+// the columns src_stride doubles apart; dst[k] null: not wanted) the levels level[0 .. nsel) (0-based, ground-first)
+// into dst[k] (nw[k], nsel, ncol), the bin fastest.  A copy: the values are the ones the integration sums.
+struct BatchSpectraParams {
+  int ncol, nsel, nl;
+  const int *level;
+  size_t src_stride;
+  const double *src[4];
+  double *dst[4];
+  int nw[4];
+};
 void launch_pack_columns(const PackParams &p, hipStream_t s);
 void launch_batch_finish(const BatchFinishParams &p, hipStream_t s);
+void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s);
 
 // The response form's work arrays (ir_green.inc), per (bin, g-point) q
 constexpr int GREEN_LB = 16;                 // levels per block of the far form

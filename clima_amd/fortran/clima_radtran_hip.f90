@@ -84,6 +84,7 @@ module clima_radtran_hip
     procedure :: ir_jacobian => Radtran_ir_jacobian
     procedure :: ir_jacobian_reduced => Radtran_ir_jacobian_reduced
     procedure :: TOA_fluxes_batch => Radtran_TOA_fluxes_batch
+    procedure :: TOA_fluxes_batch_spectra => Radtran_TOA_fluxes_batch_spectra
     procedure :: opacities2yaml => Radtran_opacities2yaml
     procedure :: set_names => Radtran_set_names
     procedure :: set_custom_optical_properties => Radtran_set_custom_optical_properties
@@ -176,6 +177,16 @@ module clima_radtran_hip
       integer(c_int), intent(in) :: ncol, has_particles
       real(c_double), intent(in) :: T_surface(*), T(*), P(*), densities(*), dz(*), pdensities(*), radii(*)
       real(c_double), intent(out) :: ISR(*), OLR(*), fluxes(*)
+      character(c_char), intent(out) :: err(*)
+    end subroutine
+    subroutine c_radtran_toa_fluxes_batch_spectra(ptr, ncol, T_surface, T, P, densities, dz, has_particles, pdensities, radii, &
+                                                  ISR, OLR, fluxes, nsel, spec_level, ir_fup, ir_fdn, sol_fup, sol_fdn, err) &
+                                                  bind(c, name="radtran_toa_fluxes_batch_spectra")
+      import; type(c_ptr), value :: ptr
+      integer(c_int), intent(in) :: ncol, has_particles, nsel, spec_level(*)
+      real(c_double), intent(in) :: T_surface(*), T(*), P(*), densities(*), dz(*), pdensities(*), radii(*)
+      real(c_double), intent(out) :: ISR(*), OLR(*), fluxes(*)
+      type(c_ptr), value :: ir_fup, ir_fdn, sol_fup, sol_fdn     ! (c_null_ptr: not wanted)
       character(c_char), intent(out) :: err(*)
     end subroutine
     subroutine c_radtran_radiate_ir_batch(ptr, ncol, T_surface, dim1_T, dim2_T, T, fup_n, fdn_n, f_total, err) &
@@ -793,6 +804,56 @@ contains
     call push_fields(self)
     call c_radtran_toa_fluxes_batch(self%handle, ncol, T_surface, T, P, densities, dz, merge(1, 0, self%np > 0), &
                                     pdensities, radii, ISR, OLR, fluxes, err_c)
+    call take_err(err_c, err)
+    if (allocated(err)) return
+    call pull_results(self, .true.)
+  end subroutine
+
+  !> `TOA_fluxes_batch` with per-bin spectra of EVERY column (afterwards `self%wrk_ir` / `self%wrk_sol` hold the last
+  !> column's only): `spec_level` lists the levels wanted, 1..nz+1 ground-first (nz+1: the top of the atmosphere), any
+  !> order, repeats allowed.  `ir_fup_a(l, a, c)` is `self%wrk_ir%fup_a(spec_level(a), l)` as column c's own
+  !> `TOA_fluxes` would leave it, bit for bit; `ir_fdn_a`, and `sol_fup_a` / `sol_fdn_a` of `self%wrk_sol`, likewise.
+  !> (nw, size(spec_level), ncol) each, at least one present.
+  subroutine Radtran_TOA_fluxes_batch_spectra(self, T_surface, T, P, densities, dz, pdensities, radii, ISR, OLR, fluxes, &
+                                              spec_level, err, ir_fup_a, ir_fdn_a, sol_fup_a, sol_fdn_a)
+    class(Radtran), intent(inout) :: self
+    real(dp), intent(in) :: T_surface(:), T(:,:), P(:,:), densities(:,:,:), dz(:,:)
+    real(dp), intent(in) :: pdensities(:,:,:), radii(:,:,:)
+    real(dp), intent(out) :: ISR(:), OLR(:), fluxes(:,:,:)
+    integer, intent(in), contiguous :: spec_level(:)
+    character(:), allocatable, intent(out) :: err
+    real(dp), intent(out), contiguous, optional, target :: ir_fup_a(:,:,:), ir_fdn_a(:,:,:), sol_fup_a(:,:,:), sol_fdn_a(:,:,:)
+    character(c_char) :: err_c(err_len+1)
+    type(c_ptr) :: sink(4)
+    integer :: ncol, nsel, nw_ir, nw_sol
+    ncol = size(T_surface); nsel = size(spec_level)
+    nw_ir = size(self%ir%freq) - 1; nw_sol = size(self%sol%freq) - 1
+    if (size(T,1) /= self%nz .or. size(T,2) /= ncol .or. any(shape(densities) /= [self%nz, self%ng, ncol]) .or. &
+        any(shape(fluxes) /= [self%nz+1, 5, ncol]) .or. size(ISR) /= ncol .or. size(OLR) /= ncol) then
+      err = '"T" has the wrong input dimension.'
+      return
+    endif
+    sink = c_null_ptr
+    if (present(ir_fup_a)) then
+      if (any(shape(ir_fup_a) /= [nw_ir, nsel, ncol])) err = 'toa_fluxes_batch_spectra: "ir_fup_a" has the wrong dimension'
+      sink(1) = c_loc(ir_fup_a)
+    endif
+    if (present(ir_fdn_a)) then
+      if (any(shape(ir_fdn_a) /= [nw_ir, nsel, ncol])) err = 'toa_fluxes_batch_spectra: "ir_fdn_a" has the wrong dimension'
+      sink(2) = c_loc(ir_fdn_a)
+    endif
+    if (present(sol_fup_a)) then
+      if (any(shape(sol_fup_a) /= [nw_sol, nsel, ncol])) err = 'toa_fluxes_batch_spectra: "sol_fup_a" has the wrong dimension'
+      sink(3) = c_loc(sol_fup_a)
+    endif
+    if (present(sol_fdn_a)) then
+      if (any(shape(sol_fdn_a) /= [nw_sol, nsel, ncol])) err = 'toa_fluxes_batch_spectra: "sol_fdn_a" has the wrong dimension'
+      sink(4) = c_loc(sol_fdn_a)
+    endif
+    if (allocated(err)) return
+    call push_fields(self)
+    call c_radtran_toa_fluxes_batch_spectra(self%handle, ncol, T_surface, T, P, densities, dz, merge(1, 0, self%np > 0), &
+                                            pdensities, radii, ISR, OLR, fluxes, nsel, spec_level, sink(1), sink(2), sink(3), sink(4), err_c)
     call take_err(err_c, err)
     if (allocated(err)) return
     call pull_results(self, .true.)

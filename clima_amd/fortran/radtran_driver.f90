@@ -26,6 +26,8 @@ program radtran_driver
   real(dp), allocatable :: h2o(:,:), frn(:,:), radii_ax(:), w0(:,:), qext(:,:), gt(:,:)
   real(dp), allocatable :: ir_wavl(:), sol_wavl(:), photons(:)
   real(dp), allocatable :: T(:), P(:), densities(:,:), dz(:), pdensities(:,:), radii(:,:)
+  real(dp), allocatable :: rad_toa_single(:)
+  real(dp) :: batch_spectra_diff
   integer :: i, u
   integer :: my_rank, n_ranks, my_device
   character(1024) :: arg, id_file
@@ -146,6 +148,7 @@ program radtran_driver
   write(u,'(es26.17e3)') rad%f_total
   write(u,'(es26.17e3)') rad%wrk_ir%fup_a(nz+1,:)   ! tests/test_radtran.f90:77
   write(u,'(es26.17e3)') rad%wrk_sol%fup_a(nz+1,:)  ! :79
+  rad_toa_single = rad%wrk_ir%fup_a(nz+1,:)
   if (sharded) then
     close(u)
     call rad%comm_destroy()
@@ -173,7 +176,7 @@ program radtran_driver
   ! two independent columns in one batch (the second 1 K warmer): column 1 must reproduce the call above
   block
     real(dp) :: Tsb(2), Tb(nz,2), Pb(nz,2), db(nz,nsp,2), dzb(nz,2), ISRb(2), OLRb(2), fl(nz+1,5,2)
-    real(dp), allocatable :: pdb(:,:,:), rab(:,:,:)
+    real(dp), allocatable :: pdb(:,:,:), rab(:,:,:), toa_single(:), toa_ir(:,:,:)
     allocate(pdb(nz,max(np,1),2), rab(nz,max(np,1),2))
     Tsb = [T_surface, T_surface + 1.0_dp]
     Tb(:,1) = T; Tb(:,2) = T + 1.0_dp
@@ -186,6 +189,13 @@ program radtran_driver
     endif
     call rad%TOA_fluxes_batch(Tsb, Tb, Pb, db, dzb, pdb(:,1:np,:), rab(:,1:np,:), ISRb, OLRb, fl, err); call check()
     write(u,'(4es26.17e3)') ISRb, OLRb
+    ! ... and once more with every column's thermal emission spectrum at the top of the atmosphere (afterwards rad%wrk_ir
+    ! holds column 2's): column 1's row against the single call's above
+    toa_single = rad_toa_single
+    allocate(toa_ir(size(toa_single), 1, 2))
+    call rad%TOA_fluxes_batch_spectra(Tsb, Tb, Pb, db, dzb, pdb(:,1:np,:), rab(:,1:np,:), ISRb, OLRb, fl, [nz+1], err, &
+                                      ir_fup_a=toa_ir); call check()
+    batch_spectra_diff = maxval(abs(toa_ir(:,1,1) - toa_single))
   end block
 
   ! custom optical properties (clima_radtran.f90:494-512): a grey absorber-scatterer, then unset
@@ -207,6 +217,7 @@ program radtran_driver
   close(u)
   write(output_unit,'(a)') 'opacities2yaml:'
   write(output_unit,'(a)') rad%opacities2yaml()
+  write(output_unit,'(a,es10.3)') 'TOA_fluxes_batch_spectra: largest |column 1 - single call| of the IR row at the top: ', batch_spectra_diff
 
   ! error convention: allocated err <=> failure, reference message text
   if (np > 0) then

@@ -63,6 +63,10 @@ SIGNATURES = {
     "radtran_names_get": [_vp, _ip, C.c_char_p, C.c_char_p],
     "radtran_toa_fluxes_batch": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _err],
     "radtran_toa_fluxes_batch_device": [_vp, _ip, _vp, _vp, _vp, _vp, _vp, _ip, _vp, _vp, _vp, _vp, _vp, _vp, _err],   # device addresses
+    "radtran_toa_fluxes_batch_spectra": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _ip,
+                                         _dp, _dp, _dp, _dp, _err],
+    "radtran_toa_fluxes_batch_spectra_device": [_vp, _ip, _vp, _vp, _vp, _vp, _vp, _ip, _vp, _vp, _vp, _vp, _vp, _ip, _ip,
+                                                _vp, _vp, _vp, _vp, _vp, _err],   # device addresses; the level list is the host's
     "clima_test_pack_columns": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _err],
     "clima_test_pack_columns_host": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _err],
     "radtran_radiate_ir_batch": [_vp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _err],

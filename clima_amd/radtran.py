@@ -296,11 +296,37 @@ class Radtran:
         """src/radtran/clima_radtran.f90:508-512"""
         self._L.radtran_unset_custom_optical_properties(self._ptr)
 
-    def TOA_fluxes_batch(self, columns, return_fluxes=False):
+    SPECTRA = ("ir_fup_a", "ir_fdn_a", "sol_fup_a", "sol_fdn_a")
+
+    def _spectra_request(self, spectra_levels, spectra):
+        """(levels 1..nz+1 as the ABI takes them, the names asked for in the ABI's order) of a batch's `spectra_levels`
+        (numpy-style indices into the ground-first level axis) and `spectra`"""
+        nl = self.nz + 1
+        idx = np.atleast_1d(np.asarray(spectra_levels))
+        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+            raise ClimaException('toa_fluxes_batch_spectra: "spectra_levels" is not a list of integer level indices')
+        for a, v in enumerate(idx.tolist()):
+            if v < -nl or v >= nl:
+                raise ClimaException("toa_fluxes_batch_spectra: spectra_levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
+        spectra = (spectra,) if isinstance(spectra, str) else tuple(spectra)
+        for name in spectra:
+            if name not in self.SPECTRA:
+                raise ClimaException('toa_fluxes_batch_spectra: "%s" is not one of %s' % (name, ", ".join(self.SPECTRA)))
+        levels = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
+        return levels, tuple(name for name in self.SPECTRA if name in spectra)
+
+    def TOA_fluxes_batch(self, columns, return_fluxes=False, spectra_levels=None,
+                         spectra=("ir_fup_a", "ir_fdn_a", "sol_fup_a", "sol_fdn_a")):
         """Many independent columns (BASELINE config 4): `columns` is a sequence of column dicts /
         `synthetic.Column`s (T_surface, T, P, densities, dz[, pdensities, radii]).  Returns
         (ISR, OLR) arrays, plus the level fluxes (nz+1, 5, ncol) = ir up, ir down, solar up,
-        solar down, f_total when `return_fluxes`."""
+        solar down, f_total when `return_fluxes`.
+
+        `spectra_levels` (radtran_toa_fluxes_batch_spectra): numpy-style indices into the ground-first level axis
+        (0 the ground, -1 or nz the top of the atmosphere; any order, repeats allowed) whose per-bin rows are wanted
+        of EVERY column.  The return value then gains a last element, a dict name -> array (nsel, nw_channel, ncol)
+        for the names in `spectra`: `d["ir_fup_a"][:, :, c]` is `wrk_ir.fup_a[spectra_levels, :]` as the handle would
+        hold it after column c's own TOA_fluxes call, bit for bit."""
         n = len(columns)
         nz = self.nz
         Ts = np.array([float(c["T_surface"]) for c in columns])
@@ -320,17 +346,25 @@ class Radtran:
             pd = ra = np.zeros(1)
         isr, olr = np.empty(n), np.empty(n)
         fl = np.empty((n, 5, nz + 1)) if return_fluxes else None
-        self._L.radtran_toa_fluxes_batch(self._ptr, _i(n), _d(Ts), _d(np.ascontiguousarray(T)), _d(np.ascontiguousarray(P)),
-                                         _d(np.ascontiguousarray(dens)), _d(np.ascontiguousarray(dz)), _i(1 if hp else 0),
-                                         _d(np.ascontiguousarray(pd)), _d(np.ascontiguousarray(ra)), _d(isr), _d(olr),
-                                         _d(fl) if return_fluxes else None, self._err)
+        args = (self._ptr, _i(n), _d(Ts), _d(np.ascontiguousarray(T)), _d(np.ascontiguousarray(P)),
+                _d(np.ascontiguousarray(dens)), _d(np.ascontiguousarray(dz)), _i(1 if hp else 0),
+                _d(np.ascontiguousarray(pd)), _d(np.ascontiguousarray(ra)), _d(isr), _d(olr),
+                _d(fl) if return_fluxes else None)
+        out = (isr, olr, np.transpose(fl, (2, 1, 0))) if return_fluxes else (isr, olr)
+        if spectra_levels is None:
+            self._L.radtran_toa_fluxes_batch(*args, self._err)
+            self._check()
+            return out
+        levels, names = self._spectra_request(spectra_levels, spectra)
+        nw = {"ir": len(self.ir.freq) - 1, "sol": len(self.sol.freq) - 1}
+        spec = {name: np.empty((n, len(levels), nw[name.split("_")[0]])) for name in names}
+        self._L.radtran_toa_fluxes_batch_spectra(*args, _i(len(levels)), levels.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 *[_d(spec[name]) if name in spec else None for name in self.SPECTRA], self._err)
         self._check()
-        if return_fluxes:
-            return isr, olr, np.transpose(fl, (2, 1, 0))
-        return isr, olr
+        return out + ({name: np.transpose(a, (1, 2, 0)) for name, a in spec.items()},)
 
     def TOA_fluxes_batch_tensors(self, T_surface, T, P, densities, dz, pdensities=None, radii=None, return_fluxes=False,
-                                 sync=True):
+                                 sync=True, spectra_levels=None, spectra=("ir_fup_a", "ir_fdn_a", "sol_fup_a", "sol_fdn_a")):
         """`TOA_fluxes_batch` for columns that live in device memory (radtran_toa_fluxes_batch_device): torch CUDA
         float64 tensors, C-contiguous, T_surface (ncol,); T, P, dz (ncol, nz); densities (ncol, nsp, nz);
         pdensities / radii (ncol, np, nz).  Nothing passes through the host.  Returns fresh tensors on the same
@@ -341,7 +375,12 @@ class Radtran:
         ends with `synchronize()`.  With `sync=False` it returns at once, torch's current stream ordered behind the
         handle's: the tensors are FINAL ONLY AFTER `synchronize()` -- that is where a fused hand-off wait that
         expired in the batch is found, and the batch is then computed again, unfused, into the same tensors
-        (`fused_fallbacks` + 1), and where an opacity failure is raised.  Keep inputs and outputs alive until then."""
+        (`fused_fallbacks` + 1), and where an opacity failure is raised.  Keep inputs and outputs alive until then.
+
+        `spectra_levels`, `spectra`: as in `TOA_fluxes_batch` (radtran_toa_fluxes_batch_spectra_device); the return
+        value gains a last element, a dict name -> fresh tensor (ncol, nsel, nw_channel) on the same device, equal
+        to the host form's arrays and final under the same rule: after `synchronize()`, which refills them too when
+        it repeats the batch."""
         import torch
         nz, hp = self.nz, self.np > 0
         if hp and (pdensities is None or radii is None):
@@ -366,16 +405,25 @@ class Radtran:
         def addr(t):
             return t.data_ptr() if t is not None else None
 
+        spec = None
+        if spectra_levels is not None:
+            levels, names = self._spectra_request(spectra_levels, spectra)
+            nw = {"ir": len(self.ir.freq) - 1, "sol": len(self.sol.freq) - 1}
+            spec = {name: torch.empty((n, len(levels), nw[name.split("_")[0]]), dtype=torch.float64, device=dev) for name in names}
         cur = torch.cuda.current_stream(dev)
         mine = torch.cuda.ExternalStream(self.stream(), device=dev)
         producer = cur.cuda_stream
         if not producer:
             # the legacy default stream: NULL tells the library that the inputs are complete, so the order is made here
             mine.wait_stream(cur)
-        self._L.radtran_toa_fluxes_batch_device(self._ptr, _i(n), addr(T_surface), addr(T), addr(P), addr(densities), addr(dz),
-                                                _i(1 if hp else 0), addr(pdensities) if hp else None,
-                                                addr(radii) if hp else None, addr(isr), addr(olr), addr(fl), producer or None,
-                                                self._err)
+        args = (self._ptr, _i(n), addr(T_surface), addr(T), addr(P), addr(densities), addr(dz), _i(1 if hp else 0),
+                addr(pdensities) if hp else None, addr(radii) if hp else None, addr(isr), addr(olr), addr(fl))
+        if spec is None:
+            self._L.radtran_toa_fluxes_batch_device(*args, producer or None, self._err)
+        else:
+            self._L.radtran_toa_fluxes_batch_spectra_device(*args, _i(len(levels)), levels.ctypes.data_as(C.POINTER(C.c_int)),
+                                                            *[addr(spec.get(name)) for name in self.SPECTRA], producer or None,
+                                                            self._err)
         self._check()
         if sync:
             self.synchronize()
@@ -383,7 +431,8 @@ class Radtran:
             ev = torch.cuda.Event()
             ev.record(mine)
             cur.wait_event(ev)
-        return (isr, olr, fl) if return_fluxes else (isr, olr)
+        out = (isr, olr, fl) if return_fluxes else (isr, olr)
+        return out if spec is None else out + (spec,)
 
     def radiate_ir_batch(self, T_surface, T, out=None, pin=False):
         """ncol IR-only calls with the resident opacities in one go: column c is

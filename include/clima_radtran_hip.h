@@ -193,6 +193,31 @@ void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d
                                      const int *has_particles, const double *d_pdensities, const double *d_radii,
                                      double *d_ISR, double *d_OLR, double *d_fluxes, const void *producer_stream,
                                      char *err);
+/* Both batches with per-bin spectra of EVERY column (a plain batch keeps the last column's only, in the handle):
+ * spec_level(nsel) lists levels 1..nz+1, ground-first (nz+1: the top of the atmosphere; row_level's convention in
+ * radtran_ir_jacobian_reduced), in any order, repeats allowed.  ir_fup, ir_fdn (nw_ir, nsel, ncol) and sol_fup,
+ * sol_fdn (nw_sol, nsel, ncol), the bin fastest and in the channel's own order (rtchannel_freq_get); any of them may
+ * be NULL, not all four.  Element (l, a, c) of ir_fup is wrk_ir%fup_a(spec_level(a), l) as the handle would hold it
+ * after column c's own TOA_fluxes call, same units -- copied out of the batch before its buffers are reused, not
+ * recomputed, so bit for bit the value the batch's integration summed -- and likewise fdn_a / wrk_sol.  Everything
+ * else is radtran_toa_fluxes_batch (radtran_toa_fluxes_batch_device): ISR, OLR, fluxes bit for bit, the handle left
+ * holding the last column.  Device form: spec_level is a HOST array, read before the call returns; the spectrum
+ * arrays are final, and after an expired hand-off wait refilled by the repeat, at the same radtran_synchronize as the
+ * other results.  Refused with nothing enqueued: what the plain batch refuses, with its texts; nsel < 1; a level
+ * outside 1..nz+1 (`spec_level(2) = 0 is outside 1..51`); all four arrays NULL; in the device form a spectrum array
+ * that is not device memory of the handle's device (`toa_fluxes_batch_device: "ir_fup" is not device memory ...`).
+ * After an opacity failure the spectrum arrays hold unspecified values, as fluxes does. */
+void radtran_toa_fluxes_batch_spectra(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                                      const double *densities, const double *dz, const int *has_particles,
+                                      const double *pdensities, const double *radii, double *ISR, double *OLR,
+                                      double *fluxes, const int *nsel, const int *spec_level, double *ir_fup,
+                                      double *ir_fdn, double *sol_fup, double *sol_fdn, char *err);
+void radtran_toa_fluxes_batch_spectra_device(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
+                                             const double *d_P, const double *d_densities, const double *d_dz,
+                                             const int *has_particles, const double *d_pdensities, const double *d_radii,
+                                             double *d_ISR, double *d_OLR, double *d_fluxes, const int *nsel,
+                                             const int *spec_level, double *d_ir_fup, double *d_ir_fdn, double *d_sol_fup,
+                                             double *d_sol_fdn, const void *producer_stream, char *err);
 /* test hooks: the column blocks (ncol * col_count doubles; blocks NULL: col_count alone) of a batch given as host
  * arrays, built by the device batch's kernel and by the host batch's pack_column */
 void clima_test_pack_columns(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
