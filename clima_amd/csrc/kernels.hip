@@ -531,18 +531,11 @@ __device__ long long *g_stamp_buf = nullptr;   // (two-stream blocks of the diag
 // normal one: k-coefficients ascend in g, and so does a rebinned mixture): the sorted order is then a
 // linear extension of the 8x8 product order, every prefix is a down-set (a Young diagram) of the
 // grid, and the bounds over down-sets of each size confine the crossings to 52 pairs.
+// The tables themselves are radtran_dev.h's (RB_WIN_* / RB_TIGHT_*), the ones the host checks the weights against.
 template <bool TIGHT>
-constexpr int rb_lo(int k) {
-  constexpr int wide[8] = {0, 1, 5, 10, 18, 27, 39, 52};
-  constexpr int tight[8] = {0, 5, 12, 19, 27, 35, 45, 55};
-  return TIGHT ? tight[k] : wide[k];
-}
+constexpr int rb_lo(int k) { return TIGHT ? RB_TIGHT_LO[k] : RB_WIN_LO[k]; }
 template <bool TIGHT>
-constexpr int rb_hi(int k) {
-  constexpr int wide[8] = {0, 11, 24, 36, 45, 53, 58, 62};
-  constexpr int tight[8] = {0, 8, 18, 28, 36, 44, 51, 58};
-  return TIGHT ? tight[k] : wide[k];
-}
+constexpr int rb_hi(int k) { return TIGHT ? RB_TIGHT_HI[k] : RB_WIN_HI[k]; }
 
 // A sort key carries the index i*8+j of its (x_i, y_j) pair in mantissa bits 3-8 -- as the byte offset
 // of the pair's weight in the LDS table, so that the lookup is one AND and the read (in bits 0-5 it
@@ -3272,7 +3265,7 @@ bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta
 // ------------------------------------------------------------------------------------
 // spectral integration: fup_n(i) = sum_l fup_a(i,l)*(freq(l)-freq(l+1)) (radiate.f90:184-192)
 // in two deterministic stages (chunks of INT_CHUNK bins in bin order, then the chunk
-// sums in order), then f_total (clima_radtran.f90:316)
+// sums in order); f_total (clima_radtran.f90:316) is the host's, from the four rows it fetches (fetch_small)
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_integrate_partial(IntegrateParams p) {
   const int nl = p.nz + 1;
@@ -3316,10 +3309,6 @@ __global__ __launch_bounds__(1024) void k_integrate_final(IntegrateParams p) {
     p.flux_n[a * nl + i] = acc;
     if (p.flux_part) p.flux_part[a * nl + i] = acc;
   }
-  __syncthreads();
-  if (p.f_total)
-    for (int i = threadIdx.x; i < nl; i += blockDim.x)
-      p.f_total[i] = f_total_level(p.flux_n[i], p.flux_n[nl + i], p.flux_n[2 * nl + i], p.flux_n[3 * nl + i]);
 }
 
 // Batched IR form (shared opacity, ncol temperature columns): the same two deterministic
@@ -3402,6 +3391,7 @@ __device__ __forceinline__ void integrate_block(const IntegrateParams &p, const 
     const int t = *p.timeout_flag;   // the fused grid of this call has drained: the word is final
     *p.timeout_out = (t == p.id_opr ? 1.0 : 0.0) + (t == p.id_sol ? 1024.0 : 0.0);
   }
+  // (host_out is a level-row block, level_rows(nz) of radtran_dev.h: row a at a * nl, the error words behind five rows)
   if (p.host_out && a == 0 && bx == 0 && cb == 0 && threadIdx.x < 2)   // the error words ride along
     reinterpret_cast<int *>(p.host_out + 5 * nl)[threadIdx.x] = p.err_words[threadIdx.x];
   if (sol && !p.do_solar) {
@@ -3509,14 +3499,6 @@ void launch_w0_from_scat(const double *tau, const double *scat, double *w0, int 
   hipLaunchKernelGGL(k_w0_from_scat, dim3(2048), dim3(256), 0, s, tau, scat, w0, nw, ng, nz);
 }
 
-__global__ void k_f_total(int nl, const double *flux_n, double *f_total) {
-  for (int i = threadIdx.x; i < nl; i += blockDim.x)
-    f_total[i] = f_total_level(flux_n[i], flux_n[nl + i], flux_n[2 * nl + i], flux_n[3 * nl + i]);
-}
-void launch_f_total(int nz, const double *flux_n, double *f_total, hipStream_t s) {
-  hipLaunchKernelGGL(k_f_total, dim3(1), dim3(256), 0, s, nz + 1, flux_n, f_total);
-}
-
 __global__ void k_scale(double *a, size_t n, double f) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) a[i] = a[i] * f;
 }
@@ -3582,12 +3564,13 @@ __global__ __launch_bounds__(PACK_THREADS) void k_pack_columns(PackParams p) {
   const int c = blockIdx.x, tid = threadIdx.x, nz = p.nz, nsp = p.nsp, np = p.np;
   const ColumnLayout lay = column_layout(nz, nsp, np);
   double *dst = p.blocks + (size_t)c * lay.count;
-  const double *T = p.T + (size_t)c * nz, *P = p.P + (size_t)c * nz, *dz = p.dz + (size_t)c * nz;
-  const double *dens = p.dens + (size_t)c * nz * nsp;
-  const double *pdens = p.has_particles ? p.pdens + (size_t)c * nz * np : nullptr;
-  const double *radii = p.has_particles ? p.radii + (size_t)c * nz * np : nullptr;
+  // (ColumnArrays::column(c, ...) of p.in, with the host's word for whether the particle arrays are given)
+  const double *T = p.in.T + (size_t)c * nz, *P = p.in.P + (size_t)c * nz, *dz = p.in.dz + (size_t)c * nz;
+  const double *dens = p.in.dens + (size_t)c * nz * nsp;
+  const double *pdens = p.has_particles ? p.in.pdens + (size_t)c * nz * np : nullptr;
+  const double *radii = p.has_particles ? p.in.radii + (size_t)c * nz * np : nullptr;
 
-  if (tid == 0) dst[0] = p.T_surface[c];
+  if (tid == 0) dst[0] = p.in.T_surface[c];
   for (int i = tid; i < nz; i += PACK_THREADS) {
     dst[lay.T + i] = T[i];
     dst[lay.P + i] = P[i];
@@ -3658,6 +3641,7 @@ void launch_pack_columns(const PackParams &p, hipStream_t s) {
 // and one sum, no product anywhere -- and the five rows out.
 __global__ __launch_bounds__(256) void k_batch_finish(BatchFinishParams p) {
   const int c = blockIdx.x, nl = p.nz + 1;
+  // (a column's level rows, level_rows(nz) of radtran_dev.h: five rows of nl, the columns its stride = 5 nl apart)
   double *h = p.flux + (size_t)c * 5 * nl;
   double *out = p.fluxes ? p.fluxes + (size_t)c * 5 * nl : nullptr;
   for (int i = threadIdx.x; i < nl; i += blockDim.x) {

@@ -236,8 +236,9 @@ struct Radtran {
   DevBuf<double> d_tau, d_w0, d_g, d_tau_band, d_scat;
   bool opr_valid = false;
   // results
-  DevBuf<double> d_small;     // flux_n[4*(nz+1)] | f_total[nz+1] | err flag slot: one D2H copy per call
-  DevBuf<double> d_flux_n, d_f_total;   // views into d_small
+  LevelRows rows{};           // level_rows(nz): the layout of d_small, h_small and a column's slice of d_flux_arena
+  DevBuf<double> d_small;     // one level-row block: one D2H copy per call
+  DevBuf<double> d_flux_n;    // view into d_small: its four flux rows
   std::vector<std::pair<void *, size_t>> host_registered;   // caller arrays page-locked by radtran_spectra_get_all / radtran_radiate_ir_batch
   double *batch_out[3] = {nullptr, nullptr, nullptr};       // the result arrays of the last radtran_radiate_ir_batch call
   size_t batch_out_n = 0;
@@ -245,7 +246,7 @@ struct Radtran {
   bool batch_pin_results = false;                           // radtran_batch_pin_results_set
   hipEvent_t bout_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // the batch's result pieces
   hipStream_t copy_streams[3] = {nullptr, nullptr, nullptr}; // radtran_spectra_get_all: the seven copies go out over four queues
-  double *h_small = nullptr;  // pinned: flux_n[4*(nz+1)] | f_total[nz+1] | err flag (as double slot)
+  double *h_small = nullptr;  // pinned: d_small's block on the host
   double *h_small_dev = nullptr;   // the same block as the device addresses it (null: not mapped)
   bool small_in_host = false;      // the last call's integration stored its rows into h_small itself: no copy to fetch them
   int *h_errflag = nullptr;
@@ -256,7 +257,7 @@ struct Radtran {
   DevBuf<double> d_flux_part;  // this rank's partial level rows (d_flux_n is all-reduced in place)
   int shard_rank = 0, shard_world = 1;
   // the library's own multi-GPU step (radtran_comm_init_rank): with a communicator every radiate() ends with ONE
-  // ncclAllReduce of the 4 (nz+1) partial level fluxes (+ one status word) on the handle's stream
+  // ncclAllReduce of the partial level fluxes and one status word (rows.reduce_count) on the handle's stream
   ncclComm_t comm = nullptr;
   int comm_n = 1, comm_rank = 0, device = 0;
   long comm_reduces = 0;       // all-reduces enqueued so far (tests)
@@ -264,7 +265,7 @@ struct Radtran {
   int op_lo = 0, op_n = 0, ir_lo = 0, ir_n = 0, sol_lo = 0, sol_n = 0;
   // stream + profiling
   hipStream_t stream = nullptr;
-  // column batches (radtran_toa_fluxes_batch): every column's block, every column's level rows [5][nz+1]
+  // column batches (radtran_toa_fluxes_batch): every column's block, every column's level rows (rows.stride each)
   DevBuf<double> d_cols_arena, d_flux_arena;
   // one-launch batches: per-column prep / opr / spectra blocks for the columns in flight
   DevBuf<double> d_prep_arena, d_opr_arena, d_res_arena;
@@ -583,7 +584,7 @@ struct CallBufs {
   bool all_pairs_exact;    // every layer is half of an exact pair (known of the resident column only)
   OprViews opr;
   SpectraViews spec;
-  double *flux_n, *f_total;
+  double *flux_n;          // the level rows (LevelRows)
   int *done;               // the fused grid's per-tile flags
   int ncol;                // columns of this launch; their blocks are bs apart (zero but for a chunk)
   BatchStrides bs;
@@ -598,7 +599,7 @@ CallBufs resident_bufs(Radtran *r, bool host_out = false) {
   b.opr = OprViews{r->d_tau.p, r->d_w0.p, r->d_g.p, r->d_tau_band.p, r->d_scat.p, r->opr_count};
   b.spec = SpectraViews{r->wrk_ir.fup_a.p, r->wrk_ir.fdn_a.p, r->wrk_ir.tau_band.p, r->wrk_sol.fup_a.p,
                         r->wrk_sol.fdn_a.p, r->wrk_sol.amean.p, r->wrk_sol.tau_band.p, 0};   // (seven buffers, no block)
-  b.flux_n = r->d_flux_n.p; b.f_total = r->d_f_total.p; b.done = r->d_done.p;
+  b.flux_n = r->d_flux_n.p; b.done = r->d_done.p;
   return b;
 }
 // column c of the arena (nsrc: what build_meta returned for it) on the handle's optical-property and spectra buffers
@@ -606,18 +607,17 @@ CallBufs arena_column_bufs(Radtran *r, int c, int nsrc) {
   CallBufs b = resident_bufs(r);
   b.kind = CALL_ARENA_COLUMN; b.nsrc = nsrc; b.all_pairs_exact = false;
   b.col = r->d_cols_arena.p + (size_t)c * r->col_layout.count;
-  b.flux_n = r->d_flux_arena.p + (size_t)c * 5 * (r->nz + 1); b.f_total = b.flux_n + 4 * (r->nz + 1);
+  b.flux_n = r->d_flux_arena.p + c * r->rows.stride;
   return b;
 }
 // columns [c0, c0 + ncol) of the arena, their prep / opr / spectra blocks from the start of those arenas
-// (f_total stays the handle's: a chunk's integration is the one-launch form, which leaves it to the host)
 CallBufs arena_chunk_bufs(Radtran *r, int c0, int ncol) {
   CallBufs b = resident_bufs(r);
   b.kind = CALL_ARENA_CHUNK; b.ncol = ncol; b.nsrc = r->nz; b.all_pairs_exact = false;
   b.col = r->d_cols_arena.p + (size_t)c0 * r->col_layout.count; b.prep = r->d_prep_arena.p;
   b.opr = opr_views(r, r->d_opr_arena.p); b.spec = spectra_views(r, r->d_res_arena.p);
-  b.flux_n = r->d_flux_arena.p + (size_t)c0 * 5 * (r->nz + 1);
-  b.bs = BatchStrides{r->col_layout.count, r->prep_count, b.opr.count, b.spec.count, (size_t)5 * (r->nz + 1),
+  b.flux_n = r->d_flux_arena.p + c0 * r->rows.stride;
+  b.bs = BatchStrides{r->col_layout.count, r->prep_count, b.opr.count, b.spec.count, r->rows.stride,
                       (int)(((size_t)r->op_n * r->nz + 255) / 256)};
   return b;
 }
@@ -638,15 +638,14 @@ ColumnDev column_dev(Radtran *r, const CallBufs &b) {
 // that the grid size and every kernel work from ONE decision.
 // meta: [0] = nsrc, [1 + m] = m-th source layer (0-based, ascending) | SRC_PAIR | SRC_EXACT,
 // [1 + nz + j] = source layer of layer j.  Returns nsrc.
-int build_meta(Radtran *r, const double *T, const double *P, const double *dz, const double *dens,
-               const double *pdens, const double *radii, int *meta) {
+int build_meta(Radtran *r, const ColumnArrays &a, int *meta) {
   const int nz = r->nz;
-  const bool use_radii = pdens && radii && !r->part.empty();  // present(radii) .and. self%npart > 0
+  const bool use_radii = a.has_particles() && !r->part.empty();  // present(radii) .and. self%npart > 0
   int nsrc = 0;
   int *srcl = meta + 1, *src = meta + 1 + nz;
   for (int j = 0; j < nz; j++) {
     PairDecision d{false, false};
-    if ((nz & 1) == 0 && (j & 1) == 1) d = pair_decision(j, nz, r->nsp, r->np, T, P, dz, dens, pdens, radii, use_radii);
+    if ((nz & 1) == 0 && (j & 1) == 1) d = pair_decision(j, nz, r->nsp, r->np, a.T, a.P, a.dz, a.dens, a.pdens, a.radii, use_radii);
     if (d.reuse) {
       srcl[nsrc - 1] |= SRC_PAIR | (d.exact ? SRC_EXACT : 0);  // layer j-1 is the entry just written
       src[j] = j - 1;
@@ -661,31 +660,32 @@ int build_meta(Radtran *r, const double *T, const double *P, const double *dz, c
 }
 
 // Packs one column into a host block (column_layout), pair_reuse table included.  Returns nsrc.
-int pack_column(Radtran *r, double *h, double T_surface, const double *T, const double *P, const double *dz,
-                const double *dens, const double *pdens, const double *radii) {
+int pack_column(Radtran *r, double *h, const ColumnArrays &in) {
   const size_t nz = r->nz;
   const ColumnLayout &l = r->col_layout;
-  if (!(pdens && radii)) pdens = radii = nullptr;   // the particle columns come together or not at all
-  h[0] = T_surface;
-  std::memcpy(h + l.T, T, sizeof(double) * nz);
-  std::memcpy(h + l.P, P, sizeof(double) * nz);
-  std::memcpy(h + l.dz, dz, sizeof(double) * nz);
-  std::memcpy(h + l.dens, dens, sizeof(double) * nz * r->nsp);
-  if (pdens) {
-    std::memcpy(h + l.pdens, pdens, sizeof(double) * nz * r->np);
-    std::memcpy(h + l.radii, radii, sizeof(double) * nz * r->np);
+  const ColumnArrays a = in.column(0, r->nz, r->nsp, r->np);   // (the particle columns together or not at all)
+  h[0] = *a.T_surface;
+  std::memcpy(h + l.T, a.T, sizeof(double) * nz);
+  std::memcpy(h + l.P, a.P, sizeof(double) * nz);
+  std::memcpy(h + l.dz, a.dz, sizeof(double) * nz);
+  std::memcpy(h + l.dens, a.dens, sizeof(double) * nz * r->nsp);
+  if (a.has_particles()) {
+    std::memcpy(h + l.pdens, a.pdens, sizeof(double) * nz * r->np);
+    std::memcpy(h + l.radii, a.radii, sizeof(double) * nz * r->np);
   }
-  return build_meta(r, T, P, dz, dens, pdens, radii, reinterpret_cast<int *>(h + l.meta));
+  return build_meta(r, a, reinterpret_cast<int *>(h + l.meta));
 }
 
-// f_total into the fifth row of a block [ir up | ir down | solar up | solar down | f_total]
-void f_total_row(double *h, int nl) {
-  for (int i = 0; i < nl; i++) h[4 * nl + i] = f_total_level(h[i], h[nl + i], h[2 * nl + i], h[3 * nl + i]);
+// f_total into the fifth row of a level-row block: THE place where a call's f_total is formed (a device batch's:
+// k_batch_finish)
+void f_total_row(double *h, const LevelRows &l) {
+  for (size_t i = 0; i < l.nl; i++)
+    h[l.f_total + i] = f_total_level(h[l.ir_up + i], h[l.ir_dn + i], h[l.sol_up + i], h[l.sol_dn + i]);
 }
 // ... and ISR, OLR from its last level
-void toa_fluxes(const double *h, int nz, double *ISR, double *OLR) {
-  const int nl = nz + 1;
-  toa_isr_olr(h[nz], h[nl + nz], h[2 * nl + nz], h[3 * nl + nz], *ISR, *OLR);
+void toa_fluxes(const double *h, const LevelRows &l, double *ISR, double *OLR) {
+  const size_t top = l.nl - 1;
+  toa_isr_olr(h[l.ir_up + top], h[l.ir_dn + top], h[l.sol_up + top], h[l.sol_dn + top], *ISR, *OLR);
 }
 
 void invalidate_small(Radtran *r) { r->small_valid = false; r->small_in_host = false; }
@@ -779,7 +779,6 @@ IntegrateParams make_integrate_params(Radtran *r, const CallBufs &b, bool comput
   ip.ir_freq = r->ir.d_freq.p; ip.sol_freq = r->sol.d_freq.p;
   ip.flux_n = b.flux_n;
   ip.flux_part = r->shard_world > 1 ? r->d_flux_part.p : nullptr;
-  ip.f_total = r->shard_world == 1 ? b.f_total : nullptr;
   ip.nchunk = integrate_chunks(std::max(r->ir_n, r->sol_n));
   ip.partial = r->d_partial.p;
   if (b.host_out && r->h_small_dev && b.kind == CALL_RESIDENT && !reduce && r->shard_world == 1 && integrate_fits_one_launch(ip.nchunk)) {
@@ -787,10 +786,9 @@ IntegrateParams make_integrate_params(Radtran *r, const CallBufs &b, bool comput
     ip.err_words = r->d_err.p;
   }
   if (reduce) {
-    // the status word rides on the all-reduce in the slot behind the four level rows (f_total's first element:
-    // on such a handle f_total is formed on the host from the REDUCED rows, fetch_small)
-    ip.f_total = nullptr;
-    ip.timeout_out = r->d_small.p + 4 * ((size_t)r->nz + 1); ip.timeout_flag = r->d_err.p + 1;
+    // the status word rides on the all-reduce in the slot behind the four level rows (LevelRows::status; f_total is
+    // formed on the host from the REDUCED rows, fetch_small)
+    ip.timeout_out = r->d_small.p + r->rows.status; ip.timeout_flag = r->d_err.p + 1;
     ip.id_opr = r->call_id; ip.id_sol = r->solar_id;
   }
   return ip;
@@ -936,7 +934,7 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
   if (reduce) {
     // the step's single collective (src/radtran/clima_radtran_radiate.f90:184-192 summed over the bins of all
     // ranks): in place, on the handle's stream, no host round trip
-    NCCLCHK(ncclAllReduce(r->d_small.p, r->d_small.p, 4 * ((size_t)r->nz + 1) + 1, ncclDouble, ncclSum, r->comm, r->stream));
+    NCCLCHK(ncclAllReduce(r->d_small.p, r->d_small.p, r->rows.reduce_count, ncclDouble, ncclSum, r->comm, r->stream));
     r->comm_reduces++;
   }
   r->small_valid = false;
@@ -949,18 +947,22 @@ void settle_pending_batch(Radtran *r);
 void fetch_small(Radtran *r) {
   settle_device_batch(r);
   if (r->small_valid) return;
-  const int nl = r->nz + 1;
+  const LevelRows &l = r->rows;
   for (int pass = 0; pass < 2; pass++) {
     if (!r->small_in_host)
-      HIPCHK(hipMemcpyAsync(r->h_small, r->d_small.p, sizeof(double) * (5 * nl + 1), hipMemcpyDeviceToHost, r->stream));
+      HIPCHK(hipMemcpyAsync(r->h_small, r->d_small.p, sizeof(double) * l.count, hipMemcpyDeviceToHost, r->stream));
     HIPCHK(hipStreamSynchronize(r->stream));
     resolve_events(r);
-    if (r->comm) r->comm_status = r->h_small[4 * nl];
+    if (r->comm) r->comm_status = r->h_small[l.status];
     if (!r->column_loaded || !recover_fused_timeout(r)) break;  // re-issued unfused: fetch again
   }
-  // the one-launch integration leaves f_total to the host, the other forms called f_total_level on the device
-  f_total_row(r->h_small, nl);
+  f_total_row(r->h_small, l);   // no kernel forms a call's f_total
   r->small_valid = true;
+}
+// ... and the handle's public f_total = the row just formed
+void fetch_f_total(Radtran *r) {
+  fetch_small(r);
+  std::copy(r->h_small + r->rows.f_total, r->h_small + r->rows.f_total + r->rows.nl, r->f_total.begin());
 }
 
 bool check_dims(Radtran *r, int dim_T, int dim_P, int d1, int d2, int dim_dz, int has_p, int p1, int p2,
@@ -979,15 +981,14 @@ bool check_dims(Radtran *r, int dim_T, int dim_P, int d1, int d2, int dim_dz, in
   return true;
 }
 
-void do_upload(Radtran *r, double T_surface, const double *T, const double *P, const double *dens,
-               const double *dz, const double *pdens, const double *radii) {
+void do_upload(Radtran *r, const ColumnArrays &a) {
   const int nz = r->nz;
   double *h = r->h_col;
   settle_pending_batch(r);   // (a pending integration stays: it does not read the column)
   // the pinned staging buffer is reused: wait (lazily, here) for the previous upload's copy
   if (r->upload_pending) { HIPCHK(hipEventSynchronize(r->ev_upload)); r->upload_pending = false; }
-  r->nsrc = pack_column(r, h, T_surface, T, P, dz, dens, pdens, radii);
-  r->column_has_particles = (pdens && radii);
+  r->nsrc = pack_column(r, h, a);
+  r->column_has_particles = a.has_particles();
   r->upload_id++;
   const int *meta = reinterpret_cast<const int *>(h + r->col_layout.meta);
   bool all = (nz % 2 == 0) && r->nsrc * 2 == nz;
@@ -999,9 +1000,9 @@ void do_upload(Radtran *r, double T_surface, const double *T, const double *P, c
   else HIPCHK(hipMemcpyAsync(r->d_col.p, h, sizeof(double) * r->col_layout.count, hipMemcpyHostToDevice, r->stream));
   HIPCHK(hipEventRecord(r->ev_upload, r->stream));
   r->upload_pending = true;
-  r->last_T.assign(T, T + nz);
-  r->last_P.assign(P, P + nz);
-  if (r->np > 0 && radii) r->last_radii.assign(radii, radii + (size_t)nz * r->np); else r->last_radii.clear();
+  r->last_T.assign(a.T, a.T + nz);
+  r->last_P.assign(a.P, a.P + nz);
+  if (r->np > 0 && a.radii) r->last_radii.assign(a.radii, a.radii + (size_t)nz * r->np); else r->last_radii.clear();
   r->column_loaded = true;
 }
 
@@ -1067,10 +1068,18 @@ void settle(Radtran *r) {
   settle_device_batch(r);
   for (int pass = 0; pass < 2; pass++) {
     if (r->comm && !r->small_valid)   // the reduced status word (the rows themselves are fetched when they are read)
-      HIPCHK(hipMemcpyAsync(&r->comm_status, r->d_small.p + 4 * (r->nz + 1), sizeof(double), hipMemcpyDeviceToHost, r->stream));
+      HIPCHK(hipMemcpyAsync(&r->comm_status, r->d_small.p + r->rows.status, sizeof(double), hipMemcpyDeviceToHost, r->stream));
     wait_error_words(r);
     if (!r->column_loaded || !recover_fused_timeout(r)) break;
   }
+}
+
+// ... and what works on the stored optical properties next finds them whole: fields current, w0 in memory
+// (a communicator handle: the level rows of the last step are the reduced ones from here on)
+void ready_stored_opacities(Radtran *r) {
+  settle(r);
+  upload_fields(r);
+  ensure_w0(r);
 }
 
 void defer_err(Radtran *r, const std::string &msg) {
@@ -1082,9 +1091,8 @@ void defer_err(Radtran *r, const std::string &msg) {
 // blocks and level rows (and their source-layer counts, where the device finds them)
 void begin_batch(Radtran *r, int n, bool nsrc_on_device) {
   settle_device_batch(r);
-  const size_t rows = (size_t)n * 5 * (r->nz + 1);
   r->d_cols_arena.reserve((size_t)n * r->col_layout.count);
-  r->d_flux_arena.reserve(rows);
+  r->d_flux_arena.reserve(n * r->rows.stride);
   if (nsrc_on_device) r->d_batch_nsrc.reserve(n);
 }
 // The launch form of a batch of n columns, decided here, once: one launch of each kernel per chunk of CH columns
@@ -1117,6 +1125,7 @@ void fetch_batch_nsrc(Radtran *r, int n) {
 // chunks (or the columns' calls), the rows out to the sink, the handle's own level rows = the last column's.  Nothing waits.
 void enqueue_batch(Radtran *r, const BatchRun &b, bool allow_fused) {
   const int n = b.n, nl = r->nz + 1;
+  const LevelRows &l = r->rows;
   // the rows asked for out of the `ncol` columns from c0 on that the launches just enqueued worked on, before the next
   // ones overwrite their spectra (the arena of a chunk, the handle's own buffers of a column's call)
   auto gather = [&](const CallBufs &cb, int c0, int ncol) {
@@ -1146,13 +1155,13 @@ void enqueue_batch(Radtran *r, const BatchRun &b, bool allow_fused) {
     }
   }
   if (b.rows) {
-    HIPCHK(hipMemcpyAsync(b.rows, r->d_flux_arena.p, sizeof(double) * n * 5 * nl, hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(hipMemcpyAsync(b.rows, r->d_flux_arena.p, sizeof(double) * n * l.stride, hipMemcpyDeviceToHost, r->stream));
     if (b.spec_count) HIPCHK(hipMemcpyAsync(b.spec_host, r->d_spec_stage.p, sizeof(double) * b.spec_count, hipMemcpyDeviceToHost, r->stream));
   } else {
     launch_batch_finish(BatchFinishParams{n, r->nz, r->d_flux_arena.p, b.ISR, b.OLR, b.fluxes}, r->stream);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipMemcpyAsync(r->d_flux_n.p, r->d_flux_arena.p + (size_t)(n - 1) * 5 * nl, sizeof(double) * 4 * nl, hipMemcpyDeviceToDevice, r->stream));
+  HIPCHK(hipMemcpyAsync(r->d_flux_n.p, r->d_flux_arena.p + (n - 1) * l.stride, sizeof(double) * l.flux_count, hipMemcpyDeviceToDevice, r->stream));
 }
 // What the handle holds after a batch is the LAST column's, like after n single calls: its level rows (enqueue_batch),
 // and its spectra / band optical depths -- the one-launch form left those in the batch arena (copied here); its optical
@@ -1197,14 +1206,13 @@ void settle_pending_batch(Radtran *r) {
   if (settle_batch(r, r->dev_batch)) defer_err(r, OPACITY_FAILED_MSG);
 }
 // the parameter block of k_pack_columns: the column blocks of a batch built on the device
-PackParams make_pack_params(Radtran *r, int n, const double *T_surface, const double *T, const double *P, const double *dens,
-                            const double *dz, const double *pdens, const double *radii, double *blocks, int *nsrc) {
+PackParams make_pack_params(Radtran *r, int n, const ColumnArrays &in, double *blocks, int *nsrc) {
   PackParams p;
   std::memset(&p, 0, sizeof(p));
   p.ncol = n; p.nz = r->nz; p.nsp = r->nsp; p.np = r->np;
-  p.has_particles = r->np > 0 && pdens && radii;
+  p.has_particles = r->np > 0 && in.has_particles();
   p.use_radii = p.has_particles && !r->part.empty();
-  p.T_surface = T_surface; p.T = T; p.P = P; p.dz = dz; p.dens = dens; p.pdens = pdens; p.radii = radii;
+  p.in = in;
   p.blocks = blocks; p.nsrc = nsrc;
   return p;
 }
@@ -1217,6 +1225,14 @@ void comm_reduce_up_down(Radtran *r, size_t arr, F total) {
   r->comm_reduces++;
   total();
   HIPCHK(hipGetLastError());
+}
+
+// The Jacobian kernels' launches (`launch`), `count` doubles from the start of d_bout -- or, on a shard without IR bins,
+// no k_green_* kernel (their grids would be empty): zeros into the all-reduce
+template <class F>
+void jacobian_of_ir_bins(Radtran *r, size_t count, F launch) {
+  if (r->ir_n > 0) { launch(); HIPCHK(hipGetLastError()); }
+  else HIPCHK(hipMemsetAsync(r->d_bout.p, 0, sizeof(double) * count, r->stream));
 }
 
 // device memory of the handle's device?  (an address the runtime does not know -- pageable host memory -- is an
@@ -1240,6 +1256,10 @@ void get2d(WrkObj *w, DevBuf<double> &buf, int dim1, int dim2, double *arr) {
 #define GUARD(r, ptr, err)                                   \
   Radtran *r = as_rad(ptr);                                  \
   if (!r) { set_err(err, "invalid Radtran handle"); return; }
+// ... of a handle that radtran_create_end has finished
+#define GUARD_BUILT(r, ptr, err) \
+  GUARD(r, ptr, err)             \
+  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
 #define TRY try {
 #define CATCH(err) } catch (const HipFail &f) { set_err(err, f.msg); } catch (const std::exception &e) { set_err(err, e.what()); }
 
@@ -1405,8 +1425,7 @@ void radtran_set_custom_optical_properties(void *ptr, const int *dim_wv, const d
                                            const double *w0, const int *dim1_g0, const int *dim2_g0,
                                            const double *g0, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   const int nwv = *dim_wv, nP = *dim_P;
   for (int i = 0; i < nwv; i++) if (wv[i] <= 0.0) { set_err(err, "All elements of `wv` must be larger than zero"); return; }
   for (int i = 0; i < nP; i++) if (P[i] <= 0.0) { set_err(err, "All elements of `P` must be larger than zero"); return; }
@@ -1738,16 +1757,16 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
   };
   mk(r->wrk_ir, 0, r->ir.nw);
   mk(r->wrk_sol, 1, r->sol.nw);
-  r->d_small.alloc((size_t)5 * (nz + 1) + 1); r->d_small.zero();
-  r->d_flux_n.view(r->d_small.p, (size_t)4 * (nz + 1));
+  const LevelRows &l = r->rows = level_rows(nz);
+  r->d_small.alloc(l.count); r->d_small.zero();
+  r->d_flux_n.view(r->d_small.p, l.flux_count);
   // two ints share the last double slot: [0] particle-radius clamp, [1] fused hand-off timeout
-  r->d_err.view(reinterpret_cast<int *>(r->d_small.p + (size_t)5 * (nz + 1)), 2);
+  r->d_err.view(reinterpret_cast<int *>(r->d_small.p + l.err_words), 2);
   r->d_partial.alloc((size_t)4 * integrate_chunks(std::max(r->ir.nw, r->sol.nw)) * (nz + 1)); r->d_partial.zero();
-  r->d_f_total.view(r->d_small.p + (size_t)4 * (nz + 1), nz + 1);
-  HIPCHK(hipHostMalloc((void **)&r->h_small, sizeof(double) * (5 * (nz + 1) + 1), hipHostMallocMapped));
-  std::memset(r->h_small, 0, sizeof(double) * (5 * (nz + 1) + 1));
+  HIPCHK(hipHostMalloc((void **)&r->h_small, sizeof(double) * l.count, hipHostMallocMapped));
+  std::memset(r->h_small, 0, sizeof(double) * l.count);
   if (hipHostGetDevicePointer((void **)&r->h_small_dev, r->h_small, 0) != hipSuccess) { r->h_small_dev = nullptr; (void)hipGetLastError(); }
-  r->h_errflag = reinterpret_cast<int *>(r->h_small + 5 * (nz + 1));
+  r->h_errflag = reinterpret_cast<int *>(r->h_small + l.err_words);
   r->f_total.assign(nz + 1, 0.0);
   HIPCHK(hipDeviceSynchronize());
   r->fields_dirty = true;
@@ -1761,18 +1780,16 @@ void radtran_upload_column(void *ptr, const double *T_surface, const double *T, 
                            const double *densities, const double *dz, const double *pdensities,
                            const double *radii, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   if (r->np > 0 && (!pdensities || !radii)) { set_err(err, "The model contains particles but \"pdensities\" and \"radii\" are not arguments."); return; }
   TRY
-  do_upload(r, *T_surface, T, P, densities, dz, pdensities, radii);
+  do_upload(r, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii});
   CATCH(err)
 }
 
 void radtran_radiate_resident(void *ptr, const int *compute_solar, const int *compute_opacity, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   if (!r->column_loaded) { set_err(err, "no column has been uploaded"); return; }
   TRY
   enqueue_radiate(r, resident_bufs(r), *compute_solar != 0, *compute_opacity != 0, true, /*defer=*/true);
@@ -2049,8 +2066,7 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
                               const int *dim2_T, const double *T, double *fup_n, double *fdn_n,
                               double *f_total, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   if (*dim1_T != r->nz || *dim2_T != *ncol || *ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return; }
   if (!r->opr_valid) { set_err(err, "radiate_ir_batch needs opacities: call radiate with compute_opacity first"); return; }
   if (r->shard_world != 1 && !r->comm) { set_err(err, "radiate_ir_batch is not available on a bin-sharded handle"); return; }
@@ -2059,9 +2075,7 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
   static const bool times = [] { const char *e = getenv("CLIMA_HIP_BATCH_TIMES"); return e && e[0] == '1'; }();
   const auto t_begin = std::chrono::steady_clock::now();
   auto since = [&] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_begin).count(); };
-  settle(r);          // (a communicator handle: the level rows of the last step are the reduced ones from here on)
-  upload_fields(r);
-  ensure_w0(r);
+  ready_stored_opacities(r);
   const int nz = r->nz, nl = nz + 1, n = *ncol;
   r->d_bout.reserve((size_t)n * 3 * nl);
   bool green = false;
@@ -2194,28 +2208,21 @@ static const int *ir_jacobian_green_part(Radtran *r, const double *T_surface, co
 void radtran_ir_jacobian(void *ptr, const double *T_surface, const int *dim_T, const double *T,
                          const int *dim1, const int *dim2, double *jac_up, double *jac_dn, double *jac_total, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   const int nz = r->nz, nl = nz + 1;
   if (*dim_T != nz) { set_err(err, "\"T\" has the wrong input dimension."); return; }
   if (*dim1 != nl || *dim2 != nl) { set_err(err, "jac has the wrong dimension"); return; }
   if (ir_jacobian_refused(r, T_surface, T, err)) return;
   TRY
-  settle(r);
-  upload_fields(r);
-  ensure_w0(r);
+  ready_stored_opacities(r);
   const size_t arr = (size_t)nl * nl;
   r->d_bout.reserve(3 * arr);
-  if (r->ir_n > 0) {
+  jacobian_of_ir_bins(r, 3 * arr, [&] {
     GreenParams g;
     ir_jacobian_green_part(r, T_surface, T, {}, g);
     g.out = r->d_bout.p; g.out_arr = arr;
     launch_green_jacobian(g, r->stream);
-    HIPCHK(hipGetLastError());
-  } else {
-    // a shard without IR bins: no k_green_* kernel (their grids would be empty), zeros into the all-reduce
-    HIPCHK(hipMemsetAsync(r->d_bout.p, 0, sizeof(double) * 3 * arr, r->stream));
-  }
+  });
   comm_reduce_up_down(r, arr, [&] { launch_jacobian_total(r->d_bout.p, arr, arr, r->stream); });
   double *const outs[3] = {jac_up, jac_dn, jac_total};
   bout_to_host(r, outs, arr);
@@ -2233,8 +2240,7 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
                                  const int *dim1, const int *dim2,
                                  double *jac_up, double *jac_dn, double *jac_total, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   const int nz = r->nz, nl = nz + 1, ng = *ngroup, nr = *nrow;
   const std::string pre = "ir_jacobian_reduced: ";
   if (*dim_T != nz) { set_err(err, "\"T\" has the wrong input dimension."); return; }
@@ -2282,25 +2288,19 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
   }
   if (ir_jacobian_refused(r, T_surface, T, err)) return;
   TRY
-  settle(r);
-  upload_fields(r);
-  ensure_w0(r);
+  ready_stored_opacities(r);
   const size_t arr = (size_t)nr * ng;
   // a communicator handle forms up and down whatever was asked for: they are what is summed over the ranks
   const bool want_parts = jac_up != nullptr, parts = want_parts || r->comm;
   const size_t need = (parts ? 3 : 1) * arr;
   r->d_bout.reserve(need);
-  if (r->ir_n > 0) {
+  jacobian_of_ir_bins(r, need, [&] {
     GreenParams g;
     const int *d_map = ir_jacobian_green_part(r, T_surface, T, csr, g);
     g.col_ptr = d_map; g.col_dev = d_map + ng + 1;
     g.out = r->d_bout.p; g.out_arr = arr;
     launch_green_jacobian_reduced(g, d_map + ng + 1 + nmem, nr, ng, parts, r->stream);
-    HIPCHK(hipGetLastError());
-  } else {
-    // a shard without IR bins: no k_green_* kernel (their grids would be empty), zeros into the all-reduce
-    HIPCHK(hipMemsetAsync(r->d_bout.p, 0, sizeof(double) * need, r->stream));
-  }
+  });
   comm_reduce_up_down(r, arr, [&] { launch_jacobian_total(r->d_bout.p, arr, arr, r->stream); });   // (2 nrow ngroup doubles)
   double *const outs[3] = {jac_up, jac_dn, jac_total};
   if (want_parts) bout_to_host(r, outs, arr);
@@ -2379,24 +2379,20 @@ static void out_spectra(Radtran *r, const BatchRun &run, const SpectraAsk &ask) 
 // T, P, dz (nz, ncol); densities (nz, nsp, ncol); pdensities, radii (nz, np, ncol).
 // Outputs: ISR, OLR (ncol); fluxes (nz+1, 5, ncol) = ir up, ir down, solar up, solar down, f_total,
 // or NULL.  The handle's own wrk / f_total hold the last column afterwards.
-static void toa_fluxes_batch_host(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
-                                  const double *densities, const double *dz, const int *has_particles,
-                                  const double *pdensities, const double *radii, double *ISR, double *OLR,
-                                  double *fluxes, const SpectraAsk *ask, char *err) {
+static void toa_fluxes_batch_host(void *ptr, const int *ncol, const ColumnArrays &in, const int *has_particles, double *ISR,
+                                  double *OLR, double *fluxes, const SpectraAsk *ask, char *err) {
   clear_err(err);
   GUARD(r, ptr, err);
   if (batch_refused(r, ncol, has_particles, err)) return;
   if (ask && spectra_refused(r, *ask, err)) return;
   TRY
-  const int nz = r->nz, nl = nz + 1, n = *ncol;
-  const size_t cc = r->col_layout.count, np_n = (size_t)nz * r->np;
+  const int n = *ncol;
+  const size_t cc = r->col_layout.count;
+  const LevelRows &l = r->rows;
   begin_batch(r, n, false);
-  std::vector<double> h((size_t)n * cc, 0.0), out((size_t)n * 5 * nl);
+  std::vector<double> h((size_t)n * cc, 0.0), out(n * l.stride);
   r->batch_nsrc.resize(n);
-  for (int c = 0; c < n; c++)
-    r->batch_nsrc[c] = pack_column(r, h.data() + (size_t)c * cc, T_surface[c], T + (size_t)c * nz, P + (size_t)c * nz, dz + (size_t)c * nz,
-                                   densities + (size_t)c * nz * r->nsp, r->np > 0 ? pdensities + c * np_n : nullptr,
-                                   r->np > 0 ? radii + c * np_n : nullptr);
+  for (int c = 0; c < n; c++) r->batch_nsrc[c] = pack_column(r, h.data() + (size_t)c * cc, in.column(c, r->nz, r->nsp, r->np));
   HIPCHK(hipMemcpyAsync(r->d_cols_arena.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, r->stream));
   BatchRun run = batch_form(r, n);
   run.rows = out.data();
@@ -2405,10 +2401,10 @@ static void toa_fluxes_batch_host(void *ptr, const int *ncol, const double *T_su
   batch_leaves_handle(r, run);
   if (settle_batch(r, run)) { set_err(err, OPACITY_FAILED_MSG); return; }
   for (int c = 0; c < n; c++) {
-    double *f = out.data() + (size_t)c * 5 * nl;
-    f_total_row(f, nl);
-    toa_fluxes(f, nz, &ISR[c], &OLR[c]);
-    if (fluxes) std::memcpy(fluxes + (size_t)c * 5 * nl, f, sizeof(double) * 5 * nl);
+    double *f = out.data() + c * l.stride;
+    f_total_row(f, l);
+    toa_fluxes(f, l, &ISR[c], &OLR[c]);
+    if (fluxes) std::memcpy(fluxes + c * l.stride, f, sizeof(double) * l.stride);
   }
   if (ask) out_spectra(r, run, *ask);
   CATCH(err)
@@ -2417,7 +2413,7 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
                               const double *densities, const double *dz, const int *has_particles,
                               const double *pdensities, const double *radii, double *ISR, double *OLR,
                               double *fluxes, char *err) {
-  toa_fluxes_batch_host(ptr, ncol, T_surface, T, P, densities, dz, has_particles, pdensities, radii, ISR, OLR, fluxes, nullptr, err);
+  toa_fluxes_batch_host(ptr, ncol, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii}, has_particles, ISR, OLR, fluxes, nullptr, err);
 }
 // ... and with the per-bin rows `spec_level` of every column: what a batch otherwise keeps of the last column only.
 // Copies of the values the batch's own integration sums (k_batch_spectra behind each chunk, enqueue_batch).
@@ -2427,7 +2423,7 @@ void radtran_toa_fluxes_batch_spectra(void *ptr, const int *ncol, const double *
                                       double *fluxes, const int *nsel, const int *spec_level, double *ir_fup,
                                       double *ir_fdn, double *sol_fup, double *sol_fdn, char *err) {
   const SpectraAsk ask{nsel ? *nsel : 0, spec_level, {ir_fup, ir_fdn, sol_fup, sol_fdn}};
-  toa_fluxes_batch_host(ptr, ncol, T_surface, T, P, densities, dz, has_particles, pdensities, radii, ISR, OLR, fluxes, &ask, err);
+  toa_fluxes_batch_host(ptr, ncol, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii}, has_particles, ISR, OLR, fluxes, &ask, err);
 }
 
 // The same batch with every array in device memory (the f64 tensors of a GPU-resident ensemble): the column blocks
@@ -2439,11 +2435,8 @@ void radtran_toa_fluxes_batch_spectra(void *ptr, const int *ncol, const double *
 // CLIMA_HIP_BATCH_ONE_LAUNCH=0): plan_radiate picks the opacity kernel and sizes the grids of such a call from the
 // column's own source-layer count, and the kernels it chooses between round differently, so the bound nsrc = nz
 // would not be the host batch's computation; the ncol counts (4 bytes each) are fetched in one copy first.
-static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
-                                 const double *d_P, const double *d_densities, const double *d_dz,
-                                 const int *has_particles, const double *d_pdensities, const double *d_radii,
-                                 double *d_ISR, double *d_OLR, double *d_fluxes, const SpectraAsk *ask,
-                                 const void *producer_stream, char *err) {
+static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const ColumnArrays &in, const int *has_particles, double *d_ISR,
+                                 double *d_OLR, double *d_fluxes, const SpectraAsk *ask, const void *producer_stream, char *err) {
   clear_err(err);
   GUARD(r, ptr, err);
   if (batch_refused(r, ncol, has_particles, err)) return;
@@ -2451,8 +2444,8 @@ static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const double *d_T_s
   const bool part = r->np > 0;
   enum { UNUSED, REQUIRED, OPTIONAL };   // (the particle arrays of a handle without particle columns are not read)
   const struct { const char *name; const void *p; int use; } args[] = {
-      {"T_surface", d_T_surface, REQUIRED}, {"T", d_T, REQUIRED}, {"P", d_P, REQUIRED}, {"densities", d_densities, REQUIRED},
-      {"dz", d_dz, REQUIRED}, {"pdensities", d_pdensities, part ? REQUIRED : UNUSED}, {"radii", d_radii, part ? REQUIRED : UNUSED},
+      {"T_surface", in.T_surface, REQUIRED}, {"T", in.T, REQUIRED}, {"P", in.P, REQUIRED}, {"densities", in.dens, REQUIRED},
+      {"dz", in.dz, REQUIRED}, {"pdensities", in.pdens, part ? REQUIRED : UNUSED}, {"radii", in.radii, part ? REQUIRED : UNUSED},
       {"ISR", d_ISR, REQUIRED}, {"OLR", d_OLR, REQUIRED}, {"fluxes", d_fluxes, OPTIONAL}};
   for (const auto &a : args) {
     if (a.use == UNUSED || (a.use == OPTIONAL && !a.p)) continue;
@@ -2477,8 +2470,7 @@ static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const double *d_T_s
     HIPCHK(hipEventRecord(r->ev_producer, reinterpret_cast<hipStream_t>(const_cast<void *>(producer_stream))));
     HIPCHK(hipStreamWaitEvent(r->stream, r->ev_producer, 0));
   }
-  launch_pack_columns(make_pack_params(r, n, d_T_surface, d_T, d_P, d_densities, d_dz, part ? d_pdensities : nullptr,
-                                       part ? d_radii : nullptr, r->d_cols_arena.p, r->d_batch_nsrc.p), r->stream);
+  launch_pack_columns(make_pack_params(r, n, in, r->d_cols_arena.p, r->d_batch_nsrc.p), r->stream);
   HIPCHK(hipGetLastError());
   BatchRun run = batch_form(r, n);
   run.ISR = d_ISR; run.OLR = d_OLR; run.fluxes = d_fluxes;
@@ -2495,8 +2487,8 @@ void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d
                                      const int *has_particles, const double *d_pdensities, const double *d_radii,
                                      double *d_ISR, double *d_OLR, double *d_fluxes, const void *producer_stream,
                                      char *err) {
-  toa_fluxes_batch_dev(ptr, ncol, d_T_surface, d_T, d_P, d_densities, d_dz, has_particles, d_pdensities, d_radii, d_ISR, d_OLR,
-                       d_fluxes, nullptr, producer_stream, err);
+  toa_fluxes_batch_dev(ptr, ncol, ColumnArrays{d_T_surface, d_T, d_P, d_densities, d_dz, d_pdensities, d_radii}, has_particles,
+                       d_ISR, d_OLR, d_fluxes, nullptr, producer_stream, err);
 }
 // ... and with the per-bin rows (device arrays; spec_level is a HOST array, read before the call returns): final, and
 // after an expired hand-off wait refilled by the repeat, at the same radtran_synchronize as ISR / OLR / fluxes.
@@ -2507,22 +2499,24 @@ void radtran_toa_fluxes_batch_spectra_device(void *ptr, const int *ncol, const d
                                              const int *spec_level, double *d_ir_fup, double *d_ir_fdn, double *d_sol_fup,
                                              double *d_sol_fdn, const void *producer_stream, char *err) {
   const SpectraAsk ask{nsel ? *nsel : 0, spec_level, {d_ir_fup, d_ir_fdn, d_sol_fup, d_sol_fdn}};
-  toa_fluxes_batch_dev(ptr, ncol, d_T_surface, d_T, d_P, d_densities, d_dz, has_particles, d_pdensities, d_radii, d_ISR, d_OLR,
-                       d_fluxes, &ask, producer_stream, err);
+  toa_fluxes_batch_dev(ptr, ncol, ColumnArrays{d_T_surface, d_T, d_P, d_densities, d_dz, d_pdensities, d_radii}, has_particles,
+                       d_ISR, d_OLR, d_fluxes, &ask, producer_stream, err);
 }
 
 /* test hooks: the column blocks of a batch (ncol * col_count doubles, host arrays as radtran_toa_fluxes_batch) as
  * k_pack_columns builds them on the device, and as the host's pack_column does */
+static bool pack_hook_refused(Radtran *r, const int *ncol, const int *has_particles, const ColumnArrays &in, int *col_count, char *err) {
+  const int hp = has_particles ? *has_particles : 0;
+  if (*ncol < 1 || (r->np > 0 && !(hp && in.has_particles()))) { set_err(err, "clima_test_pack_columns: bad arguments"); return true; }
+  *col_count = (int)r->col_layout.count;
+  return false;
+}
 void clima_test_pack_columns(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
                              const double *densities, const double *dz, const int *has_particles, const double *pdensities,
                              const double *radii, double *blocks, int *col_count, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
-  const int hp = has_particles ? *has_particles : 0;
-  if (*ncol < 1 || (r->np > 0 && !(hp && pdensities && radii))) { set_err(err, "clima_test_pack_columns: bad arguments"); return; }
-  *col_count = (int)r->col_layout.count;
-  if (!blocks) return;
+  GUARD_BUILT(r, ptr, err);
+  if (pack_hook_refused(r, ncol, has_particles, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii}, col_count, err) || !blocks) return;
   TRY
   const size_t n = *ncol, nz = r->nz;
   DevBuf<double> ts, t, p, de, z, pd, ra, out;
@@ -2532,7 +2526,7 @@ void clima_test_pack_columns(void *ptr, const int *ncol, const double *T_surface
   if (r->np > 0) { up(pd, pdensities, n * nz * r->np); up(ra, radii, n * nz * r->np); }
   out.alloc(n * r->col_layout.count);
   ns.alloc(n);
-  launch_pack_columns(make_pack_params(r, (int)n, ts.p, t.p, p.p, de.p, z.p, pd.p, ra.p, out.p, ns.p), r->stream);
+  launch_pack_columns(make_pack_params(r, (int)n, ColumnArrays{ts.p, t.p, p.p, de.p, z.p, pd.p, ra.p}, out.p, ns.p), r->stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(blocks, out.p, sizeof(double) * out.n, hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
@@ -2542,23 +2536,16 @@ void clima_test_pack_columns_host(void *ptr, const int *ncol, const double *T_su
                                   const double *densities, const double *dz, const int *has_particles,
                                   const double *pdensities, const double *radii, double *blocks, int *col_count, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
-  const int hp = has_particles ? *has_particles : 0;
-  if (*ncol < 1 || (r->np > 0 && !(hp && pdensities && radii))) { set_err(err, "clima_test_pack_columns: bad arguments"); return; }
-  *col_count = (int)r->col_layout.count;
-  if (!blocks) return;
-  const size_t nz = r->nz, np_n = nz * r->np;
+  GUARD_BUILT(r, ptr, err);
+  const ColumnArrays in{T_surface, T, P, densities, dz, pdensities, radii};
+  if (pack_hook_refused(r, ncol, has_particles, in, col_count, err) || !blocks) return;
   std::memset(blocks, 0, sizeof(double) * (size_t)*ncol * r->col_layout.count);
-  for (size_t c = 0; c < (size_t)*ncol; c++)
-    pack_column(r, blocks + c * r->col_layout.count, T_surface[c], T + c * nz, P + c * nz, dz + c * nz, densities + c * nz * r->nsp,
-                r->np > 0 ? pdensities + c * np_n : nullptr, r->np > 0 ? radii + c * np_n : nullptr);
+  for (size_t c = 0; c < (size_t)*ncol; c++) pack_column(r, blocks + c * r->col_layout.count, in.column(c, r->nz, r->nsp, r->np));
 }
 
 void radtran_synchronize(void *ptr, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   TRY
   settle(r);
   if (!r->deferred_err.empty()) {   // a getter without an `err` argument met a failure since the last check
@@ -2577,19 +2564,17 @@ void radtran_radiate_wrapper(void *ptr, const double *T_surface, const int *dim_
                              const double *pdensities, const int *dim1_r, const int *dim2_r, const double *radii,
                              const int *compute_solar, const int *compute_opacity, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   const int hp = has_particles ? *has_particles : 0;
   if (!check_dims(r, *dim_T, *dim_P, *dim1_d, *dim2_d, *dim_dz, hp, dim1_p ? *dim1_p : 0, dim2_p ? *dim2_p : 0,
                   dim1_r ? *dim1_r : 0, dim2_r ? *dim2_r : 0, hp ? pdensities : nullptr, hp ? radii : nullptr, err))
     return;
   TRY
-  do_upload(r, *T_surface, T, P, densities, dz, hp ? pdensities : nullptr, hp ? radii : nullptr);
+  do_upload(r, ColumnArrays{T_surface, T, P, densities, dz, hp ? pdensities : nullptr, hp ? radii : nullptr});
   enqueue_radiate(r, resident_bufs(r, /*host_out=*/true), *compute_solar != 0, *compute_opacity != 0);
   fetch_small(r);
   if (surface_device_error(r, err)) return;
-  const int nl = r->nz + 1;
-  for (int i = 0; i < nl; i++) r->f_total[i] = r->h_small[4 * nl + i];
+  fetch_f_total(r);
   CATCH(err)
 }
 
@@ -2604,7 +2589,7 @@ void radtran_toa_fluxes_wrapper(void *ptr, const double *T_surface, const int *d
                           has_particles, dim1_p, dim2_p, pdensities, dim1_r, dim2_r, radii, compute_solar,
                           compute_opacity, err);
   if (err && err[0]) return;
-  if (Radtran *r = as_rad(ptr)) toa_fluxes(r->h_small, r->nz, ISR, OLR);
+  if (Radtran *r = as_rad(ptr)) toa_fluxes(r->h_small, r->rows, ISR, OLR);
 }
 
 // Bench hook: `n` synchronous radtran_toa_fluxes_wrapper calls (host arrays in, ISR / OLR out, one stream
@@ -2703,19 +2688,15 @@ void radtran_apply_radiation_enhancement(void *ptr, const double *rad_enhancemen
   Radtran *r = as_rad(ptr);
   if (!r || r->state != 2) return;
   try {  // clima_radtran.f90:402-411
-    const int nl = r->nz + 1;
+    const LevelRows &l = r->rows;   // the two solar rows are adjacent
     settle(r);   // the results being scaled are final (a hand-off that timed out has been repaired BEFORE, not after)
     launch_scale(r->wrk_sol.fdn_a.p, r->wrk_sol.fdn_a.n, *rad_enhancement, r->stream);
     launch_scale(r->wrk_sol.fup_a.p, r->wrk_sol.fup_a.n, *rad_enhancement, r->stream);
-    launch_scale(r->d_flux_n.p + 2 * nl, (size_t)2 * nl, *rad_enhancement, r->stream);
+    launch_scale(r->d_flux_n.p + l.sol_up, 2 * l.nl, *rad_enhancement, r->stream);
     // a bin-sharded handle keeps its PARTIAL solar rows for the IR-only steps that follow: they are scaled too
-    if (r->shard_world > 1 && r->d_flux_part.p) launch_scale(r->d_flux_part.p + 2 * nl, (size_t)2 * nl, *rad_enhancement, r->stream);
-    // (with a communicator the slot behind the rows carries the step's status word, and f_total is formed on the host
-    // from the rows in any case: fetch_small)
-    if (!r->comm) launch_f_total(r->nz, r->d_flux_n.p, r->d_f_total.p, r->stream);
-    invalidate_small(r);   // (the device rows changed: fetch them)
-    fetch_small(r);
-    for (int i = 0; i < nl; i++) r->f_total[i] = r->h_small[4 * nl + i];
+    if (r->shard_world > 1 && r->d_flux_part.p) launch_scale(r->d_flux_part.p + l.sol_up, 2 * l.nl, *rad_enhancement, r->stream);
+    invalidate_small(r);   // (the device rows changed: fetch them; f_total is formed from them there)
+    fetch_f_total(r);
   } catch (...) {
   }
 }
@@ -2723,7 +2704,7 @@ void radtran_apply_radiation_enhancement(void *ptr, const double *rad_enhancemen
 void radtran_flux_device_ptr(void *ptr, void **dptr, int *count) {
   Radtran *r = as_rad(ptr);
   *dptr = r ? (void *)r->d_flux_n.p : nullptr;
-  *count = r ? 4 * (r->nz + 1) : 0;
+  *count = r ? (int)r->rows.flux_count : 0;
   if (!r) return;
   // whoever holds the pointer reads the rows in stream order without telling the library: every call of this handle
   // integrates at once from here on, and what is pending goes out now
@@ -2733,8 +2714,7 @@ void radtran_flux_device_ptr(void *ptr, void **dptr, int *count) {
 
 void radtran_set_bin_shard(void *ptr, const int *rank, const int *world, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   if (*world < 1 || *rank < 0 || *rank >= *world) { set_err(err, "invalid shard (rank, world)"); return; }
   // a communicator fixes the shard (rank, nranks) -- except a one-rank communicator, on which any shard may be
   // rehearsed (one rank's share of an N-GPU step on one GPU: bench.py CLIMA_BENCH_FAKE_SHARD)
@@ -2751,7 +2731,7 @@ void radtran_set_bin_shard(void *ptr, const int *rank, const int *world, char *e
   for (WrkObj *w : {&r->wrk_ir, &r->wrk_sol}) { w->fup_a.zero(r->stream); w->fdn_a.zero(r->stream); w->amean.zero(r->stream); w->tau_band.zero(r->stream); }
   r->d_flux_n.zero(r->stream);
   if (*world > 1) {
-    r->d_flux_part.reserve((size_t)4 * (r->nz + 1));
+    r->d_flux_part.reserve(r->rows.flux_count);
     r->d_flux_part.zero(r->stream);
   }
   HIPCHK(hipStreamSynchronize(r->stream));
@@ -2797,8 +2777,7 @@ static void comm_attach(Radtran *r, int nranks, int rank, const char *id) {
 
 void radtran_comm_init_rank(void *ptr, const int *nranks, const int *rank, const char *id, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   if (*nranks < 1 || *rank < 0 || *rank >= *nranks) { set_err(err, "invalid communicator (rank, nranks)"); return; }
   TRY
   comm_attach(r, *nranks, *rank, id);
@@ -2812,8 +2791,7 @@ void radtran_comm_init_rank(void *ptr, const int *nranks, const int *rank, const
 // `path` must be new for every job.
 void radtran_comm_init_file(void *ptr, const int *nranks, const int *rank, const char *path, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   if (*nranks < 1 || *rank < 0 || *rank >= *nranks) { set_err(err, "invalid communicator (rank, nranks)"); return; }
   if (!path || !path[0]) { set_err(err, "radtran_comm_init_file: empty path"); return; }
   TRY
@@ -2897,8 +2875,7 @@ void radtran_bin_shard_get(void *ptr, int *op_lo, int *op_n, int *ir_lo, int *ir
 
 void radtran_finish_reduced(void *ptr, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   // f_total = (sol_dn - sol_up) + (ir_dn - ir_up) of the reduced rows is formed on the host when the
   // results are fetched (fetch_small), like after every call: nothing to launch here, the level
   // rows just have to be read again
@@ -3037,8 +3014,7 @@ extern "C" void clima_debug_stamps(void *ptr, long long *out) {
 
 void radtran_opr_get(void *ptr, double *tau, double *w0, double *g, double *tau_band, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return; }
+  GUARD_BUILT(r, ptr, err);
   TRY
   settle(r);       // (a repaired hand-off recomputes the optical properties)
   ensure_w0(r);
@@ -3153,8 +3129,9 @@ void clima_test_two_stream(const int *nz_, const int *ng_, const int *form, cons
   ts.zen_u_v[0] = sol_par[0]; ts.zen_w_v[0] = 1.0; ts.zen_iu_v[0] = 1.0 / sol_par[0];
   ts.albedo = d_alb.p; ts.photons_sol = d_one.p; ts.photon_scale_factor = 1.0; ts.diurnal_fac = 1.0;
   ts.am_f1 = d_one.p; ts.am_f2 = d_one.p; ts.am_dw = d_one.p;
-  ts.ir_fup_a = d_out.p; ts.ir_fdn_a = d_out.p + nl; ts.sol_fup_a = d_out.p + 2 * nl; ts.sol_fdn_a = d_out.p + 3 * nl;
-  ts.sol_amean = d_out.p + 4 * nl; ts.ir_tau_band = d_out.p + 5 * nl; ts.sol_tau_band = d_out.p + 6 * nl;
+  auto out_arr = [&](int k) { return d_out.p + (size_t)k * nl; };   // seven arrays of nl; the first five go back
+  ts.ir_fup_a = out_arr(0); ts.ir_fdn_a = out_arr(1); ts.sol_fup_a = out_arr(2); ts.sol_fdn_a = out_arr(3);
+  ts.sol_amean = out_arr(4); ts.ir_tau_band = out_arr(5); ts.sol_tau_band = out_arr(6);
   bool ok = false;
   PlanIn in{};   // a call on stored opacities, no handle: forms 0 and 1 are the plan's stand-alone forms
   in.nz = nz; in.ng = ng; in.nzen = 1; in.n_ir = ts.n_ir; in.n_sol = ts.n_sol; in.ncol = 1;
@@ -3174,9 +3151,9 @@ void clima_test_two_stream(const int *nz_, const int *ng_, const int *form, cons
   HIPCHK(hipGetLastError());
   if (!ok) throw HipFail{"clima_test_two_stream: this form does not cover the requested shape"};
   HIPCHK(hipDeviceSynchronize());
-  std::vector<double> out((size_t)5 * nl);
-  HIPCHK(hipMemcpy(out.data(), d_out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost));
   double *dst[5] = {ir_fup, ir_fdn, sol_fup, sol_fdn, sol_amean};
+  std::vector<double> out(out_arr(5) - d_out.p);
+  HIPCHK(hipMemcpy(out.data(), d_out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost));
   for (int a = 0; a < 5; a++)
     for (int n = 0; n < nl; n++) dst[a][n] = out[(size_t)a * nl + (nz - n)];  // the kernels store ground-first (radiate.f90:140-154)
   CATCH(err)
@@ -3330,7 +3307,7 @@ void radtran_f_total_get(void *ptr, const int *dim1, double *arr) {
   if (!r || r->state != 2) return;
   try {
     fetch_small(r);
-    for (int i = 0; i < *dim1 && i < r->nz + 1; i++) arr[i] = r->h_small[4 * (r->nz + 1) + i];
+    for (int i = 0; i < *dim1 && i < r->nz + 1; i++) arr[i] = r->h_small[r->rows.f_total + i];
   } catch (const HipFail &f) {
     defer_err(r, f.msg);   // no `err` here (clima/fortran/Radtran.f90 getters have none): radtran_synchronize reports it
   } catch (...) {
@@ -3496,7 +3473,7 @@ WRK2D(tau_band, tau_band, 0)
       fetch_small(r);                                                                     \
       const int nl = r->nz + 1;                                                           \
       const int a = (w->which ? 2 : 0) + ((up) ? 0 : 1);                                  \
-      for (int i = 0; i < *dim1 && i < nl; i++) arr[i] = r->h_small[a * nl + i];          \
+      for (int i = 0; i < *dim1 && i < nl; i++) arr[i] = r->h_small[r->rows.row(a) + i];  \
     } catch (const HipFail &f) { defer_err(r, f.msg);                                     \
     } catch (...) { defer_err(r, "climaradtranwrk getter failed"); }                      \
   }

@@ -15,8 +15,7 @@
 //            g, tau_band    [nw][nz]
 //   results  fup_a, fdn_a, amean [nw_ch][nz+1]; tau_band [nw_ch][nz]   ground-first,
 //            == Fortran (nz+1,nw_ch) column-major (ClimaRadtranWrk, clima_radtran.f90:11-25)
-//            flux_n         [4][nz+1]          ir_up, ir_dn, sol_up, sol_dn (the all-reduce payload)
-//            f_total        [nz+1]
+//            level rows     [5][nz+1] + 1      ir_up, ir_dn, sol_up, sol_dn, f_total, error words (level_rows below)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -113,6 +112,46 @@ __host__ __device__ inline ColumnLayout column_layout(int nz, int nsp, int np) {
   l.T = 1; l.P = l.T + nz; l.dz = l.P + nz; l.dens = l.dz + nz;
   l.pdens = l.dens + (size_t)nsp * nz; l.radii = l.pdens + (size_t)np * nz; l.meta = l.radii + (size_t)np * nz;
   l.count = l.meta + nz + 1;
+  return l;
+}
+
+// A column as the callers hand it over (the ABI's order): T_surface a scalar, T / P / dz [nz], dens [nsp][nz], pdens /
+// radii [np][nz] -- of a batch, column after column in each array (T_surface [ncol]).  Host or device pointers.
+struct ColumnArrays {
+  const double *T_surface, *T, *P, *dens, *dz, *pdens, *radii;
+  __host__ __device__ bool has_particles() const { return pdens && radii; }
+  // column c of a batch; the particle arrays come together or not at all (one without the other counts as none, and
+  // so do both where the handle has no particle columns)
+  __host__ __device__ ColumnArrays column(size_t c, int nz, int nsp, int np) const {
+    const bool hp = np > 0 && has_particles();
+    return ColumnArrays{T_surface + c, T + c * nz, P + c * nz, dens + c * nz * nsp, dz + c * nz,
+                        hp ? pdens + c * nz * np : nullptr, hp ? radii + c * nz * np : nullptr};
+  }
+};
+
+// Level-row block: [ir_up | ir_dn | sol_up | sol_dn | f_total][nl] doubles, nl = nz + 1, then one double that holds the
+// two device error words (ints: opacity failure, expired fused hand-off wait).  The handle's d_small / h_small are one
+// such block; a batch's arena holds `stride` doubles of it per column (no error words).  On a handle with a communicator
+// the first double of the f_total row is the step's status word instead, and the all-reduce covers the four flux rows
+// and that word (reduce_count); f_total itself is formed on the host from the fetched rows, or by k_batch_finish.
+struct LevelRows {
+  size_t nl;
+  size_t ir_up, ir_dn, sol_up, sol_dn;   // row offsets: row a of the four at a * nl
+  size_t f_total, status;                // the fifth row == the status word's slot
+  size_t flux_count;                     // doubles of the four flux rows
+  size_t err_words;                      // offset of the double that holds the two ints
+  size_t stride;                         // doubles per column of an arena: the five rows
+  size_t count;                          // doubles of the whole block
+  size_t reduce_count;                   // doubles the all-reduce sums: the four rows and the status word
+  __host__ __device__ size_t row(int a) const { return a * nl; }
+};
+__host__ __device__ inline LevelRows level_rows(int nz) {
+  LevelRows l;
+  l.nl = (size_t)nz + 1;
+  l.ir_up = 0; l.ir_dn = l.nl; l.sol_up = 2 * l.nl; l.sol_dn = 3 * l.nl;
+  l.f_total = l.status = 4 * l.nl; l.flux_count = 4 * l.nl;
+  l.err_words = l.stride = 5 * l.nl;
+  l.count = l.err_words + 1; l.reduce_count = l.flux_count + 1;
   return l;
 }
 
@@ -301,7 +340,7 @@ struct IntegrateParams {
   const double *ir_freq, *sol_freq;        // channel freq [nw_ch+1]
   double *flux_n;                          // [4][nz+1]
   double *flux_part;                       // bin-sharded handles: this rank's partial rows (flux_n is all-reduced in place); else null
-  double *f_total;
+  double *unused;                          // (f_total is formed on the host, fetch_small, or by k_batch_finish); keeps the kernels' argument layout
   double *partial;                         // [4][nchunk][nz+1] chunk sums
   int nchunk;
   // handles with a communicator (radtran_comm_init_rank): one more word rides on the all-reduce behind the four
@@ -335,12 +374,12 @@ struct PackParams {
   int ncol, nz, nsp, np;
   int has_particles;         // pdens and radii are given (np > 0)
   int use_radii;             // ... and the handle has particle opacities: the radii take part in the pair decision
-  const double *T_surface, *T, *P, *dz, *dens, *pdens, *radii;
+  ColumnArrays in;           // the caller's device arrays, column after column
   double *blocks;
   int *nsrc;                 // [ncol] every column's source-layer count once more, contiguous (null: not wanted)
 };
-// ... and k_batch_finish ends the batch on the device: f_total into row 4 of every column's level rows [5][nz+1]
-// (flux, 5 (nz+1) apart), ISR / OLR (ncol), and the five rows into fluxes (nz+1, 5, ncol) when that is given.
+// ... and k_batch_finish ends the batch on the device: f_total into the fifth row of every column's level rows (flux,
+// level_rows(nz).stride apart), ISR / OLR (ncol), and the five rows into fluxes (nz+1, 5, ncol) when that is given.
 struct BatchFinishParams {
   int ncol, nz;
   double *flux;
@@ -509,7 +548,6 @@ void launch_integrate(const IntegrateParams &p, hipStream_t s);
 bool prep_integrate_merges(const PrepParams &pp, const IntegrateParams &ip);
 void launch_prep_integrate(const PrepParams &pp, const IntegrateParams &ip, hipStream_t s);
 void launch_integrate_batch(const BatchIntegrateParams &p, int ncol, hipStream_t s);
-void launch_f_total(int nz, const double *flux_n, double *f_total, hipStream_t s);
 void launch_scale(double *a, size_t n, double f, hipStream_t s);
 void launch_copy(double *dst, const double *src, size_t n, hipStream_t s);  // src may be pinned host memory
 void launch_test_rcp(const double *x, double *y, int n, hipStream_t s);

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "../../include/clima_radtran_hip.h"
+#include "radtran_dev.h"
 
 namespace clima_loader {
 
@@ -408,7 +409,7 @@ static bool strictly_increasing(const vec &v) {
   for (size_t i = 1; i < v.size(); i++) if (v[i] - v[i - 1] <= 0.0) return false;
   return true;
 }
-static bool is_close(double a, double b, double tol) { return std::fabs(a - b) <= tol * std::max(std::fabs(a), std::fabs(b)); }
+using clima::is_close;   // futils is_close, as the host API and the kernels apply it (radtran_dev.h)
 
 // ------------------------------------------------------------------------------------------------ the tables
 struct KTab { int sp; vec weights, log10P, temp, log10k; };

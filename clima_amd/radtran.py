@@ -297,6 +297,7 @@ class Radtran:
         self._L.radtran_unset_custom_optical_properties(self._ptr)
 
     SPECTRA = ("ir_fup_a", "ir_fdn_a", "sol_fup_a", "sol_fdn_a")
+    SPECTRA_ALL = ("ir_fup_a", "ir_fdn_a", "ir_tau_band", "sol_fup_a", "sol_fdn_a", "sol_amean", "sol_tau_band")   # spectra_all's
 
     def _spectra_request(self, spectra_levels, spectra):
         """(levels 1..nz+1 as the ABI takes them, the names asked for in the ABI's order) of a batch's `spectra_levels`
@@ -571,44 +572,17 @@ class Radtran:
         self._L.radtran_bin_shard_get(self._ptr, *[C.byref(x) for x in v])
         return tuple(x.value for x in v)
 
-    @property
-    def fused(self):
-        """True: opacity + two-stream of a compute_opacity call run as one grid (k_fused)."""
-        v = C.c_int()
-        self._L.radtran_fused_get(self._ptr, C.byref(v))
-        return bool(v.value)
-
-    @fused.setter
-    def fused(self, on):
-        self._L.radtran_fused_set(self._ptr, _i(1 if on else 0))
-
-    @property
-    def coop_items(self):
-        """ng = 8: calls with at most this many (bin, source layer) items use the group-of-lanes opacity kernel."""
-        v = C.c_int()
-        self._L.radtran_coop_items_get(self._ptr, C.byref(v))
-        return v.value
-
-    @coop_items.setter
-    def coop_items(self, n):
-        self._L.radtran_coop_items_set(self._ptr, _i(int(n)))
-
     def spectra_all(self, do_solar=True, out=None):
         """The seven per-bin arrays of the last call through radtran_spectra_get_all (one synchronise; the arrays of
         `out` -- a dict from an earlier call -- are page-locked by the library on first use).  Column-major like the
         reference's holders: fup_a, fdn_a (nz+1, nw), tau_band (nz, nw) per channel, amean for the solar one."""
         nl, ni, ns = self.nz + 1, len(self.ir.freq) - 1, len(self.sol.freq) - 1
         if out is None:
-            out = {"ir_fup_a": np.zeros((nl, ni), order="F"), "ir_fdn_a": np.zeros((nl, ni), order="F"),
-                   "ir_tau_band": np.zeros((nl - 1, ni), order="F"), "sol_fup_a": np.zeros((nl, ns), order="F"),
-                   "sol_fdn_a": np.zeros((nl, ns), order="F"), "sol_amean": np.zeros((nl, ns), order="F"),
-                   "sol_tau_band": np.zeros((nl - 1, ns), order="F")}
-        err = C.create_string_buffer(1025)
-        names = ("ir_fup_a", "ir_fdn_a", "ir_tau_band", "sol_fup_a", "sol_fdn_a", "sol_amean", "sol_tau_band")
+            out = {name: np.zeros((nl - name.endswith("tau_band"), ni if name.startswith("ir_") else ns), order="F")
+                   for name in self.SPECTRA_ALL}
         self._L.radtran_spectra_get_all(self._ptr, C.byref(C.c_bool(bool(do_solar))), _i(nl), _i(ni), _i(ns),
-                                        *[out[k].ctypes.data_as(C.POINTER(C.c_double)) for k in names], err)
-        if err.value:
-            raise ClimaException(err.value.decode())
+                                        *[_d(out[name]) for name in self.SPECTRA_ALL], self._err)
+        self._check()
         self._locked = getattr(self, "_locked", [])
         if not any(o is out for o in self._locked):
             self._locked.append(out)          # page-locked by the library: kept alive until spectra_release / the handle goes
@@ -618,56 +592,6 @@ class Radtran:
         """Un-page-lock what spectra_all locked (before those arrays are freed)."""
         self._L.radtran_spectra_release(self._ptr)
         self._locked = []
-
-    @property
-    def fused_spins(self):
-        """Polls a two-stream block of the fused grid spends waiting for its opacity tiles (0: every wait expires and
-        the call is repeated through separate launches)."""
-        v = C.c_int()
-        self._L.radtran_fused_spins_get(self._ptr, C.byref(v))
-        return v.value
-
-    @fused_spins.setter
-    def fused_spins(self, n):
-        self._L.radtran_fused_spins_set(self._ptr, _i(int(n)))
-
-    @property
-    def ir_green(self):
-        """radiate_ir_batch's response form: 0 never, 1 (default) when enough columns are sparse deviations of one
-        profile, 2 whenever any is."""
-        m, b = C.c_int(), C.c_int()
-        self._L.radtran_ir_green_get(self._ptr, C.byref(m), C.byref(b))
-        return m.value
-
-    @ir_green.setter
-    def ir_green(self, mode):
-        self._L.radtran_ir_green_set(self._ptr, _i(int(mode)))
-
-    @property
-    def ir_green_batches(self):
-        """Batches that took the response form."""
-        m, b = C.c_int(), C.c_int()
-        self._L.radtran_ir_green_get(self._ptr, C.byref(m), C.byref(b))
-        return b.value
-
-    @property
-    def fused_fallbacks(self):
-        """Calls re-issued through the separate launches after a fused hand-off wait expired."""
-        v = C.c_int()
-        self._L.radtran_fused_fallbacks_get(self._ptr, C.byref(v))
-        return v.value
-
-    @property
-    def defer_integration(self):
-        """True (default): a `radiate_resident` call keeps its frequency integration back for the next call's prep
-        launch (one grid for both); anything that reads results launches it first.  Same results bit for bit."""
-        v = C.c_int()
-        self._L.radtran_defer_integration_get(self._ptr, C.byref(v))
-        return bool(v.value)
-
-    @defer_integration.setter
-    def defer_integration(self, on):
-        self._L.radtran_defer_integration_set(self._ptr, _i(1 if on else 0))
 
     @property
     def merged_integrations(self):
@@ -789,21 +713,38 @@ class Radtran:
     photons_sol = property(lambda s: s._vec_get("photons_sol"))
     f_total = property(lambda s: s._vec_get("f_total"))
 
-    def _scalar(name, ctype):
+    def _scalar(name, ctype, to, doc=None, settable=True, getter=None, outs=1, pick=0):
+        """radtran_<name>_get / _set as a property of Python type `to`; getter: another _get, with `outs` outputs of which
+        this is number `pick`"""
         def get(self):
-            v = ctype()
-            getattr(self._L, "radtran_%s_get" % name)(self._ptr, C.byref(v))
-            return bool(v.value) if ctype is C.c_bool else v.value
+            v = [ctype() for _ in range(outs)]
+            getattr(self._L, "radtran_%s_get" % (getter or name))(self._ptr, *[C.byref(x) for x in v])
+            return to(v[pick].value)
 
         def set_(self, val):
-            getattr(self._L, "radtran_%s_set" % name)(self._ptr, C.byref(ctype(bool(val) if ctype is C.c_bool else float(val))))
+            getattr(self._L, "radtran_%s_set" % name)(self._ptr, C.byref(ctype(to(val))))
 
-        return property(get, set_)
+        return property(get, set_ if settable else None, doc=doc)
 
-    has_hard_surface = _scalar("has_hard_surface", C.c_bool)  # logical(c_bool), clima/cython/Radtran_pxd.pxd:45-46
-    photon_scale_factor = _scalar("photon_scale_factor", C.c_double)
-    ir_tau_min = _scalar("ir_tau_min", C.c_double)
-    diurnal_fac = _scalar("diurnal_fac", C.c_double)
+    has_hard_surface = _scalar("has_hard_surface", C.c_bool, bool)  # logical(c_bool), clima/cython/Radtran_pxd.pxd:45-46
+    photon_scale_factor = _scalar("photon_scale_factor", C.c_double, float)
+    ir_tau_min = _scalar("ir_tau_min", C.c_double, float)
+    diurnal_fac = _scalar("diurnal_fac", C.c_double, float)
+    fused = _scalar("fused", C.c_int, bool,
+                    "True: opacity + two-stream of a compute_opacity call run as one grid (k_fused).")
+    coop_items = _scalar("coop_items", C.c_int, int, "ng = 8: calls with at most this many (bin, source layer) items use "
+                         "the group-of-lanes opacity kernel.")
+    fused_spins = _scalar("fused_spins", C.c_int, int, "Polls a two-stream block of the fused grid spends waiting for its "
+                          "opacity tiles (0: every wait expires and the call is repeated through separate launches).")
+    fused_fallbacks = _scalar("fused_fallbacks", C.c_int, int, "Calls re-issued through the separate launches after a fused "
+                              "hand-off wait expired.", settable=False)
+    ir_green = _scalar("ir_green", C.c_int, int, "radiate_ir_batch's response form: 0 never, 1 (default) when enough columns "
+                       "are sparse deviations of one profile, 2 whenever any is.", outs=2)
+    ir_green_batches = _scalar("ir_green_batches", C.c_int, int, "Batches that took the response form.", settable=False,
+                               getter="ir_green", outs=2, pick=1)
+    defer_integration = _scalar("defer_integration", C.c_int, bool, "True (default): a `radiate_resident` call keeps its "
+                                "frequency integration back for the next call's prep launch (one grid for both); anything "
+                                "that reads results launches it first.  Same results bit for bit.")
     del _scalar
 
     def _sub(self, name, cls):

@@ -1,24 +1,12 @@
 """The device-array column batch (radtran_toa_fluxes_batch_device) as far as it can be held without a GPU: the library
 exports it and its test hooks, the ctypes table declares them with the header's argument counts, and its two kernels
 compile without scratch traffic (the pattern of tests/test_build_quality.py, for kernels that file's list predates)."""
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-from clima_amd import build as B
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+import build_inspect
 NEW = ("radtran_toa_fluxes_batch_device", "clima_test_pack_columns", "clima_test_pack_columns_host")
-
-
-def _header_arg_counts():
-    text = open(os.path.join(ROOT, "include", "clima_radtran_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return {m.group(1): m.group(2).count(",") + 1 for m in re.finditer(r"\bvoid\s+([a-z_0-9]+)\s*\(([^)]*)\)", text)}
 
 
 def test_library_exports_the_device_batch_and_its_hooks(hip_lib):
@@ -28,7 +16,7 @@ def test_library_exports_the_device_batch_and_its_hooks(hip_lib):
 
 def test_ctypes_table_declares_them_with_the_headers_argument_counts(hip_lib):
     from clima_amd import lib
-    counts = _header_arg_counts()
+    counts = build_inspect.header_arg_counts()
     assert counts["radtran_toa_fluxes_batch_device"] == 15      # the host batch's 14 + producer_stream
     assert counts["clima_test_pack_columns"] == counts["clima_test_pack_columns_host"] == 13
     for name in NEW:
@@ -45,24 +33,9 @@ def test_python_mirror_has_the_tensor_entry():
 @pytest.fixture(scope="module")
 def scratch_counts():
     """scratch instructions per kernel of kernels.hip, from the gfx950 assembly of the build's own flags"""
-    if not (os.path.exists(B.HIPCC) or shutil.which(B.HIPCC)):
+    if not build_inspect.have_hipcc():
         pytest.skip("no hipcc")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "kernels.s")
-        flags = [f for f in B.FLAGS if f not in ("-fPIC", "-shared")]
-        subprocess.check_call([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-w", os.path.join(B.CSRC, "kernels.hip"), "-o", out])
-        kernels, name, n_scratch = {}, None, 0
-        for line in open(out):
-            m = re.match(r"^(_ZN5clima\w+):", line)
-            if m:
-                name, n_scratch = m.group(1), 0
-            elif name is not None:
-                if "scratch_" in line:
-                    n_scratch += 1
-                elif line.startswith(".Lfunc_end"):
-                    kernels[name] = n_scratch
-                    name = None
-    return kernels
+    return build_inspect.scratch_counts()
 
 
 def test_pack_and_finish_kernels_have_no_scratch_traffic(scratch_counts):

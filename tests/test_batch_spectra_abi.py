@@ -13,7 +13,7 @@ import re
 
 import pytest
 
-from test_batch_device_abi import _header_arg_counts
+from build_inspect import header_arg_counts
 
 NEW = ("radtran_toa_fluxes_batch_spectra", "radtran_toa_fluxes_batch_spectra_device")
 
@@ -25,7 +25,7 @@ def test_library_exports_both_symbols(hip_lib):
 
 def test_ctypes_table_declares_them_with_the_headers_argument_counts(hip_lib):
     from clima_amd import lib
-    counts = _header_arg_counts()
+    counts = header_arg_counts()
     assert counts["radtran_toa_fluxes_batch_spectra"] == counts["radtran_toa_fluxes_batch"] + 6 == 20
     assert counts["radtran_toa_fluxes_batch_spectra_device"] == counts["radtran_toa_fluxes_batch_device"] + 6 == 21
     for name in NEW:

@@ -5,16 +5,15 @@ A wave of these kernels stalls for an L2 round trip on every scratch reload; bui
 where hipcc's register allocator spilled differed by up to 7 us per call, and a parameter block copied to
 scratch at kernel entry (what hipcc does without the flag in clima_amd/build.py) doubles the run time
 ("What bounds these kernels").  The check reads the gfx950 assembly hipcc writes for
-clima_amd/csrc/kernels.hip with the build's own flags (tools/scratch_report.py prints the same counts).
+clima_amd/csrc/kernels.hip with the build's own flags (tests/build_inspect.py; tools/scratch_report.py prints the same
+counts from the same place).
 """
 import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
+import build_inspect
 from clima_amd import build as B
 
 # kernels of the production paths: fused grid, stand-alone opacity tile, group-of-lanes opacity,
@@ -24,24 +23,9 @@ HOT = re.compile(r"k_fused|k_opacity8|k_opacity_coop|k_twostream_w|k_twostream_h
 
 @pytest.fixture(scope="module")
 def assembly():
-    if not (os.path.exists(B.HIPCC) or shutil.which(B.HIPCC)):
+    if not build_inspect.have_hipcc():
         pytest.skip("no hipcc")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "kernels.s")
-        flags = [f for f in B.FLAGS if f not in ("-fPIC", "-shared")]
-        subprocess.check_call([B.HIPCC] + flags + ["-S", "--cuda-device-only", "-w", os.path.join(B.CSRC, "kernels.hip"), "-o", out])
-        kernels, name, n_scratch = {}, None, 0
-        for line in open(out):
-            m = re.match(r"^(_ZN5clima\w+):", line)
-            if m:
-                name, n_scratch = m.group(1), 0
-            elif name is not None:
-                if "scratch_" in line:
-                    n_scratch += 1
-                elif line.startswith(".Lfunc_end"):
-                    kernels[name] = n_scratch
-                    name = None
-    return kernels
+    return build_inspect.scratch_counts()
 
 
 # The 16- and 32-lane group-of-lanes kernels are compiled for one wave per SIMD more than their registers allow

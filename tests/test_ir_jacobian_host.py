@@ -7,14 +7,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import build_inspect
 import ir_jacobian_oracle as J
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
 def test_ir_jacobian_is_declared_exported_and_in_the_signature_table(hip_lib):
     from clima_amd import lib
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "clima_radtran_hip.h")).read(), flags=re.S)
+    text = build_inspect.header_text()
     assert re.search(r"\bvoid\s+radtran_ir_jacobian\s*\(", text)
     assert hasattr(hip_lib, "radtran_ir_jacobian")
     assert len(lib.SIGNATURES["radtran_ir_jacobian"]) == 10

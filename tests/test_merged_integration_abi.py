@@ -3,18 +3,17 @@ the Python signature table, and the eligibility rule (clima_test_defer_allowed: 
 holds what include/clima_radtran_hip.h says of it."""
 import ctypes as C
 import itertools
-import os
 import re
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+import build_inspect
+
 NEW = ("radtran_defer_integration_set", "radtran_defer_integration_get", "radtran_merged_integrations_get",
        "clima_test_defer_allowed")
 
 
 def test_new_symbols_are_declared_exported_and_bound(hip_lib):
     from clima_amd import lib
-    text = open(os.path.join(ROOT, "include", "clima_radtran_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = build_inspect.header_text()
     for n in NEW:
         assert re.search(r"\bvoid\s+%s\s*\(" % n, text), "%s is not declared" % n
         assert hasattr(hip_lib, n), "library does not export %s" % n

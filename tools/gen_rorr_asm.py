@@ -38,7 +38,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import gen_sort_network_inplace as IP  # noqa: E402
 
-# tight crossing windows of the window-form rebin (kernels.hip rb_lo/rb_hi<true>; tools/gen_rebin_windows.py)
+# tight crossing windows of the window-form rebin: RB_TIGHT_LO / RB_TIGHT_HI of clima_amd/csrc/radtran_dev.h, which the
+# kernels and the host read (tests/test_rebin_windows.py holds the two copies equal; tools/gen_rebin_windows.py)
 RB_LO = [0, 5, 12, 19, 27, 35, 45, 55]
 RB_HI = [0, 8, 18, 28, 36, 44, 51, 58]
 
