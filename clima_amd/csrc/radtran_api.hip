@@ -410,6 +410,16 @@ void upload_fields(Radtran *r) {
   r->fields_dirty = false;
 }
 
+// the g-point weights' edges (weight_e) and pair products, types_create.f90:1303-1304
+void weight_edges_and_products(const std::vector<double> &wbin, std::vector<double> &wbin_e, std::vector<double> &wxy) {
+  const int ng = (int)wbin.size();
+  wbin_e.assign(ng + 1, 0.0);
+  for (int i = 1; i < ng + 1; i++) wbin_e[i] = wbin[i - 1] + wbin_e[i - 1];
+  wxy.assign((size_t)ng * ng, 0.0);
+  for (int i = 0; i < ng; i++)
+    for (int j = 0; j < ng; j++) wxy[j + (size_t)i * ng] = wbin[i] * wbin[j];
+}
+
 // Which rebin form the opacity kernels may use for these g-point weights (ng = 8).  The window form
 // evaluates, for output edge k, only the sorted elements [RB_WIN_LO[k], RB_WIN_HI[k]]; the element j*
 // that crosses E_k (C_{j*-1} < E_k <= C_{j*}) must be among them WHATEVER order the sort produces.
@@ -862,6 +872,8 @@ bool resolve_pending_integration(Radtran *r, const PrepParams *prep = nullptr) {
 // plan -> prep -> opacity (or the fused grid) -> two-stream -> integrate -> reduce, on the buffers `b` names
 // defer: the caller returns without anyone reading a result, so the integration may wait for the next call's prep launch
 void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused = true, bool defer = false) {
+  // (a one-launch batch left its optical properties in the arena: the handle's own are an earlier call's, or nothing)
+  if (!compute_opacity && !r->opr_valid) throw HipFail{"radiate needs opacities: call radiate with compute_opacity first"};
   r->timer_calls++;
   upload_fields(r);
   const bool resident = b.kind == CALL_RESIDENT, chunk = b.kind == CALL_ARENA_CHUNK;
@@ -1318,11 +1330,7 @@ void radtran_add_ktable(void *ptr, const int *sp_ind, const int *ngauss, const d
   if (r->k.empty()) {  // create_Ksettings, types_create.f90:191-224; weight_e :1303-1304
     r->ng = *ngauss;
     r->wbin = k->weights;
-    r->wbin_e.assign(r->ng + 1, 0.0);
-    for (int i = 1; i < r->ng + 1; i++) r->wbin_e[i] = r->wbin[i - 1] + r->wbin_e[i - 1];
-    r->wxy.assign((size_t)r->ng * r->ng, 0.0);
-    for (int i = 0; i < r->ng; i++)
-      for (int j = 0; j < r->ng; j++) r->wxy[j + (size_t)i * r->ng] = r->wbin[i] * r->wbin[j];
+    weight_edges_and_products(r->wbin, r->wbin_e, r->wxy);
     r->rebin_mode = rebin_mode_for(r->wbin, r->wbin_e, r->wxy, r->rebin_stream);
   }
   r->k.push_back(k);
@@ -1610,6 +1618,28 @@ void radtran_defer_integration_get(void *ptr, int *enabled) {
 void clima_test_defer_allowed(const int *switch_on, const int *shard_world, const int *has_comm, const int *profile,
                               const int *capturing, const int *flux_ptr_taken, int *allowed) {
   *allowed = defer_allowed(*switch_on != 0, *shard_world, *has_comm != 0, *profile, *capturing != 0, *flux_ptr_taken != 0) ? 1 : 0;
+}
+void clima_test_plan_radiate(const int *in, int *out) {
+  PlanIn p{};
+  p.nz = in[0]; p.ng = in[1]; p.nzen = in[2]; p.n_ir = in[3]; p.n_sol = in[4]; p.op_n = in[5]; p.nsrc = in[6]; p.ncol = in[7];
+  p.batch = in[8] != 0; p.ir_batch = in[9] != 0; p.rebin_mode = in[10]; p.cust_on = in[11] != 0;
+  p.compute_opacity = in[12] != 0; p.all_pairs = in[13] != 0; p.fused = in[14] != 0; p.allow_fused = in[15] != 0;
+  p.ts_block_mode = in[16] != 0; p.no_half = in[17] != 0; p.coop_items = in[18]; p.force_slots = in[19];
+  const LaunchPlan pl = plan_radiate(p);
+  int k = 0;
+  out[k++] = pl.opacity; out[k++] = pl.coop_ng;
+  for (const TsPlan *t : {&pl.fused, &pl.ts, &pl.block}) {
+    out[k++] = t->form; out[k++] = t->slots; out[k++] = t->groups; out[k++] = t->per_launch; out[k++] = t->zero_launch ? 1 : 0;
+  }
+  out[k++] = pl.prep_clears ? 1 : 0; out[k++] = pl.caller_clears ? 1 : 0; out[k++] = pl.write_w0 ? 1 : 0;
+  out[k++] = integrate_fits_one_launch(integrate_chunks(in[20])) ? 1 : 0;
+  static_assert(CLIMA_PLAN_IN_N == 21 && CLIMA_PLAN_OUT_N == 2 + 3 * 5 + 4, "the orders documented in clima_radtran_hip.h");
+}
+void clima_test_rebin_mode_for(const int *ng, const double *weights, const int *stream, int *mode) {
+  std::vector<double> wbin(weights, weights + std::max(*ng, 0)), wbin_e, wxy;
+  if (wbin.empty()) { *mode = -1; return; }
+  weight_edges_and_products(wbin, wbin_e, wxy);
+  *mode = rebin_mode_for(wbin, wbin_e, wxy, *stream != 0);
 }
 void radtran_merged_integrations_get(void *ptr, int *merged, int *standalone) {
   Radtran *r = as_rad(ptr);

@@ -168,7 +168,10 @@ void radtran_comm_destroy(void *ptr);
  * (src/radtran/clima_radtran.f90:320-342), moved to HBM in one copy and enqueued back to back.
  * Inputs as radtran_toa_fluxes_wrapper with the column as the last dimension: T, P, dz (nz, ncol),
  * densities (nz, nsp, ncol), pdensities / radii (nz, np, ncol), T_surface (ncol).  ISR, OLR (ncol);
- * fluxes (nz+1, 5, ncol) = ir up, ir down, solar up, solar down, f_total, or NULL. */
+ * fluxes (nz+1, 5, ncol) = ir up, ir down, solar up, solar down, f_total, or NULL.
+ * Afterwards the handle holds the last column's level rows and spectra.  Where the batch ran one launch per chunk its
+ * optical properties stayed in the batch's own memory: a call with compute_opacity = 0, radtran_radiate_ir_batch and the
+ * Jacobians then refuse ("... needs opacities: call radiate with compute_opacity first") until a compute_opacity call. */
 void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
                               const double *densities, const double *dz, const int *has_particles,
                               const double *pdensities, const double *radii, double *ISR, double *OLR,
@@ -374,6 +377,24 @@ void radtran_merged_integrations_get(void *ptr, int *merged, int *standalone);
 /* test hook: the rule above as a function of its inputs (no handle, no device) */
 void clima_test_defer_allowed(const int *switch_on, const int *shard_world, const int *has_comm, const int *profile,
                               const int *capturing, const int *flux_ptr_taken, int *allowed);
+/* test hook: the launch plan of one radiate call as the library's own planner (plan_radiate) decides it; no handle, no
+ * device.  in[CLIMA_PLAN_IN_N], the planner's inputs in this order:
+ *    0 nz   1 ng   2 nzen   3 n_ir   4 n_sol   5 op_n   6 nsrc   7 ncol   8 batch   9 ir_batch   10 rebin_mode
+ *   11 cust_on   12 compute_opacity   13 all_pairs   14 fused   15 allow_fused   16 ts_block_mode   17 no_half
+ *   18 coop_items   19 force_slots   20 nbins (of the wider channel: what the frequency integration is sized by)
+ * out[CLIMA_PLAN_OUT_N]:
+ *    0 opacity (0 stored opacities, 1 lane per item, 2 group of lanes, 3 unsupported)   1 coop_ng
+ *    2..6 the fused grid, 7..11 the stand-alone wave forms, 12..16 the workgroup-per-bin form, each as
+ *         form (0 none, 1 whole wave, 2 half wave, 3 exact pairs, 4 workgroup per bin), slots, groups, per_launch, zero_launch
+ *   17 prep_clears   18 caller_clears   19 write_w0
+ *   20 the frequency integration of nbins bins fits the one-launch kernel (a column batch takes one launch per chunk
+ *      only where this holds and the plan of a chunk is fused) */
+#define CLIMA_PLAN_IN_N 21
+#define CLIMA_PLAN_OUT_N 21
+void clima_test_plan_radiate(const int *in, int *out);
+/* test hook: the rebin form (0 window, 1 streaming, 2 streaming multi-edge) a handle takes for these ng g-point weights;
+ * stream != 0: as under CLIMA_HIP_REBIN=stream */
+void clima_test_rebin_mode_for(const int *ng, const double *weights, const int *stream, int *mode);
 /* HIP stream the handle launches on (for callers that order other work against it) */
 void radtran_stream_get(void *ptr, void **stream);
 /* per-kernel device time (HIP events on the handle's stream).  enable = 1 records events
