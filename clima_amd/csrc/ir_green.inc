@@ -39,22 +39,7 @@ constexpr int GREEN_TILE = 16;
 // of two VIRTUAL layers: above layer 0 one with e = (1, ., 0, 0), below layer nz-1 one with e = (0, 1, 0, Rsfc) whose
 // upper source value is the surface term -- with them every row is one of the two interface equations (:252-276).
 struct GreenLayer { E4 e; double rq, tau; bool thin; };
-__device__ __forceinline__ GreenLayer green_layer(const GreenParams &p, size_t qtau, size_t qg, int n, double Rsfc) {
-  GreenLayer L;
-  L.rq = 0.0; L.tau = 0.0; L.thin = true;
-  if (n < 0) { L.e.e1 = 1.0; L.e.e2 = 1.0; L.e.e3 = 0.0; L.e.e4 = 0.0; return L; }
-  if (n >= p.nz) { L.e.e1 = 0.0; L.e.e2 = 1.0; L.e.e3 = 0.0; L.e.e4 = Rsfc; return L; }
-  const double tau = p.tau[qtau + n], w0 = p.w0[qtau + n], gt = p.g[qg + n];
-  const double gam1 = 2.0 - w0 * (1.0 + gt), gam2 = w0 * (1.0 - gt);
-  const double lam = sqrt_nr(gam1 * gam1 - gam2 * gam2);
-  const double G = gam2 * rcp_nr(gam1 + lam);
-  L.e = make_e(G, fast_exp(-lam * tau));
-  L.rq = rcp_nr(gam1 + gam2);
-  L.tau = tau;
-  L.thin = tau <= p.ir_tau_min;
-  return L;
-}
-// the same from the layer's three inputs already in registers (k_green_unit issues the loads of its four layers, and of
+// From the layer's three inputs already in registers (k_green_unit issues the loads of its four layers, and of
 // everything else it reads, before the first use: one memory round trip instead of ~20 one behind the other)
 __device__ __forceinline__ GreenLayer green_layer_of(const GreenParams &p, double tau, double w0, double gt, int n, double Rsfc) {
   GreenLayer L;

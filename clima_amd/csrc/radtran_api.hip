@@ -218,12 +218,10 @@ struct Radtran {
 #endif
   double *h_col = nullptr;  // pinned staging
   double *h_col_dev = nullptr;  // the same buffer as the device addresses it (null: not mapped, use the copy engine)
-  bool column_has_particles = false;
-  bool column_loaded = false;
   hipEvent_t ev_upload = nullptr;   // marks the end of the last column copy out of the pinned staging buffer
   bool upload_pending = false;
   int call_id = 0, checked_id = 0;  // opacity passes enqueued / already checked for device errors
-  long upload_id = 0, opr_upload_id = 0;   // columns uploaded so far / the upload the stored opacities were computed from
+  Holds holds;                      // what the handle holds between calls: the column, its own optical properties, the level rows
   std::string deferred_err;         // a failure met inside a getter without an `err` argument: reported by the next call that has one
   // fused hand-off (k_fused): bound of a two-stream block's wait, the last timed-out pass already
   // handled, the pass of the last solar computation, flags of the last call, re-issued calls so far
@@ -234,7 +232,6 @@ struct Radtran {
   DevBuf<double> d_opr;
   size_t opr_count = 0;
   DevBuf<double> d_tau, d_w0, d_g, d_tau_band, d_scat;
-  bool opr_valid = false;
   // results
   LevelRows rows{};           // level_rows(nz): the layout of d_small, h_small and a column's slice of d_flux_arena
   DevBuf<double> d_small;     // one level-row block: one D2H copy per call
@@ -248,11 +245,7 @@ struct Radtran {
   hipStream_t copy_streams[3] = {nullptr, nullptr, nullptr}; // radtran_spectra_get_all: the seven copies go out over four queues
   double *h_small = nullptr;  // pinned: d_small's block on the host
   double *h_small_dev = nullptr;   // the same block as the device addresses it (null: not mapped)
-  bool small_in_host = false;      // the last call's integration stored its rows into h_small itself: no copy to fetch them
   int *h_errflag = nullptr;
-  std::vector<double> f_total;
-  bool small_valid = false;
-  bool w0_valid = true;            // false after a fused call whose tiles left w0 unwritten (ensure_w0 materialises it)
   // sharding
   DevBuf<double> d_flux_part;  // this rank's partial level rows (d_flux_n is all-reduced in place)
   int shard_rank = 0, shard_world = 1;
@@ -698,8 +691,6 @@ void toa_fluxes(const double *h, const LevelRows &l, double *ISR, double *OLR) {
   toa_isr_olr(h[l.ir_up + top], h[l.ir_dn + top], h[l.sol_up + top], h[l.sol_dn + top], *ISR, *OLR);
 }
 
-void invalidate_small(Radtran *r) { r->small_valid = false; r->small_in_host = false; }
-
 // The parameter blocks of a call's launches: each from the handle and the call's buffers
 TwoStreamParams make_twostream_params(Radtran *r, const CallBufs &b, const ColumnDev &col, bool compute_solar) {
   TwoStreamParams ts;
@@ -828,10 +819,18 @@ PlanIn plan_input(const Radtran *r, const CallBufs &b, bool compute_solar, bool 
 // whoever else wants it -- IR-only calls on the stored opacities, the batched IR kernel, radtran_opr_get --
 // gets it formed from tau and the layers' scattering optical depth first)
 void ensure_w0(Radtran *r) {
-  if (r->w0_valid) return;
+  if (r->holds.w0_stored) return;
   launch_w0_from_scat(r->d_tau.p, r->d_scat.p, r->d_w0.p, r->nw, r->ng, r->nz, r->stream);
   HIPCHK(hipGetLastError());
-  r->w0_valid = true;
+  r->holds.w0_formed();
+}
+
+// What an entry point needs of the handle (NEED_*), stated in one line at its top: true, and refused()'s text with the
+// caller's name in `err`, when the handle does not hold it.  comm_counts false: not even a communicator makes a shard do.
+bool refuse(const Radtran *r, const char *who, int needs, char *err, bool comm_counts = true) {
+  const char *t = refused(r->holds, needs, r->shard_world, comm_counts && r->comm, r->op_lo, r->op_n);
+  if (t) set_err(err, t[0] == ' ' ? std::string(who) + t : std::string(t));
+  return t != nullptr;
 }
 
 // May a resident call on this handle keep its integration back?  Not on a bin-sharded handle or one with a communicator
@@ -840,16 +839,13 @@ void ensure_w0(Radtran *r) {
 bool defer_allowed(bool switch_on, int shard_world, bool has_comm, int profile, bool capturing, bool flux_ptr_taken) {
   return switch_on && shard_world == 1 && !has_comm && profile != 1 && !capturing && !flux_ptr_taken;
 }
-bool defer_allowed_but_for_capture(const Radtran *r) {
-  return defer_allowed(r->defer_integration, r->shard_world, r->comm != nullptr, r->profile, false, r->flux_ptr_taken);
-}
 bool stream_capturing(Radtran *r) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   HIPCHK(hipStreamIsCapturing(r->stream, &st));
   return st != hipStreamCaptureStatusNone;
 }
-bool defer_eligible(Radtran *r) {
-  return defer_allowed_but_for_capture(r) && !stream_capturing(r);   // (the runtime is asked only where the answer decides)
+bool defer_eligible(Radtran *r) {   // (the runtime is asked only where the answer decides)
+  return defer_allowed(r->defer_integration, r->shard_world, r->comm != nullptr, r->profile, false, r->flux_ptr_taken) && !stream_capturing(r);
 }
 // THE place where a pending integration is resolved.  With the prep parameters of a compute_opacity call that is about
 // to launch its prep pass (and clears nothing there): both in one grid where k_prep_integrate covers them -- returns
@@ -872,8 +868,8 @@ bool resolve_pending_integration(Radtran *r, const PrepParams *prep = nullptr) {
 // plan -> prep -> opacity (or the fused grid) -> two-stream -> integrate -> reduce, on the buffers `b` names
 // defer: the caller returns without anyone reading a result, so the integration may wait for the next call's prep launch
 void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused = true, bool defer = false) {
-  // (a one-launch batch left its optical properties in the arena: the handle's own are an earlier call's, or nothing)
-  if (!compute_opacity && !r->opr_valid) throw HipFail{"radiate needs opacities: call radiate with compute_opacity first"};
+  char why[CLIMA_ERR_LEN + 1];   // (a one-launch batch left its optical properties in the arena, another shard's pass covers other bins)
+  if (!compute_opacity && refuse(r, "radiate", NEED_OPACITIES, why)) throw HipFail{why};
   r->timer_calls++;
   upload_fields(r);
   const bool resident = b.kind == CALL_RESIDENT, chunk = b.kind == CALL_ARENA_CHUNK;
@@ -913,9 +909,7 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
         throw HipFail{"k-distributions with " + std::to_string(r->ng) + " g-points are not supported (1..32)"};
       t.stop();
     }
-    r->opr_valid = true;
-    if (!chunk) r->w0_valid = op.write_w0 != 0;             // the handle's own optical-property block was written
-    if (resident) r->opr_upload_id = r->upload_id;          // ... from the resident column
+    r->holds.opacities_written(!chunk, op.write_w0 != 0, resident, r->op_lo, r->op_n);
   } else {
     resolve_pending_integration(r);   // (an IR-only call's solar rows are the last solar call's)
     if (!chunk) ensure_w0(r);   // this call's two-stream kernels read the stored optical properties
@@ -936,7 +930,7 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
 
   const bool reduce = r->comm && resident;
   const IntegrateParams ip = make_integrate_params(r, b, compute_solar, reduce);
-  r->small_in_host = ip.host_out != nullptr;
+  r->holds.rows_enqueued(ip.host_out != nullptr);
   if (defer && resident && !reduce && !ip.host_out && integrate_fits_one_launch(ip.nchunk) && defer_eligible(r)) {
     r->pending_ip = ip;
     r->int_pending = true;
@@ -949,7 +943,6 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
     NCCLCHK(ncclAllReduce(r->d_small.p, r->d_small.p, r->rows.reduce_count, ncclDouble, ncclSum, r->comm, r->stream));
     r->comm_reduces++;
   }
-  r->small_valid = false;
 }
 
 bool recover_fused_timeout(Radtran *r);
@@ -958,23 +951,18 @@ void settle_pending_batch(Radtran *r);
 
 void fetch_small(Radtran *r) {
   settle_device_batch(r);
-  if (r->small_valid) return;
+  if (r->holds.rows_on_host) return;
   const LevelRows &l = r->rows;
   for (int pass = 0; pass < 2; pass++) {
-    if (!r->small_in_host)
+    if (!r->holds.rows_in_pinned)
       HIPCHK(hipMemcpyAsync(r->h_small, r->d_small.p, sizeof(double) * l.count, hipMemcpyDeviceToHost, r->stream));
     HIPCHK(hipStreamSynchronize(r->stream));
     resolve_events(r);
     if (r->comm) r->comm_status = r->h_small[l.status];
-    if (!r->column_loaded || !recover_fused_timeout(r)) break;  // re-issued unfused: fetch again
+    if (!r->holds.column || !recover_fused_timeout(r)) break;  // re-issued unfused: fetch again
   }
   f_total_row(r->h_small, l);   // no kernel forms a call's f_total
-  r->small_valid = true;
-}
-// ... and the handle's public f_total = the row just formed
-void fetch_f_total(Radtran *r) {
-  fetch_small(r);
-  std::copy(r->h_small + r->rows.f_total, r->h_small + r->rows.f_total + r->rows.nl, r->f_total.begin());
+  r->holds.rows_fetched();
 }
 
 bool check_dims(Radtran *r, int dim_T, int dim_P, int d1, int d2, int dim_dz, int has_p, int p1, int p2,
@@ -1000,8 +988,6 @@ void do_upload(Radtran *r, const ColumnArrays &a) {
   // the pinned staging buffer is reused: wait (lazily, here) for the previous upload's copy
   if (r->upload_pending) { HIPCHK(hipEventSynchronize(r->ev_upload)); r->upload_pending = false; }
   r->nsrc = pack_column(r, h, a);
-  r->column_has_particles = a.has_particles();
-  r->upload_id++;
   const int *meta = reinterpret_cast<const int *>(h + r->col_layout.meta);
   bool all = (nz % 2 == 0) && r->nsrc * 2 == nz;
   for (int m = 0; m < r->nsrc && all; m++) all = (meta[1 + m] & SRC_EXACT) != 0;
@@ -1015,7 +1001,7 @@ void do_upload(Radtran *r, const ColumnArrays &a) {
   r->last_T.assign(a.T, a.T + nz);
   r->last_P.assign(a.P, a.P + nz);
   if (r->np > 0 && a.radii) r->last_radii.assign(a.radii, a.radii + (size_t)nz * r->np); else r->last_radii.clear();
-  r->column_loaded = true;
+  r->holds.uploaded(a.has_particles());
 }
 
 // A two-stream block of the fused grid gave up waiting for its bin's opacity blocks (k_fused: the
@@ -1035,7 +1021,7 @@ bool recover_fused_timeout(Radtran *r) {
     if (!(st > 0.0)) return false;
     r->comm_status = 0.0;
     r->checked_timeout = r->call_id;
-    if (std::fmod(st, 1024.0) > 0.0 && r->upload_id != r->opr_upload_id) throw HipFail{REPLACED_MSG};
+    if (std::fmod(st, 1024.0) > 0.0 && !r->holds.opr_from_resident_column()) throw HipFail{REPLACED_MSG};
     r->fused_fallbacks++;
     enqueue_radiate(r, resident_bufs(r), st >= 1024.0 || r->last_cs, true, false);
     return true;
@@ -1051,7 +1037,7 @@ bool recover_fused_timeout(Radtran *r) {
                   "library repeats it itself)."};
   // the stored opacities came from a column that has been replaced since (upload A, opacity pass, upload B, a
   // compute_opacity = .false. pass): computing them again from column B is not what the caller asked for
-  if (stale_opr && r->upload_id != r->opr_upload_id) throw HipFail{REPLACED_MSG};
+  if (stale_opr && !r->holds.opr_from_resident_column()) throw HipFail{REPLACED_MSG};
   r->fused_fallbacks++;
   enqueue_radiate(r, resident_bufs(r), stale_sol || r->last_cs, true, false);
   return true;
@@ -1079,10 +1065,10 @@ void wait_error_words(Radtran *r) {
 void settle(Radtran *r) {
   settle_device_batch(r);
   for (int pass = 0; pass < 2; pass++) {
-    if (r->comm && !r->small_valid)   // the reduced status word (the rows themselves are fetched when they are read)
+    if (r->comm && !r->holds.rows_on_host)   // the reduced status word (the rows themselves are fetched when they are read)
       HIPCHK(hipMemcpyAsync(&r->comm_status, r->d_small.p + r->rows.status, sizeof(double), hipMemcpyDeviceToHost, r->stream));
     wait_error_words(r);
-    if (!r->column_loaded || !recover_fused_timeout(r)) break;
+    if (!r->holds.column || !recover_fused_timeout(r)) break;
   }
 }
 
@@ -1177,12 +1163,10 @@ void enqueue_batch(Radtran *r, const BatchRun &b, bool allow_fused) {
 }
 // What the handle holds after a batch is the LAST column's, like after n single calls: its level rows (enqueue_batch),
 // and its spectra / band optical depths -- the one-launch form left those in the batch arena (copied here); its optical
-// properties stay in the arena (opr_valid false: an IR-only call needs a compute_opacity call first).  One call per
+// properties stay in the arena (Holds::batch_left: an IR-only call needs a compute_opacity call first).  One call per
 // column works in the handle's own buffers; so does a repeat (settle_batch), which overwrites what is copied here.
 void batch_leaves_handle(Radtran *r, const BatchRun &b) {
-  r->column_loaded = false;   // d_col does not hold the last column: a resident call needs an upload first
-  r->column_has_particles = r->np > 0;
-  r->opr_valid = !b.one_launch;
+  r->holds.batch_left(b.one_launch, r->np);   // (d_col does not hold the last column: a resident call needs an upload first)
   if (!b.one_launch) return;
   const SpectraViews src = spectra_views(r, r->d_res_arena.p + (size_t)((b.n - 1) % b.CH) * spectra_views(r, nullptr).count);
   auto d2d = [&](DevBuf<double> &dst, const double *from) { HIPCHK(hipMemcpyAsync(dst.p, from, sizeof(double) * dst.n, hipMemcpyDeviceToDevice, r->stream)); };
@@ -1200,10 +1184,10 @@ bool settle_batch(Radtran *r, const BatchRun &b) {
     if (b.one_launch && !b.rows) fetch_batch_nsrc(r, b.n);   // (the host's pack_column returned them)
     enqueue_batch(r, b, false);
     wait_error_words(r);
-    r->opr_valid = true;   // one call per column works in the handle's own buffers: they hold the last column's
+    r->holds.batch_repeated();
   }
   r->checked_timeout = r->checked_id = r->call_id;
-  invalidate_small(r);   // (the device rows changed: fetch them)
+  r->holds.rows_changed();
   return *r->h_errflag >= b.first_call;
 }
 // What the handle still owes before anything else is enqueued or read: a resident call's integration that was kept
@@ -1258,7 +1242,7 @@ bool on_handle_device(const Radtran *r, const void *p) {
 
 void get2d(WrkObj *w, DevBuf<double> &buf, int dim1, int dim2, double *arr) {
   Radtran *r = w->parent;
-  if (!r->small_valid) settle(r);   // (valid rows: the call was synchronised and checked when they were fetched, nothing enqueued since)
+  if (!r->holds.rows_on_host) settle(r);   // (valid rows: the call was synchronised and checked when they were fetched, nothing enqueued since)
   size_t n = std::min((size_t)dim1 * dim2, buf.n);
   if (n) HIPCHK(hipMemcpy(arr, buf.p, n * sizeof(double), hipMemcpyDeviceToHost));
 }
@@ -1635,6 +1619,32 @@ void clima_test_plan_radiate(const int *in, int *out) {
   out[k++] = integrate_fits_one_launch(integrate_chunks(in[20])) ? 1 : 0;
   static_assert(CLIMA_PLAN_IN_N == 21 && CLIMA_PLAN_OUT_N == 2 + 3 * 5 + 4, "the orders documented in clima_radtran_hip.h");
 }
+void clima_test_handle_holds(const int *n, const int *events, int *out) {
+  Holds h;
+  const int shard_world = events[0], has_comm = events[1], op_lo = events[2], op_n = events[3];
+  for (int i = 0; i < *n; i++) {
+    const int *e = events + 4 + (size_t)i * CLIMA_HOLDS_EVENT_N;
+    switch (e[0]) {
+      case 0: h.uploaded(e[1] != 0); break;
+      case 1: h.opacities_written(e[1] != 0, e[2] != 0, e[3] != 0, e[4], e[5]); break;
+      case 2: h.w0_formed(); break;
+      case 3: h.rows_enqueued(e[1] != 0); break;
+      case 4: h.rows_changed(); break;
+      case 5: h.rows_fetched(); break;
+      case 6: h.batch_left(e[1] != 0, e[2]); break;
+      case 7: h.batch_repeated(); break;
+      case 8: h.results_dropped(); break;
+      default: out[0] = -1; return;
+    }
+  }
+  int k = 0;
+  out[k++] = h.column; out[k++] = h.column_particles; out[k++] = (int)h.uploads;
+  out[k++] = h.opr; out[k++] = h.w0_stored; out[k++] = (int)h.opr_upload; out[k++] = h.opr_lo; out[k++] = h.opr_n;
+  out[k++] = h.rows_on_host; out[k++] = h.rows_in_pinned;
+  for (int need : {NEED_COLUMN, NEED_OPACITIES, NEED_SPECTRUM}) out[k++] = refused(h, need, shard_world, has_comm != 0, op_lo, op_n) ? 1 : 0;
+  out[k++] = h.opr_from_resident_column();
+  static_assert(CLIMA_HOLDS_EVENT_N == 6 && CLIMA_HOLDS_OUT_N == 14, "the orders documented in clima_radtran_hip.h");
+}
 void clima_test_rebin_mode_for(const int *ng, const double *weights, const int *stream, int *mode) {
   std::vector<double> wbin(weights, weights + std::max(*ng, 0)), wbin_e, wxy;
   if (wbin.empty()) { *mode = -1; return; }
@@ -1797,11 +1807,10 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
   std::memset(r->h_small, 0, sizeof(double) * l.count);
   if (hipHostGetDevicePointer((void **)&r->h_small_dev, r->h_small, 0) != hipSuccess) { r->h_small_dev = nullptr; (void)hipGetLastError(); }
   r->h_errflag = reinterpret_cast<int *>(r->h_small + l.err_words);
-  r->f_total.assign(nz + 1, 0.0);
   HIPCHK(hipDeviceSynchronize());
   r->fields_dirty = true;
   compute_shard(r);
-  r->small_valid = true;
+  r->holds.rows_fetched();   // (zeros on both sides)
   r->state = 2;
   CATCH(err)
 }
@@ -1820,7 +1829,7 @@ void radtran_upload_column(void *ptr, const double *T_surface, const double *T, 
 void radtran_radiate_resident(void *ptr, const int *compute_solar, const int *compute_opacity, char *err) {
   clear_err(err);
   GUARD_BUILT(r, ptr, err);
-  if (!r->column_loaded) { set_err(err, "no column has been uploaded"); return; }
+  if (refuse(r, "radiate_resident", NEED_COLUMN, err)) return;
   TRY
   enqueue_radiate(r, resident_bufs(r), *compute_solar != 0, *compute_opacity != 0, true, /*defer=*/true);
   CATCH(err)
@@ -2098,8 +2107,7 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
   clear_err(err);
   GUARD_BUILT(r, ptr, err);
   if (*dim1_T != r->nz || *dim2_T != *ncol || *ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return; }
-  if (!r->opr_valid) { set_err(err, "radiate_ir_batch needs opacities: call radiate with compute_opacity first"); return; }
-  if (r->shard_world != 1 && !r->comm) { set_err(err, "radiate_ir_batch is not available on a bin-sharded handle"); return; }
+  if (refuse(r, "radiate_ir_batch", NEED_OPACITIES | NEED_SPECTRUM, err)) return;
   TRY
   // CLIMA_HIP_BATCH_TIMES=1: the call's host-side phases on stderr (a diagnostic: tools/gpu_ir_batch.py)
   static const bool times = [] { const char *e = getenv("CLIMA_HIP_BATCH_TIMES"); return e && e[0] == '1'; }();
@@ -2192,7 +2200,7 @@ static bool ir_jacobian_refused(const Radtran *r, const double *T_surface, const
     const double v = j < nz ? T[j] : *T_surface;
     if (!(std::isfinite(v) && v > 0.0)) { set_err(err, "ir_jacobian: temperatures must be finite and positive"); return true; }
   }
-  if (r->shard_world != 1 && !r->comm) { set_err(err, "ir_jacobian is not available on a bin-sharded handle"); return true; }
+  if (refuse(r, "ir_jacobian", NEED_SPECTRUM, err)) return true;
   // the response form's range (that of radtran_radiate_ir_batch's): no other solver stands behind it
   if (nz < 4 || nz > 512) { set_err(err, "ir_jacobian: the response form takes 4 <= nz <= 512 (nz = " + std::to_string(nz) + ")"); return true; }
   if ((long)r->ir_n * r->ng > 65535) {     // (k_green_unit / k_green_local: one (bin, g-point) pair per blockIdx.y)
@@ -2200,8 +2208,7 @@ static bool ir_jacobian_refused(const Radtran *r, const double *T_surface, const
     return true;
   }
   if (green_work_bytes(r, nl) > 16.0e9) { set_err(err, "ir_jacobian: the response form's work arrays would take more than 16 GB"); return true; }
-  if (!r->opr_valid) { set_err(err, "ir_jacobian needs opacities: call radiate with compute_opacity first"); return true; }
-  return false;
+  return refuse(r, "ir_jacobian", NEED_OPACITIES, err);   // (last: what the form cannot take is refused before any opacity is needed)
 }
 // The opacity-only part and the accumulation's arrays for the Jacobian's deviations: every level k, sorted
 // (dev_k[d] = d).  `extra`: further ints of the caller's, staged behind the lists; returns their place on the device.
@@ -2340,9 +2347,8 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
 
 // What every column batch refuses before anything else, with the texts of radtran_toa_fluxes_batch
 static bool batch_refused(Radtran *r, const int *ncol, const int *has_particles, char *err) {
-  if (r->state != 2) { set_err(err, "Radtran is not constructed"); return true; }
   if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return true; }
-  if (r->shard_world != 1) { set_err(err, "toa_fluxes_batch is not available on a bin-sharded handle"); return true; }
+  if (refuse(r, "toa_fluxes_batch", NEED_SPECTRUM, err, /*comm_counts=*/false)) return true;
   const int hp = has_particles ? *has_particles : 0;
   if (r->np > 0 && !hp) { set_err(err, "\"pdensities\" and \"radii\" are required arguments."); return true; }
   return false;
@@ -2412,7 +2418,7 @@ static void out_spectra(Radtran *r, const BatchRun &run, const SpectraAsk &ask) 
 static void toa_fluxes_batch_host(void *ptr, const int *ncol, const ColumnArrays &in, const int *has_particles, double *ISR,
                                   double *OLR, double *fluxes, const SpectraAsk *ask, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
+  GUARD_BUILT(r, ptr, err);
   if (batch_refused(r, ncol, has_particles, err)) return;
   if (ask && spectra_refused(r, *ask, err)) return;
   TRY
@@ -2468,7 +2474,7 @@ void radtran_toa_fluxes_batch_spectra(void *ptr, const int *ncol, const double *
 static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const ColumnArrays &in, const int *has_particles, double *d_ISR,
                                  double *d_OLR, double *d_fluxes, const SpectraAsk *ask, const void *producer_stream, char *err) {
   clear_err(err);
-  GUARD(r, ptr, err);
+  GUARD_BUILT(r, ptr, err);
   if (batch_refused(r, ncol, has_particles, err)) return;
   TRY
   const bool part = r->np > 0;
@@ -2603,8 +2609,7 @@ void radtran_radiate_wrapper(void *ptr, const double *T_surface, const int *dim_
   do_upload(r, ColumnArrays{T_surface, T, P, densities, dz, hp ? pdensities : nullptr, hp ? radii : nullptr});
   enqueue_radiate(r, resident_bufs(r, /*host_out=*/true), *compute_solar != 0, *compute_opacity != 0);
   fetch_small(r);
-  if (surface_device_error(r, err)) return;
-  fetch_f_total(r);
+  surface_device_error(r, err);
   CATCH(err)
 }
 
@@ -2665,7 +2670,7 @@ void clima_bench_resident_sync(void *ptr, const int *n, double *us, char *err) {
 void clima_bench_resident_graph(void *ptr, const int *n, const int *k, double *us, char *err) {
   clear_err(err);
   GUARD(r, ptr, err);
-  if (r->state != 2 || !r->column_loaded) { set_err(err, "no column has been uploaded"); return; }
+  if (refuse(r, "resident_graph", NEED_COLUMN, err)) return;   // (no column on a handle that is not constructed either)
   TRY
   const int one = 1;
   radtran_radiate_resident(ptr, &one, &one, err);     // steady state: buffers allocated, fields uploaded
@@ -2707,7 +2712,7 @@ void clima_bench_resident_graph(void *ptr, const int *n, const int *k, double *u
   }
   (void)hipGraphExecDestroy(exec);
   (void)hipGraphDestroy(graph);
-  invalidate_small(r); r->opr_valid = false;
+  r->holds.results_dropped();
   radtran_radiate_resident(ptr, &one, &one, err);     // leave the handle with a valid call
   if (err && err[0]) return;
   HIPCHK(hipStreamSynchronize(r->stream));
@@ -2725,8 +2730,8 @@ void radtran_apply_radiation_enhancement(void *ptr, const double *rad_enhancemen
     launch_scale(r->d_flux_n.p + l.sol_up, 2 * l.nl, *rad_enhancement, r->stream);
     // a bin-sharded handle keeps its PARTIAL solar rows for the IR-only steps that follow: they are scaled too
     if (r->shard_world > 1 && r->d_flux_part.p) launch_scale(r->d_flux_part.p + l.sol_up, 2 * l.nl, *rad_enhancement, r->stream);
-    invalidate_small(r);   // (the device rows changed: fetch them; f_total is formed from them there)
-    fetch_f_total(r);
+    r->holds.rows_changed();   // (f_total is formed from the scaled rows when they are fetched)
+    fetch_small(r);
   } catch (...) {
   }
 }
@@ -2912,7 +2917,7 @@ void radtran_finish_reduced(void *ptr, char *err) {
   TRY
   settle_device_batch(r);
   CATCH(err)
-  invalidate_small(r);   // (the device rows changed: fetch them)
+  r->holds.rows_changed();
 }
 
 void radtran_stream_get(void *ptr, void **stream) {
@@ -2945,53 +2950,54 @@ void radtran_kernel_time_get(void *ptr, const int *kernel_id, double *ms_total, 
   CATCH(err)
 }
 
+// Distinct nodes of a 1-D axis that the stencils of `vals` touch, and of a k-table's (P,T) grid that the last uploaded column's do
+static double distinct_nodes(const std::vector<double> &axis, const std::vector<double> &vals) {
+  std::set<int> s;
+  const double lo = *std::min_element(axis.begin(), axis.end()), hi = *std::max_element(axis.begin(), axis.end());
+  for (double v : vals) { const int i = host_bracket(axis, std::min(std::max(v, lo), hi)); s.insert(i); s.insert(i + 1); }
+  return (double)s.size();
+}
+static double distinct_pt_nodes(const Radtran *r, const KTabHost *k) {
+  std::set<std::pair<int, int>> s;
+  const double plo = *std::min_element(k->log10P.begin(), k->log10P.end()), phi = *std::max_element(k->log10P.begin(), k->log10P.end());
+  const double tlo = *std::min_element(k->temp.begin(), k->temp.end()), thi = *std::max_element(k->temp.begin(), k->temp.end());
+  for (int j = 0; j < r->nz; j++) {
+    const int iP = host_bracket(k->log10P, std::min(std::max(std::log10(r->last_P[j]), plo), phi));
+    const int iT = host_bracket(k->temp, std::min(std::max(r->last_T[j], tlo), thi));
+    for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) s.insert({iP + a, iT + b});
+  }
+  return (double)s.size();
+}
+
 void radtran_algorithmic_bytes(void *ptr, double *bytes_tables_distinct, double *bytes_in, double *bytes_out,
                                double *bytes_tables_full, char *err) {
   // B_alg = B_tab(distinct interpolation nodes touched by the column)
   // + B_in + B_out; intermediates (opr) get no credit.
   clear_err(err);
   GUARD(r, ptr, err);
-  if (r->state != 2 || !r->column_loaded) { set_err(err, "no column has been uploaded"); return; }
+  if (refuse(r, "algorithmic_bytes", NEED_COLUMN, err)) return;
   const int nz = r->nz;
   const double nw = r->nw;
   double distinct = 0.0, full = 0.0;
-  auto nodes1d = [&](const std::vector<double> &axis, const std::vector<double> &vals) {
-    std::set<int> s;
-    double lo = *std::min_element(axis.begin(), axis.end()), hi = *std::max_element(axis.begin(), axis.end());
-    for (double v : vals) { int i = host_bracket(axis, std::min(std::max(v, lo), hi)); s.insert(i); s.insert(i + 1); }
-    return (double)s.size();
-  };
-  std::vector<double> lp(nz);
-  for (int j = 0; j < nz; j++) lp[j] = std::log10(r->last_P[j]);
   for (auto *k : r->k) {
-    std::set<std::pair<int, int>> s;
-    double plo = *std::min_element(k->log10P.begin(), k->log10P.end()), phi = *std::max_element(k->log10P.begin(), k->log10P.end());
-    double tlo = *std::min_element(k->temp.begin(), k->temp.end()), thi = *std::max_element(k->temp.begin(), k->temp.end());
-    for (int j = 0; j < nz; j++) {
-      int iP = host_bracket(k->log10P, std::min(std::max(lp[j], plo), phi));
-      int iT = host_bracket(k->temp, std::min(std::max(r->last_T[j], tlo), thi));
-      for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) s.insert({iP + a, iT + b});
-    }
-    distinct += 8.0 * k->ng * nw * (double)s.size();
+    distinct += 8.0 * k->ng * nw * distinct_pt_nodes(r, k);
     full += 8.0 * k->ng * nw * k->nP * k->nT;
   }
   for (auto *v : {&r->cia, &r->pxs, &r->ray})
     for (auto *xs : *v) {
-      if (xs->dim) { distinct += 8.0 * nw * nodes1d(xs->temp, r->last_T); full += 8.0 * nw * xs->nT; }
+      if (xs->dim) { distinct += 8.0 * nw * distinct_nodes(xs->temp, r->last_T); full += 8.0 * nw * xs->nT; }
       else { distinct += 8.0 * nw; full += 8.0 * nw; }
     }
-  if (r->has_cont) { distinct += 2 * 8.0 * nw * nodes1d(r->cont_temp, r->last_T); full += 2 * 8.0 * nw * r->cont_nT; }
+  if (r->has_cont) { distinct += 2 * 8.0 * nw * distinct_nodes(r->cont_temp, r->last_T); full += 2 * 8.0 * nw * r->cont_nT; }
   for (auto *p : r->part) {
     if (!r->last_radii.empty()) {
       std::vector<double> rr(r->last_radii.begin() + (size_t)p->p_ind * nz, r->last_radii.begin() + (size_t)(p->p_ind + 1) * nz);
-      distinct += 3 * 8.0 * nw * nodes1d(p->radii, rr);
+      distinct += 3 * 8.0 * nw * distinct_nodes(p->radii, rr);
     }
     full += 3 * 8.0 * nw * p->nrad;
   }
-  const int nzen = (int)r->zenith_u.size();
-  *bytes_tables_distinct = distinct;
-  *bytes_tables_full = full;
-  *bytes_in = 8.0 * (nz * (3.0 + r->nsp + 2.0 * r->np) + 2.0 * nw + nzen * 2.0 + r->sol.nw);
+  *bytes_tables_distinct = distinct; *bytes_tables_full = full;
+  *bytes_in = 8.0 * (nz * (3.0 + r->nsp + 2.0 * r->np) + 2.0 * nw + (int)r->zenith_u.size() * 2.0 + r->sol.nw);
   *bytes_out = 8.0 * ((2.0 * (nz + 1) + nz) * r->ir.nw + (3.0 * (nz + 1) + nz) * r->sol.nw + 5.0 * (nz + 1));
 }
 
@@ -3000,34 +3006,15 @@ void radtran_algorithmic_bytes(void *ptr, double *bytes_tables_distinct, double 
 void radtran_algorithmic_nodes(void *ptr, double *n_pt, double *n_pt_full, double *n_t, double *n_t_full, char *err) {
   clear_err(err);
   GUARD(r, ptr, err);
-  if (r->state != 2 || !r->column_loaded) { set_err(err, "no column has been uploaded"); return; }
-  const int nz = r->nz;
-  std::vector<double> lp(nz);
-  for (int j = 0; j < nz; j++) lp[j] = std::log10(r->last_P[j]);
+  if (refuse(r, "algorithmic_nodes", NEED_COLUMN, err)) return;
   double spt = 0.0, sptf = 0.0;
-  for (auto *k : r->k) {
-    std::set<std::pair<int, int>> s;
-    const double plo = *std::min_element(k->log10P.begin(), k->log10P.end()), phi = *std::max_element(k->log10P.begin(), k->log10P.end());
-    const double tlo = *std::min_element(k->temp.begin(), k->temp.end()), thi = *std::max_element(k->temp.begin(), k->temp.end());
-    for (int j = 0; j < nz; j++) {
-      const int iP = host_bracket(k->log10P, std::min(std::max(lp[j], plo), phi));
-      const int iT = host_bracket(k->temp, std::min(std::max(r->last_T[j], tlo), thi));
-      for (int a = 0; a < 2; a++) for (int b = 0; b < 2; b++) s.insert({iP + a, iT + b});
-    }
-    spt += (double)s.size(); sptf += (double)k->nP * k->nT;
-  }
-  auto nodes1d = [&](const std::vector<double> &axis) {
-    std::set<int> s;
-    const double lo = *std::min_element(axis.begin(), axis.end()), hi = *std::max_element(axis.begin(), axis.end());
-    for (double v : r->last_T) { const int i = host_bracket(axis, std::min(std::max(v, lo), hi)); s.insert(i); s.insert(i + 1); }
-    return (double)s.size();
-  };
+  for (auto *k : r->k) { spt += distinct_pt_nodes(r, k); sptf += (double)k->nP * k->nT; }
   double st = 0.0, stf = 0.0;
   int n1 = 0;
   for (auto *v : {&r->cia, &r->pxs})
     for (auto *xs : *v)
-      if (xs->dim) { st += nodes1d(xs->temp); stf += xs->nT; n1++; }
-  if (r->has_cont) { st += 2 * nodes1d(r->cont_temp); stf += 2 * r->cont_nT; n1 += 2; }
+      if (xs->dim) { st += distinct_nodes(xs->temp, r->last_T); stf += xs->nT; n1++; }
+  if (r->has_cont) { st += 2 * distinct_nodes(r->cont_temp, r->last_T); stf += 2 * r->cont_nT; n1 += 2; }
   *n_pt = r->k.empty() ? 0.0 : spt / r->k.size();
   *n_pt_full = r->k.empty() ? 0.0 : sptf / r->k.size();
   *n_t = n1 ? st / n1 : 0.0;
@@ -3045,6 +3032,7 @@ extern "C" void clima_debug_stamps(void *ptr, long long *out) {
 void radtran_opr_get(void *ptr, double *tau, double *w0, double *g, double *tau_band, char *err) {
   clear_err(err);
   GUARD_BUILT(r, ptr, err);
+  if (refuse(r, "opr_get", NEED_OPACITIES, err)) return;
   TRY
   settle(r);       // (a repaired hand-off recomputes the optical properties)
   ensure_w0(r);
@@ -3433,7 +3421,7 @@ void radtran_spectra_get_all(void *ptr, const bool *do_solar, const int *nlev, c
   if (r->state != 2) throw HipFail{"radtran_spectra_get_all: the handle is not constructed"};
   if (*nlev != r->nz + 1 || *nw_ir != r->ir.nw || *nw_sol != r->sol.nw)
     throw HipFail{"radtran_spectra_get_all: array extents do not match the handle (nz+1, ir%nw, sol%nw)"};
-  if (!r->small_valid) settle(r);   // (after a synchronous call the results are final already)
+  if (!r->holds.rows_on_host) settle(r);   // (after a synchronous call the results are final already)
   struct Job { double *dst; DevBuf<double> *src; };
   Job jobs[7] = {{ir_fup_a, &r->wrk_ir.fup_a}, {ir_fdn_a, &r->wrk_ir.fdn_a}, {ir_tau_band, &r->wrk_ir.tau_band},
                  {sol_fup_a, &r->wrk_sol.fup_a}, {sol_fdn_a, &r->wrk_sol.fdn_a}, {sol_amean, &r->wrk_sol.amean},

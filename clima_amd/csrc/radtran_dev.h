@@ -486,6 +486,44 @@ void green_vector_form_set(int vector_form);   // test hook: the far accumulatio
 int green_far_waves(int ndev, int nl);   // per bin split
 int green_far_splits(int n_ir, int waves);
 
+// ---- what a handle holds between calls, stated once (host only, no HIP call: clima_test_handle_holds replays it without
+// a device).  The member functions are the transitions and the only writers of the fields; refused() alone says what
+// cannot run on what is held.  After a batch the handle holds what n single calls would have left, but for the column
+// and, after one launch per chunk, the optical properties (they stayed in the arena).  DESIGN.md section 4: the table ----
+struct Holds {
+  bool column = false, column_particles = false;   // the resident column (d_col): loaded, given with particles
+  long uploads = 0;                                // ... columns uploaded so far
+  bool opr = false, w0_stored = true;   // the handle's own optical-property block: valid; w0 stored, or still to be formed from scat (ensure_w0)
+  long opr_upload = 0;                  // ... the upload it was computed from
+  int opr_lo = 0, opr_n = 0;            // ... the opacity bins [opr_lo, opr_lo + opr_n) it was computed for
+  bool rows_on_host = false, rows_in_pinned = false;   // the level rows: h_small is current; the last integration stored them there itself
+
+  void uploaded(bool has_particles) { column = true; column_particles = has_particles; uploads++; }
+  void opacities_written(bool own_block, bool w0, bool from_resident, int lo, int n) {
+    if (!own_block) return;   // (a chunk of a one-launch batch wrote the arena's blocks)
+    opr = true; w0_stored = w0; opr_lo = lo; opr_n = n;
+    if (from_resident) opr_upload = uploads;
+  }
+  void w0_formed() { w0_stored = true; }
+  void rows_enqueued(bool in_pinned) { rows_on_host = false; rows_in_pinned = in_pinned; }
+  void rows_changed() { rows_on_host = rows_in_pinned = false; }   // on the device, behind the host's back: fetch them
+  void rows_fetched() { rows_on_host = true; }
+  void batch_left(bool one_launch, int np) { column = false; column_particles = np > 0; opr = !one_launch; }
+  void batch_repeated() { opr = true; }                     // one call per column: the handle's own block holds the last column's
+  void results_dropped() { rows_changed(); opr = false; }   // a graph replay: nothing on the handle is a call's result
+  bool opr_from_resident_column() const { return opr_upload == uploads; }
+};
+enum { NEED_COLUMN = 1, NEED_OPACITIES = 2, NEED_SPECTRUM = 4 };
+// What keeps a call with these needs from running on the shard's opacity bins [op_lo, op_lo + op_n) (null: nothing); a
+// text that begins with a blank follows the entry point's name.  Opacities: valid AND computed for the bins asked for.
+inline const char *refused(const Holds &h, int needs, int shard_world, bool has_comm, int op_lo, int op_n) {
+  if ((needs & NEED_COLUMN) && !h.column) return "no column has been uploaded";
+  if ((needs & NEED_OPACITIES) && !(h.opr && op_lo >= h.opr_lo && op_lo + op_n <= h.opr_lo + h.opr_n))
+    return " needs opacities: call radiate with compute_opacity first";
+  if ((needs & NEED_SPECTRUM) && shard_world != 1 && !has_comm) return " is not available on a bin-sharded handle";
+  return nullptr;
+}
+
 // ---- the launch plan of one radiate call: decided once by plan_radiate (kernels.hip, beside the kernels whose limits
 // it applies), executed by the launchers, which decide nothing ----
 struct PlanIn {

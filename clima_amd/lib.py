@@ -49,6 +49,7 @@ SIGNATURES = {
     "radtran_merged_integrations_get": [_vp, _ip, _ip],
     "clima_test_defer_allowed": [_ip, _ip, _ip, _ip, _ip, _ip, _ip],
     "clima_test_plan_radiate": [_ip, _ip],
+    "clima_test_handle_holds": [_ip, _ip, _ip],
     "clima_test_rebin_mode_for": [_ip, _dp, _ip, _ip],
     "radtran_ir_green_set": [_vp, _ip],
     "radtran_ir_green_get": [_vp, _ip, _ip],

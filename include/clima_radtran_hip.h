@@ -131,7 +131,10 @@ void radtran_synchronize(void *ptr, char *err);
  * the buffer a bin-sharded run all-reduces over RCCL. */
 void radtran_flux_device_ptr(void *ptr, void **dptr, int *count);
 /* restrict this handle to opacity bins of shard `rank` out of `world` (work-balanced
- * contiguous ranges; rank 0-based).  world=1 restores the full grid. */
+ * contiguous ranges; rank 0-based).  world=1 restores the full grid.  The stored optical properties stay what they
+ * were: a call on them (compute_opacity = 0, radtran_radiate_ir_batch, the Jacobians, radtran_opr_get) runs where they
+ * were computed for every bin of the new shard -- an unsharded pass, then a shard -- and otherwise refuses
+ * ("... needs opacities: call radiate with compute_opacity first"). */
 void radtran_set_bin_shard(void *ptr, const int *rank, const int *world, char *err);
 /* the ranges this handle owns: first opacity bin / count (0-based), then the channel-local
  * IR and solar sub-ranges */
@@ -392,6 +395,22 @@ void clima_test_defer_allowed(const int *switch_on, const int *shard_world, cons
 #define CLIMA_PLAN_IN_N 21
 #define CLIMA_PLAN_OUT_N 21
 void clima_test_plan_radiate(const int *in, int *out);
+/* test hook: the account of what a handle holds between calls (Holds, clima_amd/csrc/radtran_dev.h) replayed on a bare
+ * one; no handle, no device.  events: the question's shard_world, has_comm, op_lo, op_n (the opacity bins
+ * [op_lo, op_lo + op_n) a call would work on), then n transitions of CLIMA_HOLDS_EVENT_N ints each, a code and its
+ * arguments in order (the rest 0):
+ *   0 uploaded(has_particles)   1 opacities_written(own_block, w0_stored, from_resident, lo, n)   2 w0_formed
+ *   3 rows_enqueued(in_pinned)   4 rows_changed   5 rows_fetched   6 batch_left(one_launch, np)   7 batch_repeated
+ *   8 results_dropped            (another code: out[0] = -1)
+ * out[CLIMA_HOLDS_OUT_N]:
+ *    0 column loaded   1 given with particles   2 uploads so far
+ *    3 optical properties valid   4 w0 stored   5 the upload they were computed from   6, 7 their bins: first, count
+ *    8 level rows current on the host   9 the last integration stored them into the pinned block itself
+ *   10, 11, 12 a call that needs a column / opacities / the whole spectrum is refused (1) or not (0)
+ *   13 the optical properties are the resident column's (what a repair after an expired hand-off wait asks) */
+#define CLIMA_HOLDS_EVENT_N 6
+#define CLIMA_HOLDS_OUT_N 14
+void clima_test_handle_holds(const int *n, const int *events, int *out);
 /* test hook: the rebin form (0 window, 1 streaming, 2 streaming multi-edge) a handle takes for these ng g-point weights;
  * stream != 0: as under CLIMA_HIP_REBIN=stream */
 void clima_test_rebin_mode_for(const int *ng, const double *weights, const int *stream, int *mode);
@@ -473,7 +492,8 @@ void clima_test_ir_response(const int *nz, const int *ng, const double *tau, con
 void clima_test_green_far_form_set(const int *vector_form);
 
 /* OpticalPropertiesResult (clima_radtran_types.f90:242-247), for parity checks:
- * tau,w0 (nz,ngauss,nw) and g,tau_band (nz,nw), column-major, TOA-first. */
+ * tau,w0 (nz,ngauss,nw) and g,tau_band (nz,nw), column-major, TOA-first.  Refused ("opr_get needs opacities: ...")
+ * where the handle's own block holds none: a fresh handle, after a batch that ran one launch per chunk. */
 void radtran_opr_get(void *ptr, double *tau, double *w0, double *g, double *tau_band, char *err);
 
 /* ------------------------------------------------------------------------------------

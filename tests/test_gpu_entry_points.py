@@ -45,7 +45,10 @@ for bit); E5 holds the same batch to the oracle.
 
 What the rows found: radiate(compute_opacity=False) directly after a one-launch batch ran on the handle's own optical
 properties -- an earlier call's, or none -- where radiate_ir_batch and ir_jacobian refuse; it refuses now (every
-one-launch row, first h65)."""
+one-launch row, first h65).  The same class, found by reading once the handle's state was stated in one place (Holds,
+radtran_dev.h): opr() after a one-launch batch copied out an earlier call's optical properties (E3 holds it to the
+refusal, and on the other rows to the single call's arrays), and an IR-only call after a change of shard ran on bins
+the handle never computed (test_stored_opacities_cover_the_shard_asked_for)."""
 import numpy as np
 import pytest
 
@@ -282,7 +285,14 @@ def test_e3_host_batch(states, row):
     if row.one_launch:
         with pytest.raises(ClimaException, match="needs opacities"):
             r.radiate(*warm.args(), compute_solar=False, compute_opacity=False)
+        with pytest.raises(ClimaException, match="needs opacities"):     # (it copied out an earlier call's, or zeros)
+            r.opr()
     else:
+        # one call per column is bit for bit the single call: the optical properties the batch left are column 3's
+        single = s.handle()
+        single.radiate(*cols[3].args())
+        for got_a, want_a, name in zip(r.opr(), single.opr(), ("tau", "w0", "g", "tau_band")):
+            np.testing.assert_array_equal(got_a, want_a, err_msg="opr() after the batch of 4: " + name)
         o = s.oracle()
         o.radiate(*cols[3].args())
         _compare_once(r, o, warm, compute_solar=False, compute_opacity=False)
@@ -367,6 +377,36 @@ def test_e6_ir_on_stored_opacities(states, row):
             assert e <= TOL_IR_BATCH, (mode, c, e)
     r.ir_green = 1
     assert r.fused_fallbacks == 0
+
+
+def test_stored_opacities_cover_the_shard_asked_for(states):
+    """Row h65, no communicator.  One shard's opacity pass, then the other shard: the stored block holds none of the bins
+    an IR-only call would now work on, and the call refuses (it returned rows of bins nobody computed).  The legitimate
+    order stays: an unsharded pass covers every bin, so a shard taken afterwards runs its IR-only step, and its per-bin
+    fup_a on the shard's own bins is the unsharded handle's IR-only call's, bit for bit: measured so on an MI355X (the
+    planner picks the same stand-alone half-wave form for the shard's IR bins as for all five), and asserted."""
+    from clima_amd.radtran import ClimaException
+    row = LF.BY_NAME["h65"]
+    s, col = states(row), row.column()
+    warm = type(col)(col, T=np.asarray(col["T"]) + 2.0)
+    a = s.handle()
+    a.set_bin_shard(0, 2)
+    a.radiate(*col.args())
+    a.set_bin_shard(1, 2)
+    with pytest.raises(ClimaException, match="needs opacities"):
+        a.radiate(*warm.args(), compute_opacity=False)
+    shard, whole = s.handle(), s.handle()
+    for h in (shard, whole):
+        h.radiate(*col.args())
+    shard.set_bin_shard(0, 2)
+    ir_lo, ir_n = shard.bin_shard()[2:4]
+    assert 0 < ir_n < row.bins()[0]
+    for h in (shard, whole):
+        h.radiate(*warm.args(), compute_solar=False, compute_opacity=False)
+    got, want = (np.array(h.wrk_ir.fup_a)[:, ir_lo:ir_lo + ir_n] for h in (shard, whole))
+    print("h65      IR-only fup_a of shard (0, 2) against the unsharded call: %.2e  [%.0e]" % (_scaled(got, want), TOL_LEVEL))
+    np.testing.assert_array_equal(got, want)
+    assert shard.fused_fallbacks == 0 and whole.fused_fallbacks == 0
 
 
 # ------------------------------------------------------------------ E7

@@ -140,7 +140,7 @@ def test_split_after_a_column_batch(O, hip_lib, name, route, monkeypatch):
     """A batch that runs one call per column (at most 64 layers, other g-point counts) works in the handle's own buffers
     and `opr()` holds the last column's.  The one-launch form (8 g-points, more than 64 layers: the lane-per-item tile
     inside the fused grid, 64 columns per launch) leaves its optical properties in the batch arena BY DESIGN
-    (radtran_api.hip, `opr_valid`): of the last column the handle keeps the spectra and the band optical depths, which
+    (radtran_dev.h, `Holds::batch_left`): of the last column the handle keeps the spectra and the band optical depths, which
     are compared with the exact split's weighted mean; the split itself is then compared on the same batch with
     CLIMA_HIP_BATCH_ONE_LAUNCH=0 (read per call), and the tile's split inside the fused grid is
     test_split_in_every_launch_form's lanes-fused."""
