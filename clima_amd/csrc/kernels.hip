@@ -29,6 +29,8 @@
 //                      the four level rows it fetches anyway.
 //   k_pack_columns, k_batch_finish, k_batch_spectra   the ends of a column batch out of device memory (column blocks
 //                      in, f_total / ISR / OLR out) and the gather of the per-bin rows a batch is asked to return.
+//   k_pack_bounds      the per-column bounds blocks of a bounds batch out of device memory (albedo, emissivity, zenith
+//                      angles, photon scale factor: what twostream_p_body's BND instances and k_twostream read).
 //
 // All arithmetic is IEEE binary64.  No MFMA: there is no dense contraction on this path.
 #include "radtran_dev.h"
@@ -39,6 +41,19 @@
 #include <utility>
 
 namespace clima {
+
+// This file is compiled twice.  On its own it is what it was before the bounds batches: every kernel of the calls WITHOUT
+// per-column bounds, and nothing else, in one code object.  kernels_bounds.hip includes it with CLIMA_BOUNDS_TU defined
+// and gets the BND instances of k_fused, k_twostream_w, k_twostream_h and k_twostream with their three launchers (named
+// launch_*_bounds there: TU_LAUNCHER) and k_pack_bounds -- a code object of their own, which a process that runs no
+// bounds batch never loads.  What only the first compilation holds stands between #ifndef CLIMA_BOUNDS_TU and #endif.
+#ifdef CLIMA_BOUNDS_TU
+constexpr bool TU_BND = true;
+#define TU_LAUNCHER(name) name##_bounds
+#else
+constexpr bool TU_BND = false;
+#define TU_LAUNCHER(name) name
+#endif
 
 // hipFuncAttributeMaxDynamicSharedMemorySize = 160 KiB, once per (device, kernel).  false when the
 // runtime refuses it (the error stays in hipGetLastError for the caller to report).
@@ -459,11 +474,13 @@ __device__ __forceinline__ void prep_block(const PrepParams &p, const int bx, co
   }
 }
 
+#ifndef CLIMA_BOUNDS_TU
 __global__ __launch_bounds__(256) void k_prep(PrepParams p) { prep_block(p, blockIdx.x, blockIdx.y); }
 
 void launch_prep(const PrepParams &p, hipStream_t s) {
   hipLaunchKernelGGL(k_prep, dim3(1 + p.nslots + p.nabs + p.nzero * PREP_ZERO_BLOCKS, p.ncol > 0 ? p.ncol : 1), dim3(256), 0, s, p);
 }
+#endif
 
 // ------------------------------------------------------------------------------------
 // k_opacity
@@ -494,6 +511,9 @@ __device__ __forceinline__ double ld_opr(const double *p) {
 }
 
 #ifdef CLIMA_STAMPS
+#ifdef CLIMA_BOUNDS_TU
+static
+#endif
 __device__ long long *g_stamp_buf = nullptr;   // (two-stream blocks of the diagnostic build find the buffer here)
 #endif
 
@@ -1388,6 +1408,7 @@ __global__ __launch_bounds__(OP_THREADS, coop_min_waves(NG)) void k_opacity_coop
   }
 }
 
+#ifndef CLIMA_BOUNDS_TU
 template <int NG>
 static void launch_coop(const OpacityParams &p, hipStream_t s) {
   const long lanes = (long)p.nbins * p.nsrc * NG;
@@ -1417,6 +1438,7 @@ bool launch_opacity(const OpacityParams &p, const LaunchPlan &pl, hipStream_t s)
   }
   return true;
 }
+#endif
 
 // ------------------------------------------------------------------------------------
 // k_twostream
@@ -1586,7 +1608,7 @@ __device__ void dd_solve(const TsLds &s, const int nz, const int nc, const int S
   s.Bnd[(1 * S + j) * nc + c] = myDin;
 }
 
-template <int MAXT, int MINW>
+template <int MAXT, int MINW, bool BND = false>
 __global__ __launch_bounds__(MAXT, MINW) void k_twostream(TwoStreamParams p) {
   extern __shared__ __align__(16) double lds[];
   const int nz = p.nz, ng = p.ng, nc = p.ncols, S = p.nchunks;
@@ -1606,6 +1628,11 @@ __global__ __launch_bounds__(MAXT, MINW) void k_twostream(TwoStreamParams p) {
   const double *tauL = p.tau + ((size_t)l * ng + cg0) * nz;
   const double *w0L = p.w0 + ((size_t)l * ng + cg0) * nz;
   const double *gL = p.g + (size_t)l * nz;
+  // BND: a bounds batch's column (one call per column: p.albedo is its bounds block): its arrays in place of the handle's
+  const BoundsLayout bl = bounds_layout(p.bnd_nw_sol, p.bnd_nw_ir, p.nzen);
+  const double *const albedo = p.albedo, *const emissivity = BND ? p.albedo + bl.emissivity : p.emissivity;   // (bl.albedo == 0)
+  const double *const zen_u = BND ? p.albedo + bl.u : p.zen_u, *const zen_w = BND ? p.albedo + bl.w : p.zen_w,
+               *const zen_iu = BND ? p.albedo + bl.iu : p.zen_iu;
 
   // values each thread keeps for its pairs across the solve
   double kG[TS_MAXP], kx[TS_MAXP], kcpb[TS_MAXP], kcmb[TS_MAXP], kdir[TS_MAXP], kdiru[TS_MAXP];
@@ -1614,7 +1641,7 @@ __global__ __launch_bounds__(MAXT, MINW) void k_twostream(TwoStreamParams p) {
 
   if (solar) {
     // =========================== solar (two_stream_solar, twostream.f90:10-154) ======
-    Rsfc = p.albedo[ll];
+    Rsfc = albedo[ll];
     double ktau[TS_MAXP], kw0[TS_MAXP], kgt[TS_MAXP], klam[TS_MAXP];
     const double sqrt3 = 1.7320508075688772;  // sqrt(3.0_dp)
 #pragma unroll
@@ -1667,7 +1694,7 @@ __global__ __launch_bounds__(MAXT, MINW) void k_twostream(TwoStreamParams p) {
     // system matrix does not depend on u0, so sum_z w_z * solve(E_z) == solve(sum_z w_z E_z)
     // (radiate.f90:83-136 applies the same weights to the solved fluxes).
     double wsum = 0.0, dir0 = 0.0;
-    for (int z = 0; z < p.nzen; z++) { wsum = wsum + p.zen_w[z]; dir0 = dir0 + p.zen_w[z] * p.zen_u[z]; }
+    for (int z = 0; z < p.nzen; z++) { wsum = wsum + zen_w[z]; dir0 = dir0 + zen_w[z] * zen_u[z]; }
 #pragma unroll
     for (int k = 0; k < TS_MAXP; k++) {
       const int pr = tid + k * nt;
@@ -1678,7 +1705,7 @@ __global__ __launch_bounds__(MAXT, MINW) void k_twostream(TwoStreamParams p) {
         const double lam2 = klam[k] * klam[k];
         double CP0 = 0.0, CPB = 0.0, CM0 = 0.0, CMB = 0.0, DIR = 0.0, DIRU = 0.0;
         for (int z = 0; z < p.nzen; z++) {
-          const double u0 = p.zen_u[z], wz = p.zen_w[z], iu = p.zen_iu[z];
+          const double u0 = zen_u[z], wz = zen_w[z], iu = zen_iu[z];
           const double gam3 = (1.0 - sqrt3 * kgt[k] * u0) / 2.0;
           const double gam4 = 1.0 - gam3;
           const double facp = kw0[k] * ((gam1 - iu) * gam3 + gam4 * gam2);
@@ -1708,7 +1735,7 @@ __global__ __launch_bounds__(MAXT, MINW) void k_twostream(TwoStreamParams p) {
     }
   } else {
     // =========================== IR (two_stream_ir, twostream.f90:156-295) ===========
-    const double emis = p.emissivity[ll];
+    const double emis = emissivity[ll];
     Rsfc = p.has_hard_surface ? 1.0 - emis : 0.0;  // :186-190
     const double avg_freq = 0.5 * (p.freq[l] + p.freq[l + 1]);  // radiate.f90:64
     for (int n = tid; n < nz + 1; n += nt)                        // radiate.f90:65-69
@@ -1788,7 +1815,7 @@ __global__ __launch_bounds__(MAXT, MINW) void k_twostream(TwoStreamParams p) {
         if (solar) {
           Ssfc = Rsfc * kdir[k];  // :89 (zenith-weighted direct beam at the ground)
         } else if (p.has_hard_surface) {
-          Ssfc = p.emissivity[ll] * PI * s.Bp[nz];  // :237
+          Ssfc = emissivity[ll] * PI * s.Bp[nz];  // :237
         } else {  // :241-246
           const double tau = tauL[c * nz + i];
           const double b1_bot = (tau <= p.ir_tau_min) ? 0.0 : (s.Bp[nz] - s.Bp[nz - 1]) / tau;
@@ -1855,7 +1882,7 @@ __global__ __launch_bounds__(MAXT, MINW) void k_twostream(TwoStreamParams p) {
   //      their weighted partial sums into pre-zeroed outputs.
   const bool split = gridDim.y > 1;
   double scale = 1.0;
-  if (solar) scale = p.photons_sol[ll] * p.photon_scale_factor;  // clima_radtran.f90:302
+  if (solar) scale = p.photons_sol[ll] * (BND ? p.albedo[bl.scale] : p.photon_scale_factor);  // clima_radtran.f90:302
   for (int n = tid; n < nz + 1; n += nt) {
     double fu = 0.0, fd = 0.0, am = 0.0;
     for (int c = 0; c < nc; c++) {
@@ -1895,13 +1922,15 @@ struct ZeroParams {
   size_t count[6];
   int n;
 };
+#ifndef CLIMA_BOUNDS_TU
 __global__ __launch_bounds__(256) void k_zero(ZeroParams z) {
   double *p = z.ptr[blockIdx.y];
   const size_t n = z.count[blockIdx.y];
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0.0;
 }
+#endif
 
-static void ts_zero_outputs(const TwoStreamParams &p, hipStream_t s);
+void ts_zero_outputs(const TwoStreamParams &p, hipStream_t s);   // (below; the first compilation's)
 
 // LDS bytes for nc columns per block
 static size_t ts_lds_bytes(int nz, int nc, int S) {
@@ -1932,7 +1961,10 @@ static TsPlan plan_block(int nz, int ng) {
   return b;
 }
 
-bool launch_twostream(TwoStreamParams &p, const TsPlan &t, hipStream_t s) {
+bool TU_LAUNCHER(launch_twostream)(TwoStreamParams &p, const TsPlan &t, hipStream_t s) {
+#ifndef CLIMA_BOUNDS_TU
+  if (p.bounds) return launch_twostream_bounds(p, t, s);   // a bounds batch's column: the other code object's kernels
+#endif
   if (t.form != TS_BLOCK) return false;
   p.ncols = t.cols;
   p.nchunks = t.slots;
@@ -1943,11 +1975,11 @@ bool launch_twostream(TwoStreamParams &p, const TsPlan &t, hipStream_t s) {
   const dim3 g(grid, t.groups);
   if (t.zero_launch) ts_zero_outputs(p, s);
   if (t.threads <= 512) {
-    if (!ensure_max_lds((const void *)k_twostream<512, 4>)) return false;
-    hipLaunchKernelGGL((k_twostream<512, 4>), g, dim3(t.threads), t.lds, s, p);
+    if (!ensure_max_lds((const void *)k_twostream<512, 4, TU_BND>)) return false;
+    hipLaunchKernelGGL((k_twostream<512, 4, TU_BND>), g, dim3(t.threads), t.lds, s, p);
   } else {
-    if (!ensure_max_lds((const void *)k_twostream<1024, 4>)) return false;
-    hipLaunchKernelGGL((k_twostream<1024, 4>), g, dim3(t.threads), t.lds, s, p);
+    if (!ensure_max_lds((const void *)k_twostream<1024, 4, TU_BND>)) return false;
+    hipLaunchKernelGGL((k_twostream<1024, 4, TU_BND>), g, dim3(t.threads), t.lds, s, p);
   }
   return true;
 }
@@ -2100,11 +2132,14 @@ constexpr int TSW_COLS = 4;  // waves (g-point columns) per block
 // ------------------------------------------------------------------------------------
 // element offsets of a batch column (all 0 for a single call)
 struct TsOfs {
-  size_t opr, col, res;
+  size_t opr, col, res, bnd;
 };
+// a bounds block as the wave forms read it: its address is the same for the whole workgroup and nothing writes it while
+// the kernel runs, so the loads are scalar loads like those of the kernel-argument segment they stand in for
+typedef const __attribute__((address_space(4))) double *BoundsPtr;
 
 // PAIRED: every layer 2m+1 carries the optical properties of layer 2m bit for bit (AdiabatClimate's
-// doubled radiative grid, src/adiabat/clima_adiabat.f90:729-773: the host sets TwoStreamParams::paired
+// doubled radiative grid, src/adiabat/clima_adiabat.f90:729-773: the planner picks it
 // when pair_reuse marked every pair as exact).  The lanes' chunks are then cut at pair boundaries, a
 // pair's tau / w0 / g are loaded once, and everything that depends on them alone -- the gammas, lambda,
 // Gamma, exp(-lambda tau), and per zenith angle the attenuation factor and the source factors -- is
@@ -2115,10 +2150,14 @@ struct TsOfs {
 // lane (a block of 4 waves then covers all 8 g-points of a bin).  A column of 200 layers fills 200 of
 // 4 x 64 = 256 slots in the whole-wave form and 400 of 7 x 64 = 448 here, the chunk scans have one
 // step fewer and there are half as many of them -- about a fifth fewer instructions per column.
-template <int L, bool SOLAR, int NZMAX, bool COHERENT, bool RESK, bool PAIRED = false, bool HALF = false>
+//
+// BND: the column's albedo, emissivity, zenith angles and photon scale factor come from its bounds block (p.albedo +
+// co.bnd, bounds_layout; the launchers pick these instances where p.bounds is set) instead of the handle's fields in
+// the parameter block.
+template <int L, bool SOLAR, int NZMAX, bool COHERENT, bool RESK, bool PAIRED = false, bool HALF = false, bool BND = false>
 __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const int bin_local, double *lds,
                                                  const int gy, const int bz, const int tslot = -1,
-                                                 const TsOfs co = TsOfs{0, 0, 0}) {
+                                                 const TsOfs co = TsOfs{0, 0, 0, 0}) {
   static_assert(!PAIRED || (L % 2) == 0, "paired slots come in twos");
   static_assert(!(PAIRED && HALF), "no paired half-wave form");
   constexpr int W = HALF ? 32 : 64, WSH = HALF ? 5 : 6;   // lanes per column
@@ -2145,6 +2184,8 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
     else return planck_fcn(nu, T);
   };
   const int nz = p.nz, ng = p.ng, nl = nz + 1;
+  const BoundsLayout bl = bounds_layout(p.bnd_nw_sol, p.bnd_nw_ir, p.nzen);
+  const BoundsPtr bq = BND ? (BoundsPtr)(p.albedo + co.bnd) : nullptr;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & (W - 1);   // lane within the column's group
   const int wc = HALF ? (int)(threadIdx.x >> 5) : wave;               // column within the block
   const int ll = (solar ? p.sol_lo : p.ir_lo) + bin_local;
@@ -2282,7 +2323,7 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
     //      is evaluated at the chunk's top and carried down as a running product (:78-79).
     double wsum = 0.0, dir0 = 0.0;
     auto zen = [&](const int z) {
-      const double u0 = p.zen_u_v[z], wz = p.zen_w_v[z], iu = p.zen_iu_v[z];
+      const double u0 = BND ? bq[bl.u + z] : p.zen_u_v[z], wz = BND ? bq[bl.w + z] : p.zen_w_v[z], iu = BND ? bq[bl.iu + z] : p.zen_iu_v[z];
       wsum = wsum + wz;
       dir0 = dir0 + wz * u0;
       const double iu2 = iu * iu, wzu = wz * u0;
@@ -2318,7 +2359,7 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
         if (z < p.nzen) zen(z);
     }
     for (int z = NZMAX; z < p.nzen; z++) zen(z);
-    Rsfc = p.albedo[ll];
+    Rsfc = BND ? bq[bl.albedo + ll] : p.albedo[ll];
     Ssfc = Rsfc * dir[L - 1];  // :89 (used by the surface row only)
 #pragma unroll
     for (int t = 0; t < L; t++) {
@@ -2342,7 +2383,7 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
     lvl0_dn = dir0;   // direct(1) = u0 (:73)
     lvl0_am = wsum;   // direct(1)/u0 = 1
   } else {
-    Rsfc = p.has_hard_surface ? 1.0 - p.emissivity[ll] : 0.0;  // :186-190
+    Rsfc = p.has_hard_surface ? 1.0 - (BND ? bq[bl.emissivity + ll] : p.emissivity[ll]) : 0.0;  // :186-190
     const double avg_freq = 0.5 * (p.freq[l] + p.freq[l + 1]);  // radiate.f90:64
     // Planck source at the levels (radiate.f90:65-69): the same for the block's g-point columns, so
     // each of the nz+1 values is computed once per block instead of L+1 times per lane of every wave
@@ -2393,7 +2434,7 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
     {  // surface source (:236-247), used by the surface row only
       const double tau_in = tau_s[L - 1], bpl_top = bpl[L - 1], bpl_bot = bpl[L];
       if (p.has_hard_surface) {
-        Ssfc = p.emissivity[ll] * PI * bpl_bot;
+        Ssfc = (BND ? bq[bl.emissivity + ll] : p.emissivity[ll]) * PI * bpl_bot;
       } else {
         const double b1_bot = (tau_in <= p.ir_tau_min) ? 0.0 : (bpl_bot - bpl_top) / tau_in;
         Ssfc = PI * (bpl_bot + 0.5 * b1_bot);
@@ -2527,7 +2568,7 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
   asm volatile("" ::: "memory");
   double scale = 1.0, amf = 1.0, band_tau = 0.0;
   if (solar) {
-    scale = p.photons_sol[ll] * p.photon_scale_factor;  // clima_radtran.f90:302
+    scale = p.photons_sol[ll] * (BND ? bq[bl.scale] : p.photon_scale_factor);  // clima_radtran.f90:302
     amf = p.am_f1[ll];
   }
   const double amf2 = solar ? p.am_f2[ll] : 1.0, amdw = solar ? p.am_dw[ll] : 1.0;
@@ -2572,24 +2613,27 @@ __device__ __forceinline__ void twostream_p_body(const TwoStreamParams &p, const
 // blocks [n_sol, n_sol+n_ir) IR bins
 // LMAX = 8 would take 260 VGPRs (one wave per SIMD); capping it at 256 costs a few spills and buys
 // the second wave
-template <int LMAX>
+// BND: the launch of a bounds batch's column (twostream_p_body) -- kernels of their own, so that the kernels of every
+// call without bounds are what they were
+template <int LMAX, bool BND = false>
 __global__ __launch_bounds__(64 * TSW_COLS, LMAX > 4 ? 2 : 1) void k_twostream_w(TwoStreamParams p) {
   extern __shared__ __align__(16) double lds[];  // [TSW_COLS][nz+1][3] weighted level values, then the Planck table
-  if ((int)blockIdx.x < p.n_sol) twostream_p_body<LMAX, true, 0, false, false>(p, (int)blockIdx.x, lds, (int)blockIdx.y, (int)blockIdx.z);
-  else twostream_p_body<LMAX, false, 0, false, false>(p, (int)blockIdx.x - p.n_sol, lds, (int)blockIdx.y, (int)blockIdx.z);
+  if ((int)blockIdx.x < p.n_sol) twostream_p_body<LMAX, true, 0, false, false, false, false, BND>(p, (int)blockIdx.x, lds, (int)blockIdx.y, (int)blockIdx.z);
+  else twostream_p_body<LMAX, false, 0, false, false, false, false, BND>(p, (int)blockIdx.x - p.n_sol, lds, (int)blockIdx.y, (int)blockIdx.z);
 }
 
 // The half-wave form as a launch of its own (round 3): a wave solves two g-point columns, a block of 4 waves the 8
 // g-point columns of group blockIdx.y -- for k-distribution settings of 16, 24, 32 g-points (their calls take one
 // launch per kernel) at 65-224 layers: half as many blocks as the whole-wave kernel needs, each adding one addend per
 // level instead of two.  16 g-points: 98 -> ~55 us of two-stream launches per call.
-template <int L>
+template <int L, bool BND = false>
 __global__ __launch_bounds__(64 * TSW_COLS, 2) void k_twostream_h(TwoStreamParams p) {
   extern __shared__ __align__(16) double lds[];  // [2 TSW_COLS][nz+1][3] weighted level values, then the Planck table
-  if ((int)blockIdx.x < p.n_sol) twostream_p_body<L, true, 0, false, false, false, true>(p, (int)blockIdx.x, lds, (int)blockIdx.y, (int)blockIdx.z);
-  else twostream_p_body<L, false, 0, false, false, false, true>(p, (int)blockIdx.x - p.n_sol, lds, (int)blockIdx.y, (int)blockIdx.z);
+  if ((int)blockIdx.x < p.n_sol) twostream_p_body<L, true, 0, false, false, false, true, BND>(p, (int)blockIdx.x, lds, (int)blockIdx.y, (int)blockIdx.z);
+  else twostream_p_body<L, false, 0, false, false, false, true, BND>(p, (int)blockIdx.x - p.n_sol, lds, (int)blockIdx.y, (int)blockIdx.z);
 }
 
+#ifndef CLIMA_BOUNDS_TU
 int ts_clear_ranges(const TwoStreamParams &p, double *ptr[6], size_t count[6]) {
   const size_t nl = (size_t)p.nz + 1;
   int n = 0;
@@ -2604,12 +2648,13 @@ int ts_clear_ranges(const TwoStreamParams &p, double *ptr[6], size_t count[6]) {
   }
   return n;
 }
-static void ts_zero_outputs(const TwoStreamParams &p, hipStream_t s) {
+void ts_zero_outputs(const TwoStreamParams &p, hipStream_t s) {
   // partial sums over g-point groups accumulate into zeroed outputs: one launch
   ZeroParams z;
   z.n = ts_clear_ranges(p, z.ptr, z.count);
   if (z.n > 0) hipLaunchKernelGGL(k_zero, dim3(128, z.n), dim3(256), 0, s, z);
 }
+#endif
 
 // The wave-per-column launcher: the whole-wave kernel (4 g-point columns per block) or the half-wave one (8: for 8, 16,
 // 24, 32 g-points at 65-224 layers.  With 8 g-points a block holds its bin's whole g-point sum and stores it: nothing to
@@ -2618,14 +2663,18 @@ static void ts_zero_outputs(const TwoStreamParams &p, hipStream_t s) {
 // Up to two g-point groups go in one launch: two partial sums added into a zeroed output are order-independent.  More
 // groups run as one launch per group on the same stream, each adding a single addend, so results stay bitwise
 // reproducible.
-bool launch_twostream_w(TwoStreamParams &p, const TsPlan &t, hipStream_t s) {
+bool TU_LAUNCHER(launch_twostream_w)(TwoStreamParams &p, const TsPlan &t, hipStream_t s) {
+#ifndef CLIMA_BOUNDS_TU
+  if (p.bounds) return launch_twostream_w_bounds(p, t, s);
+#endif
   if (t.form != TS_WAVE && t.form != TS_HALF) return false;
   const int grid = p.n_sol + p.n_ir;
   if (grid <= 0) return true;
   using Kern = void (*)(TwoStreamParams);
-  static const Kern kh[5] = {k_twostream_h<3>, k_twostream_h<4>, k_twostream_h<5>, k_twostream_h<6>, k_twostream_h<7>};
-  static const Kern kw[8] = {k_twostream_w<1>, k_twostream_w<2>, k_twostream_w<3>, k_twostream_w<4>,
-                             k_twostream_w<5>, k_twostream_w<6>, k_twostream_w<7>, k_twostream_w<8>};
+  static const Kern kh[5] = {k_twostream_h<3, TU_BND>, k_twostream_h<4, TU_BND>, k_twostream_h<5, TU_BND>, k_twostream_h<6, TU_BND>,
+                             k_twostream_h<7, TU_BND>};
+  static const Kern kw[8] = {k_twostream_w<1, TU_BND>, k_twostream_w<2, TU_BND>, k_twostream_w<3, TU_BND>, k_twostream_w<4, TU_BND>,
+                             k_twostream_w<5, TU_BND>, k_twostream_w<6, TU_BND>, k_twostream_w<7, TU_BND>, k_twostream_w<8, TU_BND>};
   const Kern k = t.form == TS_HALF ? kh[t.slots - 3] : kw[t.slots - 1];
   if (t.lds > 48 * 1024 && !ensure_max_lds((const void *)k, 64 * 1024)) return false;  // (static LDS on top)
   if (t.zero_launch) ts_zero_outputs(p, s);
@@ -2637,6 +2686,7 @@ bool launch_twostream_w(TwoStreamParams &p, const TsPlan &t, hipStream_t s) {
   return true;
 }
 
+#ifndef CLIMA_BOUNDS_TU
 __global__ void k_test_wscan(const double *a, const double *b, double *out, int nwaves) {
   // out[0]: inclusive affine scan x_i = a_i + b_i x_{i-1}; out[1]: the same through build + apply;
   // out[2]: x shifted up by one lane; out[3]: reversed
@@ -2653,6 +2703,7 @@ __global__ void k_test_wscan(const double *a, const double *b, double *out, int 
 void launch_test_wscan(const double *a, const double *b, double *out, int nwaves, hipStream_t s) {
   hipLaunchKernelGGL(k_test_wscan, dim3(nwaves), dim3(64), 0, s, a, b, out, nwaves);
 }
+#endif
 
 // ------------------------------------------------------------------------------------
 // k_twostream_ir_batch: many temperature columns on ONE set of opacities (the RCE Jacobian's
@@ -2947,6 +2998,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_twostream_ir_batch(TwoStreamPara
 
 // false when the configuration is outside what the kernel covers: more than 8 layer slots per lane (nz > 512)
 // or an LDS image beyond 160 KiB.  force_nw (test hook): 4 selects the four-wave form for 1-4 slots too.
+#ifndef CLIMA_BOUNDS_TU
 bool launch_twostream_ir_batch(TwoStreamParams &p, int ncol, hipStream_t s, int force_nw) {
   const int lmax = std::max((p.nz + 63) / 64, p.force_slots);
   if (lmax > 8 || p.n_ir <= 0 || ncol <= 0 || p.ng < 1) return false;
@@ -2966,6 +3018,7 @@ bool launch_twostream_ir_batch(TwoStreamParams &p, int ncol, hipStream_t s, int 
   hipLaunchKernelGGL(k, grid, blk, lds, s, p, ncol, cpb);  // layer slots per lane = ceil(nz/64)
   return true;
 }
+#endif
 
 // ------------------------------------------------------------------------------------
 constexpr int FUSED_NZMAX = 8;
@@ -2992,7 +3045,8 @@ constexpr int FUSED_NZMAX = 8;
 // not disturb the allocation of the others.
 // HALF: the two-stream items are one block per bin, its waves solving two g-point columns each
 // (twostream_p_body's half-wave form) with LSEL = ceil(nz/32) slots per lane.
-template <int RM, bool CUSTOM, int LSEL, bool PAIRED = false, bool HALF = false>
+// BND: a bounds batch's launch (ts.bounds set), the two-stream items read their column's bounds block.
+template <int RM, bool CUSTOM, int LSEL, bool PAIRED = false, bool HALF = false, bool BND = false>
 __global__ __launch_bounds__(OP_THREADS, 2) void k_fused(OpacityParams op, TwoStreamParams ts, FusedParams fp) {
   extern __shared__ __align__(16) double lds[];
   const int per_col = fp.n_op + fp.n_ts;
@@ -3077,37 +3131,37 @@ __global__ __launch_bounds__(OP_THREADS, 2) void k_fused(OpacityParams op, TwoSt
 #else
   const int tslot = -1;
 #endif
-  const TsOfs co{(size_t)cb * fp.bs.opr, (size_t)cb * fp.bs.col, (size_t)cb * fp.bs.res};
+  const TsOfs co{(size_t)cb * fp.bs.opr, (size_t)cb * fp.bs.col, (size_t)cb * fp.bs.res, (size_t)cb * fp.bs.bnd};
   // The number of slots per lane follows the column height (65-128 layers: 2, up to 192: 3, up to
   // 256: 4; 5-8 in the LSEL kernels).  Columns of at most 64 layers are not fused at all
   // (plan_radiate): their opacity tiles do not fill the machine once, so there is no half-empty
   // second round to fill, and the stand-alone one-slot two-stream kernel runs at five waves per SIMD
   // instead of two.
   if constexpr (HALF) {
-    if (solar) twostream_p_body<LSEL, true, FUSED_NZMAX, true, false, false, true>(ts, bl, lds, gy, 0, tslot, co);
-    else twostream_p_body<LSEL, false, 0, true, false, false, true>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
+    if (solar) twostream_p_body<LSEL, true, FUSED_NZMAX, true, false, false, true, BND>(ts, bl, lds, gy, 0, tslot, co);
+    else twostream_p_body<LSEL, false, 0, true, false, false, true, BND>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
   } else if constexpr (LSEL == 0 && PAIRED) {
     if (fp.slots == 2) {
-      if (solar) twostream_p_body<2, true, FUSED_NZMAX, true, true, true>(ts, bl, lds, gy, 0, tslot, co);
-      else twostream_p_body<2, false, 0, true, true, true>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
+      if (solar) twostream_p_body<2, true, FUSED_NZMAX, true, true, true, false, BND>(ts, bl, lds, gy, 0, tslot, co);
+      else twostream_p_body<2, false, 0, true, true, true, false, BND>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
     } else {
-      if (solar) twostream_p_body<4, true, FUSED_NZMAX, true, true, true>(ts, bl, lds, gy, 0, tslot, co);
-      else twostream_p_body<4, false, 0, true, true, true>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
+      if (solar) twostream_p_body<4, true, FUSED_NZMAX, true, true, true, false, BND>(ts, bl, lds, gy, 0, tslot, co);
+      else twostream_p_body<4, false, 0, true, true, true, false, BND>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
     }
   } else if constexpr (LSEL == 0) {
     if (fp.slots == 2) {
-      if (solar) twostream_p_body<2, true, FUSED_NZMAX, true, true>(ts, bl, lds, gy, 0, tslot, co);
-      else twostream_p_body<2, false, 0, true, true>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
+      if (solar) twostream_p_body<2, true, FUSED_NZMAX, true, true, false, false, BND>(ts, bl, lds, gy, 0, tslot, co);
+      else twostream_p_body<2, false, 0, true, true, false, false, BND>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
     } else if (fp.slots == 3) {
-      if (solar) twostream_p_body<3, true, FUSED_NZMAX, true, true>(ts, bl, lds, gy, 0, tslot, co);
-      else twostream_p_body<3, false, 0, true, true>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
+      if (solar) twostream_p_body<3, true, FUSED_NZMAX, true, true, false, false, BND>(ts, bl, lds, gy, 0, tslot, co);
+      else twostream_p_body<3, false, 0, true, true, false, false, BND>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
     } else {
-      if (solar) twostream_p_body<4, true, FUSED_NZMAX, true, true>(ts, bl, lds, gy, 0, tslot, co);
-      else twostream_p_body<4, false, 0, true, true>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
+      if (solar) twostream_p_body<4, true, FUSED_NZMAX, true, true, false, false, BND>(ts, bl, lds, gy, 0, tslot, co);
+      else twostream_p_body<4, false, 0, true, true, false, false, BND>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
     }
   } else {
-    if (solar) twostream_p_body<LSEL, true, FUSED_NZMAX, true, false, PAIRED>(ts, bl, lds, gy, 0, tslot, co);
-    else twostream_p_body<LSEL, false, 0, true, false, PAIRED>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
+    if (solar) twostream_p_body<LSEL, true, FUSED_NZMAX, true, false, PAIRED, false, BND>(ts, bl, lds, gy, 0, tslot, co);
+    else twostream_p_body<LSEL, false, 0, true, false, PAIRED, false, BND>(ts, bl - ts.n_sol, lds, gy, 0, tslot, co);
   }
 #ifdef CLIMA_STAMPS
   __syncthreads();
@@ -3115,6 +3169,7 @@ __global__ __launch_bounds__(OP_THREADS, 2) void k_fused(OpacityParams op, TwoSt
 #endif
 }
 
+#ifndef CLIMA_BOUNDS_TU
 int fused_tiles(const OpacityParams &op) {
   return (int)(((long)op.nbins * op.nsrc + OP_THREADS - 1) / OP_THREADS);
 }
@@ -3197,23 +3252,31 @@ LaunchPlan plan_radiate(const PlanIn &in) {
   pl.ts.zero_launch = pl.ts.groups > 1 && !pl.prep_clears && !pl.caller_clears;
   return pl;
 }
+#endif
 
 using FusedKern = void (*)(OpacityParams, TwoStreamParams, FusedParams);
-static FusedKern fused_kernel(const TsPlan &f, int rebin_mode, bool cust_on) {
-  static const FusedKern kp[3] = {k_fused<0, false, 0, true>, k_fused<0, false, 6, true>, k_fused<0, false, 8, true>};   // slots 2 and 4, 6, 8
-  static const FusedKern kh[5] = {k_fused<0, false, 3, false, true>, k_fused<0, false, 4, false, true>, k_fused<0, false, 5, false, true>,
-                                  k_fused<0, false, 6, false, true>, k_fused<0, false, 7, false, true>};
-  static const FusedKern k04[2][3] = {{k_fused<0, false, 0>, k_fused<1, false, 0>, k_fused<2, false, 0>},
-                                      {k_fused<0, true, 0>, k_fused<1, true, 0>, k_fused<2, true, 0>}};
-  static const FusedKern k58[4] = {k_fused<0, false, 5>, k_fused<0, false, 6>, k_fused<0, false, 7>, k_fused<0, false, 8>};
+// the fused grid's kernels for one value of BND (this compilation's: TU_BND)
+template <bool BND>
+static FusedKern fused_kernel_of(const TsPlan &f, int rebin_mode, bool cust_on) {
+  static const FusedKern kp[3] = {k_fused<0, false, 0, true, false, BND>, k_fused<0, false, 6, true, false, BND>, k_fused<0, false, 8, true, false, BND>};   // slots 2 and 4, 6, 8
+  static const FusedKern kh[5] = {k_fused<0, false, 3, false, true, BND>, k_fused<0, false, 4, false, true, BND>, k_fused<0, false, 5, false, true, BND>,
+                                  k_fused<0, false, 6, false, true, BND>, k_fused<0, false, 7, false, true, BND>};
+  static const FusedKern k04[2][3] = {{k_fused<0, false, 0, false, false, BND>, k_fused<1, false, 0, false, false, BND>, k_fused<2, false, 0, false, false, BND>},
+                                      {k_fused<0, true, 0, false, false, BND>, k_fused<1, true, 0, false, false, BND>, k_fused<2, true, 0, false, false, BND>}};
+  static const FusedKern k58[4] = {k_fused<0, false, 5, false, false, BND>, k_fused<0, false, 6, false, false, BND>, k_fused<0, false, 7, false, false, BND>,
+                                   k_fused<0, false, 8, false, false, BND>};
   if (f.form == TS_HALF) return kh[f.slots - 3];
   if (f.form == TS_PAIRED) return kp[f.slots <= 4 ? 0 : f.slots == 6 ? 1 : 2];
   return f.slots <= 4 ? k04[cust_on ? 1 : 0][rebin_mode] : k58[f.slots - 5];
 }
+static FusedKern fused_kernel(const TsPlan &f, int rebin_mode, bool cust_on) { return fused_kernel_of<TU_BND>(f, rebin_mode, cust_on); }
 
 // fp.ncol, fp.bs, fp.call_id, fp.max_spins, fp.done, fp.timeout_flag come from the caller.
 // op.nsrc = source layers per column (nz for a batch, where the tile count is an upper bound).
-bool launch_fused(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, const TsPlan &f, hipStream_t s) {
+bool TU_LAUNCHER(launch_fused)(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, const TsPlan &f, hipStream_t s) {
+#ifndef CLIMA_BOUNDS_TU
+  if (ts.bounds) return launch_fused_bounds(op, ts, fp, f, s);
+#endif
   if (f.form == TS_NONE) return false;
   fp.n_op = fused_tiles(op);
   fp.n_ts = (ts.n_sol + ts.n_ir) * f.groups;
@@ -3233,6 +3296,7 @@ bool launch_fused(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, c
   return true;
 }
 
+#ifndef CLIMA_BOUNDS_TU
 bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta_nsrc, hipStream_t s, bool half, bool paired) {
   if (ts.ng != 8 || slots < 2 || slots > 8 || (ts.nz + 63) / 64 > slots || ts.nzen > MAX_ZEN) return false;
   if (half && (paired || slots < 3 || slots > 7 || (ts.nz + 31) / 32 > slots)) return false;
@@ -3684,5 +3748,16 @@ void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s) {
 }
 
 #include "ir_green.inc"
+#else
+// The bounds blocks of a batch out of device arrays: column blockIdx.y, one element per thread (bounds_element: the
+// host's pack_bounds takes the same values the same way, so the blocks are bit for bit the host's).
+__global__ __launch_bounds__(256) void k_pack_bounds(PackBoundsParams p) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, c = blockIdx.y;
+  if (i < p.l.count) p.blocks[c * p.l.count + i] = bounds_element(p.l, i, c, p.in, p.own, p.own_scale);
+}
+void launch_pack_bounds(const PackBoundsParams &p, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_bounds, dim3((unsigned)((p.l.count + 255) / 256), p.ncol), dim3(256), 0, s, p);
+}
+#endif
 
 }  // namespace clima

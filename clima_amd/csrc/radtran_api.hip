@@ -146,11 +146,15 @@ struct WrkObj {  // ClimaRadtranWrk, clima_radtran.f90:11-25
 // spec_level[0 .. nsel) (device, 0-based, ground-first) of every column's ir fup_a / ir fdn_a / sol fup_a / sol fdn_a
 // go to spec[k] (device, (nw, nsel, n); null: not wanted) -- the caller's arrays, or, with `rows`, slices of the
 // handle's staging buffer, whose spec_count doubles come back into spec_host beside the rows.
+// A bounds batch (radtran_toa_fluxes_batch_bounds): `bounds`, its n bounds blocks (bounds_layout) behind the column
+// blocks in d_cols_arena, where they stay for a repeat; null: every column under the handle's fields.
 struct BatchRun {
   int n = 0, first_call = 0, CH = 0;
   bool one_launch = false, pending = false;
   double *ISR = nullptr, *OLR = nullptr, *fluxes = nullptr;
   double *rows = nullptr;
+  const double *bounds = nullptr;
+  size_t bounds_count = 0;   // doubles per block, as laid out when the batch was enqueued (a repeat steps by the same)
   int nsel = 0;
   const int *spec_level = nullptr;
   double *spec[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -583,6 +587,7 @@ enum CallKind { CALL_RESIDENT, CALL_ARENA_COLUMN, CALL_ARENA_CHUNK };
 struct CallBufs {
   CallKind kind;
   double *col, *prep;      // column block, prep block
+  const double *bounds;    // a bounds batch: the bounds block of the (first) column; null: the handle's fields
   int nsrc;                // source layers of the column (a chunk: nz, the bound of its columns')
   bool all_pairs_exact;    // every layer is half of an exact pair (known of the resident column only)
   OprViews opr;
@@ -605,23 +610,28 @@ CallBufs resident_bufs(Radtran *r, bool host_out = false) {
   b.flux_n = r->d_flux_n.p; b.done = r->d_done.p;
   return b;
 }
-// column c of the arena (nsrc: what build_meta returned for it) on the handle's optical-property and spectra buffers
-CallBufs arena_column_bufs(Radtran *r, int c, int nsrc) {
+// the bounds blocks' layout on this handle
+BoundsLayout handle_bounds_layout(const Radtran *r) { return bounds_layout(r->sol.nw, r->ir.nw, (int)r->zenith_u.size()); }
+// column c of the arena (nsrc: what build_meta returned for it) on the handle's optical-property and spectra buffers;
+// bounds: the batch's bounds blocks, bounds_count doubles each (null: none)
+CallBufs arena_column_bufs(Radtran *r, int c, int nsrc, const double *bounds = nullptr, size_t bounds_count = 0) {
   CallBufs b = resident_bufs(r);
+  b.bounds = bounds ? bounds + (size_t)c * bounds_count : nullptr;
   b.kind = CALL_ARENA_COLUMN; b.nsrc = nsrc; b.all_pairs_exact = false;
   b.col = r->d_cols_arena.p + (size_t)c * r->col_layout.count;
   b.flux_n = r->d_flux_arena.p + c * r->rows.stride;
   return b;
 }
 // columns [c0, c0 + ncol) of the arena, their prep / opr / spectra blocks from the start of those arenas
-CallBufs arena_chunk_bufs(Radtran *r, int c0, int ncol) {
+CallBufs arena_chunk_bufs(Radtran *r, int c0, int ncol, const double *bounds = nullptr, size_t bounds_count = 0) {
   CallBufs b = resident_bufs(r);
+  b.bounds = bounds ? bounds + (size_t)c0 * bounds_count : nullptr;
   b.kind = CALL_ARENA_CHUNK; b.ncol = ncol; b.nsrc = r->nz; b.all_pairs_exact = false;
   b.col = r->d_cols_arena.p + (size_t)c0 * r->col_layout.count; b.prep = r->d_prep_arena.p;
   b.opr = opr_views(r, r->d_opr_arena.p); b.spec = spectra_views(r, r->d_res_arena.p);
   b.flux_n = r->d_flux_arena.p + c0 * r->rows.stride;
   b.bs = BatchStrides{r->col_layout.count, r->prep_count, b.opr.count, b.spec.count, r->rows.stride,
-                      (int)(((size_t)r->op_n * r->nz + 255) / 256)};
+                      (int)(((size_t)r->op_n * r->nz + 255) / 256), (int)bounds_count};
   return b;
 }
 
@@ -679,6 +689,15 @@ int pack_column(Radtran *r, double *h, const ColumnArrays &in) {
   return build_meta(r, a, reinterpret_cast<int *>(h + l.meta));
 }
 
+// The bounds blocks of n columns (bounds_layout) on the host: bounds_element of the caller's arrays and the handle's
+// fields, as k_pack_bounds takes them on the device
+void pack_bounds(const Radtran *r, int n, const BoundsArrays &in, double *blocks) {
+  const BoundsLayout l = handle_bounds_layout(r);
+  const BoundsArrays own{r->surface_albedo.data(), r->surface_emissivity.data(), r->zenith_u.data(), r->zenith_w.data(), nullptr};
+  for (size_t c = 0; c < (size_t)n; c++)
+    for (size_t i = 0; i < l.count; i++) blocks[c * l.count + i] = bounds_element(l, i, c, in, own, r->photon_scale_factor);
+}
+
 // f_total into the fifth row of a level-row block: THE place where a call's f_total is formed (a device batch's:
 // k_batch_finish)
 void f_total_row(double *h, const LevelRows &l) {
@@ -711,6 +730,7 @@ TwoStreamParams make_twostream_params(Radtran *r, const CallBufs &b, const Colum
   ts.albedo = r->d_albedo.p; ts.photons_sol = r->d_photons.p;
   ts.photon_scale_factor = r->photon_scale_factor; ts.diurnal_fac = r->diurnal_fac;
   ts.am_f1 = r->d_am_f1.p; ts.am_f2 = r->d_am_f2.p; ts.am_dw = r->d_am_dw.p;
+  if (b.bounds) { ts.bounds = 1; ts.albedo = b.bounds; ts.bnd_nw_sol = r->sol.nw; ts.bnd_nw_ir = r->ir.nw; }   // (TwoStreamParams::bounds)
   ts.ir_fup_a = b.spec.ir_fup_a; ts.ir_fdn_a = b.spec.ir_fdn_a; ts.ir_tau_band = b.spec.ir_tau_band;
   ts.sol_fup_a = b.spec.sol_fup_a; ts.sol_fdn_a = b.spec.sol_fdn_a; ts.sol_amean = b.spec.sol_amean;
   ts.sol_tau_band = b.spec.sol_tau_band;
@@ -1086,13 +1106,15 @@ void defer_err(Radtran *r, const std::string &msg) {
 
 // ---- column batches (radtran_toa_fluxes_batch, radtran_toa_fluxes_batch_device): one path, two sinks ----
 // An earlier batch's checks (and its repeat, which reads the arena this one overwrites), then room for n columns'
-// blocks and level rows (and their source-layer counts, where the device finds them)
-void begin_batch(Radtran *r, int n, bool nsrc_on_device) {
+// blocks and level rows (and their source-layer counts, where the device finds them); with_bounds: and for their bounds
+// blocks behind the column blocks (batch_bounds_base)
+void begin_batch(Radtran *r, int n, bool nsrc_on_device, bool with_bounds = false) {
   settle_device_batch(r);
-  r->d_cols_arena.reserve((size_t)n * r->col_layout.count);
+  r->d_cols_arena.reserve((size_t)n * (r->col_layout.count + (with_bounds ? handle_bounds_layout(r).count : 0)));
   r->d_flux_arena.reserve(n * r->rows.stride);
   if (nsrc_on_device) r->d_batch_nsrc.reserve(n);
 }
+double *batch_bounds_base(Radtran *r, int n) { return r->d_cols_arena.p + (size_t)n * r->col_layout.count; }
 // The launch form of a batch of n columns, decided here, once: one launch of each kernel per chunk of CH columns
 // (the fused grid takes the columns' work items in turn, so one column's two-stream tail runs beside the next
 // column's opacity tiles) where the fused form covers the configuration -- the per-column arenas of a chunk are
@@ -1141,13 +1163,13 @@ void enqueue_batch(Radtran *r, const BatchRun &b, bool allow_fused) {
   };
   if (b.one_launch && allow_fused) {
     for (int c0 = 0; c0 < n; c0 += b.CH) {
-      const CallBufs cb = arena_chunk_bufs(r, c0, std::min(b.CH, n - c0));
+      const CallBufs cb = arena_chunk_bufs(r, c0, std::min(b.CH, n - c0), b.bounds, b.bounds_count);
       enqueue_radiate(r, cb, true, true);
       gather(cb, c0, cb.ncol);
     }
   } else {
     for (int c = 0; c < n; c++) {
-      const CallBufs cb = arena_column_bufs(r, c, r->batch_nsrc[c]);
+      const CallBufs cb = arena_column_bufs(r, c, r->batch_nsrc[c], b.bounds, b.bounds_count);
       enqueue_radiate(r, cb, true, true, allow_fused);
       gather(cb, c, 1);
     }
@@ -1200,6 +1222,18 @@ void settle_pending_batch(Radtran *r) {
   if (!r->dev_batch.pending) return;
   r->dev_batch.pending = false;
   if (settle_batch(r, r->dev_batch)) defer_err(r, OPACITY_FAILED_MSG);
+}
+// the parameter block of k_pack_bounds: the bounds blocks of a batch built on the device (the handle's device copies of
+// its fields must be current: upload_fields)
+PackBoundsParams make_pack_bounds_params(Radtran *r, int n, const BoundsArrays &in, double *blocks) {
+  PackBoundsParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.ncol = n; p.l = handle_bounds_layout(r);
+  p.in = in;
+  p.own = BoundsArrays{r->d_albedo.p, r->d_emis.p, r->d_zen_u.p, r->d_zen_w.p, nullptr};
+  p.own_scale = r->photon_scale_factor;
+  p.blocks = blocks;
+  return p;
 }
 // the parameter block of k_pack_columns: the column blocks of a batch built on the device
 PackParams make_pack_params(Radtran *r, int n, const ColumnArrays &in, double *blocks, int *nsrc) {
@@ -2415,8 +2449,10 @@ static void out_spectra(Radtran *r, const BatchRun &run, const SpectraAsk &ask) 
 // T, P, dz (nz, ncol); densities (nz, nsp, ncol); pdensities, radii (nz, np, ncol).
 // Outputs: ISR, OLR (ncol); fluxes (nz+1, 5, ncol) = ir up, ir down, solar up, solar down, f_total,
 // or NULL.  The handle's own wrk / f_total hold the last column afterwards.
+// bnd: a bounds batch (radtran_toa_fluxes_batch_bounds) -- the columns' bounds blocks are built here beside the column
+// blocks and go up in the same copy.
 static void toa_fluxes_batch_host(void *ptr, const int *ncol, const ColumnArrays &in, const int *has_particles, double *ISR,
-                                  double *OLR, double *fluxes, const SpectraAsk *ask, char *err) {
+                                  double *OLR, double *fluxes, const SpectraAsk *ask, const BoundsArrays *bnd, char *err) {
   clear_err(err);
   GUARD_BUILT(r, ptr, err);
   if (batch_refused(r, ncol, has_particles, err)) return;
@@ -2425,13 +2461,15 @@ static void toa_fluxes_batch_host(void *ptr, const int *ncol, const ColumnArrays
   const int n = *ncol;
   const size_t cc = r->col_layout.count;
   const LevelRows &l = r->rows;
-  begin_batch(r, n, false);
-  std::vector<double> h((size_t)n * cc, 0.0), out(n * l.stride);
+  begin_batch(r, n, false, bnd != nullptr);
+  std::vector<double> h((size_t)n * (cc + (bnd ? handle_bounds_layout(r).count : 0)), 0.0), out(n * l.stride);
   r->batch_nsrc.resize(n);
   for (int c = 0; c < n; c++) r->batch_nsrc[c] = pack_column(r, h.data() + (size_t)c * cc, in.column(c, r->nz, r->nsp, r->np));
+  if (bnd) pack_bounds(r, n, *bnd, h.data() + (size_t)n * cc);
   HIPCHK(hipMemcpyAsync(r->d_cols_arena.p, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, r->stream));
   BatchRun run = batch_form(r, n);
   run.rows = out.data();
+  if (bnd) { run.bounds = batch_bounds_base(r, n); run.bounds_count = handle_bounds_layout(r).count; }
   if (ask) stage_spectra(r, run, *ask, true);
   enqueue_batch(r, run, true);
   batch_leaves_handle(r, run);
@@ -2449,7 +2487,7 @@ void radtran_toa_fluxes_batch(void *ptr, const int *ncol, const double *T_surfac
                               const double *densities, const double *dz, const int *has_particles,
                               const double *pdensities, const double *radii, double *ISR, double *OLR,
                               double *fluxes, char *err) {
-  toa_fluxes_batch_host(ptr, ncol, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii}, has_particles, ISR, OLR, fluxes, nullptr, err);
+  toa_fluxes_batch_host(ptr, ncol, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii}, has_particles, ISR, OLR, fluxes, nullptr, nullptr, err);
 }
 // ... and with the per-bin rows `spec_level` of every column: what a batch otherwise keeps of the last column only.
 // Copies of the values the batch's own integration sums (k_batch_spectra behind each chunk, enqueue_batch).
@@ -2459,7 +2497,21 @@ void radtran_toa_fluxes_batch_spectra(void *ptr, const int *ncol, const double *
                                       double *fluxes, const int *nsel, const int *spec_level, double *ir_fup,
                                       double *ir_fdn, double *sol_fup, double *sol_fdn, char *err) {
   const SpectraAsk ask{nsel ? *nsel : 0, spec_level, {ir_fup, ir_fdn, sol_fup, sol_fdn}};
-  toa_fluxes_batch_host(ptr, ncol, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii}, has_particles, ISR, OLR, fluxes, &ask, err);
+  toa_fluxes_batch_host(ptr, ncol, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii}, has_particles, ISR, OLR, fluxes, &ask, nullptr, err);
+}
+// ... and with per-column surface albedo, surface emissivity, zenith angles and photon scale factor (the header states
+// the contract): the spectra batch with five optional arrays; nsel = 0: no spectra
+void radtran_toa_fluxes_batch_bounds(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                                     const double *densities, const double *dz, const int *has_particles,
+                                     const double *pdensities, const double *radii, double *ISR, double *OLR,
+                                     double *fluxes, const double *surface_albedo, const double *surface_emissivity,
+                                     const double *zenith_u, const double *zenith_weights, const double *photon_scale_factor,
+                                     const int *nsel, const int *spec_level, double *ir_fup, double *ir_fdn,
+                                     double *sol_fup, double *sol_fdn, char *err) {
+  const SpectraAsk ask{nsel ? *nsel : 0, spec_level, {ir_fup, ir_fdn, sol_fup, sol_fdn}};
+  const BoundsArrays bnd{surface_albedo, surface_emissivity, zenith_u, zenith_weights, photon_scale_factor};
+  toa_fluxes_batch_host(ptr, ncol, ColumnArrays{T_surface, T, P, densities, dz, pdensities, radii}, has_particles, ISR, OLR, fluxes,
+                        ask.nsel != 0 ? &ask : nullptr, &bnd, err);
 }
 
 // The same batch with every array in device memory (the f64 tensors of a GPU-resident ensemble): the column blocks
@@ -2471,8 +2523,10 @@ void radtran_toa_fluxes_batch_spectra(void *ptr, const int *ncol, const double *
 // CLIMA_HIP_BATCH_ONE_LAUNCH=0): plan_radiate picks the opacity kernel and sizes the grids of such a call from the
 // column's own source-layer count, and the kernels it chooses between round differently, so the bound nsrc = nz
 // would not be the host batch's computation; the ncol counts (4 bytes each) are fetched in one copy first.
+// bnd: a bounds batch (radtran_toa_fluxes_batch_bounds_device) -- k_pack_bounds builds the columns' bounds blocks.
 static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const ColumnArrays &in, const int *has_particles, double *d_ISR,
-                                 double *d_OLR, double *d_fluxes, const SpectraAsk *ask, const void *producer_stream, char *err) {
+                                 double *d_OLR, double *d_fluxes, const SpectraAsk *ask, const BoundsArrays *bnd,
+                                 const void *producer_stream, char *err) {
   clear_err(err);
   GUARD_BUILT(r, ptr, err);
   if (batch_refused(r, ncol, has_particles, err)) return;
@@ -2482,7 +2536,10 @@ static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const ColumnArrays 
   const struct { const char *name; const void *p; int use; } args[] = {
       {"T_surface", in.T_surface, REQUIRED}, {"T", in.T, REQUIRED}, {"P", in.P, REQUIRED}, {"densities", in.dens, REQUIRED},
       {"dz", in.dz, REQUIRED}, {"pdensities", in.pdens, part ? REQUIRED : UNUSED}, {"radii", in.radii, part ? REQUIRED : UNUSED},
-      {"ISR", d_ISR, REQUIRED}, {"OLR", d_OLR, REQUIRED}, {"fluxes", d_fluxes, OPTIONAL}};
+      {"ISR", d_ISR, REQUIRED}, {"OLR", d_OLR, REQUIRED}, {"fluxes", d_fluxes, OPTIONAL},
+      {"surface_albedo", bnd ? bnd->albedo : nullptr, OPTIONAL}, {"surface_emissivity", bnd ? bnd->emissivity : nullptr, OPTIONAL},
+      {"zenith_u", bnd ? bnd->zenith_u : nullptr, OPTIONAL}, {"zenith_weights", bnd ? bnd->zenith_w : nullptr, OPTIONAL},
+      {"photon_scale_factor", bnd ? bnd->scale : nullptr, OPTIONAL}};
   for (const auto &a : args) {
     if (a.use == UNUSED || (a.use == OPTIONAL && !a.p)) continue;
     if (!a.p) { set_err(err, std::string("toa_fluxes_batch_device: \"") + a.name + "\" is a required argument"); return; }
@@ -2500,7 +2557,7 @@ static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const ColumnArrays 
       }
   }
   const int n = *ncol;
-  begin_batch(r, n, true);
+  begin_batch(r, n, true, bnd != nullptr);
   if (producer_stream) {
     if (!r->ev_producer) HIPCHK(hipEventCreateWithFlags(&r->ev_producer, hipEventDisableTiming));
     HIPCHK(hipEventRecord(r->ev_producer, reinterpret_cast<hipStream_t>(const_cast<void *>(producer_stream))));
@@ -2508,7 +2565,13 @@ static void toa_fluxes_batch_dev(void *ptr, const int *ncol, const ColumnArrays 
   }
   launch_pack_columns(make_pack_params(r, n, in, r->d_cols_arena.p, r->d_batch_nsrc.p), r->stream);
   HIPCHK(hipGetLastError());
+  if (bnd) {
+    upload_fields(r);   // (an array not given is filled from the handle's device copy of the field)
+    launch_pack_bounds(make_pack_bounds_params(r, n, *bnd, batch_bounds_base(r, n)), r->stream);
+    HIPCHK(hipGetLastError());
+  }
   BatchRun run = batch_form(r, n);
+  if (bnd) { run.bounds = batch_bounds_base(r, n); run.bounds_count = handle_bounds_layout(r).count; }
   run.ISR = d_ISR; run.OLR = d_OLR; run.fluxes = d_fluxes;
   if (ask) stage_spectra(r, run, *ask, false);
   if (!run.one_launch) fetch_batch_nsrc(r, n);
@@ -2524,7 +2587,7 @@ void radtran_toa_fluxes_batch_device(void *ptr, const int *ncol, const double *d
                                      double *d_ISR, double *d_OLR, double *d_fluxes, const void *producer_stream,
                                      char *err) {
   toa_fluxes_batch_dev(ptr, ncol, ColumnArrays{d_T_surface, d_T, d_P, d_densities, d_dz, d_pdensities, d_radii}, has_particles,
-                       d_ISR, d_OLR, d_fluxes, nullptr, producer_stream, err);
+                       d_ISR, d_OLR, d_fluxes, nullptr, nullptr, producer_stream, err);
 }
 // ... and with the per-bin rows (device arrays; spec_level is a HOST array, read before the call returns): final, and
 // after an expired hand-off wait refilled by the repeat, at the same radtran_synchronize as ISR / OLR / fluxes.
@@ -2536,7 +2599,21 @@ void radtran_toa_fluxes_batch_spectra_device(void *ptr, const int *ncol, const d
                                              double *d_sol_fdn, const void *producer_stream, char *err) {
   const SpectraAsk ask{nsel ? *nsel : 0, spec_level, {d_ir_fup, d_ir_fdn, d_sol_fup, d_sol_fdn}};
   toa_fluxes_batch_dev(ptr, ncol, ColumnArrays{d_T_surface, d_T, d_P, d_densities, d_dz, d_pdensities, d_radii}, has_particles,
-                       d_ISR, d_OLR, d_fluxes, &ask, producer_stream, err);
+                       d_ISR, d_OLR, d_fluxes, &ask, nullptr, producer_stream, err);
+}
+// ... and the bounds batch out of device arrays (the five bounds arrays device memory as well, or NULL)
+void radtran_toa_fluxes_batch_bounds_device(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
+                                            const double *d_P, const double *d_densities, const double *d_dz,
+                                            const int *has_particles, const double *d_pdensities, const double *d_radii,
+                                            double *d_ISR, double *d_OLR, double *d_fluxes, const double *d_surface_albedo,
+                                            const double *d_surface_emissivity, const double *d_zenith_u,
+                                            const double *d_zenith_weights, const double *d_photon_scale_factor,
+                                            const int *nsel, const int *spec_level, double *d_ir_fup, double *d_ir_fdn,
+                                            double *d_sol_fup, double *d_sol_fdn, const void *producer_stream, char *err) {
+  const SpectraAsk ask{nsel ? *nsel : 0, spec_level, {d_ir_fup, d_ir_fdn, d_sol_fup, d_sol_fdn}};
+  const BoundsArrays bnd{d_surface_albedo, d_surface_emissivity, d_zenith_u, d_zenith_weights, d_photon_scale_factor};
+  toa_fluxes_batch_dev(ptr, ncol, ColumnArrays{d_T_surface, d_T, d_P, d_densities, d_dz, d_pdensities, d_radii}, has_particles,
+                       d_ISR, d_OLR, d_fluxes, ask.nsel != 0 ? &ask : nullptr, &bnd, producer_stream, err);
 }
 
 /* test hooks: the column blocks of a batch (ncol * col_count doubles, host arrays as radtran_toa_fluxes_batch) as
@@ -2577,6 +2654,42 @@ void clima_test_pack_columns_host(void *ptr, const int *ncol, const double *T_su
   if (pack_hook_refused(r, ncol, has_particles, in, col_count, err) || !blocks) return;
   std::memset(blocks, 0, sizeof(double) * (size_t)*ncol * r->col_layout.count);
   for (size_t c = 0; c < (size_t)*ncol; c++) pack_column(r, blocks + c * r->col_layout.count, in.column(c, r->nz, r->nsp, r->np));
+}
+
+/* ... and the bounds blocks of a batch (ncol * block_count doubles, host arrays as radtran_toa_fluxes_batch_bounds, any
+ * of them NULL) as k_pack_bounds builds them on the device, and as the host's pack_bounds does */
+void clima_test_pack_bounds(void *ptr, const int *ncol, const double *surface_albedo, const double *surface_emissivity,
+                            const double *zenith_u, const double *zenith_weights, const double *photon_scale_factor,
+                            double *blocks, int *block_count, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  if (*ncol < 1) { set_err(err, "clima_test_pack_bounds: bad arguments"); return; }
+  const BoundsLayout l = handle_bounds_layout(r);
+  *block_count = (int)l.count;
+  if (!blocks) return;
+  TRY
+  const size_t n = *ncol, nzen = r->zenith_u.size();
+  DevBuf<double> al, em, zu, zw, sc, out;
+  auto up = [&](DevBuf<double> &d, const double *h, size_t count) { if (h) d.upload(std::vector<double>(h, h + count)); };
+  up(al, surface_albedo, n * r->sol.nw); up(em, surface_emissivity, n * r->ir.nw); up(zu, zenith_u, n * nzen);
+  up(zw, zenith_weights, n * nzen); up(sc, photon_scale_factor, n);
+  out.alloc(n * l.count);
+  settle_device_batch(r);
+  upload_fields(r);
+  launch_pack_bounds(make_pack_bounds_params(r, (int)n, BoundsArrays{al.p, em.p, zu.p, zw.p, sc.p}, out.p), r->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(blocks, out.p, sizeof(double) * out.n, hipMemcpyDeviceToHost, r->stream));
+  HIPCHK(hipStreamSynchronize(r->stream));
+  CATCH(err)
+}
+void clima_test_pack_bounds_host(void *ptr, const int *ncol, const double *surface_albedo, const double *surface_emissivity,
+                                 const double *zenith_u, const double *zenith_weights, const double *photon_scale_factor,
+                                 double *blocks, int *block_count, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  if (*ncol < 1) { set_err(err, "clima_test_pack_bounds: bad arguments"); return; }
+  *block_count = (int)handle_bounds_layout(r).count;
+  if (blocks) pack_bounds(r, *ncol, BoundsArrays{surface_albedo, surface_emissivity, zenith_u, zenith_weights, photon_scale_factor}, blocks);
 }
 
 void radtran_synchronize(void *ptr, char *err) {

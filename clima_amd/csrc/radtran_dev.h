@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 
 namespace clima {
 
@@ -115,6 +116,37 @@ __host__ __device__ inline ColumnLayout column_layout(int nz, int nsp, int np) {
   return l;
 }
 
+// Bounds block of one column of a batch (radtran_toa_fluxes_batch_bounds): [albedo | emissivity | u | w | 1/u | scale],
+// offsets in doubles: surface_albedo [nw_sol] and surface_emissivity [nw_ir] in the channels' own bin order, the zenith
+// cosines, their weights and the cosines' reciprocals [nzen] each, photon_scale_factor.  Built by the host beside the
+// column blocks (pack_bounds) or by k_pack_bounds; read by the two-stream kernels in place of the handle's fields.
+struct BoundsLayout { size_t albedo, emissivity, u, w, iu, scale, count; };
+__host__ __device__ inline BoundsLayout bounds_layout(int nw_sol, int nw_ir, int nzen) {
+  BoundsLayout l;
+  l.albedo = 0; l.emissivity = l.albedo + nw_sol; l.u = l.emissivity + nw_ir; l.w = l.u + nzen; l.iu = l.w + nzen;
+  l.scale = l.iu + nzen; l.count = l.scale + 1;
+  return l;
+}
+// ... and the five arrays a caller gives (column after column in each: albedo (nw_sol, ncol), emissivity (nw_ir, ncol),
+// zenith_u / zenith_w (nzen, ncol), scale (ncol)); a null array: every column takes the handle's value of that field.
+// Host or device pointers.
+struct BoundsArrays {
+  const double *albedo, *emissivity, *zenith_u, *zenith_w, *scale;
+  __host__ __device__ bool any() const { return albedo || emissivity || zenith_u || zenith_w || scale; }
+};
+// Element i of column c's block: the caller's value, or the handle's (`own`: its four arrays the same way, one column;
+// own_scale: its photon_scale_factor)
+__host__ __device__ inline double bounds_element(const BoundsLayout &l, size_t i, size_t c, const BoundsArrays &in, const BoundsArrays &own,
+                                                 double own_scale) {
+  const size_t nzen = l.w - l.u;
+  if (i < l.emissivity) return in.albedo ? in.albedo[c * l.emissivity + i] : own.albedo[i];
+  if (i < l.u) { const size_t k = i - l.emissivity, n = l.u - l.emissivity; return in.emissivity ? in.emissivity[c * n + k] : own.emissivity[k]; }
+  if (i < l.w) { const size_t k = i - l.u; return in.zenith_u ? in.zenith_u[c * nzen + k] : own.zenith_u[k]; }
+  if (i < l.iu) { const size_t k = i - l.w; return in.zenith_w ? in.zenith_w[c * nzen + k] : own.zenith_w[k]; }
+  if (i < l.scale) { const size_t k = i - l.iu; return 1.0 / (in.zenith_u ? in.zenith_u[c * nzen + k] : own.zenith_u[k]); }   // a correctly rounded division on both sides
+  return in.scale ? in.scale[c] : own_scale;
+}
+
 // A column as the callers hand it over (the ABI's order): T_surface a scalar, T / P / dz [nz], dens [nsp][nz], pdens /
 // radii [np][nz] -- of a batch, column after column in each array (T_surface [ncol]).  Host or device pointers.
 struct ColumnArrays {
@@ -205,10 +237,10 @@ inline bool integrate_fits_one_launch(int nchunk) { return integrate_lds_bytes(n
 // Element strides from one column of a batch to the next (0 everywhere for a single call).  Every
 // per-column array of a group lives in ONE block per column with the same internal layout, so a
 // group needs one stride: the column inputs, the prep results, the optical properties, the per-bin
-// spectra, the level fluxes, the hand-off flags.
+// spectra, the level fluxes, the bounds blocks (where the batch has them), the hand-off flags.
 struct BatchStrides {
   size_t col, prep, opr, res, flux;
-  int done;
+  int done, bnd;
 };
 
 struct ColumnDev {
@@ -286,6 +318,7 @@ struct TwoStreamParams {
   const double *tau, *w0, *g, *tau_band;   // opr
   const double *scat;                      // see OpacityParams
   int w0_from_scat;                        // the layers' w0 = min(MAX_W0, scat / tau) instead of the stored array
+  int bnd_nw_sol;                          // a bounds batch: the channels' bin counts (bounds_layout; bnd_nw_ir below)
   const double *wbin;
   const double *freq;                      // opacity grid [nw+1]
   // test hook (clima_test_two_stream): Planck values at the levels given directly [nz+1] TOA-first
@@ -293,18 +326,25 @@ struct TwoStreamParams {
   // launcher reads it, the other forms take theirs from the launch plan)
   const double *bplanck;
   int force_slots;
-  int paired;                              // unused (LaunchPlan::fused says when the paired form runs); keeps the argument layout
+  // A bounds batch's launch (radtran_toa_fluxes_batch_bounds): 1 when `albedo` below is the (first) column's bounds block
+  // (bounds_layout(bnd_nw_sol, bnd_nw_ir, nzen), whose first array is the albedo; column c of a chunk at + c *
+  // BatchStrides::bnd), read in place of albedo, emissivity, the zenith arrays and photon_scale_factor.  0: the
+  // handle's fields (every single call, the plain batches).  The block's address and these three ints sit in fields and
+  // alignment gaps the block already had: its size, and with it the place of the hidden arguments behind it, is what
+  // it was -- one more field changed how hipcc schedules the kernels of the calls WITHOUT bounds (the 8-slot ones began to spill).
+  int bounds;
   // IR
   const double *T, *T_surface;
   const double *emissivity;                // [nw_ir]
   int has_hard_surface;
+  int bnd_nw_ir;
   double ir_tau_min;
   // solar
   int nzen;
   const double *zen_u, *zen_w, *zen_iu;    // cos(zenith), weights, 1/cos (device arrays)
   // the same by value (kernarg segment -> scalar loads in the zenith loop); valid for nzen <= MAX_ZEN
   double zen_u_v[MAX_ZEN], zen_w_v[MAX_ZEN], zen_iu_v[MAX_ZEN];
-  const double *albedo;                    // [nw_sol]
+  const double *albedo;                    // [nw_sol]; bounds: the bounds block
   const double *photons_sol;               // [nw_sol], unscaled
   double photon_scale_factor, diurnal_fac;
   const double *am_f1, *am_f2, *am_dw;     // per solar bin amean unit factors (radiate.f90:174-178)
@@ -328,6 +368,12 @@ struct FusedParams {
   int sol_early;   // solar bins whose opacities the first round of opacity tiles produces (launcher)
   BatchStrides bs;
 };
+
+// (TwoStreamParams::bounds: the calls without bounds keep their kernels only while these hold)
+static_assert(sizeof(TwoStreamParams) == 720 && offsetof(TwoStreamParams, bounds) == 148 && offsetof(TwoStreamParams, bnd_nw_sol) == 116 &&
+              offsetof(TwoStreamParams, bnd_nw_ir) == 180 && offsetof(TwoStreamParams, albedo) == 608,
+              "TwoStreamParams has moved: the plain kernels' register allocation depends on its layout (see `bounds`)");
+static_assert(sizeof(BatchStrides) == 48 && offsetof(BatchStrides, bnd) == 44, "BatchStrides has grown: see TwoStreamParams::bounds");
 
 struct IntegrateParams {
   int ncol;                                // gridDim.z
@@ -397,7 +443,17 @@ struct BatchSpectraParams {
   double *dst[4];
   int nw[4];
 };
+// ... and k_pack_bounds the bounds blocks (bounds_layout) at blocks + c * its count: bounds_element of the caller's device
+// arrays and the handle's device copies of its fields
+struct PackBoundsParams {
+  int ncol;
+  BoundsLayout l;
+  BoundsArrays in, own;
+  double own_scale;
+  double *blocks;
+};
 void launch_pack_columns(const PackParams &p, hipStream_t s);
+void launch_pack_bounds(const PackBoundsParams &p, hipStream_t s);
 void launch_batch_finish(const BatchFinishParams &p, hipStream_t s);
 void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s);
 
@@ -578,6 +634,11 @@ bool launch_twostream_w(TwoStreamParams &p, const TsPlan &t, hipStream_t s);
 bool launch_twostream_ir_batch(TwoStreamParams &p, int ncol, hipStream_t s, int force_nw = 0);
 int fused_tiles(const OpacityParams &op);   // opacity tiles per column (size of a column's done[] slice)
 bool launch_fused(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, const TsPlan &f, hipStream_t s);
+// the same three launchers for a launch with bounds blocks (TwoStreamParams::bounds; kernels_bounds.hip): launch_fused,
+// launch_twostream_w and launch_twostream hand such a launch on to them
+bool launch_fused_bounds(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, const TsPlan &f, hipStream_t s);
+bool launch_twostream_w_bounds(TwoStreamParams &p, const TsPlan &t, hipStream_t s);
+bool launch_twostream_bounds(TwoStreamParams &p, const TsPlan &t, hipStream_t s);
 // test hook: the two-stream blocks of the fused grid alone (no opacity blocks), on opacities already in HBM
 // (meta_nsrc: a device int, any value >= 1)
 bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta_nsrc, hipStream_t s, bool half = false, bool paired = false);

@@ -85,6 +85,7 @@ module clima_radtran_hip
     procedure :: ir_jacobian_reduced => Radtran_ir_jacobian_reduced
     procedure :: TOA_fluxes_batch => Radtran_TOA_fluxes_batch
     procedure :: TOA_fluxes_batch_spectra => Radtran_TOA_fluxes_batch_spectra
+    procedure :: TOA_fluxes_batch_bounds => Radtran_TOA_fluxes_batch_bounds
     procedure :: opacities2yaml => Radtran_opacities2yaml
     procedure :: set_names => Radtran_set_names
     procedure :: set_custom_optical_properties => Radtran_set_custom_optical_properties
@@ -187,6 +188,18 @@ module clima_radtran_hip
       real(c_double), intent(in) :: T_surface(*), T(*), P(*), densities(*), dz(*), pdensities(*), radii(*)
       real(c_double), intent(out) :: ISR(*), OLR(*), fluxes(*)
       type(c_ptr), value :: ir_fup, ir_fdn, sol_fup, sol_fdn     ! (c_null_ptr: not wanted)
+      character(c_char), intent(out) :: err(*)
+    end subroutine
+    subroutine c_radtran_toa_fluxes_batch_bounds(ptr, ncol, T_surface, T, P, densities, dz, has_particles, pdensities, radii, &
+                                                 ISR, OLR, fluxes, surface_albedo, surface_emissivity, zenith_u, zenith_weights, &
+                                                 photon_scale_factor, nsel, spec_level, ir_fup, ir_fdn, sol_fup, sol_fdn, err) &
+                                                 bind(c, name="radtran_toa_fluxes_batch_bounds")
+      import; type(c_ptr), value :: ptr
+      integer(c_int), intent(in) :: ncol, has_particles, nsel
+      real(c_double), intent(in) :: T_surface(*), T(*), P(*), densities(*), dz(*), pdensities(*), radii(*)
+      real(c_double), intent(out) :: ISR(*), OLR(*), fluxes(*)
+      type(c_ptr), value :: surface_albedo, surface_emissivity, zenith_u, zenith_weights, photon_scale_factor   ! (c_null_ptr: the handle's)
+      type(c_ptr), value :: spec_level, ir_fup, ir_fdn, sol_fup, sol_fdn     ! (c_null_ptr: not wanted)
       character(c_char), intent(out) :: err(*)
     end subroutine
     subroutine c_radtran_radiate_ir_batch(ptr, ncol, T_surface, dim1_T, dim2_T, T, fup_n, fdn_n, f_total, err) &
@@ -854,6 +867,84 @@ contains
     call push_fields(self)
     call c_radtran_toa_fluxes_batch_spectra(self%handle, ncol, T_surface, T, P, densities, dz, merge(1, 0, self%np > 0), &
                                             pdensities, radii, ISR, OLR, fluxes, nsel, spec_level, sink(1), sink(2), sink(3), sink(4), err_c)
+    call take_err(err_c, err)
+    if (allocated(err)) return
+    call pull_results(self, .true.)
+  end subroutine
+
+  !> `TOA_fluxes_batch` with per-column surface, zenith and stellar scaling: column c is computed as if
+  !> `self%surface_albedo = surface_albedo(:,c)` (nw_sol, ncol), `self%surface_emissivity = surface_emissivity(:,c)`
+  !> (nw_ir, ncol), `self%zenith_u = zenith_u(:,c)`, `self%zenith_weights = zenith_weights(:,c)` (nzen, ncol) and
+  !> `self%photon_scale_factor = photon_scale_factor(c)` had been set before its own `TOA_fluxes`, bit for bit; an array
+  !> not present: every column under `self`'s field.  `self`'s fields are not changed.  `spec_level` with any of the
+  !> four spectrum arrays: as in `TOA_fluxes_batch_spectra`.
+  subroutine Radtran_TOA_fluxes_batch_bounds(self, T_surface, T, P, densities, dz, pdensities, radii, ISR, OLR, fluxes, err, &
+                                             surface_albedo, surface_emissivity, zenith_u, zenith_weights, photon_scale_factor, &
+                                             spec_level, ir_fup_a, ir_fdn_a, sol_fup_a, sol_fdn_a)
+    class(Radtran), intent(inout) :: self
+    real(dp), intent(in) :: T_surface(:), T(:,:), P(:,:), densities(:,:,:), dz(:,:)
+    real(dp), intent(in) :: pdensities(:,:,:), radii(:,:,:)
+    real(dp), intent(out) :: ISR(:), OLR(:), fluxes(:,:,:)
+    character(:), allocatable, intent(out) :: err
+    real(dp), intent(in), contiguous, optional, target :: surface_albedo(:,:), surface_emissivity(:,:), zenith_u(:,:), zenith_weights(:,:)
+    real(dp), intent(in), contiguous, optional, target :: photon_scale_factor(:)
+    integer(c_int), intent(in), contiguous, optional, target :: spec_level(:)
+    real(dp), intent(out), contiguous, optional, target :: ir_fup_a(:,:,:), ir_fdn_a(:,:,:), sol_fup_a(:,:,:), sol_fdn_a(:,:,:)
+    character(c_char) :: err_c(err_len+1)
+    type(c_ptr) :: bnd(5), sink(4), levels
+    integer :: ncol, nsel, nw_ir, nw_sol, nzen
+    ncol = size(T_surface); nsel = 0
+    nw_ir = size(self%ir%freq) - 1; nw_sol = size(self%sol%freq) - 1; nzen = size(self%zenith_u)
+    if (size(T,1) /= self%nz .or. size(T,2) /= ncol .or. any(shape(densities) /= [self%nz, self%ng, ncol]) .or. &
+        any(shape(fluxes) /= [self%nz+1, 5, ncol]) .or. size(ISR) /= ncol .or. size(OLR) /= ncol) then
+      err = '"T" has the wrong input dimension.'
+      return
+    endif
+    bnd = c_null_ptr; sink = c_null_ptr; levels = c_null_ptr
+    if (present(surface_albedo)) then
+      if (any(shape(surface_albedo) /= [nw_sol, ncol])) err = 'toa_fluxes_batch_bounds: "surface_albedo" has the wrong dimension'
+      bnd(1) = c_loc(surface_albedo)
+    endif
+    if (present(surface_emissivity)) then
+      if (any(shape(surface_emissivity) /= [nw_ir, ncol])) err = 'toa_fluxes_batch_bounds: "surface_emissivity" has the wrong dimension'
+      bnd(2) = c_loc(surface_emissivity)
+    endif
+    if (present(zenith_u)) then
+      if (any(shape(zenith_u) /= [nzen, ncol])) err = 'toa_fluxes_batch_bounds: "zenith_u" has the wrong dimension'
+      bnd(3) = c_loc(zenith_u)
+    endif
+    if (present(zenith_weights)) then
+      if (any(shape(zenith_weights) /= [nzen, ncol])) err = 'toa_fluxes_batch_bounds: "zenith_weights" has the wrong dimension'
+      bnd(4) = c_loc(zenith_weights)
+    endif
+    if (present(photon_scale_factor)) then
+      if (size(photon_scale_factor) /= ncol) err = 'toa_fluxes_batch_bounds: "photon_scale_factor" has the wrong dimension'
+      bnd(5) = c_loc(photon_scale_factor)
+    endif
+    if (present(spec_level)) then
+      nsel = size(spec_level); levels = c_loc(spec_level)
+      if (present(ir_fup_a)) then
+        if (any(shape(ir_fup_a) /= [nw_ir, nsel, ncol])) err = 'toa_fluxes_batch_bounds: "ir_fup_a" has the wrong dimension'
+        sink(1) = c_loc(ir_fup_a)
+      endif
+      if (present(ir_fdn_a)) then
+        if (any(shape(ir_fdn_a) /= [nw_ir, nsel, ncol])) err = 'toa_fluxes_batch_bounds: "ir_fdn_a" has the wrong dimension'
+        sink(2) = c_loc(ir_fdn_a)
+      endif
+      if (present(sol_fup_a)) then
+        if (any(shape(sol_fup_a) /= [nw_sol, nsel, ncol])) err = 'toa_fluxes_batch_bounds: "sol_fup_a" has the wrong dimension'
+        sink(3) = c_loc(sol_fup_a)
+      endif
+      if (present(sol_fdn_a)) then
+        if (any(shape(sol_fdn_a) /= [nw_sol, nsel, ncol])) err = 'toa_fluxes_batch_bounds: "sol_fdn_a" has the wrong dimension'
+        sink(4) = c_loc(sol_fdn_a)
+      endif
+    endif
+    if (allocated(err)) return
+    call push_fields(self)
+    call c_radtran_toa_fluxes_batch_bounds(self%handle, ncol, T_surface, T, P, densities, dz, merge(1, 0, self%np > 0), &
+                                           pdensities, radii, ISR, OLR, fluxes, bnd(1), bnd(2), bnd(3), bnd(4), bnd(5), nsel, levels, &
+                                           sink(1), sink(2), sink(3), sink(4), err_c)
     call take_err(err_c, err)
     if (allocated(err)) return
     call pull_results(self, .true.)

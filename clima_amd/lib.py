@@ -70,6 +70,12 @@ SIGNATURES = {
                                          _dp, _dp, _dp, _dp, _err],
     "radtran_toa_fluxes_batch_spectra_device": [_vp, _ip, _vp, _vp, _vp, _vp, _vp, _ip, _vp, _vp, _vp, _vp, _vp, _ip, _ip,
                                                 _vp, _vp, _vp, _vp, _vp, _err],   # device addresses; the level list is the host's
+    "radtran_toa_fluxes_batch_bounds": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                        _ip, _ip, _dp, _dp, _dp, _dp, _err],   # ... + albedo, emissivity, zenith_u, zenith_weights, scale
+    "radtran_toa_fluxes_batch_bounds_device": [_vp, _ip, _vp, _vp, _vp, _vp, _vp, _ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _ip, _ip, _vp, _vp, _vp, _vp, _vp, _err],   # device addresses; the level list is the host's
+    "clima_test_pack_bounds": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _err],
+    "clima_test_pack_bounds_host": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _err],
     "clima_test_pack_columns": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _err],
     "clima_test_pack_columns_host": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _err],
     "radtran_radiate_ir_batch": [_vp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _err],

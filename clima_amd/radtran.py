@@ -316,8 +316,42 @@ class Radtran:
         levels = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
         return levels, tuple(name for name in self.SPECTRA if name in spectra)
 
+    BOUNDS = ("surface_albedo", "surface_emissivity", "zenith_u", "zenith_weights", "photon_scale_factor")   # the ABI's order
+
+    def _bounds_request(self, bounds, n, dims, tensors=False):
+        """The five per-column arrays of a bounds batch in the ABI's order (None: not given) out of the dict `bounds`:
+        float64, C-contiguous, (n, nw_sol), (n, nw_ir), (n, nzen), (n, nzen), (n,) for dims = (nw_sol, nw_ir, nzen) --
+        numpy arrays, or with `tensors` torch tensors, which are taken as they are or refused.  Unknown keys and wrong
+        shapes are refused by name before anything is called."""
+        who = "toa_fluxes_batch_bounds_device" if tensors else "toa_fluxes_batch_bounds"
+        if not isinstance(bounds, dict):
+            raise ClimaException('%s: "bounds" is not a dict of %s' % (who, ", ".join(self.BOUNDS)))
+        for name in bounds:
+            if name not in self.BOUNDS:
+                raise ClimaException('%s: "%s" is not one of %s' % (who, name, ", ".join(self.BOUNDS)))
+        nw_sol, nw_ir, nzen = dims
+        shapes = dict(zip(self.BOUNDS, ((n, nw_sol), (n, nw_ir), (n, nzen), (n, nzen), (n,))))
+        out = []
+        for name in self.BOUNDS:
+            a = bounds.get(name)
+            if a is not None and tensors:
+                import torch
+                if not isinstance(a, torch.Tensor) or a.dtype != torch.float64:
+                    raise ClimaException('%s: "%s" is not a float64 torch tensor' % (who, name))
+                if not a.is_contiguous():
+                    raise ClimaException('%s: "%s" is not C-contiguous' % (who, name))
+            elif a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+            if a is not None and tuple(a.shape) != shapes[name]:
+                raise ClimaException('%s: "%s" has the shape %s, not %s' % (who, name, tuple(a.shape), shapes[name]))
+            out.append(a)
+        return out
+
+    def _bounds_dims(self):
+        return len(self.sol.freq) - 1, len(self.ir.freq) - 1, len(self.zenith_u)
+
     def TOA_fluxes_batch(self, columns, return_fluxes=False, spectra_levels=None,
-                         spectra=("ir_fup_a", "ir_fdn_a", "sol_fup_a", "sol_fdn_a")):
+                         spectra=("ir_fup_a", "ir_fdn_a", "sol_fup_a", "sol_fdn_a"), bounds=None):
         """Many independent columns (BASELINE config 4): `columns` is a sequence of column dicts /
         `synthetic.Column`s (T_surface, T, P, densities, dz[, pdensities, radii]).  Returns
         (ISR, OLR) arrays, plus the level fluxes (nz+1, 5, ncol) = ir up, ir down, solar up,
@@ -327,7 +361,12 @@ class Radtran:
         (0 the ground, -1 or nz the top of the atmosphere; any order, repeats allowed) whose per-bin rows are wanted
         of EVERY column.  The return value then gains a last element, a dict name -> array (nsel, nw_channel, ncol)
         for the names in `spectra`: `d["ir_fup_a"][:, :, c]` is `wrk_ir.fup_a[spectra_levels, :]` as the handle would
-        hold it after column c's own TOA_fluxes call, bit for bit."""
+        hold it after column c's own TOA_fluxes call, bit for bit.
+
+        `bounds` (radtran_toa_fluxes_batch_bounds): a dict with any of `surface_albedo` (ncol, nw_sol),
+        `surface_emissivity` (ncol, nw_ir), `zenith_u`, `zenith_weights` (ncol, nzen) and `photon_scale_factor` (ncol,):
+        column c is computed as if these had been set on the handle before its own TOA_fluxes call, bit for bit; a
+        field not given is the handle's for every column.  The handle's own fields are not changed."""
         n = len(columns)
         nz = self.nz
         Ts = np.array([float(c["T_surface"]) for c in columns])
@@ -352,20 +391,29 @@ class Radtran:
                 _d(np.ascontiguousarray(pd)), _d(np.ascontiguousarray(ra)), _d(isr), _d(olr),
                 _d(fl) if return_fluxes else None)
         out = (isr, olr, np.transpose(fl, (2, 1, 0))) if return_fluxes else (isr, olr)
+        bnd = None if bounds is None else self._bounds_request(bounds, n, self._bounds_dims())
         if spectra_levels is None:
-            self._L.radtran_toa_fluxes_batch(*args, self._err)
+            if bnd is None:
+                self._L.radtran_toa_fluxes_batch(*args, self._err)
+            else:
+                self._L.radtran_toa_fluxes_batch_bounds(*args, *[_d(a) if a is not None else None for a in bnd], _i(0), None,
+                                                        None, None, None, None, self._err)
             self._check()
             return out
         levels, names = self._spectra_request(spectra_levels, spectra)
         nw = {"ir": len(self.ir.freq) - 1, "sol": len(self.sol.freq) - 1}
         spec = {name: np.empty((n, len(levels), nw[name.split("_")[0]])) for name in names}
-        self._L.radtran_toa_fluxes_batch_spectra(*args, _i(len(levels)), levels.ctypes.data_as(C.POINTER(C.c_int)),
-                                                 *[_d(spec[name]) if name in spec else None for name in self.SPECTRA], self._err)
+        ask = (_i(len(levels)), levels.ctypes.data_as(C.POINTER(C.c_int)), *[_d(spec[name]) if name in spec else None for name in self.SPECTRA])
+        if bnd is None:
+            self._L.radtran_toa_fluxes_batch_spectra(*args, *ask, self._err)
+        else:
+            self._L.radtran_toa_fluxes_batch_bounds(*args, *[_d(a) if a is not None else None for a in bnd], *ask, self._err)
         self._check()
         return out + ({name: np.transpose(a, (1, 2, 0)) for name, a in spec.items()},)
 
     def TOA_fluxes_batch_tensors(self, T_surface, T, P, densities, dz, pdensities=None, radii=None, return_fluxes=False,
-                                 sync=True, spectra_levels=None, spectra=("ir_fup_a", "ir_fdn_a", "sol_fup_a", "sol_fdn_a")):
+                                 sync=True, spectra_levels=None, spectra=("ir_fup_a", "ir_fdn_a", "sol_fup_a", "sol_fdn_a"),
+                                 bounds=None):
         """`TOA_fluxes_batch` for columns that live in device memory (radtran_toa_fluxes_batch_device): torch CUDA
         float64 tensors, C-contiguous, T_surface (ncol,); T, P, dz (ncol, nz); densities (ncol, nsp, nz);
         pdensities / radii (ncol, np, nz).  Nothing passes through the host.  Returns fresh tensors on the same
@@ -381,7 +429,11 @@ class Radtran:
         `spectra_levels`, `spectra`: as in `TOA_fluxes_batch` (radtran_toa_fluxes_batch_spectra_device); the return
         value gains a last element, a dict name -> fresh tensor (ncol, nsel, nw_channel) on the same device, equal
         to the host form's arrays and final under the same rule: after `synchronize()`, which refills them too when
-        it repeats the batch."""
+        it repeats the batch.
+
+        `bounds`: as in `TOA_fluxes_batch`, the arrays torch CUDA float64 tensors of the same shapes
+        (radtran_toa_fluxes_batch_bounds_device); a repeat of the batch runs under the same bounds, so keep them alive
+        until `synchronize()` as well."""
         import torch
         nz, hp = self.nz, self.np > 0
         if hp and (pdensities is None or radii is None):
@@ -398,6 +450,7 @@ class Radtran:
                 raise ClimaException('"%s" has the wrong input dimension.' % name)
             if not t.is_contiguous():   # (no silent copy: the caller decides where a transposed view is materialised)
                 raise ClimaException('toa_fluxes_batch_device: "%s" is not C-contiguous' % name)
+        bnd = None if bounds is None else self._bounds_request(bounds, n, self._bounds_dims(), tensors=True)
         # (a tensor that is not on the handle's device is refused by the library, which names it)
         dev = next((t.device for _, t, _ in want if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
         isr, olr = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
@@ -420,11 +473,15 @@ class Radtran:
         args = (self._ptr, _i(n), addr(T_surface), addr(T), addr(P), addr(densities), addr(dz), _i(1 if hp else 0),
                 addr(pdensities) if hp else None, addr(radii) if hp else None, addr(isr), addr(olr), addr(fl))
         if spec is None:
+            ask = (_i(0), None, None, None, None, None)
+        else:
+            ask = (_i(len(levels)), levels.ctypes.data_as(C.POINTER(C.c_int)), *[addr(spec.get(name)) for name in self.SPECTRA])
+        if bnd is not None:
+            self._L.radtran_toa_fluxes_batch_bounds_device(*args, *[addr(a) for a in bnd], *ask, producer or None, self._err)
+        elif spec is None:
             self._L.radtran_toa_fluxes_batch_device(*args, producer or None, self._err)
         else:
-            self._L.radtran_toa_fluxes_batch_spectra_device(*args, _i(len(levels)), levels.ctypes.data_as(C.POINTER(C.c_int)),
-                                                            *[addr(spec.get(name)) for name in self.SPECTRA], producer or None,
-                                                            self._err)
+            self._L.radtran_toa_fluxes_batch_spectra_device(*args, *ask, producer or None, self._err)
         self._check()
         if sync:
             self.synchronize()

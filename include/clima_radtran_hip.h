@@ -224,6 +224,44 @@ void radtran_toa_fluxes_batch_spectra_device(void *ptr, const int *ncol, const d
                                              double *d_ISR, double *d_OLR, double *d_fluxes, const int *nsel,
                                              const int *spec_level, double *d_ir_fup, double *d_ir_fdn, double *d_sol_fup,
                                              double *d_sol_fdn, const void *producer_stream, char *err);
+/* The spectra batches with per-column surface, zenith and stellar scaling: five optional arrays, the column last --
+ * surface_albedo (nw_sol, ncol), surface_emissivity (nw_ir, ncol), the bins in the channel's own order
+ * (radtran_surface_albedo_get); zenith_u, zenith_weights (nzen, ncol), nzen the handle's; photon_scale_factor (ncol).
+ * A NULL array: every column takes the handle's current value of that field.  Column c is TOA_fluxes on that column
+ * after surface_albedo = surface_albedo(:, c), surface_emissivity, zenith_u, zenith_weights likewise and
+ * photon_scale_factor = photon_scale_factor(c) had been set on the handle, bit for bit; diurnal_fac, has_hard_surface
+ * and ir_tau_min are the handle's.  The values are used as given (the setters check nothing either).  The handle's own
+ * fields are NOT changed by the call and not marked changed -- a later single call runs under them.
+ * Afterwards the handle holds the last column's rows and spectra, and of the opacities what the plain batch leaves.
+ * nsel = 0 (spec_level and the four spectrum arrays then unread, NULL will do): no spectra, unlike the spectra batches.
+ * Device form: the five arrays are device memory as well; everything else is
+ * radtran_toa_fluxes_batch_spectra_device, the repeat after an expired hand-off wait under the same bounds included.
+ * Refused with nothing enqueued: what the plain batch refuses, with its texts; with nsel != 0 what the spectra batch
+ * refuses; in the device form a given array that is not device memory of the handle's device
+ * (`toa_fluxes_batch_device: "surface_albedo" is not device memory ...`). */
+void radtran_toa_fluxes_batch_bounds(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
+                                     const double *densities, const double *dz, const int *has_particles,
+                                     const double *pdensities, const double *radii, double *ISR, double *OLR,
+                                     double *fluxes, const double *surface_albedo, const double *surface_emissivity,
+                                     const double *zenith_u, const double *zenith_weights, const double *photon_scale_factor,
+                                     const int *nsel, const int *spec_level, double *ir_fup, double *ir_fdn,
+                                     double *sol_fup, double *sol_fdn, char *err);
+void radtran_toa_fluxes_batch_bounds_device(void *ptr, const int *ncol, const double *d_T_surface, const double *d_T,
+                                            const double *d_P, const double *d_densities, const double *d_dz,
+                                            const int *has_particles, const double *d_pdensities, const double *d_radii,
+                                            double *d_ISR, double *d_OLR, double *d_fluxes, const double *d_surface_albedo,
+                                            const double *d_surface_emissivity, const double *d_zenith_u,
+                                            const double *d_zenith_weights, const double *d_photon_scale_factor,
+                                            const int *nsel, const int *spec_level, double *d_ir_fup, double *d_ir_fdn,
+                                            double *d_sol_fup, double *d_sol_fdn, const void *producer_stream, char *err);
+/* test hooks: the bounds blocks (ncol * block_count doubles; blocks NULL: block_count alone) of a bounds batch given as
+ * host arrays (any of them NULL), built by the device batch's kernel and by the host batch's pack_bounds */
+void clima_test_pack_bounds(void *ptr, const int *ncol, const double *surface_albedo, const double *surface_emissivity,
+                            const double *zenith_u, const double *zenith_weights, const double *photon_scale_factor,
+                            double *blocks, int *block_count, char *err);
+void clima_test_pack_bounds_host(void *ptr, const int *ncol, const double *surface_albedo, const double *surface_emissivity,
+                                 const double *zenith_u, const double *zenith_weights, const double *photon_scale_factor,
+                                 double *blocks, int *block_count, char *err);
 /* test hooks: the column blocks (ncol * col_count doubles; blocks NULL: col_count alone) of a batch given as host
  * arrays, built by the device batch's kernel and by the host batch's pack_column */
 void clima_test_pack_columns(void *ptr, const int *ncol, const double *T_surface, const double *T, const double *P,
