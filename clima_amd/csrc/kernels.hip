@@ -22,6 +22,8 @@
 //   k_green_*          (ir_green.inc) the same batch as a response problem: columns that are one profile with a few
 //                      temperatures changed = F(profile) + unit responses x Planck differences; what depends on the
 //                      opacities alone once per (bin, g-point), two FMAs per (level, deviation, bin, g-point).
+//   k_twostream_sol_batch  (solar_batch.inc) many illumination cases (zenith angles, albedo, photon scale factor) on one
+//                      set of opacities: what the opacities alone decide once per (bin, g-point), the surface row per case.
 //   k_fused            the production grid of a compute_opacity call: the opacity tiles of k_opacity8 followed, in
 //                      the SAME launch, by the two-stream blocks of twostream_p_body, each waiting (bounded) for the
 //                      tiles of its bin -- write-through hand-off, no cache-wide fence.
@@ -3748,6 +3750,7 @@ void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s) {
 }
 
 #include "ir_green.inc"
+#include "solar_batch.inc"
 #else
 // The bounds blocks of a batch out of device arrays: column blockIdx.y, one element per thread (bounds_element: the
 // host's pack_bounds takes the same values the same way, so the blocks are bit for bit the host's).

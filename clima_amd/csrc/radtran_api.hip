@@ -206,6 +206,11 @@ struct Radtran {
   PinnedBuf<double> h_bout;        // the batch's three result arrays on their way to the caller's
   PinnedBuf<char> h_green;         // what the host hands the response form (base profile, deviation lists)
   DevBuf<int> d_green_idx;
+  // illumination cases on the stored opacities (radtran_radiate_solar_batch): the cases' inputs, the spectra of the cases
+  // in flight, a place for the per-case form's copy of the band optical depth
+  DevBuf<double> d_sb_in, d_sb_spec, d_sb_band;
+  bool solar_batch_shared = true;        // radtran_solar_batch_shared_set: 0 forces one full solve per case
+  long solar_batch_shared_batches = 0;   // batches that took k_twostream_sol_batch (radtran_solar_batch_shared_get)
   int ir_green_mode = 1;           // CLIMA_HIP_IR_GREEN: 0 never, 1 when enough columns are sparse deviations of one profile, 2 whenever any is
   long ir_green_batches = 0;       // batches that took the response form (radtran_ir_green_batches_get)
   DevBuf<double> d_col;  // one column block
@@ -1621,6 +1626,15 @@ void radtran_ir_green_get(void *ptr, int *mode, int *batches) {
   *mode = r ? r->ir_green_mode : 0;
   *batches = r ? (int)std::min<long>(r->ir_green_batches, 2147483647L) : 0;
 }
+void radtran_solar_batch_shared_set(void *ptr, const int *on) {
+  Radtran *r = as_rad(ptr);
+  if (r) r->solar_batch_shared = *on != 0;
+}
+void radtran_solar_batch_shared_get(void *ptr, int *on, int *batches) {
+  Radtran *r = as_rad(ptr);
+  *on = r && r->solar_batch_shared ? 1 : 0;
+  *batches = r ? (int)std::min<long>(r->solar_batch_shared_batches, 2147483647L) : 0;
+}
 void radtran_fused_fallbacks_get(void *ptr, int *count) {
   Radtran *r = as_rad(ptr);
   *count = r ? r->fused_fallbacks : 0;
@@ -2224,6 +2238,182 @@ void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surfac
   if (times)
     fprintf(stderr, "radiate_ir_batch: %d columns%s: plan + enqueue %.0f us, kernels done at %.0f, results with the caller at %.0f%s\n",
             n, green ? " (response form)" : "", t_enq, t_kern, t_d2h, direct ? " (its arrays page-locked)" : " (through the pinned block, six pieces)");
+  CATCH(err)
+}
+
+// Batched form of solar calls that differ in how the star lights ONE atmosphere: case c is `radiate(...,
+// compute_solar=.true., compute_opacity=.false.)` (clima_radtran.f90:291-316) on the stored optical properties after
+// zenith_u, zenith_weights, surface_albedo and photon_scale_factor had been set to the case's.  include/clima_radtran_hip.h
+// has the contract.  Two forms: k_twostream_sol_batch (solar_batch.inc: what the opacities alone decide once per (bin,
+// g-point) and block), or one full solve per case by the stand-alone two-stream kernels.
+static bool solar_batch_refused(Radtran *r, int n, int nzen, const double *zenith_u, const double *zenith_weights, const double *fup_n,
+                                const double *fdn_n, const double *f_total, int nsel, const int *spec_level, const double *const *spec,
+                                char *err) {
+  const std::string pre = "radiate_solar_batch: ";
+  if (refuse(r, "radiate_solar_batch", NEED_OPACITIES, err)) return true;
+  if (r->shard_world != 1 || r->comm) {
+    const std::string shard = r->shard_world != 1 ? "a bin shard of " + std::to_string(r->shard_world) : "";
+    set_err(err, pre + "needs the whole spectrum (" + shard + (r->comm ? (shard.empty() ? "a communicator" : ", a communicator") : "") + ")");
+    return true;
+  }
+  if (n < 1) { set_err(err, pre + "ncol must be at least 1 (ncol = " + std::to_string(n) + ")"); return true; }
+  if (nzen < 1 || nzen > MAX_ZEN) { set_err(err, pre + "nzen must lie in 1.." + std::to_string(MAX_ZEN) + " (nzen = " + std::to_string(nzen) + ")"); return true; }
+  if (!zenith_u) { set_err(err, pre + "\"zenith_u\" is a required argument"); return true; }
+  if (!zenith_weights) { set_err(err, pre + "\"zenith_weights\" is a required argument"); return true; }
+  if (!fup_n) { set_err(err, pre + "\"fup_n\" is a required argument"); return true; }
+  if (!fdn_n) { set_err(err, pre + "\"fdn_n\" is a required argument"); return true; }
+  // (what Holds records: no call has left level rows, or a graph replay dropped them)
+  if (f_total && !r->holds.rows) { set_err(err, pre + "\"f_total\" was asked for, but the handle holds no level rows"); return true; }
+  if (nsel < 0) { set_err(err, pre + "nsel must not be negative (nsel = " + std::to_string(nsel) + ")"); return true; }
+  if (nsel > 0) {
+    const int nl = r->nz + 1;
+    if (!spec_level) { set_err(err, pre + "\"spec_level\" is a required argument"); return true; }
+    for (int a = 0; a < nsel; a++) {
+      const int v = spec_level[a];
+      if (v < 1 || v > nl) {
+        set_err(err, pre + "spec_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
+        return true;
+      }
+    }
+    if (!spec[0] && !spec[1] && !spec[2]) { set_err(err, pre + "nsel = " + std::to_string(nsel) + ", but none of sol_fup, sol_fdn, sol_amean was given"); return true; }
+  }
+  return false;
+}
+
+void radtran_radiate_solar_batch(void *ptr, const int *ncol, const int *nzen_, const double *zenith_u, const double *zenith_weights,
+                                 const double *surface_albedo, const double *photon_scale_factor, double *fup_n, double *fdn_n,
+                                 double *f_total, const int *nsel_, const int *spec_level, double *sol_fup, double *sol_fdn,
+                                 double *sol_amean, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const int n = *ncol, nzen = *nzen_, nsel = *nsel_;
+  double *spec_out[3] = {sol_fup, sol_fdn, sol_amean};
+  if (solar_batch_refused(r, n, nzen, zenith_u, zenith_weights, fup_n, fdn_n, f_total, nsel, spec_level, spec_out, err)) return;
+  TRY
+  ready_stored_opacities(r);
+  const int nz = r->nz, nl = nz + 1, nw_sol = r->sol.nw;
+  const size_t spec = (size_t)nw_sol * nl, arr = (size_t)n * nl;
+  // the cases' inputs in one block: [zen (u0 | weight | 1/u0)[nzen]] per case, then the albedos and scale factors
+  const size_t o_alb = (size_t)n * 3 * nzen, o_scale = o_alb + (surface_albedo ? (size_t)n * nw_sol : 0), n_in = o_scale + n;
+  std::vector<double> h_in(n_in);
+  for (int c = 0; c < n; c++)
+    for (int z = 0; z < nzen; z++) {
+      const double u0 = zenith_u[(size_t)c * nzen + z];
+      double *q = h_in.data() + (size_t)c * 3 * nzen;
+      q[z] = u0; q[nzen + z] = zenith_weights[(size_t)c * nzen + z]; q[2 * nzen + z] = 1.0 / u0;
+    }
+  if (surface_albedo) std::memcpy(h_in.data() + o_alb, surface_albedo, sizeof(double) * (size_t)n * nw_sol);
+  for (int c = 0; c < n; c++) h_in[o_scale + c] = photon_scale_factor ? photon_scale_factor[c] : r->photon_scale_factor;
+  r->d_sb_in.reserve(n_in);
+  HIPCHK(hipMemcpyAsync(r->d_sb_in.p, h_in.data(), sizeof(double) * n_in, hipMemcpyHostToDevice, r->stream));
+  const double *d_alb = surface_albedo ? r->d_sb_in.p + o_alb : r->d_albedo.p;
+  const size_t alb_stride = surface_albedo ? (size_t)nw_sol : 0;
+  // cases per launch: bounds the three per-case spectra held in device memory (ir_batch_general's CH)
+  const int CH = std::min(n, 512);
+  const int nchunk = integrate_chunks(r->sol_n);
+  r->d_sb_spec.reserve(3 * spec * CH); r->d_bpartial.reserve((size_t)CH * 2 * nchunk * nl); r->d_bout.reserve(3 * arr);
+  double *d_fup = r->d_sb_spec.p, *d_fdn = d_fup + spec * CH, *d_am = d_fdn + spec * CH;
+  std::vector<int> lv0(nsel);
+  size_t spec_off[3], spec_total = 0;
+  if (nsel > 0) {
+    for (int a = 0; a < nsel; a++) lv0[a] = spec_level[a] - 1;
+    r->d_spec_level.reserve(nsel);
+    HIPCHK(hipMemcpyAsync(r->d_spec_level.p, lv0.data(), sizeof(int) * nsel, hipMemcpyHostToDevice, r->stream));
+    for (int k = 0; k < 3; k++) { spec_off[k] = spec_total; if (spec_out[k]) spec_total += (size_t)nw_sol * nsel * n; }
+    r->d_spec_stage.reserve(spec_total);
+  }
+  const CallBufs b = resident_bufs(r);
+  bool shared_ran = false;
+  for (int c0 = 0; c0 < n; c0 += CH) {
+    const int nc = std::min(CH, n - c0);
+    bool shared_ok = false;
+    if (r->solar_batch_shared && r->sol_n > 0) {
+      SolBatchParams sp;
+      std::memset(&sp, 0, sizeof(sp));
+      sp.nz = nz; sp.ng = r->ng; sp.n_sol = r->sol_n; sp.sol_lo = r->sol_lo; sp.sol_start = r->sol.ind_start;
+      sp.ncase = nc; sp.nzen = nzen;
+      sp.tau = b.opr.tau; sp.w0 = b.opr.w0; sp.g = b.opr.g; sp.wbin = r->d_wbin.p;
+      sp.zen = r->d_sb_in.p + (size_t)c0 * 3 * nzen; sp.albedo = d_alb + (size_t)c0 * alb_stride; sp.alb_stride = alb_stride;
+      sp.scale = r->d_sb_in.p + o_scale + c0;
+      sp.photons_sol = r->d_photons.p; sp.am_f1 = r->d_am_f1.p; sp.am_f2 = r->d_am_f2.p; sp.am_dw = r->d_am_dw.p;
+      sp.diurnal_fac = r->diurnal_fac;
+      sp.fup = d_fup; sp.fdn = d_fdn; sp.amean = d_am; sp.out_stride = spec;
+      shared_ok = launch_twostream_sol_batch(sp, r->stream);
+      HIPCHK(hipGetLastError());
+    }
+    if (shared_ok) shared_ran = true;
+    else {
+      // one full solve per case: the stand-alone kernels of the single call with the case's angles, albedo and scale
+      // in the handle's place (the copy of the band optical depth they write goes to a buffer nobody reads)
+      r->d_sb_band.reserve((size_t)nw_sol * nz);
+      TwoStreamParams ts = make_twostream_params(r, b, column_dev(r, b), true);
+      ts.n_ir = 0; ts.nzen = nzen; ts.sol_tau_band = r->d_sb_band.p;
+      PlanIn in = plan_input(r, b, true, false, false);
+      in.n_ir = 0; in.nzen = nzen;
+      const LaunchPlan plan = plan_radiate(in);
+      for (int ci = 0; ci < nc; ci++) {
+        const int c = c0 + ci;
+        TwoStreamParams tc = ts;
+        const double *q = r->d_sb_in.p + (size_t)c * 3 * nzen, *hq = h_in.data() + (size_t)c * 3 * nzen;
+        tc.zen_u = q; tc.zen_w = q + nzen; tc.zen_iu = q + 2 * nzen;
+        for (int z = 0; z < nzen; z++) { tc.zen_u_v[z] = hq[z]; tc.zen_w_v[z] = hq[nzen + z]; tc.zen_iu_v[z] = hq[2 * nzen + z]; }
+        tc.albedo = d_alb + (size_t)c * alb_stride;
+        tc.photon_scale_factor = h_in[o_scale + c];
+        tc.sol_fup_a = d_fup + spec * ci; tc.sol_fdn_a = d_fdn + spec * ci; tc.sol_amean = d_am + spec * ci;
+        if (plan.ts.zero_launch || plan.ts.groups > 1) {   // g-point groups add into cleared spectra
+          HIPCHK(hipMemsetAsync(tc.sol_fup_a, 0, sizeof(double) * spec, r->stream));
+          HIPCHK(hipMemsetAsync(tc.sol_fdn_a, 0, sizeof(double) * spec, r->stream));
+          HIPCHK(hipMemsetAsync(tc.sol_amean, 0, sizeof(double) * spec, r->stream));
+        }
+        TsPlan wp = plan.ts;
+        wp.zero_launch = false;
+        bool ok = launch_twostream_w(tc, wp, r->stream);
+        if (!ok) { HIPCHK(hipGetLastError()); ok = launch_twostream(tc, plan.block, r->stream); }
+        HIPCHK(hipGetLastError());
+        if (!ok) throw HipFail{"radiate_solar_batch: nz*ngauss = " + std::to_string(nz * r->ng) + " exceeds what the two-stream kernels can stage"};
+      }
+    }
+    // frequency integration of the cases' up and down spectra (radiate.f90:184-192), two deterministic stages per case
+    BatchIntegrateParams bp;
+    std::memset(&bp, 0, sizeof(bp));
+    bp.nz = nz; bp.ir_lo = r->sol_lo; bp.ir_n = r->sol_n; bp.nchunk = nchunk; bp.col0 = c0;
+    bp.fup_a = d_fup; bp.fdn_a = d_fdn; bp.spec_stride = spec;
+    bp.freq = r->sol.d_freq.p; bp.partial = r->d_bpartial.p; bp.flux_n = r->d_flux_n.p; bp.out = r->d_bout.p; bp.out_arr = arr;
+    launch_integrate_batch(bp, nc, r->stream);
+    HIPCHK(hipGetLastError());
+    if (nsel > 0) {
+      BatchSpectraParams q;
+      std::memset(&q, 0, sizeof(q));
+      q.ncol = nc; q.nsel = nsel; q.nl = nl; q.level = r->d_spec_level.p; q.src_stride = spec;
+      const double *src[3] = {d_fup, d_fdn, d_am};
+      for (int k = 0; k < 3; k++) {
+        q.src[k] = src[k]; q.nw[k] = nw_sol;
+        q.dst[k] = spec_out[k] ? r->d_spec_stage.p + spec_off[k] + (size_t)c0 * nw_sol * nsel : nullptr;
+      }
+      launch_batch_spectra(q, r->stream);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  if (shared_ran) r->solar_batch_shared_batches++;
+  if (nsel > 0) {
+    double *h = r->h_spec.reserve(spec_total);
+    HIPCHK(hipMemcpyAsync(h, r->d_spec_stage.p, sizeof(double) * spec_total, hipMemcpyDeviceToHost, r->stream));
+  }
+  double *outs[2] = {fup_n, fdn_n};
+  bout_to_host(r, outs, arr, 2);
+  HIPCHK(hipStreamSynchronize(r->stream));
+  if (nsel > 0)
+    for (int k = 0; k < 3; k++)
+      if (spec_out[k]) std::memcpy(spec_out[k], r->h_spec.p + spec_off[k], sizeof(double) * (size_t)nw_sol * nsel * n);
+  if (f_total) {
+    // (fdn_n - fup_n) of the case plus the IR rows the handle holds from its last IR call (clima_radtran.f90:287)
+    fetch_small(r);
+    const double *h = r->h_small;
+    const LevelRows &lr = r->rows;
+    for (int c = 0; c < n; c++)
+      for (int i = 0; i < nl; i++)
+        f_total[(size_t)c * nl + i] = f_total_level(h[lr.ir_up + i], h[lr.ir_dn + i], fup_n[(size_t)c * nl + i], fdn_n[(size_t)c * nl + i]);
+  }
   CATCH(err)
 }
 
@@ -3289,6 +3479,54 @@ void clima_test_two_stream(const int *nz_, const int *ng_, const int *form, cons
     for (int n = 0; n < nl; n++) dst[a][n] = out[(size_t)a * nl + (nz - n)];  // the kernels store ground-first (radiate.f90:140-154)
   CATCH(err)
 }
+
+// Test hook of k_twostream_sol_batch, the counterpart of clima_test_two_stream for it: one column's tau / w0 / g (nz,
+// TOA-first; the same for every one of the ng g-points, weights wbin) as one solar bin, `ncol` cases of nzen angles
+// (zen_u, zen_w (nzen, ncol)) and surface reflectance rsfc (ncol) through the production kernel with unit stellar flux
+// and unit factors.  force_nw = 4: blocks of four waves at every slot count.  Outputs (nz+1, ncol), TOA-first.
+void clima_test_solar_batch(const int *nz_, const int *ng_, const int *force_nw, const double *tau, const double *w0,
+                            const double *g, const double *wbin, const int *ncol, const int *nzen_, const double *zen_u,
+                            const double *zen_w, const double *rsfc, double *fup, double *fdn, double *amean, char *err) {
+  clear_err(err);
+  TRY
+  const int nz = *nz_, ng = *ng_, nl = nz + 1, n = *ncol, nzen = *nzen_;
+  if (nz < 1 || ng < 1 || ng > 32 || n < 1 || nzen < 1 || nzen > MAX_ZEN) throw HipFail{"clima_test_solar_batch: bad nz / ng / ncol / nzen"};
+  std::vector<double> h_tau((size_t)ng * nz), h_w0((size_t)ng * nz), h_zen((size_t)n * 3 * nzen);
+  for (int c = 0; c < ng; c++)
+    for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau[i]; h_w0[(size_t)c * nz + i] = w0[i]; }
+  for (int c = 0; c < n; c++)
+    for (int z = 0; z < nzen; z++) {
+      double *q = h_zen.data() + (size_t)c * 3 * nzen;
+      q[z] = zen_u[(size_t)c * nzen + z]; q[nzen + z] = zen_w[(size_t)c * nzen + z]; q[2 * nzen + z] = 1.0 / q[z];
+    }
+  DevBuf<double> d_tau, d_w0, d_g, d_wbin, d_zen, d_alb, d_ones, d_out;
+  d_tau.upload(h_tau); d_w0.upload(h_w0);
+  d_g.upload(std::vector<double>(g, g + nz));
+  d_wbin.upload(std::vector<double>(wbin, wbin + ng));
+  d_zen.upload(h_zen);
+  d_alb.upload(std::vector<double>(rsfc, rsfc + n));
+  d_ones.upload(std::vector<double>(std::max(n, 1), 1.0));
+  d_out.alloc((size_t)3 * n * nl); d_out.zero();
+  SolBatchParams sp;
+  std::memset(&sp, 0, sizeof(sp));
+  sp.nz = nz; sp.ng = ng; sp.n_sol = 1; sp.ncase = n; sp.nzen = nzen;
+  sp.tau = d_tau.p; sp.w0 = d_w0.p; sp.g = d_g.p; sp.wbin = d_wbin.p;
+  sp.zen = d_zen.p; sp.albedo = d_alb.p; sp.alb_stride = 1; sp.scale = d_ones.p;
+  sp.photons_sol = d_ones.p; sp.am_f1 = d_ones.p; sp.am_f2 = d_ones.p; sp.am_dw = d_ones.p; sp.diurnal_fac = 1.0;
+  sp.fup = d_out.p; sp.fdn = d_out.p + (size_t)n * nl; sp.amean = d_out.p + (size_t)2 * n * nl; sp.out_stride = nl;
+  const bool ok = launch_twostream_sol_batch(sp, nullptr, *force_nw);
+  HIPCHK(hipGetLastError());
+  if (!ok) throw HipFail{"clima_test_solar_batch: the kernel does not cover the requested shape"};
+  HIPCHK(hipDeviceSynchronize());
+  std::vector<double> out((size_t)3 * n * nl);
+  HIPCHK(hipMemcpy(out.data(), d_out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost));
+  double *dst[3] = {fup, fdn, amean};
+  for (int k = 0; k < 3; k++)
+    for (int c = 0; c < n; c++)
+      for (int i = 0; i < nl; i++) dst[k][(size_t)c * nl + i] = out[((size_t)k * n + c) * nl + (nz - i)];  // the kernel stores ground-first
+  CATCH(err)
+}
+void clima_test_solar_batch_cases_per_block(const int *ncol, int *cases) { *cases = solar_batch_cases_per_block(*ncol); }
 
 // Test hook of the response form (ir_green.inc), the counterpart of clima_test_two_stream for it: one column's tau / w0 /
 // g (the same for every g-point, weights wbin) and ndev deviations (level k TOA-first, k = nz the surface; change of the

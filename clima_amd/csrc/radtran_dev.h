@@ -553,6 +553,7 @@ struct Holds {
   long opr_upload = 0;                  // ... the upload it was computed from
   int opr_lo = 0, opr_n = 0;            // ... the opacity bins [opr_lo, opr_lo + opr_n) it was computed for
   bool rows_on_host = false, rows_in_pinned = false;   // the level rows: h_small is current; the last integration stored them there itself
+  bool rows = false;                                   // ... some call has left level rows on the handle at all
 
   void uploaded(bool has_particles) { column = true; column_particles = has_particles; uploads++; }
   void opacities_written(bool own_block, bool w0, bool from_resident, int lo, int n) {
@@ -561,12 +562,12 @@ struct Holds {
     if (from_resident) opr_upload = uploads;
   }
   void w0_formed() { w0_stored = true; }
-  void rows_enqueued(bool in_pinned) { rows_on_host = false; rows_in_pinned = in_pinned; }
-  void rows_changed() { rows_on_host = rows_in_pinned = false; }   // on the device, behind the host's back: fetch them
+  void rows_enqueued(bool in_pinned) { rows = true; rows_on_host = false; rows_in_pinned = in_pinned; }
+  void rows_changed() { rows = true; rows_on_host = rows_in_pinned = false; }   // on the device, behind the host's back: fetch them
   void rows_fetched() { rows_on_host = true; }
   void batch_left(bool one_launch, int np) { column = false; column_particles = np > 0; opr = !one_launch; }
   void batch_repeated() { opr = true; }                     // one call per column: the handle's own block holds the last column's
-  void results_dropped() { rows_changed(); opr = false; }   // a graph replay: nothing on the handle is a call's result
+  void results_dropped() { rows_changed(); rows = false; opr = false; }   // a graph replay: nothing on the handle is a call's result
   bool opr_from_resident_column() const { return opr_upload == uploads; }
 };
 enum { NEED_COLUMN = 1, NEED_OPACITIES = 2, NEED_SPECTRUM = 4 };
@@ -632,6 +633,27 @@ bool launch_twostream(TwoStreamParams &p, const TsPlan &t, hipStream_t s);
 bool launch_twostream_w(TwoStreamParams &p, const TsPlan &t, hipStream_t s);
 // T + c*b_T, T_surface + c*b_Ts, IR spectra + c*b_out for column c of ncol
 bool launch_twostream_ir_batch(TwoStreamParams &p, int ncol, hipStream_t s, int force_nw = 0);
+// Illumination cases on the stored opacities (k_twostream_sol_batch, solar_batch.inc): a block of its own, so that
+// TwoStreamParams and the kernels that take it stay what they are.  Case c reads zen + c * 3 * nzen ([u0 | weight | 1/u0]
+// [nzen]), albedo + c * alb_stride ([nw_sol], the channel's bin order; stride 0: one albedo for every case) and scale[c],
+// and writes its three spectra ([nw_sol][nz+1], ground-first) at out_stride doubles from the previous case's.
+struct SolBatchParams {
+  int nz, ng;
+  int n_sol, sol_lo, sol_start;            // blocks = solar bins sol_lo .. ; channel -> opacity-bin offset
+  int ncase, nzen;
+  int cases_per_block;                     // (launcher)
+  const double *tau, *w0, *g, *wbin;       // opr, g-point weights
+  const double *zen, *albedo, *scale;
+  size_t alb_stride;
+  const double *photons_sol;               // [nw_sol], unscaled
+  const double *am_f1, *am_f2, *am_dw;     // per solar bin amean unit factors (radiate.f90:174-178)
+  double diurnal_fac;
+  double *fup, *fdn, *amean;
+  size_t out_stride;
+};
+// false: outside what the kernel covers (nz > 512, nzen > MAX_ZEN, LDS); force_nw = 4: blocks of four waves at every slot count
+bool launch_twostream_sol_batch(SolBatchParams &p, hipStream_t s, int force_nw = 0);
+int solar_batch_cases_per_block(int ncase);   // the launcher's rule (tests size their batches by it)
 int fused_tiles(const OpacityParams &op);   // opacity tiles per column (size of a column's done[] slice)
 bool launch_fused(const OpacityParams &op, TwoStreamParams ts, FusedParams fp, const TsPlan &f, hipStream_t s);
 // the same three launchers for a launch with bounds blocks (TwoStreamParams::bounds; kernels_bounds.hip): launch_fused,

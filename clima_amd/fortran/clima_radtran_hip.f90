@@ -81,6 +81,7 @@ module clima_radtran_hip
     procedure :: equilibrium_temperature => Radtran_equilibrium_temperature
     procedure :: apply_radiation_enhancement => Radtran_apply_radiation_enhancement
     procedure :: radiate_ir_batch => Radtran_radiate_ir_batch
+    procedure :: radiate_solar_batch => Radtran_radiate_solar_batch
     procedure :: ir_jacobian => Radtran_ir_jacobian
     procedure :: ir_jacobian_reduced => Radtran_ir_jacobian_reduced
     procedure :: TOA_fluxes_batch => Radtran_TOA_fluxes_batch
@@ -208,6 +209,17 @@ module clima_radtran_hip
       integer(c_int), intent(in) :: ncol, dim1_T, dim2_T
       real(c_double), intent(in) :: T_surface(*), T(*)
       real(c_double), intent(out) :: fup_n(*), fdn_n(*), f_total(*)
+      character(c_char), intent(out) :: err(*)
+    end subroutine
+    subroutine c_radtran_radiate_solar_batch(ptr, ncol, nzen, zenith_u, zenith_weights, surface_albedo, photon_scale_factor, &
+                                             fup_n, fdn_n, f_total, nsel, spec_level, sol_fup, sol_fdn, sol_amean, err) &
+                                             bind(c, name="radtran_radiate_solar_batch")
+      import; type(c_ptr), value :: ptr
+      integer(c_int), intent(in) :: ncol, nzen, nsel
+      real(c_double), intent(in) :: zenith_u(*), zenith_weights(*)
+      type(c_ptr), value :: surface_albedo, photon_scale_factor   ! (c_null_ptr: the handle's)
+      real(c_double), intent(out) :: fup_n(*), fdn_n(*)
+      type(c_ptr), value :: f_total, spec_level, sol_fup, sol_fdn, sol_amean     ! (c_null_ptr: not wanted)
       character(c_char), intent(out) :: err(*)
     end subroutine
     subroutine c_radtran_ir_jacobian(ptr, T_surface, dim_T, T, dim1, dim2, jac_up, jac_dn, jac_total, err) &
@@ -972,6 +984,67 @@ contains
     endif
     call c_radtran_batch_pin_results_set(self%handle, merge(1_c_int, 0_c_int, self%pin_batch_results))
     call c_radtran_radiate_ir_batch(self%handle, ncol, T_surface, size(T,1), size(T,2), T, fup_n, fdn_n, f_total, err_c)
+    call take_err(err_c, err)
+  end subroutine
+
+  !> Solar calls that differ in how the star lights one atmosphere, in one go (radtran_radiate_solar_batch): case c is
+  !> `radiate(..., compute_solar=.true., compute_opacity=.false.)` on the opacities of the last compute_opacity call as if
+  !> `self%zenith_u = zenith_u(:,c)`, `self%zenith_weights = zenith_weights(:,c)` (nzen, ncol; nzen is the batch's own,
+  !> 1..16), `self%surface_albedo = surface_albedo(:,c)` (nw_sol, ncol) and `self%photon_scale_factor =
+  !> photon_scale_factor(c)` had been set; an array not present: every case under `self`'s field.  `fup_n`, `fdn_n` (nz+1,
+  !> ncol) are what the call would leave in `self%wrk_sol`; `f_total` adds the IR rows of the last IR call.  `spec_level`
+  !> (levels 1..nz+1, ground-first) with any of `sol_fup_a`, `sol_fdn_a`, `sol_amean` (nw_sol, nsel, ncol): the per-bin rows
+  !> of every case.  `self` is not changed.
+  subroutine Radtran_radiate_solar_batch(self, zenith_u, zenith_weights, fup_n, fdn_n, err, surface_albedo, photon_scale_factor, &
+                                         f_total, spec_level, sol_fup_a, sol_fdn_a, sol_amean)
+    class(Radtran), intent(inout) :: self
+    real(dp), intent(in), contiguous :: zenith_u(:,:), zenith_weights(:,:)     !! (nzen, ncol)
+    real(dp), intent(out), contiguous :: fup_n(:,:), fdn_n(:,:)                !! (nz+1, ncol)
+    character(:), allocatable, intent(out) :: err
+    real(dp), intent(in), contiguous, optional, target :: surface_albedo(:,:), photon_scale_factor(:)
+    real(dp), intent(out), contiguous, optional, target :: f_total(:,:)
+    integer(c_int), intent(in), contiguous, optional, target :: spec_level(:)
+    real(dp), intent(out), contiguous, optional, target :: sol_fup_a(:,:,:), sol_fdn_a(:,:,:), sol_amean(:,:,:)
+    character(c_char) :: err_c(err_len+1)
+    type(c_ptr) :: opt(3), sink(3), levels
+    integer :: ncol, nzen, nsel, nw_sol
+    nzen = size(zenith_u, 1); ncol = size(zenith_u, 2); nsel = 0
+    nw_sol = size(self%sol%freq) - 1
+    if (any(shape(zenith_weights) /= [nzen, ncol])) err = 'radiate_solar_batch: "zenith_weights" has the wrong dimension'
+    if (any(shape(fup_n) /= [self%nz+1, ncol])) err = 'radiate_solar_batch: "fup_n" has the wrong dimension'
+    if (any(shape(fdn_n) /= [self%nz+1, ncol])) err = 'radiate_solar_batch: "fdn_n" has the wrong dimension'
+    opt = c_null_ptr; sink = c_null_ptr; levels = c_null_ptr
+    if (present(surface_albedo)) then
+      if (any(shape(surface_albedo) /= [nw_sol, ncol])) err = 'radiate_solar_batch: "surface_albedo" has the wrong dimension'
+      opt(1) = c_loc(surface_albedo)
+    endif
+    if (present(photon_scale_factor)) then
+      if (size(photon_scale_factor) /= ncol) err = 'radiate_solar_batch: "photon_scale_factor" has the wrong dimension'
+      opt(2) = c_loc(photon_scale_factor)
+    endif
+    if (present(f_total)) then
+      if (any(shape(f_total) /= [self%nz+1, ncol])) err = 'radiate_solar_batch: "f_total" has the wrong dimension'
+      opt(3) = c_loc(f_total)
+    endif
+    if (present(spec_level)) then
+      nsel = size(spec_level); levels = c_loc(spec_level)
+      if (present(sol_fup_a)) then
+        if (any(shape(sol_fup_a) /= [nw_sol, nsel, ncol])) err = 'radiate_solar_batch: "sol_fup_a" has the wrong dimension'
+        sink(1) = c_loc(sol_fup_a)
+      endif
+      if (present(sol_fdn_a)) then
+        if (any(shape(sol_fdn_a) /= [nw_sol, nsel, ncol])) err = 'radiate_solar_batch: "sol_fdn_a" has the wrong dimension'
+        sink(2) = c_loc(sol_fdn_a)
+      endif
+      if (present(sol_amean)) then
+        if (any(shape(sol_amean) /= [nw_sol, nsel, ncol])) err = 'radiate_solar_batch: "sol_amean" has the wrong dimension'
+        sink(3) = c_loc(sol_amean)
+      endif
+    endif
+    if (allocated(err)) return
+    call push_fields(self)
+    call c_radtran_radiate_solar_batch(self%handle, ncol, nzen, zenith_u, zenith_weights, opt(1), opt(2), fup_n, fdn_n, opt(3), &
+                                       nsel, levels, sink(1), sink(2), sink(3), err_c)
     call take_err(err_c, err)
   end subroutine
 

@@ -79,6 +79,11 @@ SIGNATURES = {
     "clima_test_pack_columns": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _err],
     "clima_test_pack_columns_host": [_vp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _err],
     "radtran_radiate_ir_batch": [_vp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _err],
+    "radtran_radiate_solar_batch": [_vp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _err],
+    "radtran_solar_batch_shared_set": [_vp, _ip],
+    "radtran_solar_batch_shared_get": [_vp, _ip, _ip],
+    "clima_test_solar_batch": [_ip, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _err],
+    "clima_test_solar_batch_cases_per_block": [_ip, _ip],
     "radtran_ir_jacobian": [_vp, _dp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _err],
     "radtran_ir_jacobian_reduced": [_vp, _dp, _ip, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _dp, _dp, _dp, _err],
     "radtran_upload_column": [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _err],

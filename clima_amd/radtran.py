@@ -516,6 +516,87 @@ class Radtran:
         self._check()
         return tuple(out)
 
+    SOLAR_BATCH_SPECTRA = ("fup", "fdn", "amean")
+
+    def _solar_batch_request(self, dims, zenith_u, zenith_weights, surface_albedo, photon_scale_factor, spectra_levels, spectra):
+        """The arrays of `radiate_solar_batch` as the ABI takes them -- (ncol, nzen, zenith_u, zenith_weights, surface_albedo
+        or None, photon_scale_factor or None, levels 1..nz+1 or None, names in the ABI's order) -- for dims = (nz, nw_sol);
+        wrong shapes and unknown spectrum names are refused by name (reads SOLAR_BATCH_SPECTRA alone: no handle needed)"""
+        who = "radiate_solar_batch: "
+        nz, nw_sol = dims
+        u = _c(zenith_u)
+        if u.ndim == 1:
+            u = u.reshape(-1, 1)
+            if zenith_weights is None:
+                zenith_weights = np.ones_like(u)
+            elif np.ndim(zenith_weights) == 1:
+                zenith_weights = np.reshape(zenith_weights, (-1, 1))
+        if u.ndim != 2 or u.shape[0] < 1 or u.shape[1] < 1:
+            raise ClimaException(who + '"zenith_u" has the shape %s, not (ncol,) or (ncol, nzen)' % (tuple(np.shape(zenith_u)),))
+        n, nzen = u.shape
+        if zenith_weights is None:
+            raise ClimaException(who + '"zenith_weights" is required with a two-dimensional "zenith_u"')
+        want = {"zenith_weights": (n, nzen), "surface_albedo": (n, nw_sol), "photon_scale_factor": (n,)}
+        got = {"zenith_weights": zenith_weights, "surface_albedo": surface_albedo, "photon_scale_factor": photon_scale_factor}
+        for name, a in got.items():
+            if a is None:
+                continue
+            a = _c(a)
+            if a.shape != want[name]:
+                raise ClimaException(who + '"%s" has the shape %s, not %s' % (name, a.shape, want[name]))
+            got[name] = a
+        levels, names = None, ()
+        if spectra_levels is not None:
+            nl = nz + 1
+            idx = np.atleast_1d(np.asarray(spectra_levels))
+            if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+                raise ClimaException(who + '"spectra_levels" is not a list of integer level indices')
+            for a, v in enumerate(idx.tolist()):
+                if v < -nl or v >= nl:
+                    raise ClimaException(who + "spectra_levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
+            spectra = (spectra,) if isinstance(spectra, str) else tuple(spectra)
+            for name in spectra:
+                if name not in self.SOLAR_BATCH_SPECTRA:
+                    raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.SOLAR_BATCH_SPECTRA)))
+            levels = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
+            names = tuple(name for name in self.SOLAR_BATCH_SPECTRA if name in spectra)
+        return n, nzen, u, got["zenith_weights"], got["surface_albedo"], got["photon_scale_factor"], levels, names
+
+    def radiate_solar_batch(self, zenith_u, zenith_weights=None, surface_albedo=None, photon_scale_factor=None,
+                            spectra_levels=None, spectra=("fup", "fdn", "amean")):
+        """ncol solar calls on the resident opacities in one go (radtran_radiate_solar_batch): case c is
+        `radiate(..., compute_solar=True, compute_opacity=False)` after `zenith_u`, `zenith_weights`, `surface_albedo` and
+        `photon_scale_factor` had been set to the case's.  Arrays carry the case first: `zenith_u`, `zenith_weights` (ncol,
+        nzen) -- nzen is the batch's own, 1..16; a 1-D `zenith_u` means one angle of weight 1 per case --, `surface_albedo`
+        (ncol, nw_sol), `photon_scale_factor` (ncol,); None: the handle's current value.  Returns (fup_n, fdn_n, f_total),
+        each (nz+1, ncol), f_total = (fdn_n - fup_n) plus the IR rows of the handle's last IR call; with `spectra_levels`
+        (numpy-style indices into the ground-first level axis) also a dict name -> (nsel, nw_sol, ncol) for the names in
+        `spectra` ("fup", "fdn", "amean": wrk_sol.fup_a / fdn_a / amean at those levels).  The handle's state is left
+        untouched."""
+        nz, nw_sol = self.nz, len(self.sol.freq) - 1
+        n, nzen, u, w, alb, scale, levels, names = self._solar_batch_request(
+            (nz, nw_sol), zenith_u, zenith_weights, surface_albedo, photon_scale_factor, spectra_levels, spectra)
+        out = [np.empty((nz + 1, n), order="F") for _ in range(3)]
+        spec = {name: np.empty((len(levels), nw_sol, n)) for name in names}
+        opt = lambda a: _d(a) if a is not None else None   # noqa: E731
+        self._L.radtran_radiate_solar_batch(
+            self._ptr, _i(n), _i(nzen), _d(u), _d(w), opt(alb), opt(scale), _d(out[0]), _d(out[1]), _d(out[2]),
+            _i(0 if levels is None else len(levels)), None if levels is None else levels.ctypes.data_as(C.POINTER(C.c_int)),
+            *[opt(spec.get(name)) for name in self.SOLAR_BATCH_SPECTRA], self._err)
+        self._check()
+        # (the ABI's (nw_sol, nsel, ncol) column-major is (ncol, nsel, nw_sol) in C order)
+        spec = {k: np.ascontiguousarray(v.reshape(n, len(levels), nw_sol).transpose(1, 2, 0)) for k, v in spec.items()}
+        return tuple(out) if levels is None else tuple(out) + (spec,)
+
+    def solar_batch_shared(self, on=None):
+        """(on, batches): whether `radiate_solar_batch` may take the shared kernel, and the batches that took it so far;
+        `on` 0 / 1 sets it first (radtran_solar_batch_shared_set / _get: for tests and measurements)"""
+        if on is not None:
+            self._L.radtran_solar_batch_shared_set(self._ptr, _i(1 if on else 0))
+        a, b = C.c_int(), C.c_int()
+        self._L.radtran_solar_batch_shared_get(self._ptr, C.byref(a), C.byref(b))
+        return a.value, b.value
+
     def ir_jacobian(self, T_surface, T):
         """The exact IR temperature Jacobian of the level fluxes at the resident opacities (radtran_ir_jacobian):
         (jac_up, jac_dn, jac_total), each (nz+1, nz+1) Fortran-ordered, [i, j] = d flux(level i, ground-first) / d x(j)

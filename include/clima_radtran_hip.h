@@ -287,6 +287,42 @@ void clima_test_pack_columns_host(void *ptr, const int *ncol, const double *T_su
 void radtran_radiate_ir_batch(void *ptr, const int *ncol, const double *T_surface, const int *dim1_T,
                               const int *dim2_T, const double *T, double *fup_n, double *fdn_n,
                               double *f_total, char *err);
+/* Batched solar calls on shared opacities: many illumination cases of ONE atmosphere (an albedo as a function of zenith
+ * angle, latitude bands, a surface-albedo sweep, an insolation loop).  Case c is radiate(..., compute_solar = .true.,
+ * compute_opacity = .false.) (clima_radtran.f90:291-316) on the handle's stored optical properties, the handle taken as
+ * constructed with `nzen` zenith angles, after zenith_u = zenith_u(:, c), zenith_weights = zenith_weights(:, c),
+ * surface_albedo = surface_albedo(:, c) and photon_scale_factor = photon_scale_factor(c) had been set.
+ *   zenith_u, zenith_weights  (nzen, ncol); nzen is the batch's own, 1 <= nzen <= 16, independent of the handle's (nzen =
+ *                             1 with weight 1: one zenith angle per case)
+ *   surface_albedo            (nw_sol, ncol), or NULL: the handle's current albedo in every case
+ *   photon_scale_factor       (ncol), or NULL: the handle's current value.  diurnal_fac is always the handle's.  Values are
+ *                             used as given.
+ *   fup_n, fdn_n              (nz+1, ncol): that call's wrk_sol%fup_n, wrk_sol%fdn_n, ground-first
+ *   f_total                   (nz+1, ncol) or NULL: (fdn_n - fup_n) plus the IR rows the handle holds from its last IR call
+ *                             (as radtran_radiate_ir_batch uses the last solar rows)
+ *   nsel, spec_level(nsel)    levels 1..nz+1 ground-first, any order, repeats allowed (the spectra batches' convention);
+ *                             nsel = 0: no spectra, the arrays below are unread
+ *   sol_fup, sol_fdn, sol_amean  (nw_sol, nsel, ncol), any of them NULL: element (l, a, c) is wrk_sol%fup_a(spec_level(a),
+ *                             l) of case c (fdn_a, amean -- photons cm^-2 s^-1 -- likewise), in the same units
+ * The handle's wrk_ir, wrk_sol, f_total, spectra, stored opacities and its five fields are left untouched.  Synchronous,
+ * host arrays; the results come back as radtran_radiate_ir_batch's do, the cases run in chunks of 512 so that the
+ * per-case spectra in device memory stay bounded.  Two forms give the same results to rounding: k_twostream_sol_batch
+ * (nz <= 512), which does what the opacities alone decide once per (bin, g-point) and block of cases, and one full solve
+ * per case by the stand-alone two-stream kernels (nz > 512, and whatever else the shared kernel does not cover).
+ * Refused (err) with nothing enqueued, the text naming the argument and its value: a handle that is not constructed or
+ * holds no opacities ("radiate_solar_batch needs opacities: ..."); a bin shard or a communicator ("needs the whole
+ * spectrum": a multi-GPU form is out of scope); ncol < 1; nzen outside 1..16; NULL zenith_u, zenith_weights, fup_n or
+ * fdn_n; f_total on a handle that holds no level rows; nsel < 0; nsel > 0 with NULL spec_level; a level outside 1..nz+1;
+ * nsel > 0 with all three spectrum arrays NULL. */
+void radtran_radiate_solar_batch(void *ptr, const int *ncol, const int *nzen, const double *zenith_u,
+                                 const double *zenith_weights, const double *surface_albedo,
+                                 const double *photon_scale_factor, double *fup_n, double *fdn_n, double *f_total,
+                                 const int *nsel, const int *spec_level, double *sol_fup, double *sol_fdn,
+                                 double *sol_amean, char *err);
+/* ... its forms, for tests and measurements: on = 0 forces one full solve per case (default 1: the shared kernel where
+ * it covers the shape); `batches` counts the batches that took the shared kernel. */
+void radtran_solar_batch_shared_set(void *ptr, const int *on);
+void radtran_solar_batch_shared_get(void *ptr, int *on, int *batches);
 /* The exact IR temperature Jacobian of the level fluxes at fixed opacities: the limit, as the step goes to 0, of what
  * the RCE Jacobian's one-sided differences compute (src/adiabat/clima_adiabat_solve.f90:768-822), in one call.  For the
  * base profile T_surface, T (dim_T = nz) and the opacities of the last compute_opacity call, jac_up, jac_dn and
@@ -515,6 +551,14 @@ void clima_test_two_stream(const int *nz, const int *ng, const int *form, const 
                            const double *w0, const double *g, const double *bplanck, const double *ir_par,
                            const double *sol_par, const double *wbin, double *ir_fup, double *ir_fdn,
                            double *sol_fup, double *sol_fdn, double *sol_amean, char *err);
+/* The same for k_twostream_sol_batch (solar_batch.inc): one column of tau, w0, g (nz, TOA-first) carried by ng g-points of
+ * weights wbin as one solar bin; ncol cases of nzen angles (zen_u, zen_w (nzen, ncol)) and surface reflectance rsfc (ncol)
+ * go through the production kernel with photon factor 1.  force_nw = 4 selects the 4-wave form at every slot count.
+ * Outputs (nz+1, ncol), TOA-first.  ..._cases_per_block: the launcher's rule for the cases a block takes. */
+void clima_test_solar_batch(const int *nz, const int *ng, const int *force_nw, const double *tau, const double *w0,
+                            const double *g, const double *wbin, const int *ncol, const int *nzen, const double *zen_u,
+                            const double *zen_w, const double *rsfc, double *fup, double *fdn, double *amean, char *err);
+void clima_test_solar_batch_cases_per_block(const int *ncol, int *cases);
 /* The same for the response form of radtran_radiate_ir_batch (ir_green.inc): the column of clima_test_two_stream and
  * `ndev` changes of the Planck value at levels dev_k (TOA-first, nz = the surface) -> per change the change of the level
  * fluxes, resp_up / resp_dn (nz+1, ndev) TOA-first, summed over the g-points with the weights wbin -- produced by the
