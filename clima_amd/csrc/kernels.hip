@@ -3751,6 +3751,7 @@ void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s) {
 
 #include "ir_green.inc"
 #include "solar_batch.inc"
+#include "ir_adjoint.inc"
 #else
 // The bounds blocks of a batch out of device arrays: column blockIdx.y, one element per thread (bounds_element: the
 // host's pack_bounds takes the same values the same way, so the blocks are bit for bit the host's).

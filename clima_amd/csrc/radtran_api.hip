@@ -206,6 +206,7 @@ struct Radtran {
   PinnedBuf<double> h_bout;        // the batch's three result arrays on their way to the caller's
   PinnedBuf<char> h_green;         // what the host hands the response form (base profile, deviation lists)
   DevBuf<int> d_green_idx;
+  DevBuf<double> d_adjoint;        // the adjoint rows' work buffer (radtran_ir_jacobian_spectral_rows, ir_adjoint.inc)
   // illumination cases on the stored opacities (radtran_radiate_solar_batch): the cases' inputs, the spectra of the cases
   // in flight, a place for the per-case form's copy of the band optical depth
   DevBuf<double> d_sb_in, d_sb_spec, d_sb_band;
@@ -2569,6 +2570,94 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
   CATCH(err)
 }
 
+// Rows of the same derivative BEFORE the sum over the bins: jac_*_a(l, a, j) = d wrk_ir%f*_a(row_level(a), l) / d x(j), per
+// Hz.  Not the response form: one adjoint two-stream solve per (bin, g-point, requested row, direction) gives the whole
+// row (ir_adjoint.inc), so none of the response form's limits apply; what bounds the call is its work buffer.
+// include/clima_radtran_hip.h has the contract.
+constexpr double IR_ADJOINT_MAX_BYTES = 4294967296.0;
+void radtran_ir_jacobian_spectral_rows(void *ptr, const double *T_surface, const int *dim_T, const double *T,
+                                       const int *nrow, const int *row_level,
+                                       const int *dim1, const int *dim2, const int *dim3,
+                                       double *jac_up_a, double *jac_dn_a, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const int nz = r->nz, nl = nz + 1, nw_ir = r->ir.nw, nr = *nrow;
+  const std::string pre = "ir_jacobian_spectral_rows: ";
+  if (*dim_T != nz) { set_err(err, "\"T\" has the wrong input dimension."); return; }
+  if (nr < 1) { set_err(err, pre + "nrow must be at least 1 (nrow = " + std::to_string(nr) + ")"); return; }
+  if (!row_level) { set_err(err, pre + "\"row_level\" is a required argument"); return; }
+  if (*dim1 != nw_ir || *dim2 != nr || *dim3 != nl) {
+    set_err(err, pre + "jac has the wrong dimension (" + std::to_string(*dim1) + ", " + std::to_string(*dim2) + ", " + std::to_string(*dim3) +
+                     "), not (nw_ir, nrow, nz + 1) = (" + std::to_string(nw_ir) + ", " + std::to_string(nr) + ", " + std::to_string(nl) + ")");
+    return;
+  }
+  if (!jac_up_a && !jac_dn_a) { set_err(err, pre + "neither jac_up_a nor jac_dn_a was given"); return; }
+  const int ndir = (jac_up_a ? 1 : 0) + (jac_dn_a ? 1 : 0), nfun = nr * ndir;
+  std::vector<int> fun((size_t)nfun);
+  for (int a = 0; a < nr; a++) {
+    const int v = row_level[a];
+    if (v < 1 || v > nl) {
+      set_err(err, pre + "row_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
+      return;
+    }
+    int f = a * ndir;
+    if (jac_up_a) fun[f++] = 2 * (nz - (v - 1));
+    if (jac_dn_a) fun[f] = 2 * (nz - (v - 1)) + 1;
+  }
+  for (int j = 0; j <= nz; j++) {
+    const double v = j < nz ? T[j] : *T_surface;
+    if (!(std::isfinite(v) && v > 0.0)) {
+      set_err(err, pre + "temperatures must be finite and positive (" + (j < nz ? "T(" + std::to_string(j + 1) + ")" : std::string("T_surface")) +
+                       " = " + std::to_string(v) + ")");
+      return;
+    }
+  }
+  if (r->shard_world != 1 || r->comm) {
+    const std::string shard = r->shard_world != 1 ? "a bin shard of " + std::to_string(r->shard_world) : "";
+    set_err(err, pre + "needs the whole spectrum (" + shard + (r->comm ? (shard.empty() ? "a communicator" : ", a communicator") : "") + ")");
+    return;
+  }
+  if (refuse(r, "ir_jacobian_spectral_rows", NEED_OPACITIES, err)) return;
+  const int NQ = r->ir_n * r->ng;
+  const size_t n_work = ir_adjoint_work_count(nz, NQ, nfun), n_part = ir_adjoint_part_count(nz, NQ, nfun);
+  if (sizeof(double) * ((double)n_work + (double)n_part) > IR_ADJOINT_MAX_BYTES) {
+    set_err(err, pre + "the work buffer of nrow = " + std::to_string(nr) + " rows in " + std::to_string(ndir) + " direction(s) would take " +
+                     std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " + std::to_string((long long)IR_ADJOINT_MAX_BYTES) +
+                     ": ask for fewer rows per call");
+    return;
+  }
+  TRY
+  ready_stored_opacities(r);
+  const size_t arr = (size_t)nw_ir * nr * nl;
+  r->d_bout.reserve(ndir * arr);
+  jacobian_of_ir_bins(r, ndir * arr, [&] {
+    // through the handle's pinned block: base_T by level k [nl] (radiate.f90:65-69: level k is layer nz-1-k), then the functionals
+    double *hd = reinterpret_cast<double *>(green_stage(r, sizeof(double) * nl + sizeof(int) * nfun));
+    int *hi = reinterpret_cast<int *>(hd + nl);
+    for (int k = 0; k < nz; k++) hd[k] = T[nz - 1 - k];
+    hd[nz] = *T_surface;
+    std::copy(fun.begin(), fun.end(), hi);
+    r->d_green_in.reserve(nl); r->d_green_idx.reserve(nfun); r->d_adjoint.reserve(n_work + n_part);
+    HIPCHK(hipMemcpyAsync(r->d_green_in.p, hd, sizeof(double) * nl, hipMemcpyHostToDevice, r->stream));
+    HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * nfun, hipMemcpyHostToDevice, r->stream));
+    IrAdjointParams p;
+    std::memset(&p, 0, sizeof(p));
+    GreenParams &g = p.g;
+    g.nz = nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
+    g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
+    g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
+    g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
+    g.base_T = r->d_green_in.p;
+    p.nfun = nfun; p.nrow = nr; p.ndir = ndir; p.dir0 = jac_up_a ? 0 : 1; p.fun = r->d_green_idx.p;
+    p.work = r->d_adjoint.p; p.part = p.work + n_work;
+    p.out_up = jac_up_a ? r->d_bout.p : nullptr; p.out_dn = jac_dn_a ? r->d_bout.p + (jac_up_a ? arr : 0) : nullptr;
+    launch_ir_adjoint(p, r->stream);
+  });
+  double *const outs[2] = {jac_up_a ? jac_up_a : jac_dn_a, jac_dn_a};
+  bout_to_host(r, outs, arr, ndir);
+  CATCH(err)
+}
+
 // What every column batch refuses before anything else, with the texts of radtran_toa_fluxes_batch
 static bool batch_refused(Radtran *r, const int *ncol, const int *has_particles, char *err) {
   if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return true; }
@@ -3582,6 +3671,53 @@ void clima_test_ir_response(const int *nz_, const int *ng_, const double *tau, c
     for (int lv = 0; lv < nl; lv++) {
       resp_up[(size_t)order[d] * nl + lv] = out[((size_t)d * 2 + 0) * nl + lv];
       resp_dn[(size_t)order[d] * nl + lv] = out[((size_t)d * 2 + 1) * nl + lv];
+    }
+  CATCH(err)
+}
+
+// Test hook of the adjoint rows (ir_adjoint.inc), the counterpart of clima_test_ir_response for them: one column's tau /
+// w0 / g (the same for every g-point, weights wbin) as one IR bin and nrow levels (0..nz, TOA-first) -> d fup(level) /
+// d bplanck(k) and d fdn(level) / d bplanck(k), (nrow, nz+1) row after row, k TOA-first, summed over the g-points by the
+// production kernels with unit amplitudes in place of the Planck derivatives.
+void clima_test_ir_adjoint(const int *nz_, const int *ng_, const double *tau, const double *w0, const double *g,
+                           const double *ir_par, const double *wbin, const int *nrow_, const int *level,
+                           double *dfup, double *dfdn, char *err) {
+  clear_err(err);
+  TRY
+  const int nz = *nz_, ng = *ng_, nl = nz + 1, nr = *nrow_, nfun = 2 * nr;
+  if (nz < 1 || ng < 1 || ng > 32 || nr < 1) throw HipFail{"clima_test_ir_adjoint: bad nz / ng / nrow"};
+  std::vector<int> fun((size_t)nfun);
+  for (int a = 0; a < nr; a++) {
+    if (level[a] < 0 || level[a] > nz) throw HipFail{"clima_test_ir_adjoint: bad level"};
+    fun[2 * a] = 2 * level[a]; fun[2 * a + 1] = 2 * level[a] + 1;
+  }
+  std::vector<double> h_tau((size_t)ng * nz), h_w0((size_t)ng * nz);
+  for (int c = 0; c < ng; c++)
+    for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau[i]; h_w0[(size_t)c * nz + i] = w0[i]; }
+  DevBuf<double> d_tau, d_w0, d_g, d_wbin, d_em, d_work, d_out;
+  DevBuf<int> d_fun;
+  d_tau.upload(h_tau); d_w0.upload(h_w0); d_g.upload(std::vector<double>(g, g + nz));
+  d_wbin.upload(std::vector<double>(wbin, wbin + ng)); d_em.upload(std::vector<double>{ir_par[0]});
+  d_fun.upload(fun);
+  const size_t n_work = ir_adjoint_work_count(nz, ng, nfun), n_part = ir_adjoint_part_count(nz, ng, nfun), arr = (size_t)nr * nl;
+  d_work.alloc(n_work + n_part); d_work.zero();
+  d_out.alloc(2 * arr); d_out.zero();
+  IrAdjointParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.g.nz = nz; p.g.ng = ng; p.g.n_ir = 1; p.g.NQ = ng;
+  p.g.tau = d_tau.p; p.g.w0 = d_w0.p; p.g.g = d_g.p; p.g.wbin = d_wbin.p; p.g.emissivity = d_em.p;
+  p.g.has_hard_surface = ir_par[1] != 0.0 ? 1 : 0; p.g.ir_tau_min = ir_par[2];
+  p.nfun = nfun; p.nrow = nr; p.ndir = 2; p.fun = d_fun.p;
+  p.work = d_work.p; p.part = p.work + n_work; p.out_up = d_out.p; p.out_dn = d_out.p + arr;
+  launch_ir_adjoint(p, nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  std::vector<double> out(2 * arr);
+  HIPCHK(hipMemcpy(out.data(), d_out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost));
+  for (int a = 0; a < nr; a++)
+    for (int k = 0; k < nl; k++) {      // the kernel writes (bin, a, j = nz - k)
+      dfup[(size_t)a * nl + k] = out[a + (size_t)nr * (nz - k)];
+      dfdn[(size_t)a * nl + k] = out[arr + a + (size_t)nr * (nz - k)];
     }
   CATCH(err)
 }

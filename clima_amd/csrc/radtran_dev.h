@@ -537,6 +537,23 @@ void launch_green_accumulate(const GreenParams &p, hipStream_t s);   // the accu
 void launch_green_jacobian(const GreenParams &p, hipStream_t s);     // Planck derivatives, accumulation, the three matrices
 void launch_green_jacobian_reduced(const GreenParams &p, const int *row_lv, int nrow, int ngroup, bool parts, hipStream_t s);   // ... summed over groups of columns, rows picked
 void launch_jacobian_total(double *jac, size_t arr, size_t n, hipStream_t s);
+// Rows of the per-bin IR temperature Jacobian by adjoint solves (ir_adjoint.inc, radtran_ir_jacobian_spectral_rows): a
+// block of its own beside the response form's.  `g` carries the opacities, the surface fields and base_T (null: unit
+// amplitudes, the test hook) -- none of the response form's work arrays.  fun[f] = 2 level + (0 up | 1 down), levels
+// TOA-first, the ndir directions of requested level a side by side at f = a ndir (dir0: the one direction of ndir = 1).
+struct IrAdjointParams {
+  GreenParams g;
+  int nfun, nrow, ndir, dir0;
+  const int *fun;
+  double *work;                            // [NQ][4 + nfun][2 nz]: c', 1 / pivot, sub-diagonal, y, the functionals' lambdas
+  double *part;                            // [NQ][nfun][nz+1]: a g-point's weighted row, levels TOA-first
+  double *out_up, *out_dn;                 // (n_ir, nrow, nz+1), the bin fastest, x ground-first (null: not asked for)
+};
+// work rows of 2 nz doubles per q; doubles of `work` (then `part` behind it) in all
+__host__ __device__ inline size_t adjoint_work_rows(int nfun) { return 4 + (size_t)nfun; }
+inline size_t ir_adjoint_work_count(int nz, int NQ, int nfun) { return (size_t)NQ * adjoint_work_rows(nfun) * 2 * nz; }
+inline size_t ir_adjoint_part_count(int nz, int NQ, int nfun) { return (size_t)NQ * nfun * (nz + 1); }
+void launch_ir_adjoint(const IrAdjointParams &p, hipStream_t s);
 int green_far_resident_waves();
 void green_vector_form_set(int vector_form);   // test hook: the far accumulation's vector form (1) or matrix form (0)
 int green_far_waves(int ndev, int nl);   // per bin split

@@ -84,6 +84,7 @@ module clima_radtran_hip
     procedure :: radiate_solar_batch => Radtran_radiate_solar_batch
     procedure :: ir_jacobian => Radtran_ir_jacobian
     procedure :: ir_jacobian_reduced => Radtran_ir_jacobian_reduced
+    procedure :: ir_jacobian_spectral_rows => Radtran_ir_jacobian_spectral_rows
     procedure :: TOA_fluxes_batch => Radtran_TOA_fluxes_batch
     procedure :: TOA_fluxes_batch_spectra => Radtran_TOA_fluxes_batch_spectra
     procedure :: TOA_fluxes_batch_bounds => Radtran_TOA_fluxes_batch_bounds
@@ -238,6 +239,14 @@ module clima_radtran_hip
       real(c_double), intent(in) :: T_surface, T(*)
       type(c_ptr), value :: jac_up, jac_dn     ! (c_null_ptr: not wanted)
       real(c_double), intent(out) :: jac_total(*)
+      character(c_char), intent(out) :: err(*)
+    end subroutine
+    subroutine c_radtran_ir_jacobian_spectral_rows(ptr, T_surface, dim_T, T, nrow, row_level, dim1, dim2, dim3, &
+                                                   jac_up_a, jac_dn_a, err) bind(c, name="radtran_ir_jacobian_spectral_rows")
+      import; type(c_ptr), value :: ptr
+      integer(c_int), intent(in) :: dim_T, nrow, dim1, dim2, dim3, row_level(*)
+      real(c_double), intent(in) :: T_surface, T(*)
+      type(c_ptr), value :: jac_up_a, jac_dn_a     ! (c_null_ptr: not wanted)
       character(c_char), intent(out) :: err(*)
     end subroutine
     subroutine c_radtran_opacities2yaml_wrapper_1(ptr, out_len, out_cp) bind(c, name="radtran_opacities2yaml_wrapper_1")
@@ -1105,6 +1114,44 @@ contains
     call c_radtran_ir_jacobian_reduced(self%handle, T_surface, size(T), T, size(group_of_x), group_of_x, ngroup, &
                                        size(row_level), row_level, size(jac_total,1), size(jac_total,2), &
                                        p_up, p_dn, jac_total, err_c)
+    call take_err(err_c, err)
+  end subroutine
+
+  !> Rows of `ir_jacobian` before the sum over the bins: jac_up_a(l,a,j) = d self%wrk_ir%fup_a(row_level(a), l) / d x(j),
+  !> jac_dn_a the same of fdn_a, (nw_ir, size(row_level), nz+1) each, the bin in the IR channel's own order, x(1) =
+  !> T_surface, x(1+m) = T(m); row_level the levels wanted, 1..nz+1 ground-first (mW m-2 Hz-1 K-1).  One adjoint
+  !> two-stream solve per (bin, g-point, row, direction); at least one of the two arrays must be present.  self%wrk_ir
+  !> and self%f_total stay as they are.
+  subroutine Radtran_ir_jacobian_spectral_rows(self, T_surface, T, row_level, err, jac_up_a, jac_dn_a)
+    class(Radtran), intent(inout) :: self
+    real(dp), intent(in) :: T_surface
+    real(dp), intent(in), contiguous :: T(:)                                !! (nz)
+    integer, intent(in), contiguous :: row_level(:)                         !! (nrow)
+    character(:), allocatable, intent(out) :: err
+    real(dp), intent(out), contiguous, optional, target :: jac_up_a(:,:,:), jac_dn_a(:,:,:)
+    character(c_char) :: err_c(err_len+1)
+    type(c_ptr) :: p_up, p_dn
+    integer :: dims(3)
+    p_up = c_null_ptr; p_dn = c_null_ptr
+    dims = 0
+    if (present(jac_up_a)) then
+      p_up = c_loc(jac_up_a); dims = shape(jac_up_a)
+    endif
+    if (present(jac_dn_a)) then
+      if (present(jac_up_a)) then
+        if (any(shape(jac_dn_a) /= dims)) then
+          err = 'jac has the wrong dimension'
+          return
+        endif
+      endif
+      p_dn = c_loc(jac_dn_a); dims = shape(jac_dn_a)
+    endif
+    if (.not. (present(jac_up_a) .or. present(jac_dn_a))) then
+      err = 'ir_jacobian_spectral_rows: neither jac_up_a nor jac_dn_a was given'
+      return
+    endif
+    call c_radtran_ir_jacobian_spectral_rows(self%handle, T_surface, size(T), T, size(row_level), row_level, &
+                                             dims(1), dims(2), dims(3), p_up, p_dn, err_c)
     call take_err(err_c, err)
   end subroutine
 

@@ -639,6 +639,50 @@ class Radtran:
         self._check()
         return tuple(out) if parts else out[2]
 
+    IR_JACOBIAN_SPECTRAL_PARTS = ("up", "dn")
+
+    def _ir_jacobian_spectral_request(self, nz, T_surface, T, levels, parts):
+        """The arrays of `ir_jacobian_spectral` as the ABI takes them -- (T_surface, T, levels 1..nz+1, names in the
+        ABI's order) -- for a handle of nz layers; wrong shapes, unknown parts and levels outside -(nz+1)..nz are refused
+        by name (reads IR_JACOBIAN_SPECTRAL_PARTS alone: no handle needed)"""
+        who = "ir_jacobian_spectral: "
+        T, Ts = _c(np.atleast_1d(T)), _c(np.atleast_1d(T_surface))
+        if Ts.shape != (1,):
+            raise ClimaException(who + '"T_surface" has the shape %s, not a scalar' % (tuple(np.shape(T_surface)),))
+        if T.shape != (nz,):
+            raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz,)))
+        parts = (parts,) if isinstance(parts, str) else tuple(parts)
+        for name in parts:
+            if name not in self.IR_JACOBIAN_SPECTRAL_PARTS:
+                raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.IR_JACOBIAN_SPECTRAL_PARTS)))
+        if not parts:
+            raise ClimaException(who + '"parts" names none of %s' % ", ".join(self.IR_JACOBIAN_SPECTRAL_PARTS))
+        nl = nz + 1
+        idx = np.atleast_1d(np.asarray(levels))
+        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+            raise ClimaException(who + '"levels" is not a non-empty list of integer level indices')
+        for a, v in enumerate(idx.tolist()):
+            if v < -nl or v >= nl:
+                raise ClimaException(who + "levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
+        rows = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
+        return Ts, T, rows, tuple(name for name in self.IR_JACOBIAN_SPECTRAL_PARTS if name in parts)
+
+    def ir_jacobian_spectral(self, T_surface, T, levels=(-1,), parts=("up",)):
+        """Rows of `ir_jacobian` before the sum over the bins (radtran_ir_jacobian_spectral_rows): a dict name ->
+        (nw_ir, nrow, nz+1) Fortran-ordered array for the names in `parts` ("up", "dn"), [l, a, j] = d wrk_ir.fup_a (fdn_a)
+        [levels[a], l] / d x(j) with x(0) = T_surface, x(1 + m) = T[m]; mW m^-2 Hz^-1 K^-1.  `levels` are numpy-style indices
+        into the ground-first level axis (-1: the top of the atmosphere, 0: the surface), repeats allowed.  Times the bins'
+        widths and summed over l it is `ir_jacobian`'s row.  One adjoint two-stream solve per (bin, g-point, row,
+        direction); the handle's state is left untouched."""
+        Ts, T, rows, names = self._ir_jacobian_spectral_request(self.nz, T_surface, T, levels, parts)
+        nw_ir, nrow, nl = len(self.ir.freq) - 1, len(rows), self.nz + 1
+        out = {name: np.empty((nw_ir, nrow, nl), order="F") for name in names}
+        self._L.radtran_ir_jacobian_spectral_rows(
+            self._ptr, _d(Ts), _i(len(T)), _d(T), _i(nrow), rows.ctypes.data_as(C.POINTER(C.c_int)), _i(nw_ir), _i(nrow), _i(nl),
+            *[_d(out[name]) if name in out else None for name in self.IR_JACOBIAN_SPECTRAL_PARTS], self._err)
+        self._check()
+        return out
+
     # ---- HBM-resident form (bench / batched callers)
     def upload_column(self, T_surface, T, P, densities, dz, pdensities=None, radii=None):
         T, P, dz, densities = _c(T), _c(P), _c(dz), _fo(densities)

@@ -367,6 +367,36 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
                                  const int *nrow, const int *row_level,
                                  const int *dim1, const int *dim2,
                                  double *jac_up, double *jac_dn, double *jac_total, char *err);
+/* Rows of the same derivative BEFORE the sum over the bins: the spectral contribution function of the emission spectrum
+ * and spectral radiative kernels dOLR_nu / dT(p) at the top, the downward flux's at the surface.
+ *   row_level (nrow):   levels 1..nz+1, ground-first, in any order, repeats allowed (radtran_ir_jacobian_reduced's)
+ *   jac_up_a, jac_dn_a: (nw_ir, nrow, nz+1) column-major, the bin fastest and in the channel's own order
+ *                       (rtchannel_freq_get); dim1 = nw_ir, dim2 = nrow, dim3 = nz+1.  Either may be NULL, not both.
+ *   jac_up_a(l, a, j) = d wrk_ir%fup_a(row_level(a), l) / d x(j), x(1) = T_surface, x(1+m) = T(m) (radtran_ir_jacobian's
+ *   x); jac_dn_a likewise with fdn_a; mW m^-2 Hz^-1 K^-1.
+ * The derivative of radiate(..., compute_solar = .false., compute_opacity = .false.) on the stored opacities at the base
+ * profile T_surface, T, as this library computes that call: both surface forms, per-bin emissivity and thin layers
+ * (ir_tau_min) included; the library's IR solve does not read the zenith weights (the constructor's sum to 1, which is
+ * what clima_radtran_radiate.f90:83-134 multiplies the IR fluxes by), and neither does this call.  The amplitude at level k is dB/dT(avg_freq(l), T_k), NOT times the bin's width; the g-points
+ * are summed with wbin in g order, so the result is bitwise repeatable.  Contract:
+ *   sum over l of jac_up_a(l, a, j) (freq(l) - freq(l+1)) is jac_up(row_level(a), j) of radtran_ir_jacobian (to
+ *   rounding: another algorithm); the same for dn;
+ *   the dn row of level nz+1 is exactly 0.0 (fdn(1) = 0, clima_radtran_twostream.f90:289);
+ *   without a hard surface the emissivity is not read.
+ * Not the response form: two_stream_ir solves M Y = E with E linear in the Planck values and every level flux is
+ * c . Y + s . bplanck, so ONE transposed tridiagonal solve M^T lambda = c per (bin, g-point, row, direction) gives the
+ * whole row (clima_amd/csrc/ir_adjoint.inc).  Every nz >= 1 and every g-point count of the single call; what bounds the
+ * call is its work buffer, 8 NQ ((4 + nfun) 2 nz + nfun (nz+1)) bytes for NQ (bin, g-point) pairs and nfun = nrow x
+ * directions functionals, at most 4 GiB.  Synchronous, host arrays.  The handle's wrk_ir, wrk_sol, f_total, spectra,
+ * stored opacities and fields are left untouched.  Refused (err; nothing is enqueued, the argument and its value are
+ * named): a handle that is not constructed; one without opacities ("ir_jacobian_spectral_rows needs opacities: ...");
+ * a bin shard or a communicator ("needs the whole spectrum"); dim_T /= nz ('"T" has the wrong input dimension.');
+ * wrong dim1..3 ("jac has the wrong dimension"); nrow < 1; a NULL row_level; a level outside 1..nz+1; both arrays
+ * NULL; a temperature that is not finite and positive; a work buffer above the bound. */
+void radtran_ir_jacobian_spectral_rows(void *ptr, const double *T_surface, const int *dim_T, const double *T,
+                                       const int *nrow, const int *row_level,
+                                       const int *dim1, const int *dim2, const int *dim3,
+                                       double *jac_up_a, double *jac_dn_a, char *err);
 /* clima/fortran/Radtran.f90:41-75 (same names and argument lists): the YAML text of
  * OpticalProperties_opacities2yaml (src/radtran/clima_radtran_types.f90:328-430).  _1 allocates
  * the string and returns its length, _2 copies it into out_c (out_len + 1 chars) and frees it.
@@ -568,6 +598,13 @@ void clima_test_solar_batch_cases_per_block(const int *ncol, int *cases);
 void clima_test_ir_response(const int *nz, const int *ng, const double *tau, const double *w0, const double *g,
                             const double *ir_par, const double *wbin, const int *ndev, const int *dev_k,
                             const double *dev_db, double *resp_up, double *resp_dn, char *err);
+/* The same for the adjoint rows of radtran_ir_jacobian_spectral_rows (ir_adjoint.inc): the column of
+ * clima_test_two_stream as one IR bin and nrow levels (0..nz, TOA-first) -> dfup(a, k) = d fup(level(a)) / d bplanck(k)
+ * and dfdn likewise, (nrow, nz+1) row after row, k TOA-first, summed over the g-points with the weights wbin -- produced
+ * by the production kernels (k_adjoint_rows, k_adjoint_sum) with unit amplitudes.  nz >= 1. */
+void clima_test_ir_adjoint(const int *nz, const int *ng, const double *tau, const double *w0, const double *g,
+                           const double *ir_par, const double *wbin, const int *nrow, const int *level,
+                           double *dfup, double *dfdn, char *err);
 
 /* The far accumulation of the response form has two kernels: 0 (default) the matrix-core one (v_mfma_f64_16x16x4_f64),
  * 1 the vector one it replaced.  Process-wide; tests hold the two against each other. */
