@@ -207,6 +207,7 @@ struct Radtran {
   PinnedBuf<char> h_green;         // what the host hands the response form (base profile, deviation lists)
   DevBuf<int> d_green_idx;
   DevBuf<double> d_adjoint;        // the adjoint rows' work buffer (radtran_ir_jacobian_spectral_rows, ir_adjoint.inc)
+  DevBuf<double> d_rows_w, d_rows_out;   // radtran_ir_spectra_batch: the weights of both directions; a chunk's spectra and sums
   // illumination cases on the stored opacities (radtran_radiate_solar_batch): the cases' inputs, the spectra of the cases
   // in flight, a place for the per-case form's copy of the band optical depth
   DevBuf<double> d_sb_in, d_sb_spec, d_sb_band;
@@ -306,8 +307,8 @@ struct Radtran {
   struct Ev { hipEvent_t a, b; int id; };
   std::vector<Ev> pending;
   std::vector<hipEvent_t> pool;
-  double k_ms[4] = {0, 0, 0, 0};
-  int k_n[4] = {0, 0, 0, 0};
+  double k_ms[6] = {0, 0, 0, 0, 0, 0};
+  int k_n[6] = {0, 0, 0, 0, 0, 0};
 
   ~Radtran() {
     for (auto *x : k) delete x;
@@ -2658,6 +2659,163 @@ void radtran_ir_jacobian_spectral_rows(void *ptr, const double *T_surface, const
   CATCH(err)
 }
 
+// `count` doubles from device memory into the caller's array through the handle's pinned block; a large array in pieces,
+// the host copying piece i out while piece i + 1 is still on the link (bout_to_host's way).  Returns when all are there.
+static void rows_to_host(Radtran *r, const double *d_src, double *dst, size_t count) {
+  if (!count) return;
+  double *const h = r->h_bout.reserve(count);
+  const int npiece = count < 32768 ? 1 : 6;
+  const size_t piece = (count + npiece - 1) / npiece;
+  for (auto &e : r->bout_ev)
+    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  for (int k = 0; k < npiece; k++) {
+    const size_t lo = std::min(count, (size_t)k * piece), hi = std::min(count, lo + piece);
+    if (hi > lo) HIPCHK(hipMemcpyAsync(h + lo, d_src + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
+    HIPCHK(hipEventRecord(r->bout_ev[k], r->stream));
+  }
+  for (int k = 0; k < npiece; k++) {
+    const size_t lo = std::min(count, (size_t)k * piece), hi = std::min(count, lo + piece);
+    HIPCHK(hipEventSynchronize(r->bout_ev[k]));
+    if (hi > lo) std::memcpy(dst + lo, h + lo, sizeof(double) * (hi - lo));
+  }
+}
+
+// Per-bin IR spectra (and their sums over the bins) of many temperature profiles on the stored opacities, at requested
+// levels: ONE adjoint pass with unit amplitudes gives the weights W of every requested (level, direction) (ir_adjoint.inc),
+// after which a column is W times its Planck values (ir_rows_apply.inc) -- no solve per column.
+// include/clima_radtran_hip.h has the contract.
+constexpr int IR_ROWS_CHUNK = 512;                     // columns per launch (radtran_radiate_solar_batch's)
+constexpr double IR_ROWS_CHUNK_BYTES = 268435456.0;    // ... fewer where their spectra would take more than this
+void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surface, const int *dim1_T, const int *dim2_T,
+                              const double *T, const int *nsel_, const int *spec_level, double *ir_fup, double *ir_fdn,
+                              double *fup_n, double *fdn_n, double *w_up, double *w_dn, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const int nz = r->nz, nl = nz + 1, nw_ir = r->ir.nw, n = *ncol, nsel = *nsel_;
+  const std::string pre = "ir_spectra_batch: ";
+  if (n < 0) { set_err(err, pre + "ncol must not be negative (ncol = " + std::to_string(n) + ")"); return; }
+  if (*dim1_T != nz || *dim2_T != n) { set_err(err, "\"T\" has the wrong input dimension."); return; }
+  if (nsel < 1) { set_err(err, pre + "nsel must be at least 1 (nsel = " + std::to_string(nsel) + ")"); return; }
+  if (!spec_level) { set_err(err, pre + "\"spec_level\" is a required argument"); return; }
+  const bool up = ir_fup || fup_n || w_up, dn = ir_fdn || fdn_n || w_dn;
+  if (!up && !dn) { set_err(err, pre + "none of ir_fup, ir_fdn, fup_n, fdn_n, w_up, w_dn was given"); return; }
+  const int ndir = (up ? 1 : 0) + (dn ? 1 : 0), nfun = nsel * ndir;
+  std::vector<int> fun((size_t)nfun);
+  for (int a = 0; a < nsel; a++) {
+    const int v = spec_level[a];
+    if (v < 1 || v > nl) {
+      set_err(err, pre + "spec_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
+      return;
+    }
+    int f = a * ndir;
+    if (up) fun[f++] = 2 * (nz - (v - 1));
+    if (dn) fun[f] = 2 * (nz - (v - 1)) + 1;
+  }
+  if (n == 0 && (ir_fup || ir_fdn || fup_n || fdn_n)) {
+    set_err(err, pre + "ncol = 0 gives the weights alone, but " + (ir_fup ? "ir_fup" : ir_fdn ? "ir_fdn" : fup_n ? "fup_n" : "fdn_n") + " was asked for");
+    return;
+  }
+  if (n > 0) {
+    if (!T) { set_err(err, pre + "\"T\" is a required argument (ncol = " + std::to_string(n) + ")"); return; }
+    if (!T_surface) { set_err(err, pre + "\"T_surface\" is a required argument (ncol = " + std::to_string(n) + ")"); return; }
+    for (int c = 0; c < n; c++) {
+      if (!(std::isfinite(T_surface[c]) && T_surface[c] > 0.0)) {
+        set_err(err, pre + "temperatures must be finite and positive (T_surface(" + std::to_string(c + 1) + ") = " + std::to_string(T_surface[c]) + ")");
+        return;
+      }
+      for (int i = 0; i < nz; i++) {
+        const double v = T[(size_t)c * nz + i];
+        if (!(std::isfinite(v) && v > 0.0)) {
+          set_err(err, pre + "temperatures must be finite and positive (T(" + std::to_string(i + 1) + ", " + std::to_string(c + 1) + ") = " + std::to_string(v) + ")");
+          return;
+        }
+      }
+    }
+  }
+  if (r->shard_world != 1 || r->comm) {
+    const std::string shard = r->shard_world != 1 ? "a bin shard of " + std::to_string(r->shard_world) : "";
+    set_err(err, pre + "needs the whole spectrum (" + shard + (r->comm ? (shard.empty() ? "a communicator" : ", a communicator") : "") + ")");
+    return;
+  }
+  if (refuse(r, "ir_spectra_batch", NEED_OPACITIES, err)) return;
+  const int NQ = r->ir_n * r->ng;
+  const size_t n_work = ir_adjoint_work_count(nz, NQ, nfun), n_part = ir_adjoint_part_count(nz, NQ, nfun);
+  if (sizeof(double) * ((double)n_work + (double)n_part) > IR_ADJOINT_MAX_BYTES) {
+    set_err(err, pre + "the work buffer of nsel = " + std::to_string(nsel) + " levels in " + std::to_string(ndir) + " direction(s) would take " +
+                     std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " + std::to_string((long long)IR_ADJOINT_MAX_BYTES) +
+                     ": ask for fewer levels per call");
+    return;
+  }
+  TRY
+  ready_stored_opacities(r);
+  // the weights: (nw_ir, nsel, nz+1) per direction asked for, up before down
+  const size_t arr_w = (size_t)nw_ir * nsel * nl;
+  r->d_rows_w.reserve(std::max<size_t>(1, ndir * arr_w));
+  double *const d_w_up = up ? r->d_rows_w.p : nullptr, *const d_w_dn = dn ? r->d_rows_w.p + (up ? arr_w : 0) : nullptr;
+  if (r->ir_n > 0) {
+    int *hi = reinterpret_cast<int *>(green_stage(r, sizeof(int) * nfun));
+    std::copy(fun.begin(), fun.end(), hi);
+    r->d_green_idx.reserve(nfun); r->d_adjoint.reserve(n_work + n_part);
+    HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * nfun, hipMemcpyHostToDevice, r->stream));
+    IrAdjointParams p;
+    std::memset(&p, 0, sizeof(p));
+    GreenParams &g = p.g;
+    g.nz = nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
+    g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
+    g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
+    g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
+    g.base_T = nullptr;      // unit amplitudes: the rows are the weights themselves
+    p.nfun = nfun; p.nrow = nsel; p.ndir = ndir; p.dir0 = up ? 0 : 1; p.fun = r->d_green_idx.p;
+    p.work = r->d_adjoint.p; p.part = p.work + n_work;
+    p.out_up = d_w_up; p.out_dn = d_w_dn;
+    KernelTimer t(r, 4);
+    launch_ir_adjoint(p, r->stream);
+    HIPCHK(hipGetLastError());
+    t.stop();
+  }
+  if (w_up) rows_to_host(r, d_w_up, w_up, arr_w);
+  if (w_dn) rows_to_host(r, d_w_dn, w_dn, arr_w);
+  if (n > 0) {
+    r->d_bT.reserve((size_t)n * nz); r->d_bTs.reserve(n);
+    HIPCHK(hipMemcpyAsync(r->d_bT.p, T, sizeof(double) * (size_t)n * nz, hipMemcpyHostToDevice, r->stream));
+    HIPCHK(hipMemcpyAsync(r->d_bTs.p, T_surface, sizeof(double) * n, hipMemcpyHostToDevice, r->stream));
+    // columns per launch: bounds the spectra held in device memory
+    int CH = std::min(n, IR_ROWS_CHUNK);
+    while (CH > 1 && sizeof(double) * (double)ndir * nw_ir * nsel * CH > IR_ROWS_CHUNK_BYTES) CH = (CH + 1) / 2;
+    const size_t spec = (size_t)nw_ir * nsel, sums = (size_t)nsel;      // per column and direction
+    r->d_rows_out.reserve(std::max<size_t>(1, (size_t)ndir * (spec + sums) * CH));
+    double *const outs[2] = {up ? ir_fup : ir_fdn, dn && up ? ir_fdn : nullptr};
+    double *const fns[2] = {up ? fup_n : fdn_n, dn && up ? fdn_n : nullptr};
+    for (int c0 = 0; c0 < n; c0 += CH) {
+      const int nc = std::min(CH, n - c0);
+      double *const d_spec = r->d_rows_out.p, *const d_sum = d_spec + (size_t)ndir * spec * nc;
+      if (r->ir_n > 0) {
+        IrRowsApplyParams q;
+        std::memset(&q, 0, sizeof(q));
+        q.n_ir = r->ir_n; q.nsel = nsel; q.nz = nz; q.ncol = nc; q.ndir = ndir;
+        q.l0 = r->ir.ind_start + r->ir_lo; q.ir_lo = r->ir_lo;
+        q.freq = r->d_freq.p; q.ir_freq = r->ir.d_freq.p;
+        q.T = r->d_bT.p + (size_t)c0 * nz; q.Ts = r->d_bTs.p + c0;
+        q.w0 = r->d_rows_w.p; q.w1 = ndir == 2 ? r->d_rows_w.p + arr_w : nullptr;
+        q.out0 = d_spec; q.out1 = ndir == 2 ? d_spec + spec * nc : nullptr;
+        q.fn0 = fns[0] ? d_sum : nullptr; q.fn1 = fns[1] ? d_sum + sums * nc : nullptr;
+        KernelTimer t(r, 5);
+        launch_ir_rows_apply(q, r->stream);
+        HIPCHK(hipGetLastError());
+        t.stop();
+      } else {
+        HIPCHK(hipMemsetAsync(d_sum, 0, sizeof(double) * ndir * sums * nc, r->stream));   // (no IR bins: empty spectra, sums of nothing)
+      }
+      for (int d = 0; d < ndir; d++) {
+        if (outs[d]) rows_to_host(r, d_spec + (size_t)d * spec * nc, outs[d] + spec * c0, spec * nc);
+        if (fns[d]) rows_to_host(r, d_sum + (size_t)d * sums * nc, fns[d] + sums * c0, sums * nc);
+      }
+    }
+  }
+  HIPCHK(hipStreamSynchronize(r->stream));
+  CATCH(err)
+}
+
 // What every column batch refuses before anything else, with the texts of radtran_toa_fluxes_batch
 static bool batch_refused(Radtran *r, const int *ncol, const int *has_particles, char *err) {
   if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return true; }
@@ -3328,13 +3486,13 @@ void radtran_profile_stride_set(void *ptr, const int *stride) {
 void radtran_profile_reset(void *ptr) {
   Radtran *r = as_rad(ptr);
   if (!r) return;
-  for (int i = 0; i < 4; i++) { r->k_ms[i] = 0; r->k_n[i] = 0; }
+  for (int i = 0; i < 6; i++) { r->k_ms[i] = 0; r->k_n[i] = 0; }
   r->timer_calls = r->profile_stride - 1;  // with a sampling stride, the next call is a sampled one
 }
 void radtran_kernel_time_get(void *ptr, const int *kernel_id, double *ms_total, int *launches, char *err) {
   clear_err(err);
   GUARD(r, ptr, err);
-  if (*kernel_id < 0 || *kernel_id > 3) { set_err(err, "kernel id out of range"); return; }
+  if (*kernel_id < 0 || *kernel_id > 5) { set_err(err, "kernel id out of range"); return; }
   TRY
   if (!r->pending.empty()) { HIPCHK(hipStreamSynchronize(r->stream)); resolve_events(r); }
   *ms_total = r->k_ms[*kernel_id];

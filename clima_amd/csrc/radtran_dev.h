@@ -554,6 +554,20 @@ __host__ __device__ inline size_t adjoint_work_rows(int nfun) { return 4 + (size
 inline size_t ir_adjoint_work_count(int nz, int NQ, int nfun) { return (size_t)NQ * adjoint_work_rows(nfun) * 2 * nz; }
 inline size_t ir_adjoint_part_count(int nz, int NQ, int nfun) { return (size_t)NQ * nfun * (nz + 1); }
 void launch_ir_adjoint(const IrAdjointParams &p, hipStream_t s);
+// IR spectra of many temperature profiles from the adjoint's unit-amplitude rows (ir_rows_apply.inc,
+// radtran_ir_spectra_batch): f(bin, a, c) = sum over j of w(bin, a, j) B(avg_freq(bin), x_c(j)).  The ndir directions
+// asked for stand at places 0 and 1 (w0 / out0 / fn0, then w1 / out1 / fn1); functional F = place nsel + a.
+struct IrRowsApplyParams {
+  int n_ir, nsel, nz, ncol, ndir, F0;      // F0: the pass's first functional (the launcher's)
+  int l0, ir_lo;                           // opacity-grid bin of the first IR bin here; its place in the IR channel
+  const double *freq, *ir_freq;            // opacity grid [nw+1], IR channel [nw_ir+1]
+  const double *T, *Ts;                    // (nz, ncol) ground-first layers, (ncol)
+  const double *w0, *w1;                   // (n_ir, nsel, nz+1), the bin fastest, j ground-first
+  double *out0, *out1;                     // (n_ir, nsel, ncol)
+  double *fn0, *fn1;                       // (nsel, ncol): out summed over the bins times their widths (null: not asked for)
+};
+void launch_ir_rows_apply(const IrRowsApplyParams &p, hipStream_t s);
+int ir_rows_column_tile(int ncol);         // the launcher's rule: columns per wave
 int green_far_resident_waves();
 void green_vector_form_set(int vector_form);   // test hook: the far accumulation's vector form (1) or matrix form (0)
 int green_far_waves(int ndev, int nl);   // per bin split

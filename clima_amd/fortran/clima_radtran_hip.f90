@@ -85,6 +85,7 @@ module clima_radtran_hip
     procedure :: ir_jacobian => Radtran_ir_jacobian
     procedure :: ir_jacobian_reduced => Radtran_ir_jacobian_reduced
     procedure :: ir_jacobian_spectral_rows => Radtran_ir_jacobian_spectral_rows
+    procedure :: ir_spectra_batch => Radtran_ir_spectra_batch
     procedure :: TOA_fluxes_batch => Radtran_TOA_fluxes_batch
     procedure :: TOA_fluxes_batch_spectra => Radtran_TOA_fluxes_batch_spectra
     procedure :: TOA_fluxes_batch_bounds => Radtran_TOA_fluxes_batch_bounds
@@ -247,6 +248,14 @@ module clima_radtran_hip
       integer(c_int), intent(in) :: dim_T, nrow, dim1, dim2, dim3, row_level(*)
       real(c_double), intent(in) :: T_surface, T(*)
       type(c_ptr), value :: jac_up_a, jac_dn_a     ! (c_null_ptr: not wanted)
+      character(c_char), intent(out) :: err(*)
+    end subroutine
+    subroutine c_radtran_ir_spectra_batch(ptr, ncol, T_surface, dim1_T, dim2_T, T, nsel, spec_level, ir_fup, ir_fdn, &
+                                          fup_n, fdn_n, w_up, w_dn, err) bind(c, name="radtran_ir_spectra_batch")
+      import; type(c_ptr), value :: ptr
+      integer(c_int), intent(in) :: ncol, dim1_T, dim2_T, nsel, spec_level(*)
+      real(c_double), intent(in) :: T_surface(*), T(*)
+      type(c_ptr), value :: ir_fup, ir_fdn, fup_n, fdn_n, w_up, w_dn     ! (c_null_ptr: not wanted)
       character(c_char), intent(out) :: err(*)
     end subroutine
     subroutine c_radtran_opacities2yaml_wrapper_1(ptr, out_len, out_cp) bind(c, name="radtran_opacities2yaml_wrapper_1")
@@ -1152,6 +1161,58 @@ contains
     endif
     call c_radtran_ir_jacobian_spectral_rows(self%handle, T_surface, size(T), T, size(row_level), row_level, &
                                              dims(1), dims(2), dims(3), p_up, p_dn, err_c)
+    call take_err(err_c, err)
+  end subroutine
+
+  !> Per-bin IR spectra of many temperature profiles on the opacities of the last compute_opacity call, in one go
+  !> (radtran_ir_spectra_batch): column c is `radiate(T_surface(c), T(:,c), ..., compute_solar=.false.,
+  !> compute_opacity=.false.)` read at self%wrk_ir%fup_a / fdn_a (spec_level(a), l), without a solve per column.
+  !> `spec_level`: levels 1..nz+1, ground-first, repeats allowed.  ir_fup_a, ir_fdn_a (nw_ir, nsel, ncol); fup_n, fdn_n
+  !> (nsel, ncol): the spectra summed over the bins times their widths; w_up, w_dn (nw_ir, nsel, nz+1): the weights,
+  !> ir_fup_a(l,a,c) = sum over j of w_up(l,a,j) B(avg_freq(l), x_c(j)), x_c(1) = T_surface(c), x_c(1+m) = T(m,c).  At
+  !> least one of the six must be present; ncol = 0 gives the weights alone.  `self` is not changed.
+  subroutine Radtran_ir_spectra_batch(self, T_surface, T, spec_level, err, ir_fup_a, ir_fdn_a, fup_n, fdn_n, w_up, w_dn)
+    class(Radtran), intent(inout) :: self
+    real(dp), intent(in), contiguous :: T_surface(:)                        !! (ncol)
+    real(dp), intent(in), contiguous :: T(:,:)                              !! (nz, ncol)
+    integer, intent(in), contiguous :: spec_level(:)                        !! (nsel)
+    character(:), allocatable, intent(out) :: err
+    real(dp), intent(out), contiguous, optional, target :: ir_fup_a(:,:,:), ir_fdn_a(:,:,:), w_up(:,:,:), w_dn(:,:,:)
+    real(dp), intent(out), contiguous, optional, target :: fup_n(:,:), fdn_n(:,:)
+    character(c_char) :: err_c(err_len+1)
+    type(c_ptr) :: sink(6)
+    integer :: ncol, nsel, nw_ir
+    ncol = size(T_surface); nsel = size(spec_level)
+    nw_ir = size(self%ir%freq) - 1
+    sink = c_null_ptr
+    if (present(ir_fup_a)) then
+      if (any(shape(ir_fup_a) /= [nw_ir, nsel, ncol])) err = 'ir_spectra_batch: "ir_fup_a" has the wrong dimension'
+      sink(1) = c_loc(ir_fup_a)
+    endif
+    if (present(ir_fdn_a)) then
+      if (any(shape(ir_fdn_a) /= [nw_ir, nsel, ncol])) err = 'ir_spectra_batch: "ir_fdn_a" has the wrong dimension'
+      sink(2) = c_loc(ir_fdn_a)
+    endif
+    if (present(fup_n)) then
+      if (any(shape(fup_n) /= [nsel, ncol])) err = 'ir_spectra_batch: "fup_n" has the wrong dimension'
+      sink(3) = c_loc(fup_n)
+    endif
+    if (present(fdn_n)) then
+      if (any(shape(fdn_n) /= [nsel, ncol])) err = 'ir_spectra_batch: "fdn_n" has the wrong dimension'
+      sink(4) = c_loc(fdn_n)
+    endif
+    if (present(w_up)) then
+      if (any(shape(w_up) /= [nw_ir, nsel, self%nz+1])) err = 'ir_spectra_batch: "w_up" has the wrong dimension'
+      sink(5) = c_loc(w_up)
+    endif
+    if (present(w_dn)) then
+      if (any(shape(w_dn) /= [nw_ir, nsel, self%nz+1])) err = 'ir_spectra_batch: "w_dn" has the wrong dimension'
+      sink(6) = c_loc(w_dn)
+    endif
+    if (allocated(err)) return
+    call push_fields(self)
+    call c_radtran_ir_spectra_batch(self%handle, ncol, T_surface, size(T,1), size(T,2), T, nsel, spec_level, &
+                                    sink(1), sink(2), sink(3), sink(4), sink(5), sink(6), err_c)
     call take_err(err_c, err)
   end subroutine
 

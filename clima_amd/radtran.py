@@ -683,6 +683,69 @@ class Radtran:
         self._check()
         return out
 
+    IR_SPECTRA_BATCH_PARTS = ("up", "dn")
+
+    def _ir_spectra_batch_request(self, nz, T_surface, T, levels, parts, weights):
+        """The arrays of `ir_spectra_batch` as the ABI takes them -- (T_surface (ncol), T (nz, ncol) Fortran-ordered, levels
+        1..nz+1, names in the ABI's order) -- for a handle of nz layers; wrong shapes, unknown parts, levels outside
+        -(nz+1)..nz and a request that names no output are refused by name (reads IR_SPECTRA_BATCH_PARTS alone: no handle
+        needed).  T_surface None with T None: no columns, the weights alone."""
+        who = "ir_spectra_batch: "
+        if T is None and T_surface is None:
+            T, Ts = np.empty((nz, 0), order="F"), np.empty(0)
+        else:
+            T, Ts = np.asfortranarray(T, dtype=np.float64), _c(np.atleast_1d(T_surface))
+        if Ts.ndim != 1:
+            raise ClimaException(who + '"T_surface" has the shape %s, not (ncol,)' % (Ts.shape,))
+        if T.ndim == 1 and len(Ts) == 1:
+            T = np.asfortranarray(T[:, None])
+        if T.shape != (nz, len(Ts)):
+            raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz, len(Ts))))
+        parts = (parts,) if isinstance(parts, str) else tuple(parts)
+        for name in parts:
+            if name not in self.IR_SPECTRA_BATCH_PARTS:
+                raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.IR_SPECTRA_BATCH_PARTS)))
+        if not parts:
+            raise ClimaException(who + '"parts" names none of %s' % ", ".join(self.IR_SPECTRA_BATCH_PARTS))
+        if len(Ts) == 0 and not weights:
+            raise ClimaException(who + "no columns and weights=False: nothing is asked for")
+        nl = nz + 1
+        idx = np.atleast_1d(np.asarray(levels))
+        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+            raise ClimaException(who + '"levels" is not a non-empty list of integer level indices')
+        for a, v in enumerate(idx.tolist()):
+            if v < -nl or v >= nl:
+                raise ClimaException(who + "levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
+        rows = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
+        return Ts, T, rows, tuple(name for name in self.IR_SPECTRA_BATCH_PARTS if name in parts)
+
+    def ir_spectra_batch(self, T_surface, T, levels=(-1,), parts=("up",), fluxes=False, weights=False):
+        """Per-bin IR spectra of many temperature profiles on the stored opacities (radtran_ir_spectra_batch): column c is
+        `radiate(T_surface[c], T[:, c], ..., compute_solar=False, compute_opacity=False)` read at `wrk_ir.fup_a / fdn_a
+        [levels[a], l]`, without a solve per column.  Returns a dict of Fortran-ordered arrays for the directions in `parts`
+        ("up", "dn"): "fup" / "fdn" (nw_ir, nsel, ncol); with `fluxes` also "fup_n" / "fdn_n" (nsel, ncol), the spectra
+        summed over the bins times their widths (`wrk_ir.fup_n[levels[a]]`); with `weights` also "w_up" / "w_dn"
+        (nw_ir, nsel, nz+1), the temperature-independent weights with fup[l, a, c] = sum_j w_up[l, a, j] B(avg_freq[l], x_c[j]),
+        x_c[0] = T_surface[c], x_c[1 + m] = T[m, c].  `levels` are numpy-style indices into the ground-first level axis
+        (-1: the top of the atmosphere, 0: the surface), repeats allowed.  T_surface = T = None with `weights`: the weights
+        alone.  One adjoint pass per call, then Planck values and FMAs per column; the handle's state is left untouched."""
+        Ts, T, rows, names = self._ir_spectra_batch_request(self.nz, T_surface, T, levels, parts, weights)
+        nw_ir, nsel, nl, n = len(self.ir.freq) - 1, len(rows), self.nz + 1, len(Ts)
+        out = {}
+        for name in names:
+            if n > 0:
+                out["f" + name] = np.empty((nw_ir, nsel, n), order="F")
+                if fluxes:
+                    out["f%s_n" % name] = np.empty((nsel, n), order="F")
+            if weights:
+                out["w_" + name] = np.empty((nw_ir, nsel, nl), order="F")
+        ptr = lambda key: _d(out[key]) if key in out else None   # noqa: E731
+        self._L.radtran_ir_spectra_batch(
+            self._ptr, _i(n), _d(Ts), _i(T.shape[0]), _i(n), _d(T), _i(nsel), rows.ctypes.data_as(C.POINTER(C.c_int)),
+            ptr("fup"), ptr("fdn"), ptr("fup_n"), ptr("fdn_n"), ptr("w_up"), ptr("w_dn"), self._err)
+        self._check()
+        return out
+
     # ---- HBM-resident form (bench / batched callers)
     def upload_column(self, T_surface, T, P, densities, dz, pdensities=None, radii=None):
         T, P, dz, densities = _c(T), _c(P), _c(dz), _fo(densities)

@@ -397,6 +397,48 @@ void radtran_ir_jacobian_spectral_rows(void *ptr, const double *T_surface, const
                                        const int *nrow, const int *row_level,
                                        const int *dim1, const int *dim2, const int *dim3,
                                        double *jac_up_a, double *jac_dn_a, char *err);
+/* Per-bin IR spectra of MANY temperature profiles on the stored opacities, at chosen levels: column c is
+ * radiate(T_surface(c), T(:, c), ..., compute_solar = .false., compute_opacity = .false.) read at wrk_ir%fup_a / fdn_a
+ * (spec_level(a), l) -- day / night or latitude profiles of one atmosphere, a Monte-Carlo spread of a retrieved T(p), an
+ * OLR(T_surface) sweep at fixed opacity -- without a solve per column.
+ *   T (nz, ncol) column-major, T_surface (ncol): as in radtran_radiate_ir_batch; dim1_T = nz, dim2_T = ncol
+ *   spec_level (nsel):  levels 1..nz+1, ground-first, any order, repeats allowed (the spectra batches' convention)
+ *   ir_fup, ir_fdn (nw_ir, nsel, ncol): the bin fastest and in rtchannel_freq_get order; element (l, a, c) is
+ *                       wrk_ir%fup_a(spec_level(a), l) (fdn_a likewise) of column c, in its units, to rounding (another
+ *                       algorithm than the single call's)
+ *   fup_n, fdn_n (nsel, ncol): sum over l of ir_fup(l, a, c) (freq(l) - freq(l+1)), summed on the device in ascending l:
+ *                       wrk_ir%fup_n(spec_level(a)) to rounding; available without ir_fup being given
+ *   w_up, w_dn (nw_ir, nsel, nz+1): the weights, j ground-first in radtran_ir_jacobian's x order (x(1) = T_surface,
+ *                       x(1+m) = T(m)):  ir_fup(l, a, c) = sum over j of w_up(l, a, j) B(avg_freq(l), x_c(j)) with B the
+ *                       library's planck_fcn -- the temperature-independent weighting function of the emission spectrum
+ * Any of the six outputs may be NULL, not all; the up direction is solved only if an up output is asked for, down
+ * likewise.  ncol = 0 is allowed when only w_* are asked for (T and T_surface are then unread).
+ * Method: at fixed opacities two_stream_ir is homogeneously linear in the Planck values of the levels (the surface term,
+ * both surface forms and the thin-layer source rule included), so a level flux of a bin is a fixed row of weights times
+ * Planck values.  The weights are radtran_ir_jacobian_spectral_rows' adjoint rows with unit amplitudes: ONE adjoint
+ * pass per call (clima_amd/csrc/ir_adjoint.inc), then nw_ir (nz+1) Planck evaluations and as many FMAs per requested
+ * row and column (clima_amd/csrc/ir_rows_apply.inc).  Contract:
+ *   the dn outputs of level nz+1 are exactly 0.0 (w_dn too);
+ *   a column's results do not depend on ncol or on the other columns, bit for bit;
+ *   the call is bitwise repeatable (no atomics, fixed summation orders: j ascending, then l ascending);
+ *   w_up(l, a, j) dB/dT(avg_freq(l), x(j)) is radtran_ir_jacobian_spectral_rows' jac_up_a(l, a, j) at the same T, to
+ *   rounding; the same for dn;
+ *   without a hard surface the emissivity is not read; the zenith weights are not read, as in the library's IR solve.
+ * Synchronous, host arrays; columns run in chunks of at most 512 (fewer where a chunk's spectra would exceed 256 MiB) and
+ * results come back through the handle's pinned block.  The handle's wrk_ir, wrk_sol, f_total, spectra, stored
+ * opacities and fields are left untouched; a pending deferred integration is settled first.  Every nz >= 1 and every
+ * g-point count of the single call.  Refused (err; nothing is enqueued, the argument and its value are named): a handle
+ * that is not constructed; one without opacities ("ir_spectra_batch needs opacities: ..."); a bin shard or a
+ * communicator ("needs the whole spectrum"); dim1_T /= nz or dim2_T /= ncol ('"T" has the wrong input dimension.');
+ * ncol < 0; ncol = 0 with a flux output asked for; nsel < 1; a NULL spec_level; a level outside 1..nz+1
+ * ("spec_level(2) = 0 is outside 1..51"); all six outputs NULL; a NULL T or T_surface with ncol > 0; a temperature that
+ * is not finite and positive ("T(i, c) = ..." or "T_surface(c) = ..."); an adjoint work buffer above
+ * radtran_ir_jacobian_spectral_rows' 4 GiB bound. */
+void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surface,
+                              const int *dim1_T, const int *dim2_T, const double *T,
+                              const int *nsel, const int *spec_level,
+                              double *ir_fup, double *ir_fdn, double *fup_n, double *fdn_n,
+                              double *w_up, double *w_dn, char *err);
 /* clima/fortran/Radtran.f90:41-75 (same names and argument lists): the YAML text of
  * OpticalProperties_opacities2yaml (src/radtran/clima_radtran_types.f90:328-430).  _1 allocates
  * the string and returns its length, _2 copies it into out_c (out_len + 1 chars) and frees it.
@@ -523,7 +565,8 @@ void radtran_stream_get(void *ptr, void **stream);
 /* per-kernel device time (HIP events on the handle's stream).  enable = 1 records events
  * around every kernel, enable = 2 around the dominant kernel (id 1, opacity) only, 0 turns
  * them off; kernel_time_get returns accumulated ms and launch count for kernel id
- * (0 prep, 1 opacity, 2 twostream, 3 integrate) and resets nothing. */
+ * (0 prep, 1 opacity, 2 twostream, 3 integrate; of radtran_ir_spectra_batch: 4 the weights' adjoint pass, 5 the
+ * apply and integrate kernels of all its chunks) and resets nothing. */
 void radtran_profile_set(void *ptr, const int *enable);
 /* record the events on every stride-th call only (default 1): an event pair drains the queue for a
  * few microseconds, which a throughput measurement should not pay on every call */
