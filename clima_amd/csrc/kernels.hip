@@ -3755,6 +3755,9 @@ void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s) {
 #ifndef CLIMA_WITHOUT_IR_ROWS_APPLY   // (tests/test_ir_spectra_batch_abi.py: the other kernels' assembly with and without it)
 #include "ir_rows_apply.inc"
 #endif
+#ifndef CLIMA_WITHOUT_IR_ROWS_VJP     // (tests/test_ir_spectra_vjp_abi.py: the same)
+#include "ir_rows_vjp.inc"
+#endif
 #else
 // The bounds blocks of a batch out of device arrays: column blockIdx.y, one element per thread (bounds_element: the
 // host's pack_bounds takes the same values the same way, so the blocks are bit for bit the host's).

@@ -307,8 +307,8 @@ struct Radtran {
   struct Ev { hipEvent_t a, b; int id; };
   std::vector<Ev> pending;
   std::vector<hipEvent_t> pool;
-  double k_ms[6] = {0, 0, 0, 0, 0, 0};
-  int k_n[6] = {0, 0, 0, 0, 0, 0};
+  double k_ms[7] = {0, 0, 0, 0, 0, 0, 0};
+  int k_n[7] = {0, 0, 0, 0, 0, 0, 0};
 
   ~Radtran() {
     for (auto *x : k) delete x;
@@ -2686,6 +2686,71 @@ static void rows_to_host(Radtran *r, const double *d_src, double *dst, size_t co
 // include/clima_radtran_hip.h has the contract.
 constexpr int IR_ROWS_CHUNK = 512;                     // columns per launch (radtran_radiate_solar_batch's)
 constexpr double IR_ROWS_CHUNK_BYTES = 268435456.0;    // ... fewer where their spectra would take more than this
+// the functionals of the requested levels (fun[a ndir + place] = 2 (level from the top) + (0 up | 1 down)); false, and
+// the level named in `err`, where one lies outside 1..nz+1
+static bool ir_rows_functionals(const std::string &pre, int nz, int nsel, const int *spec_level, bool up, bool dn, std::vector<int> &fun, char *err) {
+  const int nl = nz + 1, ndir = (up ? 1 : 0) + (dn ? 1 : 0);
+  fun.assign((size_t)nsel * ndir, 0);
+  for (int a = 0; a < nsel; a++) {
+    const int v = spec_level[a];
+    if (v < 1 || v > nl) {
+      set_err(err, pre + "spec_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
+      return false;
+    }
+    int f = a * ndir;
+    if (up) fun[f++] = 2 * (nz - (v - 1));
+    if (dn) fun[f] = 2 * (nz - (v - 1)) + 1;
+  }
+  return true;
+}
+// the adjoint work buffer of nsel levels in ndir directions: false, and its size in `err`, where it passes IR_ADJOINT_MAX_BYTES
+static bool ir_rows_work_fits(Radtran *r, const std::string &pre, int nsel, int ndir, char *err) {
+  const int NQ = r->ir_n * r->ng, nfun = nsel * ndir;
+  const size_t n_work = ir_adjoint_work_count(r->nz, NQ, nfun), n_part = ir_adjoint_part_count(r->nz, NQ, nfun);
+  if (sizeof(double) * ((double)n_work + (double)n_part) <= IR_ADJOINT_MAX_BYTES) return true;
+  set_err(err, pre + "the work buffer of nsel = " + std::to_string(nsel) + " levels in " + std::to_string(ndir) + " direction(s) would take " +
+                   std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " + std::to_string((long long)IR_ADJOINT_MAX_BYTES) +
+                   ": ask for fewer levels per call");
+  return false;
+}
+// The weights of the stored opacities: one adjoint pass with unit amplitudes into d_w_up / d_w_dn ((nw_ir, nsel, nz+1) each;
+// null: the direction is not among `fun`).  Enqueued on the handle's stream, behind ready_stored_opacities; kernel id 4.
+static void ir_rows_weights(Radtran *r, const std::vector<int> &fun, int nsel, int ndir, bool up, double *d_w_up, double *d_w_dn) {
+  if (r->ir_n < 1) return;
+  const int nz = r->nz, NQ = r->ir_n * r->ng, nfun = nsel * ndir;
+  const size_t n_work = ir_adjoint_work_count(nz, NQ, nfun), n_part = ir_adjoint_part_count(nz, NQ, nfun);
+  int *hi = reinterpret_cast<int *>(green_stage(r, sizeof(int) * nfun));
+  std::copy(fun.begin(), fun.end(), hi);
+  r->d_green_idx.reserve(nfun); r->d_adjoint.reserve(n_work + n_part);
+  HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * nfun, hipMemcpyHostToDevice, r->stream));
+  IrAdjointParams p;
+  std::memset(&p, 0, sizeof(p));
+  GreenParams &g = p.g;
+  g.nz = nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
+  g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
+  g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
+  g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
+  g.base_T = nullptr;      // unit amplitudes: the rows are the weights themselves
+  p.nfun = nfun; p.nrow = nsel; p.ndir = ndir; p.dir0 = up ? 0 : 1; p.fun = r->d_green_idx.p;
+  p.work = r->d_adjoint.p; p.part = p.work + n_work;
+  p.out_up = d_w_up; p.out_dn = d_w_dn;
+  KernelTimer t(r, 4);
+  launch_ir_adjoint(p, r->stream);
+  HIPCHK(hipGetLastError());
+  t.stop();
+}
+// nc columns (d_T, d_Ts) times the weights w0 / w1 of the ndir directions; the caller adds out0 / out1 and fn0 / fn1
+static IrRowsApplyParams ir_rows_apply_params(Radtran *r, int nsel, int ndir, int nc, const double *d_T, const double *d_Ts,
+                                              const double *w0, const double *w1) {
+  IrRowsApplyParams q;
+  std::memset(&q, 0, sizeof(q));
+  q.n_ir = r->ir_n; q.nsel = nsel; q.nz = r->nz; q.ncol = nc; q.ndir = ndir;
+  q.l0 = r->ir.ind_start + r->ir_lo; q.ir_lo = r->ir_lo;
+  q.freq = r->d_freq.p; q.ir_freq = r->ir.d_freq.p;
+  q.T = d_T; q.Ts = d_Ts;
+  q.w0 = w0; q.w1 = w1;
+  return q;
+}
 void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surface, const int *dim1_T, const int *dim2_T,
                               const double *T, const int *nsel_, const int *spec_level, double *ir_fup, double *ir_fdn,
                               double *fup_n, double *fdn_n, double *w_up, double *w_dn, char *err) {
@@ -2699,18 +2764,9 @@ void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surfac
   if (!spec_level) { set_err(err, pre + "\"spec_level\" is a required argument"); return; }
   const bool up = ir_fup || fup_n || w_up, dn = ir_fdn || fdn_n || w_dn;
   if (!up && !dn) { set_err(err, pre + "none of ir_fup, ir_fdn, fup_n, fdn_n, w_up, w_dn was given"); return; }
-  const int ndir = (up ? 1 : 0) + (dn ? 1 : 0), nfun = nsel * ndir;
-  std::vector<int> fun((size_t)nfun);
-  for (int a = 0; a < nsel; a++) {
-    const int v = spec_level[a];
-    if (v < 1 || v > nl) {
-      set_err(err, pre + "spec_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
-      return;
-    }
-    int f = a * ndir;
-    if (up) fun[f++] = 2 * (nz - (v - 1));
-    if (dn) fun[f] = 2 * (nz - (v - 1)) + 1;
-  }
+  const int ndir = (up ? 1 : 0) + (dn ? 1 : 0);
+  std::vector<int> fun;
+  if (!ir_rows_functionals(pre, nz, nsel, spec_level, up, dn, fun, err)) return;
   if (n == 0 && (ir_fup || ir_fdn || fup_n || fdn_n)) {
     set_err(err, pre + "ncol = 0 gives the weights alone, but " + (ir_fup ? "ir_fup" : ir_fdn ? "ir_fdn" : fup_n ? "fup_n" : "fdn_n") + " was asked for");
     return;
@@ -2738,41 +2794,14 @@ void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surfac
     return;
   }
   if (refuse(r, "ir_spectra_batch", NEED_OPACITIES, err)) return;
-  const int NQ = r->ir_n * r->ng;
-  const size_t n_work = ir_adjoint_work_count(nz, NQ, nfun), n_part = ir_adjoint_part_count(nz, NQ, nfun);
-  if (sizeof(double) * ((double)n_work + (double)n_part) > IR_ADJOINT_MAX_BYTES) {
-    set_err(err, pre + "the work buffer of nsel = " + std::to_string(nsel) + " levels in " + std::to_string(ndir) + " direction(s) would take " +
-                     std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " + std::to_string((long long)IR_ADJOINT_MAX_BYTES) +
-                     ": ask for fewer levels per call");
-    return;
-  }
+  if (!ir_rows_work_fits(r, pre, nsel, ndir, err)) return;
   TRY
   ready_stored_opacities(r);
   // the weights: (nw_ir, nsel, nz+1) per direction asked for, up before down
   const size_t arr_w = (size_t)nw_ir * nsel * nl;
   r->d_rows_w.reserve(std::max<size_t>(1, ndir * arr_w));
   double *const d_w_up = up ? r->d_rows_w.p : nullptr, *const d_w_dn = dn ? r->d_rows_w.p + (up ? arr_w : 0) : nullptr;
-  if (r->ir_n > 0) {
-    int *hi = reinterpret_cast<int *>(green_stage(r, sizeof(int) * nfun));
-    std::copy(fun.begin(), fun.end(), hi);
-    r->d_green_idx.reserve(nfun); r->d_adjoint.reserve(n_work + n_part);
-    HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * nfun, hipMemcpyHostToDevice, r->stream));
-    IrAdjointParams p;
-    std::memset(&p, 0, sizeof(p));
-    GreenParams &g = p.g;
-    g.nz = nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
-    g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
-    g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
-    g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
-    g.base_T = nullptr;      // unit amplitudes: the rows are the weights themselves
-    p.nfun = nfun; p.nrow = nsel; p.ndir = ndir; p.dir0 = up ? 0 : 1; p.fun = r->d_green_idx.p;
-    p.work = r->d_adjoint.p; p.part = p.work + n_work;
-    p.out_up = d_w_up; p.out_dn = d_w_dn;
-    KernelTimer t(r, 4);
-    launch_ir_adjoint(p, r->stream);
-    HIPCHK(hipGetLastError());
-    t.stop();
-  }
+  ir_rows_weights(r, fun, nsel, ndir, up, d_w_up, d_w_dn);
   if (w_up) rows_to_host(r, d_w_up, w_up, arr_w);
   if (w_dn) rows_to_host(r, d_w_dn, w_dn, arr_w);
   if (n > 0) {
@@ -2790,13 +2819,8 @@ void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surfac
       const int nc = std::min(CH, n - c0);
       double *const d_spec = r->d_rows_out.p, *const d_sum = d_spec + (size_t)ndir * spec * nc;
       if (r->ir_n > 0) {
-        IrRowsApplyParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.n_ir = r->ir_n; q.nsel = nsel; q.nz = nz; q.ncol = nc; q.ndir = ndir;
-        q.l0 = r->ir.ind_start + r->ir_lo; q.ir_lo = r->ir_lo;
-        q.freq = r->d_freq.p; q.ir_freq = r->ir.d_freq.p;
-        q.T = r->d_bT.p + (size_t)c0 * nz; q.Ts = r->d_bTs.p + c0;
-        q.w0 = r->d_rows_w.p; q.w1 = ndir == 2 ? r->d_rows_w.p + arr_w : nullptr;
+        IrRowsApplyParams q = ir_rows_apply_params(r, nsel, ndir, nc, r->d_bT.p + (size_t)c0 * nz, r->d_bTs.p + c0, r->d_rows_w.p,
+                                                   ndir == 2 ? r->d_rows_w.p + arr_w : nullptr);
         q.out0 = d_spec; q.out1 = ndir == 2 ? d_spec + spec * nc : nullptr;
         q.fn0 = fns[0] ? d_sum : nullptr; q.fn1 = fns[1] ? d_sum + sums * nc : nullptr;
         KernelTimer t(r, 5);
@@ -2811,6 +2835,279 @@ void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surfac
         if (fns[d]) rows_to_host(r, d_sum + (size_t)d * sums * nc, fns[d] + sums * c0, sums * nc);
       }
     }
+  }
+  HIPCHK(hipStreamSynchronize(r->stream));
+  CATCH(err)
+}
+
+// what the spectra batches and their gradient refuse of a handle: a bin shard or a communicator, by name
+static bool ir_rows_shard_refused(Radtran *r, const std::string &pre, char *err) {
+  if (r->shard_world == 1 && !r->comm) return false;
+  const std::string shard = r->shard_world != 1 ? "a bin shard of " + std::to_string(r->shard_world) : "";
+  set_err(err, pre + "needs the whole spectrum (" + shard + (r->comm ? (shard.empty() ? "a communicator" : ", a communicator") : "") + ")");
+  return true;
+}
+// the first of `args` that is given and is not device memory of the handle's device, named in `err` (toa_fluxes_batch_dev's check)
+struct NamedPtr { const char *name; const void *p; };
+static bool ir_rows_not_device(Radtran *r, const std::string &pre, std::initializer_list<NamedPtr> args, char *err) {
+  for (const auto &a : args)
+    if (a.p && !on_handle_device(r, a.p)) {
+      set_err(err, pre + "\"" + a.name + "\" is not device memory of this handle's device");
+      return true;
+    }
+  return false;
+}
+static void wait_for_producer(Radtran *r, const void *producer_stream) {
+  if (!producer_stream) return;
+  if (!r->ev_producer) HIPCHK(hipEventCreateWithFlags(&r->ev_producer, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(r->ev_producer, reinterpret_cast<hipStream_t>(const_cast<void *>(producer_stream))));
+  HIPCHK(hipStreamWaitEvent(r->stream, r->ev_producer, 0));
+}
+constexpr int IR_ROWS_DEVICE_CHUNK = 262144;           // columns per launch of the device forms: what the grids take
+
+// radtran_ir_spectra_batch with every array but spec_level in device memory, the weights kept by the caller
+// (weights_given = 0: computed here, and stored in d_w_up / d_w_dn where given; 1: read from there, no adjoint pass, no
+// opacities needed).  The same two launchers as the host form, writing straight into the caller's arrays; enqueued behind
+// producer_stream, nothing waited for.  include/clima_radtran_hip.h has the contract.
+void radtran_ir_spectra_batch_device(void *ptr, const int *ncol, const double *d_T_surface, const int *dim1_T, const int *dim2_T,
+                                     const double *d_T, const int *nsel_, const int *spec_level, double *d_ir_fup, double *d_ir_fdn,
+                                     double *d_fup_n, double *d_fdn_n, double *d_w_up, double *d_w_dn, const int *weights_given,
+                                     const void *producer_stream, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const int nz = r->nz, nl = nz + 1, nw_ir = r->ir.nw, n = *ncol, nsel = *nsel_;
+  const bool given = weights_given && *weights_given != 0;
+  const std::string pre = "ir_spectra_batch_device: ";
+  if (n < 0) { set_err(err, pre + "ncol must not be negative (ncol = " + std::to_string(n) + ")"); return; }
+  if (*dim1_T != nz || *dim2_T != n) { set_err(err, "\"T\" has the wrong input dimension."); return; }
+  if (nsel < 1) { set_err(err, pre + "nsel must be at least 1 (nsel = " + std::to_string(nsel) + ")"); return; }
+  if (!spec_level) { set_err(err, pre + "\"spec_level\" is a required argument"); return; }
+  const bool flux_up = d_ir_fup || d_fup_n, flux_dn = d_ir_fdn || d_fdn_n;
+  const bool up = flux_up || (!given && d_w_up), dn = flux_dn || (!given && d_w_dn);
+  if (!up && !dn) {
+    set_err(err, pre + (given ? "none of ir_fup, ir_fdn, fup_n, fdn_n was given (weights_given = 1)" : "none of ir_fup, ir_fdn, fup_n, fdn_n, w_up, w_dn was given"));
+    return;
+  }
+  if (given && ((flux_up && !d_w_up) || (flux_dn && !d_w_dn))) {
+    set_err(err, pre + "\"" + (flux_up && !d_w_up ? "w_up" : "w_dn") + "\" is a required argument (weights_given = 1 and its direction is asked for)");
+    return;
+  }
+  const int ndir = (up ? 1 : 0) + (dn ? 1 : 0);
+  std::vector<int> fun;
+  if (!ir_rows_functionals(pre, nz, nsel, spec_level, up, dn, fun, err)) return;
+  if (n == 0 && (flux_up || flux_dn)) {
+    set_err(err, pre + "ncol = 0 gives the weights alone, but " + (d_ir_fup ? "ir_fup" : d_ir_fdn ? "ir_fdn" : d_fup_n ? "fup_n" : "fdn_n") + " was asked for");
+    return;
+  }
+  if (n > 0) {
+    if (!d_T) { set_err(err, pre + "\"T\" is a required argument (ncol = " + std::to_string(n) + ")"); return; }
+    if (!d_T_surface) { set_err(err, pre + "\"T_surface\" is a required argument (ncol = " + std::to_string(n) + ")"); return; }
+  }
+  if (ir_rows_not_device(r, pre, {{"T_surface", n > 0 ? d_T_surface : nullptr}, {"T", n > 0 ? d_T : nullptr}, {"ir_fup", d_ir_fup}, {"ir_fdn", d_ir_fdn},
+                                  {"fup_n", d_fup_n}, {"fdn_n", d_fdn_n}, {"w_up", up ? d_w_up : nullptr}, {"w_dn", dn ? d_w_dn : nullptr}}, err)) return;
+  if (ir_rows_shard_refused(r, pre, err)) return;
+  if (!given) {
+    if (refuse(r, "ir_spectra_batch_device", NEED_OPACITIES, err)) return;
+    if (!ir_rows_work_fits(r, pre, nsel, ndir, err)) return;
+  }
+  TRY
+  if (given) settle_device_batch(r); else ready_stored_opacities(r);
+  wait_for_producer(r, producer_stream);
+  const size_t arr_w = (size_t)nw_ir * nsel * nl;
+  // the weights of the directions at places 0 and 1: the caller's arrays, or (computed here and not asked for) the handle's
+  const double *w[2] = {nullptr, nullptr};
+  if (given) {
+    w[0] = up ? d_w_up : d_w_dn; w[1] = up && dn ? d_w_dn : nullptr;
+  } else {
+    double *own = nullptr;
+    if ((up && !d_w_up) || (dn && !d_w_dn)) { r->d_rows_w.reserve(std::max<size_t>(1, ndir * arr_w)); own = r->d_rows_w.p; }
+    double *const wu = up ? (d_w_up ? d_w_up : own) : nullptr, *const wd = dn ? (d_w_dn ? d_w_dn : own + (up ? arr_w : 0)) : nullptr;
+    ir_rows_weights(r, fun, nsel, ndir, up, wu, wd);
+    w[0] = up ? wu : wd; w[1] = up && dn ? wd : nullptr;
+  }
+  if (n > 0) {
+    const size_t spec = (size_t)nw_ir * nsel, sums = (size_t)nsel;      // per column and direction
+    double *const outs[2] = {up ? d_ir_fup : d_ir_fdn, dn && up ? d_ir_fdn : nullptr};
+    double *const fns[2] = {up ? d_fup_n : d_fdn_n, dn && up ? d_fdn_n : nullptr};
+    // a sum asked for without its spectrum: the spectra of such a direction pass through d_rows_out, in the host form's chunks
+    bool staged[2];
+    int nstaged = 0;
+    for (int d = 0; d < ndir; d++) { staged[d] = !outs[d]; nstaged += staged[d] ? 1 : 0; }
+    int CH = std::min(n, IR_ROWS_DEVICE_CHUNK);
+    if (nstaged) {
+      CH = std::min(n, IR_ROWS_CHUNK);
+      while (CH > 1 && sizeof(double) * (double)nstaged * nw_ir * nsel * CH > IR_ROWS_CHUNK_BYTES) CH = (CH + 1) / 2;
+      r->d_rows_out.reserve(std::max<size_t>(1, (size_t)nstaged * spec * CH));
+    }
+    for (int c0 = 0; c0 < n; c0 += CH) {
+      const int nc = std::min(CH, n - c0);
+      if (r->ir_n > 0) {
+        IrRowsApplyParams q = ir_rows_apply_params(r, nsel, ndir, nc, d_T + (size_t)c0 * nz, d_T_surface + c0, w[0], w[1]);
+        double *stage = r->d_rows_out.p;
+        double *o[2] = {nullptr, nullptr};
+        for (int d = 0; d < ndir; d++) {
+          if (staged[d]) { o[d] = stage; stage += spec * nc; }
+          else o[d] = outs[d] + spec * c0;
+        }
+        q.out0 = o[0]; q.out1 = o[1];
+        q.fn0 = fns[0] ? fns[0] + sums * c0 : nullptr; q.fn1 = fns[1] ? fns[1] + sums * c0 : nullptr;
+        KernelTimer t(r, 5);
+        launch_ir_rows_apply(q, r->stream);
+        HIPCHK(hipGetLastError());
+        t.stop();
+      } else {
+        for (int d = 0; d < ndir; d++)
+          if (fns[d]) HIPCHK(hipMemsetAsync(fns[d] + sums * c0, 0, sizeof(double) * sums * nc, r->stream));   // (no IR bins: sums of nothing)
+      }
+    }
+  }
+  CATCH(err)
+}
+
+// The temperature gradient of the spectra batch: device arrays in, device arrays out, enqueued on the handle's stream in
+// chunks of columns (kernel id 6).  w / gs / gn: [up, down], null where not given; a direction without a cotangent is left out.
+static void ir_rows_vjp_enqueue(Radtran *r, int n, int nsel, const double *d_Ts, const double *d_T, const double *const w[2],
+                                const double *const gs[2], const double *const gn[2], double *d_grad_Ts, double *d_grad_T) {
+  const int nz = r->nz;
+  if (r->ir_n < 1) {   // (no IR bins: nothing depends on the temperatures)
+    HIPCHK(hipMemsetAsync(d_grad_T, 0, sizeof(double) * (size_t)n * nz, r->stream));
+    HIPCHK(hipMemsetAsync(d_grad_Ts, 0, sizeof(double) * n, r->stream));
+    return;
+  }
+  const size_t spec = (size_t)r->ir.nw * nsel, sums = (size_t)nsel;
+  IrRowsVjpParams q;
+  std::memset(&q, 0, sizeof(q));
+  q.n_ir = r->ir_n; q.nsel = nsel; q.nz = nz;
+  q.l0 = r->ir.ind_start + r->ir_lo; q.ir_lo = r->ir_lo;
+  q.freq = r->d_freq.p; q.ir_freq = r->ir.d_freq.p;
+  for (int c0 = 0; c0 < n; c0 += IR_ROWS_DEVICE_CHUNK) {
+    const int nc = std::min(IR_ROWS_DEVICE_CHUNK, n - c0);
+    q.ncol = nc; q.ndir = 0;
+    q.T = d_T + (size_t)c0 * nz; q.Ts = d_Ts + c0;
+    q.grad_T = d_grad_T + (size_t)c0 * nz; q.grad_Ts = d_grad_Ts + c0;
+    for (int d = 0; d < 2; d++) {
+      if (!gs[d] && !gn[d]) continue;
+      (q.ndir ? q.w1 : q.w0) = w[d];
+      (q.ndir ? q.gs1 : q.gs0) = gs[d] ? gs[d] + spec * c0 : nullptr;
+      (q.ndir ? q.gn1 : q.gn0) = gn[d] ? gn[d] + sums * c0 : nullptr;
+      q.ndir++;
+    }
+    KernelTimer t(r, 6);
+    launch_ir_rows_vjp(q, r->stream);
+    HIPCHK(hipGetLastError());
+    t.stop();
+  }
+}
+// what both gradient forms refuse, with the batch's wording; false: the call can run
+static bool ir_rows_vjp_refused(Radtran *r, const std::string &pre, int n, int dim1_T, int dim2_T, int nsel, const void *T_surface,
+                                const void *T, const void *const w[2], const void *const gs[2], const void *const gn[2],
+                                const void *grad_T_surface, const void *grad_T, char *err) {
+  if (n < 1) { set_err(err, pre + "ncol must be at least 1 (ncol = " + std::to_string(n) + ")"); return true; }
+  if (dim1_T != r->nz || dim2_T != n) { set_err(err, "\"T\" has the wrong input dimension."); return true; }
+  if (nsel < 1) { set_err(err, pre + "nsel must be at least 1 (nsel = " + std::to_string(nsel) + ")"); return true; }
+  if (!T) { set_err(err, pre + "\"T\" is a required argument (ncol = " + std::to_string(n) + ")"); return true; }
+  if (!T_surface) { set_err(err, pre + "\"T_surface\" is a required argument (ncol = " + std::to_string(n) + ")"); return true; }
+  if (!grad_T) { set_err(err, pre + "\"grad_T\" is a required argument"); return true; }
+  if (!grad_T_surface) { set_err(err, pre + "\"grad_T_surface\" is a required argument"); return true; }
+  if (!w[0] && !w[1]) { set_err(err, pre + "neither w_up nor w_dn was given"); return true; }
+  static const char *const GS[2] = {"g_ir_fup", "g_ir_fdn"}, *const GN[2] = {"g_fup_n", "g_fdn_n"}, *const W[2] = {"w_up", "w_dn"};
+  for (int d = 0; d < 2; d++)
+    if (!w[d] && (gs[d] || gn[d])) {
+      set_err(err, pre + "\"" + (gs[d] ? GS[d] : GN[d]) + "\" was given without \"" + W[d] + "\"");
+      return true;
+    }
+  if (!gs[0] && !gs[1] && !gn[0] && !gn[1]) { set_err(err, pre + "none of g_ir_fup, g_ir_fdn, g_fup_n, g_fdn_n was given"); return true; }
+  return ir_rows_shard_refused(r, pre, err);
+}
+
+void radtran_ir_spectra_batch_vjp_device(void *ptr, const int *ncol, const double *d_T_surface, const int *dim1_T, const int *dim2_T,
+                                         const double *d_T, const int *nsel_, const double *d_w_up, const double *d_w_dn,
+                                         const double *d_g_ir_fup, const double *d_g_ir_fdn, const double *d_g_fup_n,
+                                         const double *d_g_fdn_n, double *d_grad_T_surface, double *d_grad_T,
+                                         const void *producer_stream, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const std::string pre = "ir_spectra_batch_vjp_device: ";
+  const double *const w[2] = {d_w_up, d_w_dn}, *const gs[2] = {d_g_ir_fup, d_g_ir_fdn}, *const gn[2] = {d_g_fup_n, d_g_fdn_n};
+  const void *const wv[2] = {d_w_up, d_w_dn}, *const gsv[2] = {d_g_ir_fup, d_g_ir_fdn}, *const gnv[2] = {d_g_fup_n, d_g_fdn_n};
+  if (ir_rows_vjp_refused(r, pre, *ncol, *dim1_T, *dim2_T, *nsel_, d_T_surface, d_T, wv, gsv, gnv, d_grad_T_surface, d_grad_T, err)) return;
+  if (ir_rows_not_device(r, pre, {{"T_surface", d_T_surface}, {"T", d_T}, {"w_up", d_w_up}, {"w_dn", d_w_dn}, {"g_ir_fup", d_g_ir_fup},
+                                  {"g_ir_fdn", d_g_ir_fdn}, {"g_fup_n", d_g_fup_n}, {"g_fdn_n", d_g_fdn_n},
+                                  {"grad_T_surface", d_grad_T_surface}, {"grad_T", d_grad_T}}, err)) return;
+  TRY
+  settle_device_batch(r);
+  wait_for_producer(r, producer_stream);
+  ir_rows_vjp_enqueue(r, *ncol, *nsel_, d_T_surface, d_T, w, gs, gn, d_grad_T_surface, d_grad_T);
+  CATCH(err)
+}
+
+// ... with host arrays, synchronous: T and the weights go up whole, the cotangents and the gradient in chunks of columns
+// bounded like the batch's, the gradient back through the pinned block
+void radtran_ir_spectra_batch_vjp(void *ptr, const int *ncol, const double *T_surface, const int *dim1_T, const int *dim2_T,
+                                  const double *T, const int *nsel_, const double *w_up, const double *w_dn, const double *g_ir_fup,
+                                  const double *g_ir_fdn, const double *g_fup_n, const double *g_fdn_n, double *grad_T_surface,
+                                  double *grad_T, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const std::string pre = "ir_spectra_batch_vjp: ";
+  const int nz = r->nz, nl = nz + 1, nw_ir = r->ir.nw, n = *ncol, nsel = *nsel_;
+  const double *const w[2] = {w_up, w_dn}, *const gs[2] = {g_ir_fup, g_ir_fdn}, *const gn[2] = {g_fup_n, g_fdn_n};
+  const void *const wv[2] = {w_up, w_dn}, *const gsv[2] = {g_ir_fup, g_ir_fdn}, *const gnv[2] = {g_fup_n, g_fdn_n};
+  if (ir_rows_vjp_refused(r, pre, n, *dim1_T, *dim2_T, nsel, T_surface, T, wv, gsv, gnv, grad_T_surface, grad_T, err)) return;
+  for (int c = 0; c < n; c++) {
+    if (!(std::isfinite(T_surface[c]) && T_surface[c] > 0.0)) {
+      set_err(err, pre + "temperatures must be finite and positive (T_surface(" + std::to_string(c + 1) + ") = " + std::to_string(T_surface[c]) + ")");
+      return;
+    }
+    for (int i = 0; i < nz; i++) {
+      const double v = T[(size_t)c * nz + i];
+      if (!(std::isfinite(v) && v > 0.0)) {
+        set_err(err, pre + "temperatures must be finite and positive (T(" + std::to_string(i + 1) + ", " + std::to_string(c + 1) + ") = " + std::to_string(v) + ")");
+        return;
+      }
+    }
+  }
+  TRY
+  settle_device_batch(r);
+  bool use[2];
+  int ndir = 0;
+  for (int d = 0; d < 2; d++) { use[d] = gs[d] || gn[d]; ndir += use[d] ? 1 : 0; }
+  const size_t arr_w = (size_t)nw_ir * nsel * nl, spec = (size_t)nw_ir * nsel, sums = (size_t)nsel;
+  r->d_rows_w.reserve(std::max<size_t>(1, ndir * arr_w));
+  r->d_bT.reserve((size_t)n * nz); r->d_bTs.reserve(n);
+  HIPCHK(hipMemcpyAsync(r->d_bT.p, T, sizeof(double) * (size_t)n * nz, hipMemcpyHostToDevice, r->stream));
+  HIPCHK(hipMemcpyAsync(r->d_bTs.p, T_surface, sizeof(double) * n, hipMemcpyHostToDevice, r->stream));
+  const double *dw[2] = {nullptr, nullptr};
+  {
+    double *at = r->d_rows_w.p;
+    for (int d = 0; d < 2; d++) {
+      if (!use[d]) continue;
+      if (arr_w) HIPCHK(hipMemcpyAsync(at, w[d], sizeof(double) * arr_w, hipMemcpyHostToDevice, r->stream));
+      dw[d] = at; at += arr_w;
+    }
+  }
+  int CH = std::min(n, IR_ROWS_CHUNK);
+  while (CH > 1 && sizeof(double) * (double)ndir * nw_ir * nsel * CH > IR_ROWS_CHUNK_BYTES) CH = (CH + 1) / 2;
+  r->d_rows_out.reserve(std::max<size_t>(1, (size_t)ndir * (spec + sums) * CH));
+  r->d_bout.reserve((size_t)nl * CH);
+  for (int c0 = 0; c0 < n; c0 += CH) {
+    const int nc = std::min(CH, n - c0);
+    const double *dgs[2] = {nullptr, nullptr}, *dgn[2] = {nullptr, nullptr};
+    double *at = r->d_rows_out.p;
+    for (int d = 0; d < 2; d++) {
+      if (gs[d]) {
+        if (spec) HIPCHK(hipMemcpyAsync(at, gs[d] + spec * c0, sizeof(double) * spec * nc, hipMemcpyHostToDevice, r->stream));
+        dgs[d] = at; at += spec * nc;
+      }
+      if (gn[d]) {
+        HIPCHK(hipMemcpyAsync(at, gn[d] + sums * c0, sizeof(double) * sums * nc, hipMemcpyHostToDevice, r->stream));
+        dgn[d] = at; at += sums * nc;
+      }
+    }
+    double *const d_gT = r->d_bout.p, *const d_gTs = d_gT + (size_t)nz * nc;
+    ir_rows_vjp_enqueue(r, nc, nsel, r->d_bTs.p + c0, r->d_bT.p + (size_t)c0 * nz, dw, dgs, dgn, d_gTs, d_gT);
+    rows_to_host(r, d_gT, grad_T + (size_t)c0 * nz, (size_t)nz * nc);
+    rows_to_host(r, d_gTs, grad_T_surface + c0, nc);
   }
   HIPCHK(hipStreamSynchronize(r->stream));
   CATCH(err)
@@ -3486,13 +3783,13 @@ void radtran_profile_stride_set(void *ptr, const int *stride) {
 void radtran_profile_reset(void *ptr) {
   Radtran *r = as_rad(ptr);
   if (!r) return;
-  for (int i = 0; i < 6; i++) { r->k_ms[i] = 0; r->k_n[i] = 0; }
+  for (int i = 0; i < 7; i++) { r->k_ms[i] = 0; r->k_n[i] = 0; }
   r->timer_calls = r->profile_stride - 1;  // with a sampling stride, the next call is a sampled one
 }
 void radtran_kernel_time_get(void *ptr, const int *kernel_id, double *ms_total, int *launches, char *err) {
   clear_err(err);
   GUARD(r, ptr, err);
-  if (*kernel_id < 0 || *kernel_id > 5) { set_err(err, "kernel id out of range"); return; }
+  if (*kernel_id < 0 || *kernel_id > 6) { set_err(err, "kernel id out of range"); return; }
   TRY
   if (!r->pending.empty()) { HIPCHK(hipStreamSynchronize(r->stream)); resolve_events(r); }
   *ms_total = r->k_ms[*kernel_id];

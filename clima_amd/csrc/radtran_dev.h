@@ -568,6 +568,21 @@ struct IrRowsApplyParams {
 };
 void launch_ir_rows_apply(const IrRowsApplyParams &p, hipStream_t s);
 int ir_rows_column_tile(int ncol);         // the launcher's rule: columns per wave
+// Temperature gradient of that batch (ir_rows_vjp.inc, radtran_ir_spectra_batch_vjp): with gs the cotangent of out and gn
+// that of fn (either null: 0),  grad_x(j, c) = sum over d, a, l of (gs_d(l, a, c) + gn_d(a, c) (ir_freq(l) - ir_freq(l+1)))
+// w_d(l, a, j) dB/dT(avg_freq(l), x_c(j)).  The ndir directions that have a cotangent stand at places 0 and 1, as above.
+struct IrRowsVjpParams {
+  int n_ir, nsel, nz, ncol, ndir;
+  int l0, ir_lo;                           // as in IrRowsApplyParams
+  const double *freq, *ir_freq;
+  const double *T, *Ts;                    // (nz, ncol) ground-first layers, (ncol)
+  const double *w0, *w1;                   // (n_ir, nsel, nz+1)
+  const double *gs0, *gs1;                 // (n_ir, nsel, ncol) or null
+  const double *gn0, *gn1;                 // (nsel, ncol) or null
+  double *grad_T, *grad_Ts;                // (nz, ncol), (ncol): every element is written
+};
+void launch_ir_rows_vjp(const IrRowsVjpParams &p, hipStream_t s);
+int ir_rows_vjp_column_tile(int ncol);     // the launcher's rule: columns per wave
 int green_far_resident_waves();
 void green_vector_form_set(int vector_form);   // test hook: the far accumulation's vector form (1) or matrix form (0)
 int green_far_waves(int ndev, int nl);   // per bin split

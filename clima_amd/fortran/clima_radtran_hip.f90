@@ -86,6 +86,7 @@ module clima_radtran_hip
     procedure :: ir_jacobian_reduced => Radtran_ir_jacobian_reduced
     procedure :: ir_jacobian_spectral_rows => Radtran_ir_jacobian_spectral_rows
     procedure :: ir_spectra_batch => Radtran_ir_spectra_batch
+    procedure :: ir_spectra_batch_vjp => Radtran_ir_spectra_batch_vjp
     procedure :: TOA_fluxes_batch => Radtran_TOA_fluxes_batch
     procedure :: TOA_fluxes_batch_spectra => Radtran_TOA_fluxes_batch_spectra
     procedure :: TOA_fluxes_batch_bounds => Radtran_TOA_fluxes_batch_bounds
@@ -256,6 +257,16 @@ module clima_radtran_hip
       integer(c_int), intent(in) :: ncol, dim1_T, dim2_T, nsel, spec_level(*)
       real(c_double), intent(in) :: T_surface(*), T(*)
       type(c_ptr), value :: ir_fup, ir_fdn, fup_n, fdn_n, w_up, w_dn     ! (c_null_ptr: not wanted)
+      character(c_char), intent(out) :: err(*)
+    end subroutine
+    subroutine c_radtran_ir_spectra_batch_vjp(ptr, ncol, T_surface, dim1_T, dim2_T, T, nsel, w_up, w_dn, g_ir_fup, g_ir_fdn, &
+                                              g_fup_n, g_fdn_n, grad_T_surface, grad_T, err) &
+                                              bind(c, name="radtran_ir_spectra_batch_vjp")
+      import; type(c_ptr), value :: ptr
+      integer(c_int), intent(in) :: ncol, dim1_T, dim2_T, nsel
+      real(c_double), intent(in) :: T_surface(*), T(*)
+      type(c_ptr), value :: w_up, w_dn, g_ir_fup, g_ir_fdn, g_fup_n, g_fdn_n     ! (c_null_ptr: not given)
+      real(c_double), intent(out) :: grad_T_surface(*), grad_T(*)
       character(c_char), intent(out) :: err(*)
     end subroutine
     subroutine c_radtran_opacities2yaml_wrapper_1(ptr, out_len, out_cp) bind(c, name="radtran_opacities2yaml_wrapper_1")
@@ -1213,6 +1224,62 @@ contains
     call push_fields(self)
     call c_radtran_ir_spectra_batch(self%handle, ncol, T_surface, size(T,1), size(T,2), T, nsel, spec_level, &
                                     sink(1), sink(2), sink(3), sink(4), sink(5), sink(6), err_c)
+    call take_err(err_c, err)
+  end subroutine
+
+  !> The temperature gradient of `ir_spectra_batch` (radtran_ir_spectra_batch_vjp): with the weights w_up / w_dn
+  !> (nw_ir, nsel, nz+1) of an `ir_spectra_batch` call and cotangents g_ir_fup_a, g_ir_fdn_a (nw_ir, nsel, ncol) of its
+  !> spectra and g_fup_n, g_fdn_n (nsel, ncol) of its sums (an absent one counts as 0),
+  !> grad_T_surface (ncol) and grad_T (nz, ncol) are d loss / d T_surface(c) and d loss / d T(m,c).  At least one of
+  !> w_up, w_dn and one cotangent of a given direction must be present.  Needs no opacities; `self` is not changed.
+  subroutine Radtran_ir_spectra_batch_vjp(self, T_surface, T, grad_T_surface, grad_T, err, w_up, w_dn, g_ir_fup_a, g_ir_fdn_a, &
+                                          g_fup_n, g_fdn_n)
+    class(Radtran), intent(inout) :: self
+    real(dp), intent(in), contiguous :: T_surface(:)                        !! (ncol)
+    real(dp), intent(in), contiguous :: T(:,:)                              !! (nz, ncol)
+    real(dp), intent(out), contiguous :: grad_T_surface(:)                  !! (ncol)
+    real(dp), intent(out), contiguous :: grad_T(:,:)                        !! (nz, ncol)
+    character(:), allocatable, intent(out) :: err
+    real(dp), intent(in), contiguous, optional, target :: w_up(:,:,:), w_dn(:,:,:), g_ir_fup_a(:,:,:), g_ir_fdn_a(:,:,:)
+    real(dp), intent(in), contiguous, optional, target :: g_fup_n(:,:), g_fdn_n(:,:)
+    character(c_char) :: err_c(err_len+1)
+    type(c_ptr) :: src(6)
+    integer :: ncol, nsel, nw_ir
+    ncol = size(T_surface)
+    nw_ir = size(self%ir%freq) - 1
+    nsel = 0
+    if (present(w_dn)) nsel = size(w_dn, 2)
+    if (present(w_up)) nsel = size(w_up, 2)
+    src = c_null_ptr
+    if (size(grad_T_surface) /= ncol) err = 'ir_spectra_batch_vjp: "grad_T_surface" has the wrong dimension'
+    if (any(shape(grad_T) /= shape(T))) err = 'ir_spectra_batch_vjp: "grad_T" has the wrong dimension'
+    if (present(w_up)) then
+      if (any(shape(w_up) /= [nw_ir, nsel, self%nz+1])) err = 'ir_spectra_batch_vjp: "w_up" has the wrong dimension'
+      src(1) = c_loc(w_up)
+    endif
+    if (present(w_dn)) then
+      if (any(shape(w_dn) /= [nw_ir, nsel, self%nz+1])) err = 'ir_spectra_batch_vjp: "w_dn" has the wrong dimension'
+      src(2) = c_loc(w_dn)
+    endif
+    if (present(g_ir_fup_a)) then
+      if (any(shape(g_ir_fup_a) /= [nw_ir, nsel, ncol])) err = 'ir_spectra_batch_vjp: "g_ir_fup_a" has the wrong dimension'
+      src(3) = c_loc(g_ir_fup_a)
+    endif
+    if (present(g_ir_fdn_a)) then
+      if (any(shape(g_ir_fdn_a) /= [nw_ir, nsel, ncol])) err = 'ir_spectra_batch_vjp: "g_ir_fdn_a" has the wrong dimension'
+      src(4) = c_loc(g_ir_fdn_a)
+    endif
+    if (present(g_fup_n)) then
+      if (any(shape(g_fup_n) /= [nsel, ncol])) err = 'ir_spectra_batch_vjp: "g_fup_n" has the wrong dimension'
+      src(5) = c_loc(g_fup_n)
+    endif
+    if (present(g_fdn_n)) then
+      if (any(shape(g_fdn_n) /= [nsel, ncol])) err = 'ir_spectra_batch_vjp: "g_fdn_n" has the wrong dimension'
+      src(6) = c_loc(g_fdn_n)
+    endif
+    if (allocated(err)) return
+    call c_radtran_ir_spectra_batch_vjp(self%handle, ncol, T_surface, size(T,1), size(T,2), T, nsel, src(1), src(2), src(3), &
+                                        src(4), src(5), src(6), grad_T_surface, grad_T, err_c)
     call take_err(err_c, err)
   end subroutine
 

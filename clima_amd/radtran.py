@@ -746,6 +746,230 @@ class Radtran:
         self._check()
         return out
 
+    IR_SPECTRA_VJP_WEIGHTS = ("w_up", "w_dn")
+    IR_SPECTRA_VJP_GRADS = ("fup", "fdn", "fup_n", "fdn_n")
+
+    def _ir_spectra_vjp_request(self, nz, nw_ir, T_surface, T, weights, grads):
+        """The arrays of `ir_spectra_vjp` as the ABI takes them -- (T_surface (ncol), T (nz, ncol), nsel, the two weights and
+        the four cotangents in the ABI's order, None where absent), all Fortran-ordered float64 -- for a handle of nz
+        layers and nw_ir IR bins; unknown keys, wrong shapes, a cotangent without its weights and a request without any
+        cotangent are refused by name (reads the two name lists alone: no handle needed)."""
+        who = "ir_spectra_vjp: "
+        T, Ts = np.asfortranarray(T, dtype=np.float64), _c(np.atleast_1d(T_surface))
+        if Ts.ndim != 1:
+            raise ClimaException(who + '"T_surface" has the shape %s, not (ncol,)' % (Ts.shape,))
+        if T.ndim == 1 and len(Ts) == 1:
+            T = np.asfortranarray(T[:, None])
+        n = len(Ts)
+        if n < 1 or T.shape != (nz, n):
+            raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz, max(n, 1))))
+        for d, allowed, what in ((weights, self.IR_SPECTRA_VJP_WEIGHTS, "weights"), (grads, self.IR_SPECTRA_VJP_GRADS, "grads")):
+            if not isinstance(d, dict):
+                raise ClimaException(who + '"%s" is not a dict with keys among %s' % (what, ", ".join(allowed)))
+            for name in d:
+                if name not in allowed:
+                    raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(allowed)))
+        w = [np.asfortranarray(weights[k], dtype=np.float64) if weights.get(k) is not None else None for k in self.IR_SPECTRA_VJP_WEIGHTS]
+        g = [np.asfortranarray(grads[k], dtype=np.float64) if grads.get(k) is not None else None for k in self.IR_SPECTRA_VJP_GRADS]
+        if w[0] is None and w[1] is None:
+            raise ClimaException(who + '"weights" holds none of %s' % ", ".join(self.IR_SPECTRA_VJP_WEIGHTS))
+        if all(a is None for a in g):
+            raise ClimaException(who + '"grads" holds none of %s' % ", ".join(self.IR_SPECTRA_VJP_GRADS))
+        first = w[0] if w[0] is not None else w[1]
+        nsel = first.shape[1] if first.ndim == 3 else -1
+        for k, a in zip(self.IR_SPECTRA_VJP_WEIGHTS, w):
+            if a is not None and (nsel < 1 or a.shape != (nw_ir, nsel, nz + 1)):
+                raise ClimaException(who + '"%s" has the shape %s, not (%d, nsel, %d)' % (k, a.shape, nw_ir, nz + 1))
+        for k, a in zip(self.IR_SPECTRA_VJP_GRADS, g):
+            want = (nsel, n) if k.endswith("_n") else (nw_ir, nsel, n)
+            if a is not None and a.shape != want:
+                raise ClimaException(who + '"%s" has the shape %s, not %s' % (k, a.shape, want))
+            if a is not None and w[0 if "up" in k else 1] is None:
+                raise ClimaException(who + '"%s" was given without "%s"' % (k, "w_up" if "up" in k else "w_dn"))
+        return Ts, T, nsel, w, g
+
+    def ir_spectra_vjp(self, T_surface, T, weights, grads):
+        """The temperature gradient of `ir_spectra_batch` (radtran_ir_spectra_batch_vjp): `weights` is the dict of
+        "w_up" / "w_dn" (nw_ir, nsel, nz+1) a call with `weights=True` returned, `grads` a dict of cotangents with
+        `ir_spectra_batch`'s keys and shapes -- "fup" / "fdn" (nw_ir, nsel, ncol), "fup_n" / "fdn_n" (nsel, ncol), an
+        absent one counting as 0.  Returns (grad_T_surface (ncol,), grad_T (nz, ncol)): the derivatives of the loss whose
+        derivatives with respect to the outputs `grads` are, with respect to T_surface[c] and T[m, c].  No solve and no
+        opacities: one dB/dT per (bin, level, column); bitwise repeatable; the handle's state is left untouched."""
+        nz, nw_ir = self.nz, len(self.ir.freq) - 1
+        Ts, T, nsel, w, g = self._ir_spectra_vjp_request(nz, nw_ir, T_surface, T, weights, grads)
+        n = len(Ts)
+        gTs, gT = np.empty(n), np.empty((nz, n), order="F")
+        ptr = lambda a: _d(a) if a is not None else None   # noqa: E731
+        self._L.radtran_ir_spectra_batch_vjp(self._ptr, _i(n), _d(Ts), _i(nz), _i(n), _d(T), _i(nsel), ptr(w[0]), ptr(w[1]),
+                                             ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), _d(gTs), _d(gT), self._err)
+        self._check()
+        return gTs, gT
+
+    def _ir_tensor_check(self, who, name, t, shape):
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ClimaException('%s: "%s" is not a float64 torch tensor' % (who, name))
+        if tuple(t.shape) != tuple(shape):
+            raise ClimaException('%s: "%s" has the shape %s, not %s' % (who, name, tuple(t.shape), tuple(shape)))
+        if not t.is_contiguous():   # (no silent copy: the caller decides where a transposed view is materialised)
+            raise ClimaException('%s: "%s" is not C-contiguous' % (who, name))
+
+    def _on_handle_stream(self, dev, call, sync):
+        """`call(producer)` enqueues on the handle's stream; ordered as `TOA_fluxes_batch_tensors` orders its call: behind
+        torch's current stream on `dev`, and that stream behind the handle's afterwards (sync: `synchronize()` instead)"""
+        import torch
+        cur = torch.cuda.current_stream(dev)
+        mine = torch.cuda.ExternalStream(self.stream(), device=dev)
+        producer = cur.cuda_stream
+        if not producer:
+            # the legacy default stream: NULL tells the library that the inputs are complete, so the order is made here
+            mine.wait_stream(cur)
+        call(producer or None)
+        self._check()
+        if sync:
+            self.synchronize()
+        else:
+            ev = torch.cuda.Event()
+            ev.record(mine)
+            cur.wait_event(ev)
+
+    def ir_spectra_batch_tensors(self, T_surface, T, levels=(-1,), parts=("up",), fluxes=False, weights=None,
+                                 return_weights=False, sync=False):
+        """`ir_spectra_batch` for profiles that live in device memory (radtran_ir_spectra_batch_device): torch CUDA float64
+        tensors, C-contiguous with the column first -- T_surface (ncol,), T (ncol, nz) -- the `TOA_fluxes_batch_tensors`
+        convention; nothing passes through the host, nothing is copied, a tensor that is not contiguous is refused.
+        Returns a dict of fresh tensors on the same device: "fup" / "fdn" (ncol, nsel, nw_ir); with `fluxes` "fup_n" /
+        "fdn_n" (ncol, nsel); with `return_weights` "w_up" / "w_dn" (nz+1, nsel, nw_ir) -- bit for bit `ir_spectra_batch`'s
+        arrays, transposed.
+
+        `weights`: None computes the weights from the stored opacities (one adjoint pass).  The dict of "w_up" / "w_dn" an
+        earlier call with the same `levels` returned under `return_weights` is used as it is: no adjoint pass runs, the
+        handle needs no opacities, and the results are bit for bit those of the call that computed them.  Their validity is
+        the caller's: they describe the atmosphere, the emissivity, has_hard_surface and ir_tau_min of that call.
+
+        The library's work is ordered behind what torch's current stream has enqueued.  With `sync=False` the call returns
+        at once, torch's current stream ordered behind the handle's: work enqueued on it afterwards sees the results; the
+        host may read them after `synchronize()`.  The temperatures are not checked (that would need a host read): a T
+        that is not positive gives whatever the Planck function gives for it."""
+        import torch
+        who = "ir_spectra_batch_device"
+        nz, nl, nw_ir = self.nz, self.nz + 1, len(self.ir.freq) - 1
+        parts = (parts,) if isinstance(parts, str) else tuple(parts)
+        for name in parts:
+            if name not in self.IR_SPECTRA_BATCH_PARTS:
+                raise ClimaException('%s: "%s" is not one of %s' % (who, name, ", ".join(self.IR_SPECTRA_BATCH_PARTS)))
+        names = tuple(name for name in self.IR_SPECTRA_BATCH_PARTS if name in parts)
+        if not names:
+            raise ClimaException('%s: "parts" names none of %s' % (who, ", ".join(self.IR_SPECTRA_BATCH_PARTS)))
+        idx = np.atleast_1d(np.asarray(levels))
+        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+            raise ClimaException('%s: "levels" is not a non-empty list of integer level indices' % who)
+        for a, v in enumerate(idx.tolist()):
+            if v < -nl or v >= nl:
+                raise ClimaException("%s: levels[%d] = %d is outside %d..%d" % (who, a, v, -nl, nl - 1))
+        rows = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
+        nsel = len(rows)
+        n = int(T_surface.shape[0]) if isinstance(T_surface, torch.Tensor) and T_surface.dim() == 1 else -1
+        self._ir_tensor_check(who, "T_surface", T_surface, (max(n, 1),))
+        self._ir_tensor_check(who, "T", T, (n, nz))
+        if weights is not None:
+            if not isinstance(weights, dict):
+                raise ClimaException('%s: "weights" is not a dict with keys among w_up, w_dn' % who)
+            for name in names:
+                if weights.get("w_" + name) is None:
+                    raise ClimaException('%s: "weights" lacks "w_%s"' % (who, name))
+                self._ir_tensor_check(who, "w_" + name, weights["w_" + name], (nl, nsel, nw_ir))
+        dev = T.device if T.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        new = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+        out, w = {}, {}
+        for name in names:
+            out["f" + name] = new(n, nsel, nw_ir)
+            if fluxes:
+                out["f%s_n" % name] = new(n, nsel)
+            if weights is not None:
+                w["w_" + name] = weights["w_" + name]
+            elif return_weights:
+                w["w_" + name] = new(nl, nsel, nw_ir)
+        addr = lambda d, key: d[key].data_ptr() if key in d else None   # noqa: E731
+        self._on_handle_stream(dev, lambda producer: self._L.radtran_ir_spectra_batch_device(
+            self._ptr, _i(n), T_surface.data_ptr(), _i(nz), _i(n), T.data_ptr(), _i(nsel), rows.ctypes.data_as(C.POINTER(C.c_int)),
+            addr(out, "fup"), addr(out, "fdn"), addr(out, "fup_n"), addr(out, "fdn_n"), addr(w, "w_up"), addr(w, "w_dn"),
+            _i(0 if weights is None else 1), producer, self._err), sync)
+        if return_weights:
+            out.update(w)
+        return out
+
+    def ir_spectra_vjp_tensors(self, T_surface, T, weights, grads, sync=False):
+        """`ir_spectra_vjp` on torch CUDA float64 tensors in `ir_spectra_batch_tensors`' layout
+        (radtran_ir_spectra_batch_vjp_device): `weights` "w_up" / "w_dn" (nz+1, nsel, nw_ir), `grads` "fup" / "fdn"
+        (ncol, nsel, nw_ir), "fup_n" / "fdn_n" (ncol, nsel).  Returns fresh tensors (grad_T_surface (ncol,), grad_T
+        (ncol, nz)), bit for bit the host form's; stream ordering and `sync` as in `ir_spectra_batch_tensors`."""
+        import torch
+        who = "ir_spectra_batch_vjp_device"
+        nz, nl, nw_ir = self.nz, self.nz + 1, len(self.ir.freq) - 1
+        for d, allowed, what in ((weights, self.IR_SPECTRA_VJP_WEIGHTS, "weights"), (grads, self.IR_SPECTRA_VJP_GRADS, "grads")):
+            if not isinstance(d, dict):
+                raise ClimaException('%s: "%s" is not a dict with keys among %s' % (who, what, ", ".join(allowed)))
+            for name in d:
+                if name not in allowed:
+                    raise ClimaException('%s: "%s" is not one of %s' % (who, name, ", ".join(allowed)))
+        w = {k: v for k, v in weights.items() if v is not None}
+        g = {k: v for k, v in grads.items() if v is not None}
+        if not w:
+            raise ClimaException('%s: "weights" holds none of %s' % (who, ", ".join(self.IR_SPECTRA_VJP_WEIGHTS)))
+        if not g:
+            raise ClimaException('%s: "grads" holds none of %s' % (who, ", ".join(self.IR_SPECTRA_VJP_GRADS)))
+        n = int(T_surface.shape[0]) if isinstance(T_surface, torch.Tensor) and T_surface.dim() == 1 else -1
+        self._ir_tensor_check(who, "T_surface", T_surface, (max(n, 1),))
+        self._ir_tensor_check(who, "T", T, (n, nz))
+        first = next(iter(w.values()))
+        nsel = int(first.shape[1]) if isinstance(first, torch.Tensor) and first.dim() == 3 else 1
+        for k, t in w.items():
+            self._ir_tensor_check(who, k, t, (nl, nsel, nw_ir))
+        for k, t in g.items():
+            self._ir_tensor_check(who, k, t, (n, nsel) if k.endswith("_n") else (n, nsel, nw_ir))
+            if ("w_up" if "up" in k else "w_dn") not in w:
+                raise ClimaException('%s: "%s" was given without "%s"' % (who, k, "w_up" if "up" in k else "w_dn"))
+        dev = T.device if T.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        gTs, gT = torch.empty(n, dtype=torch.float64, device=dev), torch.empty((n, nz), dtype=torch.float64, device=dev)
+        addr = lambda d, key: d[key].data_ptr() if key in d else None   # noqa: E731
+        self._on_handle_stream(dev, lambda producer: self._L.radtran_ir_spectra_batch_vjp_device(
+            self._ptr, _i(n), T_surface.data_ptr(), _i(nz), _i(n), T.data_ptr(), _i(nsel), addr(w, "w_up"), addr(w, "w_dn"),
+            addr(g, "fup"), addr(g, "fdn"), addr(g, "fup_n"), addr(g, "fdn_n"), gTs.data_ptr(), gT.data_ptr(), producer, self._err), sync)
+        return gTs, gT
+
+    def ir_spectra_torch(self, T_surface, T, levels=(-1,), parts=("up",), fluxes=False, weights=None):
+        """`ir_spectra_batch_tensors` as a differentiable torch op: the same dict of tensors (without the weights), with
+        gradients flowing to `T_surface` (ncol,) and `T` (ncol, nz) through `ir_spectra_vjp_tensors` -- the exact gradient
+        of this library's forward model at fixed opacities, one kernel per backward pass, nothing on the host.
+        `weights=None` computes the weights once per call (forward and backward share them); the dict an
+        `ir_spectra_batch_tensors(..., return_weights=True)` call with the same `levels` returned is reused as it is,
+        which leaves a Planck pass per forward and a dB/dT pass per backward.  No gradient flows to the weights."""
+        import torch
+        rad = self
+        keys = []
+
+        class _IrSpectra(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, Ts, Tc):
+                out = rad.ir_spectra_batch_tensors(Ts, Tc, levels, parts, fluxes, weights=weights, return_weights=weights is None)
+                ctx.weights = weights if weights is not None else {k: out.pop(k) for k in list(out) if k.startswith("w_")}
+                keys[:] = [k for k in out if not k.startswith("w_")]
+                ctx.save_for_backward(Ts, Tc)
+                return tuple(out[k] for k in keys)
+
+            @staticmethod
+            def backward(ctx, *gout):
+                Ts, Tc = ctx.saved_tensors
+                g = {k: t.contiguous() for k, t in zip(keys, gout) if t is not None}
+                if not g:
+                    return None, None
+                w = {k: ctx.weights[k] for k in ctx.weights if any(("up" in k) == ("up" in q) for q in g)}
+                return rad.ir_spectra_vjp_tensors(Ts, Tc, w, g)
+
+        res = _IrSpectra.apply(T_surface, T)
+        return dict(zip(keys, res))
+
     # ---- HBM-resident form (bench / batched callers)
     def upload_column(self, T_surface, T, P, densities, dz, pdensities=None, radii=None):
         T, P, dz, densities = _c(T), _c(P), _c(dz), _fo(densities)

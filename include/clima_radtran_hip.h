@@ -439,6 +439,69 @@ void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surfac
                               const int *nsel, const int *spec_level,
                               double *ir_fup, double *ir_fdn, double *fup_n, double *fdn_n,
                               double *w_up, double *w_dn, char *err);
+/* radtran_ir_spectra_batch for arrays that live in device memory, with the weights in the caller's keeping: every array
+ * but spec_level (HOST, read before the call returns) is device memory of the handle's device, shapes and order as above
+ * (T (nz, ncol) column-major is a C-contiguous (ncol, nz) tensor; the spectra (ncol, nsel, nw_ir); the weights
+ * (nz+1, nsel, nw_ir)).  The call returns with its work enqueued on the handle's stream, behind the caller's writes of the
+ * inputs on `producer_stream` (NULL: they are complete); the results are final at the next radtran_synchronize.  The
+ * kernels are the host form's, writing straight into the caller's arrays (columns in launches of at most 262144; a sum
+ * asked for without its spectrum stages that direction's spectra through the handle, in the host form's chunks): the
+ * results are bit for bit the host form's on the same inputs.
+ *   weights_given = 0: the adjoint pass runs on the stored opacities; a non-NULL d_w_up / d_w_dn receives the weights
+ *                      (NULL: they stay in the handle, as in the host form).
+ *   weights_given = 1: d_w_up / d_w_dn are INPUTS, the weights an earlier call computed with the same nsel and
+ *                      spec_level; no adjoint pass runs and the handle needs no opacities -- the frequency grid is all the
+ *                      call reads.  Results are bit for bit those of the call that computed them.  The caller owns the
+ *                      validity of the weights: they describe the atmosphere, the emissivity, has_hard_surface and
+ *                      ir_tau_min of the time they were computed; the library keeps no cache of them.
+ * The temperatures are NOT checked (a check would need a host read): they are used as given, and a T that is not positive
+ * or not finite gives whatever planck_fcn gives for it, without an error.
+ * Refused, in the host form's words under the name ir_spectra_batch_device: what the host form refuses but for the
+ * temperatures; an array that is not device memory of the handle's device ('"T" is not device memory of this handle's
+ * device'); weights_given = 1 with a direction asked for whose w_* is NULL, or with no flux output at all.  Opacities are
+ * needed with weights_given = 0 only.  The handle's state is left as the host form leaves it; a pending deferred
+ * integration is settled first. */
+void radtran_ir_spectra_batch_device(void *ptr, const int *ncol, const double *d_T_surface,
+                                     const int *dim1_T, const int *dim2_T, const double *d_T,
+                                     const int *nsel, const int *spec_level,
+                                     double *d_ir_fup, double *d_ir_fdn, double *d_fup_n, double *d_fdn_n,
+                                     double *d_w_up, double *d_w_dn, const int *weights_given,
+                                     const void *producer_stream, char *err);
+/* The temperature gradient of radtran_ir_spectra_batch (a vector-Jacobian product): for cotangents g_ir_fup / g_ir_fdn
+ * (nw_ir, nsel, ncol) of the spectra and g_fup_n / g_fdn_n (nsel, ncol) of their sums, any of them NULL (counted as 0),
+ *   grad_x(j, c) = sum over directions d, levels a and bins l of
+ *                  (g_spec_d(l, a, c) + g_n_d(a, c) (freq(l) - freq(l+1))) w_d(l, a, j) dB/dT(avg_freq(l), x_c(j))
+ * with x_c(1) = T_surface(c), x_c(1+m) = T(m, c): grad_T_surface (ncol) takes j = 1, grad_T (nz, ncol) the rest.  w_up /
+ * w_dn (nw_ir, nsel, nz+1) are the weights of radtran_ir_spectra_batch for the levels the cotangents belong to; dB/dT is
+ * the function radtran_ir_jacobian_spectral_rows uses.  No solve, no row of the Jacobian: one dB/dT per (bin, level,
+ * column) (clima_amd/csrc/ir_rows_vjp.inc).  Contract: the result for (j, c) is bitwise repeatable and does not depend on
+ * ncol or on the other columns (each lane sums its bins in ascending l, a inside that and up before down; the 64 lanes
+ * are added in a fixed order; no atomics); all-zero cotangents give exactly 0.0; a direction without a cotangent is not
+ * read.  A constructed handle is needed, and the whole spectrum; NO opacities (the frequency grid is all that is read).
+ * Synchronous, host arrays, columns in chunks bounded like radtran_ir_spectra_batch's, results through the pinned block.
+ * The handle's wrk_ir, wrk_sol, f_total, spectra, stored opacities and fields are left untouched; a pending deferred
+ * integration is settled first.  Refused (err; nothing is written): a handle that is not constructed; ncol < 1; dim1_T /= nz
+ * or dim2_T /= ncol ('"T" has the wrong input dimension.'); nsel < 1; a NULL T, T_surface, grad_T or grad_T_surface
+ * ('"grad_T" is a required argument'); neither w_up nor w_dn; a cotangent whose direction has no weights ('"g_fdn_n" was
+ * given without "w_dn"'); no cotangent at all; a bin shard or a communicator; a temperature that is not finite and
+ * positive (radtran_ir_spectra_batch's text). */
+void radtran_ir_spectra_batch_vjp(void *ptr, const int *ncol, const double *T_surface,
+                                  const int *dim1_T, const int *dim2_T, const double *T, const int *nsel,
+                                  const double *w_up, const double *w_dn,
+                                  const double *g_ir_fup, const double *g_ir_fdn,
+                                  const double *g_fup_n, const double *g_fdn_n,
+                                  double *grad_T_surface, double *grad_T, char *err);
+/* ... with every array in device memory of the handle's device (refused by name otherwise), enqueued on the handle's
+ * stream behind `producer_stream` and final at the next radtran_synchronize, as radtran_ir_spectra_batch_device; bit for
+ * bit the host form's gradient.  The temperatures are not checked: a T that is not positive or not finite gives whatever
+ * adjoint_dbdt (clima_amd/csrc/ir_adjoint.inc) gives for it, without an error. */
+void radtran_ir_spectra_batch_vjp_device(void *ptr, const int *ncol, const double *d_T_surface,
+                                         const int *dim1_T, const int *dim2_T, const double *d_T, const int *nsel,
+                                         const double *d_w_up, const double *d_w_dn,
+                                         const double *d_g_ir_fup, const double *d_g_ir_fdn,
+                                         const double *d_g_fup_n, const double *d_g_fdn_n,
+                                         double *d_grad_T_surface, double *d_grad_T,
+                                         const void *producer_stream, char *err);
 /* clima/fortran/Radtran.f90:41-75 (same names and argument lists): the YAML text of
  * OpticalProperties_opacities2yaml (src/radtran/clima_radtran_types.f90:328-430).  _1 allocates
  * the string and returns its length, _2 copies it into out_c (out_len + 1 chars) and frees it.
@@ -565,8 +628,9 @@ void radtran_stream_get(void *ptr, void **stream);
 /* per-kernel device time (HIP events on the handle's stream).  enable = 1 records events
  * around every kernel, enable = 2 around the dominant kernel (id 1, opacity) only, 0 turns
  * them off; kernel_time_get returns accumulated ms and launch count for kernel id
- * (0 prep, 1 opacity, 2 twostream, 3 integrate; of radtran_ir_spectra_batch: 4 the weights' adjoint pass, 5 the
- * apply and integrate kernels of all its chunks) and resets nothing. */
+ * (0 prep, 1 opacity, 2 twostream, 3 integrate; of radtran_ir_spectra_batch and its device form: 4 the weights' adjoint
+ * pass, 5 the apply and integrate kernels of all its chunks; 6 the gradient kernel of all chunks of
+ * radtran_ir_spectra_batch_vjp and its device form) and resets nothing. */
 void radtran_profile_set(void *ptr, const int *enable);
 /* record the events on every stride-th call only (default 1): an event pair drains the queue for a
  * few microseconds, which a throughput measurement should not pay on every call */
