@@ -88,6 +88,7 @@ struct DevBuf {
     n = 0;
     owned = true;
   }
+  void swap(DevBuf &o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(owned, o.owned); }   // (no copy: each allocation keeps one owner)
   ~DevBuf() { release(); }
 };
 
@@ -160,6 +161,19 @@ struct BatchRun {
   double *spec[4] = {nullptr, nullptr, nullptr, nullptr};
   double *spec_host = nullptr;
   size_t spec_count = 0;
+};
+
+// The buffers of the call slot that is NOT the handle's current one ("Two resident calls in
+// flight"): everything a resident call writes.  The current slot's are the handle's own members of the same names;
+// swap_slot() exchanges the two sets, so every entry point sees "the handle's buffers" whichever slot the last call took.
+// Allocated (ensure_other_slot) the first time an upload or a call goes there.
+struct CallSlot {
+  bool allocated = false;
+  DevBuf<double> d_col, d_prep, d_opr, d_tau, d_w0, d_g, d_tau_band, d_scat;
+  DevBuf<double> spec[8];    // wrk_ir, then wrk_sol: fup_a, fdn_a, amean, tau_band
+  DevBuf<double> d_small, d_flux_n;
+  DevBuf<int> d_done;
+  long col_upload = 0;       // the upload (Holds::uploads) its column block holds
 };
 
 struct Radtran {
@@ -301,7 +315,22 @@ struct Radtran {
   bool int_pending = false;
   IntegrateParams pending_ip;
   long merged_integrations = 0, standalone_integrations = 0;   // pending integrations resolved either way (radtran_merged_integrations_get)
-  int profile = 0;   // 0 off, 1 HIP events around every kernel, 2 around the dominant kernel (id 1) only
+  // Two resident calls in flight: consecutive pipelined calls alternate between the two call slots, each on a lane
+  // (stream) of its own -- lane 0 is `stream`, the one every other entry point works on; lane 1 exists once a call has
+  // gone there.  `stream` names the lane being enqueued on: lane 0 except inside a LaneScope.
+  int calls_in_flight = 0;         // radtran_calls_in_flight_set: 0 automatic, 1 one at a time, 2 two whenever eligible
+  CallSlot other;                  // the slot that is not current
+  long col_upload = 0;             // the upload the current slot's column block holds
+  hipStream_t lane_stream[2] = {nullptr, nullptr};
+  int lane = 0;                    // lane of the latest pipelined call (0 after a join)
+  bool on_other_lane = false;      // a call is being enqueued beside the previous one: nothing joins inside it
+  hipEvent_t ev_lane1 = nullptr;   // behind the latest work of lane 1: what a join makes lane 0 wait for
+  hipEvent_t ev_fence = nullptr;   // lane 0 at the last join: lane 1 waits for it before it reuses a slot lane 0 worked in
+  hipEvent_t ev_colcopy = nullptr; // behind a slot-to-slot copy of the column: an upload into the block it read waits for it
+  bool fence_due = false, colcopy_pending = false;
+  const double *colcopy_src = nullptr;   // the block that copy read
+  int cus = 0;                     // compute units of the device (the automatic rule's measure of one residency round)
+  int profile = 0;  // 0 off, 1 HIP events around every kernel, 2 around the dominant kernel (id 1) only
   long timer_calls = 0;
   int profile_stride = 1;   // events on every profile_stride-th call only (bounds the cost of measuring)
   struct Ev { hipEvent_t a, b; int id; };
@@ -327,6 +356,9 @@ struct Radtran {
     if (ev_producer) (void)hipEventDestroy(ev_producer);
     if (comm) (void)ncclCommDestroy(comm);
     // (an integration still pending is dropped: nobody is left to read its rows)
+    for (hipEvent_t e : {ev_lane1, ev_fence, ev_colcopy}) if (e) (void)hipEventDestroy(e);
+    if (lane_stream[1]) { (void)hipStreamSynchronize(lane_stream[1]); (void)hipStreamDestroy(lane_stream[1]); }   // (its kernels write the other slot's buffers, freed below)
+    if (lane_stream[0]) stream = lane_stream[0];
     if (stream) (void)hipStreamDestroy(stream);
     magic = 0;
   }
@@ -336,6 +368,76 @@ Radtran *as_rad(void *ptr) {
   Radtran *r = reinterpret_cast<Radtran *>(ptr);
   if (!r || r->magic != MAGIC) return nullptr;
   return r;
+}
+
+// ---- two resident calls in flight: the slots and the lanes ----
+// THE join: lane 0 -- the stream every entry point but a pipelined resident call works on -- is ordered behind what lane 1
+// has been given, by an event and a stream wait, never by a host wait.  Called where the handle's debts are resolved
+// (settle_device_batch, resolve_pending_integration, wait_error_words) and in front of a write to device memory that a
+// call in flight may read (drain_lanes, do_upload).  After it the next call stays in the current slot.
+void join_lanes(Radtran *r) {
+  if (r->on_other_lane) return;
+  if (r->holds.other_in_flight) {
+    HIPCHK(hipEventRecord(r->ev_fence, r->lane_stream[0]));
+    HIPCHK(hipStreamWaitEvent(r->lane_stream[0], r->ev_lane1, 0));
+    r->fence_due = true;
+  }
+  r->holds.joined();
+  r->lane = 0;
+}
+// ... and both lanes have run dry (the one host wait of a setter that rewrites device memory the kernels read)
+void drain_lanes(Radtran *r) {
+  join_lanes(r);
+  if (r->stream) HIPCHK(hipStreamSynchronize(r->stream));
+}
+// Work goes to `lane` until the scope ends: `stream` names that lane's stream, and nothing inside joins.  Lane 1 is
+// first ordered behind what lane 0 had done at the last join (it may have worked in the slot lane 1 is about to reuse);
+// at the end an event behind lane 1's work is what the next join waits for.
+struct LaneScope {
+  Radtran *r;
+  int lane;
+  LaneScope(Radtran *r_, int lane_) : r(r_), lane(lane_) {
+    r->on_other_lane = true;
+    r->stream = r->lane_stream[lane];
+    if (lane == 1 && r->fence_due) { r->fence_due = false; HIPCHK(hipStreamWaitEvent(r->stream, r->ev_fence, 0)); }
+  }
+  ~LaneScope() {
+    if (lane == 1) { (void)hipEventRecord(r->ev_lane1, r->lane_stream[1]); r->holds.other_in_flight = true; }
+    r->stream = r->lane_stream[0];
+    r->on_other_lane = false;
+  }
+};
+// The other slot's buffers and lane 1, the first time something goes there: the sizes of the current slot's, cleared as
+// create_end clears those
+void ensure_other_slot(Radtran *r) {
+  CallSlot &o = r->other;
+  if (o.allocated) return;
+  if (!r->lane_stream[1]) HIPCHK(hipStreamCreateWithFlags(&r->lane_stream[1], hipStreamNonBlocking));
+  for (hipEvent_t *e : {&r->ev_lane1, &r->ev_fence, &r->ev_colcopy})
+    if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  auto like = [](DevBuf<double> &dst, const DevBuf<double> &src) { dst.alloc(src.n); dst.zero(); };
+  like(o.d_col, r->d_col); like(o.d_prep, r->d_prep); like(o.d_opr, r->d_opr);
+  auto view = [&](DevBuf<double> &dst, const DevBuf<double> &src) { dst.view(o.d_opr.p + (src.p - r->d_opr.p), src.n); };
+  view(o.d_tau, r->d_tau); view(o.d_w0, r->d_w0); view(o.d_g, r->d_g); view(o.d_tau_band, r->d_tau_band); view(o.d_scat, r->d_scat);
+  const DevBuf<double> *spec[8] = {&r->wrk_ir.fup_a, &r->wrk_ir.fdn_a, &r->wrk_ir.amean, &r->wrk_ir.tau_band,
+                                   &r->wrk_sol.fup_a, &r->wrk_sol.fdn_a, &r->wrk_sol.amean, &r->wrk_sol.tau_band};
+  for (int k = 0; k < 8; k++) like(o.spec[k], *spec[k]);
+  o.d_small.alloc(r->rows.count); o.d_small.zero();   // (its error-word slot is never used: the words are the handle's, d_err)
+  o.d_flux_n.view(o.d_small.p, r->rows.flux_count);
+  o.d_done.alloc(r->d_done.n); o.d_done.zero();
+  HIPCHK(hipStreamSynchronize(nullptr));   // the clears went to the null stream, which the lanes do not wait for
+  o.allocated = true;
+}
+// The handle's buffers become the other slot's and the other way round
+void swap_slot(Radtran *r) {
+  CallSlot &o = r->other;
+  r->d_col.swap(o.d_col); r->d_prep.swap(o.d_prep); r->d_opr.swap(o.d_opr);
+  r->d_tau.swap(o.d_tau); r->d_w0.swap(o.d_w0); r->d_g.swap(o.d_g); r->d_tau_band.swap(o.d_tau_band); r->d_scat.swap(o.d_scat);
+  DevBuf<double> *spec[8] = {&r->wrk_ir.fup_a, &r->wrk_ir.fdn_a, &r->wrk_ir.amean, &r->wrk_ir.tau_band,
+                             &r->wrk_sol.fup_a, &r->wrk_sol.fdn_a, &r->wrk_sol.amean, &r->wrk_sol.tau_band};
+  for (int k = 0; k < 8; k++) spec[k]->swap(o.spec[k]);
+  r->d_small.swap(o.d_small); r->d_flux_n.swap(o.d_flux_n); r->d_done.swap(o.d_done);
+  std::swap(r->col_upload, o.col_upload);
 }
 
 // futils gauss_legendre (setup only, clima_eqns.f90:26-41)
@@ -399,8 +501,8 @@ bool make_channel(Radtran *r, ChannelObj &c, int which, int n, const double *wav
 
 void upload_fields(Radtran *r) {
   if (!r->fields_dirty) return;
-  // kernels of earlier, unsynchronised calls may still be reading the old values
-  if (r->stream) HIPCHK(hipStreamSynchronize(r->stream));
+  // kernels of earlier, unsynchronised calls may still be reading the old values (on either lane)
+  drain_lanes(r);
   r->d_zen_u.upload(r->zenith_u);
   r->d_zen_w.upload(r->zenith_w);
   {
@@ -874,11 +976,62 @@ bool stream_capturing(Radtran *r) {
 bool defer_eligible(Radtran *r) {   // (the runtime is asked only where the answer decides)
   return defer_allowed(r->defer_integration, r->shard_world, r->comm != nullptr, r->profile, false, r->flux_ptr_taken) && !stream_capturing(r);
 }
+// Waves of a compute_opacity call's main grid: the fused grid's opacity tiles and two-stream items, or the opacity launch
+// of the separate form; blocks of 256 threads (OP_THREADS, kernels.hip), four waves each.
+long radiate_grid_waves(const PlanIn &in, const LaunchPlan &pl) {
+  const long items = (long)in.op_n * in.nsrc, tiles = (items + 255) / 256;
+  if (pl.fused.form != TS_NONE) return 4 * (tiles + (long)(in.n_sol + in.n_ir) * pl.fused.groups);
+  if (pl.opacity == OP_COOP) return 4 * ((items * pl.coop_ng + 255) / 256);
+  return 4 * tiles;
+}
+// Does a resident call that computes opacities and solar fluxes run BESIDE the previous call, in the call slot that is
+// not current and on that slot's lane?  THE rule, every condition of it, as plain values: the call may keep its results
+// back (defer_ok: defer_allowed, the capture state included); nobody has waited for or joined the previous pipelined call
+// since it was enqueued; its dominant kernel carries no event pair (sampled: a timed launch runs alone); the fields on the
+// device are current (stale ones are uploaded behind a join and a host wait); no integration is pending (it reads the
+// current slot's spectra on lane 0); the integration fits the one-launch kernel (the other form's partial sums are
+// shared); and the mode says so: 1 never, 2 always, 0 (automatic) when the grid does not fit the device in one residency
+// round of two waves per SIMD -- a smaller call is launch-bound, and the tests pin its launch sequence.  Everything else
+// joins first and stays in the current slot.
+struct TwoInFlight {
+  int mode;
+  bool defer_ok, prev_unjoined, sampled, fields_dirty, int_pending, integrates_in_one_launch;
+  long grid_waves;
+  int cus;
+};
+bool two_in_flight_allowed(const TwoInFlight &q) {
+  if (q.mode == 1 || !q.defer_ok || !q.prev_unjoined || q.sampled || q.fields_dirty || q.int_pending || !q.integrates_in_one_launch) return false;
+  return q.mode == 2 || q.grid_waves > 2L * 4 * q.cus;
+}
+bool call_is_sampled(const Radtran *r) {   // KernelTimer::on() of the next call's dominant kernel
+  return r->profile == 2 && (r->profile_stride <= 1 || (r->timer_calls + 1) % r->profile_stride == 0);
+}
+// The rule asked of this handle's next full resident call, the previous call taken as `prev_unjoined` and a pending
+// integration as `int_pending`.  The plan is made only where the mode needs the grid's size, and the runtime is asked for
+// the capture state only where the answer decides.
+bool two_in_flight(Radtran *r, bool prev_unjoined, bool int_pending) {
+  TwoInFlight q{};
+  q.mode = r->calls_in_flight; q.prev_unjoined = prev_unjoined; q.int_pending = int_pending;
+  q.sampled = call_is_sampled(r); q.fields_dirty = r->fields_dirty; q.cus = r->cus;
+  q.defer_ok = defer_allowed(r->defer_integration, r->shard_world, r->comm != nullptr, r->profile, false, r->flux_ptr_taken);
+  q.integrates_in_one_launch = integrate_fits_one_launch(integrate_chunks(std::max(r->ir_n, r->sol_n)));
+  if (q.mode == 0 && q.defer_ok && prev_unjoined) {
+    const PlanIn in = plan_input(r, resident_bufs(r, false), true, true, true);
+    q.grid_waves = radiate_grid_waves(in, plan_radiate(in));
+  }
+  if (!two_in_flight_allowed(q)) return false;
+  q.defer_ok = !stream_capturing(r);
+  return two_in_flight_allowed(q);
+}
+// ... were the previous call unjoined: the handle pipelines two, so its full resident calls integrate at once
+bool pipelining_two(Radtran *r) { return two_in_flight(r, true, false); }
+
 // THE place where a pending integration is resolved.  With the prep parameters of a compute_opacity call that is about
 // to launch its prep pass (and clears nothing there): both in one grid where k_prep_integrate covers them -- returns
 // true, the prep pass is launched.  Otherwise (prep null: everything else that enqueues work or reads results, through
 // settle_device_batch) the integration alone, with the parameters stored when its call was enqueued -- returns false.
 bool resolve_pending_integration(Radtran *r, const PrepParams *prep = nullptr) {
+  join_lanes(r);   // (whoever comes here enqueues work or reads results: the other lane's call first)
   if (!r->int_pending) return false;
   r->int_pending = false;
   if (prep && r->profile != 1 && prep_integrate_merges(*prep, r->pending_ip) && !stream_capturing(r)) {
@@ -892,6 +1045,30 @@ bool resolve_pending_integration(Radtran *r, const PrepParams *prep = nullptr) {
   return false;
 }
 
+// The current slot's column block is the handle's latest column: an upload went to the slot its next call was expected
+// to take, and a slot that was passed over gets the column by one device copy out of the other's block, behind the upload
+// (ev_upload).  Whatever next writes the block such a copy read -- an upload, or a copy the other way -- waits for the
+// copy's event first (wait_for_column_copy); the debt stays until that has happened.
+void wait_for_column_copy(Radtran *r, const double *block_to_write) {
+  if (!r->colcopy_pending || r->colcopy_src != block_to_write) return;
+  HIPCHK(hipStreamWaitEvent(r->stream, r->ev_colcopy, 0));
+  r->colcopy_pending = false;
+}
+void ensure_column(Radtran *r) {
+  if (r->col_upload == r->holds.uploads || !r->other.allocated || r->other.col_upload != r->holds.uploads) return;
+  if (r->upload_pending) HIPCHK(hipStreamWaitEvent(r->stream, r->ev_upload, 0));
+  wait_for_column_copy(r, r->d_col.p);
+  // (an earlier copy that read the same block and is still owed a wait: this lane waits for it too, so that the one
+  //  event, recorded anew below, stands for both)
+  if (r->colcopy_pending) HIPCHK(hipStreamWaitEvent(r->stream, r->ev_colcopy, 0));
+  launch_copy(r->d_col.p, r->other.d_col.p, r->col_layout.count, r->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(r->ev_colcopy, r->stream));
+  r->colcopy_pending = true;
+  r->colcopy_src = r->other.d_col.p;
+  r->col_upload = r->holds.uploads;
+}
+
 // plan -> prep -> opacity (or the fused grid) -> two-stream -> integrate -> reduce, on the buffers `b` names
 // defer: the caller returns without anyone reading a result, so the integration may wait for the next call's prep launch
 void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused = true, bool defer = false) {
@@ -900,6 +1077,7 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
   r->timer_calls++;
   upload_fields(r);
   const bool resident = b.kind == CALL_RESIDENT, chunk = b.kind == CALL_ARENA_CHUNK;
+  if (resident) { join_lanes(r); ensure_column(r); }   // (a call beside the previous one: nothing joins, see LaneScope)
   const ColumnDev col = column_dev(r, b);
   TwoStreamParams ts = make_twostream_params(r, b, col, compute_solar);
   const LaunchPlan plan = plan_radiate(plan_input(r, b, compute_solar, compute_opacity, allow_fused));
@@ -981,8 +1159,13 @@ void fetch_small(Radtran *r) {
   if (r->holds.rows_on_host) return;
   const LevelRows &l = r->rows;
   for (int pass = 0; pass < 2; pass++) {
-    if (!r->holds.rows_in_pinned)
-      HIPCHK(hipMemcpyAsync(r->h_small, r->d_small.p, sizeof(double) * l.count, hipMemcpyDeviceToHost, r->stream));
+    if (!r->holds.rows_in_pinned) {
+      // one copy: the error words end the handle's first level-row block.  The second slot's rows are a block of their
+      // own, and the words -- shared by the slots -- come out of the first one's
+      const bool own = reinterpret_cast<int *>(r->d_small.p + l.err_words) == r->d_err.p;
+      HIPCHK(hipMemcpyAsync(r->h_small, r->d_small.p, sizeof(double) * (own ? l.count : l.err_words), hipMemcpyDeviceToHost, r->stream));
+      if (!own) HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
+    }
     HIPCHK(hipStreamSynchronize(r->stream));
     resolve_events(r);
     if (r->comm) r->comm_status = r->h_small[l.status];
@@ -1019,11 +1202,23 @@ void do_upload(Radtran *r, const ColumnArrays &a) {
   bool all = (nz % 2 == 0) && r->nsrc * 2 == nz;
   for (int m = 0; m < r->nsrc && all; m++) all = (meta[1 + m] & SRC_EXACT) != 0;
   r->all_pairs_exact = all;
-  // ~18 KB: a kernel that reads the pinned buffer over PCIe gets the column into HBM 4 us sooner
-  // than the copy engine does (which takes over where the runtime did not map the buffer)
-  if (r->h_col_dev) launch_copy(r->d_col.p, r->h_col_dev, r->col_layout.count, r->stream);
-  else HIPCHK(hipMemcpyAsync(r->d_col.p, h, sizeof(double) * r->col_layout.count, hipMemcpyHostToDevice, r->stream));
-  HIPCHK(hipEventRecord(r->ev_upload, r->stream));
+  // The column goes into the block of the slot the handle's next call is expected to take, on that slot's lane: the
+  // other one when that call would run beside the previous pipelined call (a call that then takes the current slot
+  // after all copies the column over: ensure_column).  Otherwise into the current slot's, behind a join -- its latest
+  // call may be reading that block on the other lane.
+  const bool to_other = r->holds.unjoined && pipelining_two(r);
+  if (to_other) ensure_other_slot(r); else join_lanes(r);
+  {
+    LaneScope lane(r, to_other ? r->lane ^ 1 : 0);
+    double *d_col = to_other ? r->other.d_col.p : r->d_col.p;
+    wait_for_column_copy(r, d_col);
+    // ~18 KB: a kernel that reads the pinned buffer over PCIe gets the column into HBM 4 us sooner
+    // than the copy engine does (which takes over where the runtime did not map the buffer)
+    if (r->h_col_dev) launch_copy(d_col, r->h_col_dev, r->col_layout.count, r->stream);
+    else HIPCHK(hipMemcpyAsync(d_col, h, sizeof(double) * r->col_layout.count, hipMemcpyHostToDevice, r->stream));
+    HIPCHK(hipEventRecord(r->ev_upload, r->stream));
+    (to_other ? r->other.col_upload : r->col_upload) = r->holds.uploads + 1;   // (counted by Holds::uploaded below)
+  }
   r->upload_pending = true;
   r->last_T.assign(a.T, a.T + nz);
   r->last_P.assign(a.P, a.P + nz);
@@ -1081,6 +1276,7 @@ bool surface_device_error(Radtran *r, char *err) {
 // The two error words (opacity failure, expired fused hand-off wait: the ids of the last calls that flagged them) as
 // they stand once everything enqueued so far has run
 void wait_error_words(Radtran *r) {
+  join_lanes(r);
   HIPCHK(hipMemcpyAsync(r->h_errflag, r->d_err.p, 2 * sizeof(int), hipMemcpyDeviceToHost, r->stream));
   HIPCHK(hipStreamSynchronize(r->stream));
   resolve_events(r);
@@ -1491,7 +1687,7 @@ void radtran_set_custom_optical_properties(void *ptr, const int *dim_wv, const d
   bool ok = nP >= 2;  // linear_interp_1d%initialize: two or more strictly increasing nodes
   for (int i = 1; i < nP && ok; i++) ok = lp[i] > lp[i - 1];
   if (!ok) { set_err(err, "Interpolation initialization error in `set_custom_optical_properties`"); return; }
-  HIPCHK(hipStreamSynchronize(r->stream));  // a previous call may still read the old tables
+  drain_lanes(r);  // a previous call may still read the old tables
   r->cust_axis = lp; r->cust_nP = nP;
   r->d_cust_axis.upload(lp); r->d_cust_dtau.upload(tab[0]); r->d_cust_w0.upload(tab[1]); r->d_cust_g0.upload(tab[2]);
   r->cust_on = true;
@@ -1706,6 +1902,35 @@ void radtran_merged_integrations_get(void *ptr, int *merged, int *standalone) {
   *merged = r ? (int)std::min<long>(r->merged_integrations, 2147483647L) : 0;
   *standalone = r ? (int)std::min<long>(r->standalone_integrations, 2147483647L) : 0;
 }
+void radtran_calls_in_flight_set(void *ptr, const int *mode) {
+  Radtran *r = as_rad(ptr);
+  if (r) r->calls_in_flight = std::max(0, std::min(2, *mode));
+}
+void radtran_calls_in_flight_get(void *ptr, int *mode) {
+  Radtran *r = as_rad(ptr);
+  *mode = r ? r->calls_in_flight : 0;
+}
+void radtran_overlapped_calls_get(void *ptr, int *count) {
+  Radtran *r = as_rad(ptr);
+  *count = r ? (int)std::min<long>(r->holds.overlapped, 2147483647L) : 0;
+}
+void clima_test_two_in_flight(const int *rule, const int *in, int *out) {
+  PlanIn p{};
+  p.nz = in[0]; p.ng = in[1]; p.nzen = in[2]; p.n_ir = in[3]; p.n_sol = in[4]; p.op_n = in[5]; p.nsrc = in[6]; p.ncol = in[7];
+  p.batch = in[8] != 0; p.ir_batch = in[9] != 0; p.rebin_mode = in[10]; p.cust_on = in[11] != 0;
+  p.compute_opacity = in[12] != 0; p.all_pairs = in[13] != 0; p.fused = in[14] != 0; p.allow_fused = in[15] != 0;
+  p.ts_block_mode = in[16] != 0; p.no_half = in[17] != 0; p.coop_items = in[18]; p.force_slots = in[19];
+  const long waves = radiate_grid_waves(p, plan_radiate(p));
+  TwoInFlight q{};
+  q.mode = rule[0];
+  q.defer_ok = defer_allowed(rule[1] != 0, rule[2], rule[3] != 0, rule[4], rule[5] != 0, rule[6] != 0);
+  q.prev_unjoined = rule[7] != 0; q.sampled = rule[8] != 0; q.cus = rule[9];
+  q.fields_dirty = rule[10] != 0; q.int_pending = rule[11] != 0; q.integrates_in_one_launch = integrate_fits_one_launch(integrate_chunks(in[20]));
+  q.grid_waves = waves;
+  out[0] = two_in_flight_allowed(q) ? 1 : 0;
+  out[1] = (int)std::min<long>(waves, 2147483647L);
+  static_assert(CLIMA_TWO_IN_FLIGHT_RULE_N == 12, "the order documented in clima_radtran_hip.h");
+}
 
 // clima/fortran/Radtran.f90:109-118
 void radtran_unset_custom_optical_properties(void *ptr) {
@@ -1742,6 +1967,8 @@ void radtran_create_end(void *ptr, const int *num_zenith_angles, const double *s
   if (dev_count < 1) throw HipFail{"no HIP device available: the Radtran hot path has no CPU fallback"};
   HIPCHK(hipGetDevice(&r->device));
   HIPCHK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
+  r->lane_stream[0] = r->stream;
+  HIPCHK(hipDeviceGetAttribute(&r->cus, hipDeviceAttributeMultiprocessorCount, r->device));
   HIPCHK(hipEventCreateWithFlags(&r->ev_upload, hipEventDisableTiming));
 
   // ---- tables to HBM + interpolation slots
@@ -1881,7 +2108,33 @@ void radtran_radiate_resident(void *ptr, const int *compute_solar, const int *co
   GUARD_BUILT(r, ptr, err);
   if (refuse(r, "radiate_resident", NEED_COLUMN, err)) return;
   TRY
-  enqueue_radiate(r, resident_bufs(r), *compute_solar != 0, *compute_opacity != 0, true, /*defer=*/true);
+  const bool cs = *compute_solar != 0, co = *compute_opacity != 0;
+  // Two calls in flight (two_in_flight_allowed): where the handle pipelines two, a full call integrates at once -- the
+  // other lane's grid covers that bubble -- and, when nobody has joined the previous such call, runs beside it: in the
+  // other slot, on the other lane.  Every other call joins first (enqueue_radiate) and stays where the handle is.
+  upload_fields(r);   // (stale fields: behind a join and a host wait, as the call itself would; then it decides)
+  const bool beside = cs && co && two_in_flight(r, r->holds.unjoined, r->int_pending);
+  const bool two = beside || (cs && co && pipelining_two(r));
+  if (beside) {
+    ensure_other_slot(r);
+    swap_slot(r);
+    r->lane ^= 1;
+    try {
+      LaneScope lane(r, r->lane);
+      enqueue_radiate(r, resident_bufs(r), cs, co, true, false);
+    } catch (...) {
+      // the handle is again what it was: its buffers the previous call's slot (whatever reached the other lane is
+      // joined like a call: LaneScope left its event behind it)
+      swap_slot(r);
+      r->lane ^= 1;
+      r->holds.other_in_flight = true;
+      throw;
+    }
+    r->holds.call_pipelined(true);
+  } else {
+    enqueue_radiate(r, resident_bufs(r), cs, co, true, /*defer=*/!two);
+    if (two) r->holds.call_pipelined(false);
+  }
   CATCH(err)
 }
 
@@ -3770,6 +4023,9 @@ void radtran_finish_reduced(void *ptr, char *err) {
 void radtran_stream_get(void *ptr, void **stream) {
   Radtran *r = as_rad(ptr);
   *stream = r ? (void *)r->stream : nullptr;
+  if (!r || r->state != 2) return;
+  // whoever orders work of their own behind this stream finds every call enqueued so far on it
+  try { join_lanes(r); } catch (const HipFail &f) { defer_err(r, f.msg); }
 }
 
 void radtran_profile_set(void *ptr, const int *enable) {
@@ -3791,7 +4047,7 @@ void radtran_kernel_time_get(void *ptr, const int *kernel_id, double *ms_total, 
   GUARD(r, ptr, err);
   if (*kernel_id < 0 || *kernel_id > 6) { set_err(err, "kernel id out of range"); return; }
   TRY
-  if (!r->pending.empty()) { HIPCHK(hipStreamSynchronize(r->stream)); resolve_events(r); }
+  if (!r->pending.empty()) { drain_lanes(r); resolve_events(r); }
   *ms_total = r->k_ms[*kernel_id];
   *launches = r->k_n[*kernel_id];
   CATCH(err)

@@ -600,6 +600,17 @@ struct Holds {
   int opr_lo = 0, opr_n = 0;            // ... the opacity bins [opr_lo, opr_lo + opr_n) it was computed for
   bool rows_on_host = false, rows_in_pinned = false;   // the level rows: h_small is current; the last integration stored them there itself
   bool rows = false;                                   // ... some call has left level rows on the handle at all
+  // Two call slots (the handle's buffer members ARE the current slot's): whether work enqueued on
+  // the other one's stream has not been joined yet, and whether the previous call was a pipelined resident call that
+  // nobody has waited for or joined since (only then may the next one take the other slot)
+  bool other_in_flight = false, unjoined = false;
+  long overlapped = 0;                                 // calls enqueued on a slot while the other's call had not been joined
+
+  void call_pipelined(bool took_other) {               // a resident call that may have a successor beside it
+    if (took_other) { other_in_flight = true; overlapped++; }
+    unjoined = true;
+  }
+  void joined() { other_in_flight = false; unjoined = false; }
 
   void uploaded(bool has_particles) { column = true; column_particles = has_particles; uploads++; }
   void opacities_written(bool own_block, bool w0, bool from_resident, int lo, int n) {

@@ -48,6 +48,10 @@ SIGNATURES = {
     "radtran_defer_integration_get": [_vp, _ip],
     "radtran_merged_integrations_get": [_vp, _ip, _ip],
     "clima_test_defer_allowed": [_ip, _ip, _ip, _ip, _ip, _ip, _ip],
+    "radtran_calls_in_flight_set": [_vp, _ip],
+    "radtran_calls_in_flight_get": [_vp, _ip],
+    "radtran_overlapped_calls_get": [_vp, _ip],
+    "clima_test_two_in_flight": [_ip, _ip, _ip],
     "clima_test_plan_radiate": [_ip, _ip],
     "clima_test_handle_holds": [_ip, _ip, _ip],
     "clima_test_rebin_mode_for": [_ip, _dp, _ip, _ip],

@@ -1214,6 +1214,12 @@ class Radtran:
     defer_integration = _scalar("defer_integration", C.c_int, bool, "True (default): a `radiate_resident` call keeps its "
                                 "frequency integration back for the next call's prep launch (one grid for both); anything "
                                 "that reads results launches it first.  Same results bit for bit.")
+    calls_in_flight = _scalar("calls_in_flight", C.c_int, int, "Pipelined `radiate_resident` calls in flight: 0 (default) two "
+                              "where a call's grid does not fit the device in one residency round, 1 one at a time, 2 two "
+                              "whenever eligible.  Consecutive calls alternate between two sets of work buffers and two "
+                              "streams; everything else joins first.  Same results bit for bit.")
+    overlapped_calls = _scalar("overlapped_calls", C.c_int, int, "Calls enqueued on one call slot while the other slot's "
+                               "call had not been joined.", settable=False)
     del _scalar
 
     def _sub(self, name, cls):

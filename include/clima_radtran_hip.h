@@ -582,6 +582,7 @@ void radtran_fused_fallbacks_get(void *ptr, int *count);
  * it first, alone, exactly as the call itself would have.  Results are bitwise the same either way.  Never on a
  * bin-sharded handle or one with a communicator, with radtran_profile_set(1), while the handle's stream is being
  * captured, or once radtran_flux_device_ptr has been called (its caller reads the rows in stream order, unannounced).
+ * Nor where the handle keeps two calls in flight (radtran_calls_in_flight_set below): those calls integrate at once.
  * merged_integrations_get: pending integrations that went out with the next prep pass / alone. */
 void radtran_defer_integration_set(void *ptr, const int *enable);
 void radtran_defer_integration_get(void *ptr, int *enabled);
@@ -589,6 +590,37 @@ void radtran_merged_integrations_get(void *ptr, int *merged, int *standalone);
 /* test hook: the rule above as a function of its inputs (no handle, no device) */
 void clima_test_defer_allowed(const int *switch_on, const int *shard_world, const int *has_comm, const int *profile,
                               const int *capturing, const int *flux_ptr_taken, int *allowed);
+/* Two resident calls in flight.  Nothing orders the bulk of a pipelined radtran_radiate_resident call behind the one
+ * before it but the work buffers and the stream they share, so the handle keeps a second set of everything a call
+ * writes (a second call slot, allocated the first time it is used) and a second stream: a call that computes opacities
+ * and solar fluxes runs BESIDE the previous such call, in the slot that is not current, when it may keep its results
+ * back (the conditions of radtran_defer_integration_set above), when nobody has waited for or joined the previous call
+ * since it was enqueued, when its dominant kernel carries no event pair (radtran_profile_set(2): a timed launch runs
+ * alone), and when the mode allows it.  Such calls integrate at once; none is kept back.  Everything else -- every
+ * other call, every getter, radtran_synchronize, the batches, the Jacobians, a setter that rewrites device memory --
+ * first joins: the handle's stream waits for an event behind the other stream's work (no host wait), and the handle's
+ * buffers are those of the slot the latest call took.  radtran_upload_column between pipelined calls goes to the slot
+ * its next call will take.  Results are bitwise those of mode 1.
+ *   mode 0 (default): automatic -- when the call's grid does not fit the device in one residency round of two waves per
+ *          SIMD (waves of the fused grid, or of the separate form's opacity launch, > 8 x compute units); smaller calls
+ *          are launch-bound and keep the chain described above
+ *   mode 1: one call at a time   mode 2: two whenever eligible, whatever the size
+ * overlapped_calls_get: calls enqueued on a slot while the other slot's call had not been joined.
+ * radtran_stream_get stays the handle's first stream, and asking for it joins: ask AFTER the calls whose work is to be
+ * ordered against.  A stream obtained before them does not cover a call that ran on the second stream since (its work
+ * is ordered behind that call only by the next join: any entry point but a pipelined resident call or its upload). */
+void radtran_calls_in_flight_set(void *ptr, const int *mode);
+void radtran_calls_in_flight_get(void *ptr, int *mode);
+void radtran_overlapped_calls_get(void *ptr, int *count);
+/* test hook: the rule above as a function of its inputs (no handle, no device).  rule[CLIMA_TWO_IN_FLIGHT_RULE_N]:
+ *    0 mode   1..6 clima_test_defer_allowed's inputs in its order   7 the previous call is unjoined
+ *    8 the call's dominant kernel carries an event pair   9 compute units of the device
+ *   10 the handle's fields are stale on the device   11 an integration is pending
+ * (whether the integration fits the one-launch kernel is taken from in[20], the wider channel's bins)
+ * in[CLIMA_PLAN_IN_N]: the call, as clima_test_plan_radiate below takes it.  out[0]: the call takes the other slot;
+ * out[1]: the waves of its grid. */
+#define CLIMA_TWO_IN_FLIGHT_RULE_N 12
+void clima_test_two_in_flight(const int *rule, const int *in, int *out);
 /* test hook: the launch plan of one radiate call as the library's own planner (plan_radiate) decides it; no handle, no
  * device.  in[CLIMA_PLAN_IN_N], the planner's inputs in this order:
  *    0 nz   1 ng   2 nzen   3 n_ir   4 n_sol   5 op_n   6 nsrc   7 ncol   8 batch   9 ir_batch   10 rebin_mode
@@ -623,7 +655,9 @@ void clima_test_handle_holds(const int *n, const int *events, int *out);
 /* test hook: the rebin form (0 window, 1 streaming, 2 streaming multi-edge) a handle takes for these ng g-point weights;
  * stream != 0: as under CLIMA_HIP_REBIN=stream */
 void clima_test_rebin_mode_for(const int *ng, const double *weights, const int *stream, int *mode);
-/* HIP stream the handle launches on (for callers that order other work against it) */
+/* HIP stream the handle launches on (for callers that order other work against it).  Always the same stream.  The
+ * call joins the handle's second stream into it (radtran_calls_in_flight_set): ask after the calls to be ordered
+ * against -- a value cached earlier does not cover pipelined calls that ran on the second stream since. */
 void radtran_stream_get(void *ptr, void **stream);
 /* per-kernel device time (HIP events on the handle's stream).  enable = 1 records events
  * around every kernel, enable = 2 around the dominant kernel (id 1, opacity) only, 0 turns
