@@ -16,6 +16,10 @@ What is closed about them:
   * `radiate_closed`: the orchestration of clima_radtran_radiate.f90:50-192 and clima_radtran.f90:255-316 around the
     two sweeps.  It takes tau[nz][ng][nw] as an argument; `closed_for(case)` without one takes `mixing_split`'s, and
     the closed path stands on its own from the tables to the fluxes.
+  * `radiate_exact`: the same orchestration with scattering on, around the 50-digit solves of the two-stream SYSTEM in
+    tests/exact_two_stream.py (`ExactIr`, `ExactSolar`: one factorised column per (bin, g-point)) in place of the sweeps;
+    it takes w0[nz][ng][nw] and g[nz][nw] next to tau.  `SCATTERING_CASES` are built to scatter, and
+    `check_scattering_case` asserts on the exact reference alone that they do.
 
 Every array that the library hands out TOA-first (opr) is TOA-first here, every array it hands out ground-first
 (wrk_ir, wrk_sol, f_total) is ground-first here.
@@ -475,6 +479,147 @@ def radiate_closed(tables, tau, T_surface, T, nzen=1, albedo=0.0, emissivity=1.0
     return out
 
 
+# ------------------------------------------------------------------------------------------------ the exact call
+
+def _mp(v):
+    """a float64 as the exact number it is"""
+    return mpmath.mpf(float(v))
+
+
+def _freq_mp(wavl):
+    """clima_radtran_types_create.f90: freq = c / (wavl 1e-9), mpmath"""
+    c = mpmath.mpf(C_LIGHT)
+    return [c / (_mp(w) * mpmath.mpf("1e-9")) for w in wavl]
+
+
+class ExactIr:
+    """The IR channel of a call with scattering on: one `exact_two_stream.IrColumn` per (IR bin, g-point), factorised
+    once for every temperature profile and every unit response.  tau, w0 [nz][ng][nw], g [nz][nw]: float64, TOA-first, as
+    opr() gives them.  Every method works at exact_two_stream.DPS digits and stays in mpmath until `_ld`."""
+
+    def __init__(self, tables, tau, w0, g, emissivity, has_hard_surface, tau_min):
+        import exact_two_stream as X
+        self.dps = X.DPS
+        self.start, self.nwc = _channel_bins(tables, tables.ir_wavl)
+        self.nz, self.ng, _ = tau.shape
+        self.tables = tables
+        em = np.broadcast_to(np.asarray(emissivity, dtype=float), (self.nwc,))
+        with mpmath.workdps(self.dps):
+            self.wg = [_mp(w) for w in tables.ktables[0]["weights"]]
+            self.freq = _freq_mp(tables.ir_wavl)
+            self.cols = [[X.IrColumn(tau[:, k, self.start + l], w0[:, k, self.start + l], g[:, self.start + l], em[l],
+                                     has_hard_surface, tau_min) for k in range(self.ng)] for l in range(self.nwc)]
+
+    def nu(self, l):
+        return (self.freq[l] + self.freq[l + 1]) / 2
+
+    def bin_mp(self, l, bplanck):
+        """sum_g w_g of the bin's solves for the Planck values `bplanck` (nz+1 mpmath numbers, TOA-first, the surface's
+        last) -> up, dn (nz+1 mpmath numbers each, TOA-first)"""
+        up, dn = [mpmath.mpf(0)] * (self.nz + 1), [mpmath.mpf(0)] * (self.nz + 1)
+        for w, col in zip(self.wg, self.cols[l]):
+            fu, fd = col.solve_mp(bplanck)
+            up = [a + w * b for a, b in zip(up, fu)]
+            dn = [a + w * b for a, b in zip(dn, fd)]
+        return up, dn
+
+    def unit_mp(self, l, k):
+        """sum_g w_g d f(level) / d bplanck(k) of bin l -> up, dn (nz+1 each, TOA-first)"""
+        e = [mpmath.mpf(0)] * (self.nz + 1)
+        e[k] = mpmath.mpf(1)
+        return self.bin_mp(l, e)
+
+    def channel(self, T_surface, T):
+        """The IR call of clima_radtran.f90:262-283.  `T` ground-first as `radiate` takes it."""
+        nz, nwc = self.nz, self.nwc
+        ch = Channel()
+        ch.fup_a, ch.fdn_a = np.zeros((nz + 1, nwc), dtype=LD), np.zeros((nz + 1, nwc), dtype=LD)
+        ch.amean = np.zeros((nz + 1, nwc), dtype=LD)                                      # clima_radtran.f90:205
+        with mpmath.workdps(self.dps):
+            up_n, dn_n = [mpmath.mpf(0)] * (nz + 1), [mpmath.mpf(0)] * (nz + 1)
+            for l in range(nwc):
+                nu = self.nu(l)
+                B = [planck(nu, float(T[nz - 1 - i])) for i in range(nz)] + [planck(nu, float(T_surface))]
+                up, dn = self.bin_mp(l, B)
+                dfreq = self.freq[l] - self.freq[l + 1]
+                for i in range(nz + 1):                                                  # ground-first from here
+                    ch.fup_a[i, l], ch.fdn_a[i, l] = _ld(up[nz - i]), _ld(dn[nz - i])
+                    up_n[i] += up[nz - i] * dfreq
+                    dn_n[i] += dn[nz - i] * dfreq
+            ch.fup_n = np.array([_ld(x) for x in up_n], dtype=LD)
+            ch.fdn_n = np.array([_ld(x) for x in dn_n], dtype=LD)
+        return ch
+
+
+class ExactSolar:
+    """The solar channel of a call with scattering on: one `exact_two_stream.SolarColumn` per (solar bin, g-point); its
+    matrix serves every zenith angle and every albedo."""
+
+    def __init__(self, tables, tau, w0, g):
+        import exact_two_stream as X
+        self.dps = X.DPS
+        self.start, self.nwc = _channel_bins(tables, tables.sol_wavl)
+        self.nz, self.ng, _ = tau.shape
+        self.tables = tables
+        with mpmath.workdps(self.dps):
+            self.wg = [_mp(w) for w in tables.ktables[0]["weights"]]
+            self.cols = [[X.SolarColumn(tau[:, k, self.start + l], w0[:, k, self.start + l], g[:, self.start + l])
+                          for k in range(self.ng)] for l in range(self.nwc)]
+
+    def channel(self, zenith_u, zenith_weights, albedo, diurnal_fac, photon_scale_factor):
+        """The solar call of clima_radtran.f90:292-313 (the scale of :169-171, the photon conversion of :173-178)."""
+        nz, nwc, t = self.nz, self.nwc, self.tables
+        albedo = np.broadcast_to(np.asarray(albedo, dtype=float), (nwc,))
+        ch = Channel()
+        ch.fup_a, ch.fdn_a, ch.amean = (np.zeros((nz + 1, nwc), dtype=LD) for _ in range(3))
+        with mpmath.workdps(self.dps):
+            c, h = mpmath.mpf(C_LIGHT), mpmath.mpf(PLANK)
+            freq = _freq_mp(t.sol_wavl)
+            up_n, dn_n = [mpmath.mpf(0)] * (nz + 1), [mpmath.mpf(0)] * (nz + 1)
+            for l in range(nwc):
+                acc = [[mpmath.mpf(0)] * (nz + 1) for _ in range(3)]                      # amean, fup, fdn
+                for u0, zw in zip(zenith_u, zenith_weights):
+                    for w, col in zip(self.wg, self.cols[l]):
+                        f = _mp(zw) * w
+                        acc = [[a + f * b for a, b in zip(s, one)] for s, one in zip(acc, col.solve_mp(u0, albedo[l]))]
+                scale = _mp(t.photons_sol[l]) * _mp(photon_scale_factor) * _mp(diurnal_fac)
+                avg_freq = (freq[l] + freq[l + 1]) / 2
+                avg_wavl = mpmath.mpf("1e9") * c / avg_freq
+                to_photons = ((avg_freq / avg_wavl) * (avg_wavl / (h * c * mpmath.mpf("1e16"))) *
+                              (_mp(t.sol_wavl[l + 1]) - _mp(t.sol_wavl[l])))
+                dfreq = freq[l] - freq[l + 1]
+                for i in range(nz + 1):                                                  # ground-first from here
+                    am, up, dn = (a[nz - i] * scale for a in acc)
+                    ch.amean[i, l], ch.fup_a[i, l], ch.fdn_a[i, l] = _ld(am * to_photons), _ld(up), _ld(dn)
+                    up_n[i] += up * dfreq
+                    dn_n[i] += dn * dfreq
+            ch.fup_n = np.array([_ld(x) for x in up_n], dtype=LD)
+            ch.fdn_n = np.array([_ld(x) for x in dn_n], dtype=LD)
+        return ch
+
+
+def radiate_exact(tables, tau, w0, g, T_surface, T, nzen=1, albedo=0.0, emissivity=1.0, has_hard_surface=True,
+                  ir_tau_min=1.0e-6, diurnal_fac=0.5, photon_scale_factor=1.0):
+    """`Radtran%radiate` + `TOA_fluxes` with scattering on, for the optical properties tau, w0 [nz][ng][nw] and g [nz][nw]
+    (float64, TOA-first, as opr() gives them): `radiate_closed`'s orchestration around the 50-digit solves of
+    tests/exact_two_stream.py in place of the two sweeps.  Every sum over g-points, zenith angles and bins stays in mpmath
+    until the one rounding to np.longdouble."""
+    tau, w0, g = (np.asarray(a, dtype=float) for a in (tau, w0, g))
+    assert w0.shape == tau.shape and g.shape == (tau.shape[0], tau.shape[2])
+    out = Closed()
+    out.ir = ExactIr(tables, tau, w0, g, emissivity, has_hard_surface, ir_tau_min).channel(T_surface, T)
+    u, w = zenith(nzen)
+    out.sol = ExactSolar(tables, tau, w0, g).channel(u, w, albedo, diurnal_fac, photon_scale_factor)
+    return _totals(out, tau.shape[0])
+
+
+def _totals(out, nz):
+    out.f_total = (out.sol.fdn_n - out.sol.fup_n) + (out.ir.fdn_n - out.ir.fup_n)
+    out.isr = out.sol.fdn_n[nz] - out.sol.fup_n[nz]
+    out.olr = -(out.ir.fdn_n[nz] - out.ir.fup_n[nz])
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ measures
 
 def per_bin(got_up, got_dn, ref_up, ref_dn):
@@ -697,15 +842,139 @@ def absorption_case(name):
                 scalars=scalars)
 
 
-def closed_for(case, tau=None, T_surface=None, T=None, trans=None):
-    """`radiate_closed` with a case's settings.  Without `tau` it is `mixing_split`'s, rounded to doubles as the
-    solvers take it: the closed path then stands on its own from the tables to the fluxes."""
+def closed_for(case, tau=None, w0=None, g=None, T_surface=None, T=None, trans=None):
+    """`radiate_closed` with a case's settings, or `radiate_exact` where the case scatters (then with the w0 and g given,
+    or the stand-alone ones).  Without `tau` it is `mixing_split`'s, rounded to doubles as the solvers take it: the closed
+    path then stands on its own from the tables to the fluxes."""
     s, col = case["scalars"], case["column"]
+    if case.get("scatters"):
+        if tau is None:
+            tau, w0, g = standalone_properties(case)
+        assert w0 is not None and g is not None
+        return radiate_exact(case["tables"], tau, w0, g, col["T_surface"] if T_surface is None else T_surface,
+                             col["T"] if T is None else T, case["nzen"], case["albedo"], case["emissivity"],
+                             s["has_hard_surface"], s["ir_tau_min"], s["diurnal_fac"], s["photon_scale_factor"])
+    assert w0 is None and g is None
     if tau is None:
         tau = np.asarray(mixing_split(case["tables"], col)[0], dtype=float)
     return radiate_closed(case["tables"], tau, col["T_surface"] if T_surface is None else T_surface,
                           col["T"] if T is None else T, case["nzen"], case["albedo"], case["emissivity"],
                           s["has_hard_surface"], s["ir_tau_min"], s["diurnal_fac"], s["photon_scale_factor"], trans)
+
+
+# Scattering on.  Built as ABSORPTION_CASES are (per-bin albedo and emissivity, DIURNAL_FAC, PHOTON_SCALE, _SMALL tables);
+# make_tables' default inventory on the modern-Earth column gives a median w0 of 3e-5 in the solar channel and 0 in the IR,
+# so each case is built to scatter: `check_scattering_case` asserts on the exact reference alone that it does.
+#   rayleigh: Rayleigh scattering by every species over one weak k-species -- the conservative end, g = 0
+#   dusty:    the full inventory without photolysis cross-sections, a thin column (P x 0.03) with 1e3 x the particles at 10 x their radius
+#   custom:   `custom_props` with dtau_dz x 1e3 and w0 + 0.29, on a column that stays inside the custom pressure grid
+# id: dict(kind, tables, column, nzen, hard, tmin, channels the conditions are asserted in, cap: w0 reaches MAX_W0 there)
+_RAYLEIGH = dict(pxs_species=(), cia_pairs=(), water_continuum=False, particles=(), k_species=("CH4",))
+_DUSTY = dict(pxs_species=())
+SCATTERING_CASES = {
+    "rayleigh-sky-nz12": dict(kind="rayleigh", tables=dict(nw=10, seed=401), column=dict(nz=12), nzen=3, hard=True, tmin=1.0e-6,
+                              channels=("sol",), cap=True),
+    "dusty-nz33-no-surface": dict(kind="dusty", tables=dict(nw=10, seed=402), column=dict(nz=33), nzen=2, hard=False, tmin=1.0e-6,
+                                  channels=("sol", "ir"), cap=False),
+    "custom-nz12": dict(kind="custom", tables=dict(nw=10, seed=403), column=dict(nz=12), nzen=1, hard=True, tmin=1.0e-6,
+                        channels=("ir",), cap=True),
+    # 16 g-points at 65 layers: the half-wave two-stream launch
+    "nz65-g16": dict(kind="dusty", tables=dict(nw=5, ng=16, seed=404), column=dict(nz=65), nzen=1, hard=True, tmin=1.0e-6,
+                     channels=("sol", "ir"), cap=False),
+    # a doubled column: every upper layer of a pair reuses the lower one's opacities
+    "doubled-2x16": dict(kind="dusty", tables=dict(nw=8, seed=405), column=dict(nz=32, doubled=True), nzen=2, hard=True, tmin=1.0e-6,
+                         channels=("sol", "ir"), cap=False),
+    "nz64-unsorted": dict(kind="dusty", tables=dict(nw=6, seed=406, sorted_k=False), column=dict(nz=64), nzen=1, hard=True,
+                          tmin=1.0e-2, channels=("sol", "ir"), cap=False),
+    # 8 g-points above 64 layers, where the fused grid takes the call (coop_items = 0): its half-wave form, its whole-wave
+    # form (custom properties) and its paired form (a doubled column beyond 224 layers)
+    "nz70-fused-half": dict(kind="dusty", tables=dict(nw=5, seed=407), column=dict(nz=70), nzen=2, hard=True, tmin=1.0e-6,
+                            channels=("sol", "ir"), cap=False),
+    "custom-nz66-fused-wave": dict(kind="custom", tables=dict(nw=5, seed=408), column=dict(nz=66), nzen=1, hard=True, tmin=1.0e-6,
+                                   channels=("ir",), cap=True),
+    "doubled-2x113-fused-paired": dict(kind="dusty", tables=dict(nw=3, seed=409), column=dict(nz=226, doubled=True), nzen=1,
+                                       hard=False, tmin=1.0e-6, channels=("sol", "ir"), cap=False),
+}
+# (particles of 1e-5 cm, the column's own, leave g below 0.02 in the IR bins: the exact answer at g = 0 is then no other
+# answer there.  At 1e-4 cm g reaches 0.37 in the IR and 0.84 in the solar channel.)
+DUSTY_P_SCALE, DUSTY_PARTICLES, DUSTY_RADII = 0.03, 1.0e3, 10.0
+CUSTOM_DTAU, CUSTOM_W0 = 1.0e3, 0.4
+W0_SHARE, W0_LEVEL = 0.4, 0.1          # at least 40 % of a channel's (layer, g, bin) elements have w0 > 0.1
+WRONG_FACTOR, WRONG_SHARE = 1.0e3, 0.5  # a reference with w0 = 0 (or g = 0) misses by 1e3 bounds in half the bins or more
+
+
+def scattering_props():
+    wv, P, dtau_dz, w0, g0 = custom_props()
+    return wv, P, dtau_dz * CUSTOM_DTAU, np.clip(w0 + CUSTOM_W0, 0.0, 1.0), g0
+
+
+def scattering_case(name):
+    """-> dict(tables, column, custom, nz, nzen, albedo, emissivity, scalars, channels, cap, scatters=True)"""
+    from clima_amd import synthetic as S
+    c = SCATTERING_CASES[name]
+    kind, ckw = c["kind"], dict(c["column"])
+    tb = S.make_tables(**dict(_SMALL, **dict({"rayleigh": _RAYLEIGH, "dusty": _DUSTY, "custom": _RAYLEIGH}[kind], **c["tables"])))
+    if kind == "dusty":
+        col = _column(P_scale=DUSTY_P_SCALE, **ckw)
+        col["pdensities"] = np.asfortranarray(col["pdensities"] * DUSTY_PARTICLES)
+        col["radii"] = np.asfortranarray(col["radii"] * DUSTY_RADII)
+    else:
+        col = _column(n_particles=0, **ckw)
+    nsol, nir = len(tb.sol_wavl) - 1, len(tb.ir_wavl) - 1
+    scalars = dict(has_hard_surface=c["hard"], ir_tau_min=c["tmin"], diurnal_fac=DIURNAL_FAC, photon_scale_factor=PHOTON_SCALE)
+    return dict(tables=tb, column=col, custom=scattering_props() if kind == "custom" else None, nz=ckw["nz"], nzen=c["nzen"],
+                albedo=np.linspace(0.05, 0.8, nsol), emissivity=np.linspace(0.6, 1.0, nir), scalars=scalars,
+                channels=c["channels"], cap=c["cap"], doubled=bool(ckw.get("doubled")), scatters=True)
+
+
+def standalone_properties(case):
+    """tau, w0 from `mixing_split` and g from `band_mean`, rounded to doubles: optical properties that take nothing from
+    the code under test."""
+    tau, w0 = mixing_split(case["tables"], case["column"], case["custom"])
+    g = band_mean(case["tables"], case["column"], case["custom"])[2]
+    return tuple(np.asarray(a, dtype=float) for a in (tau, w0, g))
+
+
+def channel_slice(tables, which):
+    start, n = _channel_bins(tables, tables.ir_wavl if which == "ir" else tables.sol_wavl)
+    return slice(start, start + n)
+
+
+def scattering_errors(got_ir, got_sol, ref):
+    """-> the per-bin distances (IR, solar, amean) of results from a `Closed`"""
+    return (per_bin(got_ir.fup_a, got_ir.fdn_a, ref.ir.fup_a, ref.ir.fdn_a),
+            per_bin(got_sol.fup_a, got_sol.fdn_a, ref.sol.fup_a, ref.sol.fdn_a),
+            per_bin_one(got_sol.amean, ref.sol.amean))
+
+
+def check_scattering_case(case, tau, w0, g, exact, tol_bin):
+    """The conditions on a case, asserted on the exact reference alone (`exact` = closed_for(case, tau, w0, g)), so that no
+    test passes by dilution: the optical properties are in range; in each channel the case is for, at least W0_SHARE of
+    the elements have w0 > W0_LEVEL (and one at least sits at the cap where the case is a cap case); and the exact answer
+    at w0 = 0 -- where g != 0 also the one at g = 0 -- is WRONG_FACTOR x the per-bin bound and more away in at least
+    WRONG_SHARE of that channel's bins.  -> what was measured, for printing."""
+    tables = case["tables"]
+    assert np.all(tau > 0) and np.all((w0 >= 0) & (w0 <= MAX_W0)) and np.all(np.abs(g) <= MAX_GT)
+    out = {}
+    for ch in case["channels"]:
+        s = channel_slice(tables, ch)
+        share = float(np.mean(w0[:, :, s] > W0_LEVEL))
+        assert share >= W0_SHARE, (ch, share)
+        at_cap = float(np.mean(w0[:, :, s] == MAX_W0))
+        assert not case["cap"] or at_cap > 0, ch
+        out[ch] = dict(share=share, at_cap=at_cap, w0_max=float(np.max(w0[:, :, s])), g_max=float(np.max(np.abs(g[:, s]))))
+    wrong = [("w0=0", np.zeros_like(w0), g)]
+    if np.any(g != 0):
+        wrong.append(("g=0", w0, np.zeros_like(g)))
+    for what, w0_, g_ in wrong:
+        other = closed_for(case, tau, w0_, g_)
+        e_ir, e_sol, _ = scattering_errors(other.ir, other.sol, exact)
+        for ch in case["channels"]:
+            e = e_ir if ch == "ir" else e_sol
+            far = float(np.mean(e >= WRONG_FACTOR * tol_bin))
+            assert far >= WRONG_SHARE, (what, ch, far, e)
+            out[ch][what] = (far, float(np.max(e)))
+    return out
 
 
 def tiny_fraction(ch):

@@ -19,8 +19,10 @@ The IR fluxes are linear in the Planck values, so the nz+1 unit-vector solves gi
 factorisation of the matrix serves every right-hand side (`IrColumn`), and the solar matrix does not depend on u0
 (`SolarColumn`).  The `_mp` methods return mpmath numbers for the checks that are made before rounding.
 
-`mpmath` is imported here and in tests/golden/make_exact_two_stream.py only: the GPU tests read what the generator
-stored.
+`mpmath` is used in two ways.  The column-by-column GPU tests (test_gpu_exact_two_stream.py) read what the generator
+tests/golden/make_exact_two_stream.py stored.  The whole-call tests run it live: `closed_forms.radiate_exact` builds one
+`IrColumn` / `SolarColumn` per (bin, g-point) of a small case and keeps every sum over g-points, zenith angles and bins in
+mpmath (test_closed_forms_host.py without a GPU, test_gpu_closed_forms.py with one; 0.2-2.5 s per case).
 """
 import mpmath
 import numpy as np

@@ -12,6 +12,20 @@ Bounds (none of them comes from what the code under test gives):
     maximum ((1.5 + |x|) 2^-52 with |x| <= 70 for one exponential is 1.6e-14; the cumulative optical depth of at most
     130 layers adds 130 x 2^-53 x 70 = 1e-12 at the very worst, every rounding on one side)
 
+  * scattering on (closed_forms.SCATTERING_CASES): a whole call against `radiate_exact`, the 50-digit solves of the
+    two-stream system, on the oracle's own tau, w0, g -- per bin TOL_BIN_SOLVE = 2e-10 (test_gpu_golden.TOL, the project's
+    bound for one production solve against the reference's solver), both compilations; level fluxes, f_total, ISR, OLR
+    1e-9.  Every case first meets `check_scattering_case` on the exact reference alone: at least 40 % of its channel's
+    elements have w0 > 0.1, the cap cases reach the cap, and the exact answer at w0 = 0 (at g = 0) is 1e3 bounds away in
+    half the bins or more.  custom-nz12 also with tau, w0 from `mixing_split` and g from `band_mean`: nothing of the oracle
+
+Measured here, scattering on (worst over the nine cases and both compilations):
+  * IR per bin 1.2e-11 (rayleigh-sky-nz12, ir_tau_min = 1e-6; the two compilations are 1.2e-11 apart there): 0.057 of the
+    bound; solar per bin 1.7e-15, amean 1.2e-15; level fluxes 7.1e-12, f_total 4.6e-11, OLR 7.9e-12, ISR 8.0e-16
+  * stand-alone custom-nz12: IR 1.6e-15, solar 4.1e-16, amean 5.3e-16
+  * the exact answer at w0 = 0 is up to 0.88 of a bin's maximum away, at g = 0 up to 0.33; two bins' albedos swapped 0.60
+  * the exact call takes 0.2-2.4 s per case
+
 Measured here (worst over the cases of closed_forms.OPACITY_CASES / ABSORPTION_CASES; pytest -s prints each):
   * tau_band 4.8e-14, g 6.2e-15 (margin to 1e-12: 20x and more)
   * sum_g w_g tau against tau_band 3.6e-16; w0 tau against scat 9.7e-16, spread over the g-points 2.2e-16
@@ -32,6 +46,8 @@ RTOL_MEAN = 1e-12
 TOL_BIN = 2e-12
 TOL_LEVEL = RTOL_TOA = 1e-9          # tests/test_gpu_parity.py
 RTOL_ELEMENT = 1e-12
+TOL_BIN_SOLVE = 2e-10                # tests/test_gpu_golden.py TOL: one production solve against the reference's solver
+STANDALONE_CASE = "custom-nz12"
 
 
 def _rel(a, b, where=None):
@@ -152,6 +168,81 @@ def test_oracle_pure_absorption_against_the_exact_sweeps(O, name):
     check_levels(ir, sol, o.f_total, o.isr, o.olr, closed)
     if not np.any(case["albedo"]):
         check_albedo_zero(sol, closed.sol)
+
+
+def oracle_pair(O, case):
+    """a scattering case through both compilations of the oracle"""
+    return tuple(_oracle(O, case["tables"], case["nz"], case["nzen"], case["column"], case["custom"], v, case["albedo"],
+                         case["emissivity"], case["scalars"]) for v in ("", "fma"))
+
+
+def oracle_scattering(O, name, standalone=False):
+    """One scattering case through both compilations of the oracle, and the 50-digit solves (`CF.radiate_exact`) on the
+    oracle's own tau, w0, g -- `standalone`: on `CF.standalone_properties`, which take nothing from the oracle either.
+    -> case, the two oracles, the properties, the exact call, each oracle's per-bin distances from it (IR, solar, amean)."""
+    case = CF.scattering_case(name)
+    oracles = oracle_pair(O, case)
+    props = CF.standalone_properties(case) if standalone else tuple(np.asarray(a) for a in oracles[0].opr()[:3])
+    exact = CF.closed_for(case, *props)
+    dist = [CF.scattering_errors(o.wrk_ir, o.wrk_sol, exact) for o in oracles]
+    return case, oracles, props, exact, dist
+
+
+@pytest.mark.parametrize("name", list(CF.SCATTERING_CASES))
+def test_oracle_scattering_against_the_exact_solves(O, name):
+    """A whole call with scattering on -- the hand-over of w0 and g from the opacities to the solvers, the delta scaling and
+    the caps, per-bin albedo and emissivity, the sums over g-points, zenith angles and bins, amean -- against
+    `CF.radiate_exact`, which shares nothing with oracle/.  -> the first compilation's per-bin distance from exact, the
+    yardstick of tests/test_gpu_closed_forms.py."""
+    import time
+    t0 = time.perf_counter()
+    case, oracles, (tau, w0, g), exact, dist = oracle_scattering(O, name)
+    seconds = time.perf_counter() - t0
+    print("\n    %s (oracle twice and the exact call: %.1f s)" % (name, seconds))
+    measured = CF.check_scattering_case(case, tau, w0, g, exact, TOL_BIN_SOLVE)
+    for ch, m in measured.items():
+        print("    %-3s w0 > %.1f in %.0f %% of the elements, at the cap %.1f %%, max w0 %.5f, max |g| %.3f; %s" % (
+            ch, CF.W0_LEVEL, 100 * m["share"], 100 * m["at_cap"], m["w0_max"], m["g_max"],
+            ", ".join("%s: %.0f %% of the bins 1e3 bounds away, worst %.2e" % (k, 100 * m[k][0], m[k][1]) for k in ("w0=0", "g=0") if k in m)))
+    for variant, o, errs in zip(("plain", "fma"), oracles, dist):
+        for what, e in zip(("IR", "solar", "amean"), errs):
+            print("    %-5s %-5s per bin: worst %.2e, share of the bound %.3f" % (variant, what, e.max(), e.max() / TOL_BIN_SOLVE))
+            assert np.all(e <= TOL_BIN_SOLVE), (variant, what, e)
+        assert np.all(np.asarray(o.wrk_ir.amean) == 0.0)
+        check_levels(o.wrk_ir, o.wrk_sol, o.f_total, o.isr, o.olr, exact)
+    two = CF.scattering_errors(oracles[1].wrk_ir, oracles[1].wrk_sol, _as_closed(oracles[0]))
+    print("    the two compilations apart: IR %.2e  solar %.2e  amean %.2e" % tuple(e.max() for e in two))
+
+
+def _as_closed(o):
+    c = CF.Closed()
+    c.ir, c.sol = o.wrk_ir, o.wrk_sol
+    return c
+
+
+def test_oracle_scattering_against_the_stand_alone_reference(O):
+    """custom-nz12 with nothing taken from the code under test: tau, w0 from `mixing_split`, g from `band_mean`."""
+    case, oracles, props, exact, dist = oracle_scattering(O, STANDALONE_CASE, standalone=True)
+    print()
+    for variant, o, errs in zip(("plain", "fma"), oracles, dist):
+        for what, e in zip(("IR", "solar", "amean"), errs):
+            print("    %-5s %-5s per bin: worst %.2e, share of the bound %.3f" % (variant, what, e.max(), e.max() / TOL_BIN_SOLVE))
+            assert np.all(e <= TOL_BIN_SOLVE), (variant, what, e)
+        check_levels(o.wrk_ir, o.wrk_sol, o.f_total, o.isr, o.olr, exact)
+
+
+def test_a_wrong_exact_call_is_told_apart():
+    """`radiate_exact` with two bins' albedos (emissivities) swapped is another answer by orders of magnitude."""
+    case = CF.scattering_case("rayleigh-sky-nz12")
+    props = CF.standalone_properties(case)
+    exact = CF.closed_for(case, *props)
+    wrong = dict(case, albedo=case["albedo"][::-1].copy(), emissivity=case["emissivity"][::-1].copy())
+    other = CF.closed_for(wrong, *props)
+    e_ir, e_sol, e_am = CF.scattering_errors(other.ir, other.sol, exact)
+    mid = len(e_sol) // 2 if len(e_sol) % 2 else None            # the middle bin of an odd count keeps its albedo
+    print("\n    albedos and emissivities reversed: IR %s  solar %s" % (e_ir, e_sol))
+    assert all(e >= CF.WRONG_FACTOR * TOL_BIN_SOLVE for i, e in enumerate(e_sol) if i != mid)
+    assert np.mean(e_ir >= CF.WRONG_FACTOR * TOL_BIN_SOLVE) >= 0.5
 
 
 def test_the_cold_column_reaches_bins_far_below_the_peak():
