@@ -174,6 +174,10 @@ struct CallSlot {
   DevBuf<double> d_small, d_flux_n;
   DevBuf<int> d_done;
   long col_upload = 0;       // the upload (Holds::uploads) its column block holds
+  // the integration its latest call kept back (Radtran::int_pending): plain device pointers into the buffers above, which
+  // swap_slot hands over without moving memory
+  bool int_pending = false, pending_pipelined = false;
+  IntegrateParams pending_ip;
 };
 
 struct Radtran {
@@ -309,10 +313,12 @@ struct Radtran {
   DevBuf<int> d_done;              // per opacity block: call id of its last completed run
   // A resident call that returns with nobody reading its results keeps its frequency integration back (pending_ip): the
   // next compute_opacity call launches it in one grid with its own prep pass (k_prep_integrate), anything else launches
-  // it first as it is (resolve_pending_integration).
+  // it first as it is (resolve_pending_integration).  A pending integration belongs to its call slot: these are the
+  // current slot's, `other` holds the second pair, swap_slot exchanges them.  pending_pipelined: kept back by a call of a
+  // handle that pipelines two -- the next call into this slot, two calls on, takes it along on the slot's lane.
   bool defer_integration = true;   // radtran_defer_integration_set
   bool flux_ptr_taken = false;     // radtran_flux_device_ptr was called: its caller reads d_small in stream order, unannounced
-  bool int_pending = false;
+  bool int_pending = false, pending_pipelined = false;
   IntegrateParams pending_ip;
   long merged_integrations = 0, standalone_integrations = 0;   // pending integrations resolved either way (radtran_merged_integrations_get)
   // Two resident calls in flight: consecutive pipelined calls alternate between the two call slots, each on a lane
@@ -355,7 +361,7 @@ struct Radtran {
     if (ev_upload) (void)hipEventDestroy(ev_upload);
     if (ev_producer) (void)hipEventDestroy(ev_producer);
     if (comm) (void)ncclCommDestroy(comm);
-    // (an integration still pending is dropped: nobody is left to read its rows)
+    // (an integration still pending, in either slot, is dropped: nobody is left to read its rows)
     for (hipEvent_t e : {ev_lane1, ev_fence, ev_colcopy}) if (e) (void)hipEventDestroy(e);
     if (lane_stream[1]) { (void)hipStreamSynchronize(lane_stream[1]); (void)hipStreamDestroy(lane_stream[1]); }   // (its kernels write the other slot's buffers, freed below)
     if (lane_stream[0]) stream = lane_stream[0];
@@ -375,6 +381,11 @@ Radtran *as_rad(void *ptr) {
 // has been given, by an event and a stream wait, never by a host wait.  Called where the handle's debts are resolved
 // (settle_device_batch, resolve_pending_integration, wait_error_words) and in front of a write to device memory that a
 // call in flight may read (drain_lanes, do_upload).  After it the next call stays in the current slot.
+// The other slot's call may have kept its integration back for the next call into that slot, two calls on; that call
+// now stays here, so the integration goes out at the join, alone, on lane 0 behind lane 1 -- the older call's, in front
+// of the current slot's own (which whoever reads or enqueues resolves as ever: resolve_pending_integration).  The fence
+// is recorded anew behind it: the launch reads the spectra lane 1 writes when it next takes that slot.
+void launch_other_slot_integration(Radtran *r);
 void join_lanes(Radtran *r) {
   if (r->on_other_lane) return;
   if (r->holds.other_in_flight) {
@@ -384,6 +395,11 @@ void join_lanes(Radtran *r) {
   }
   r->holds.joined();
   r->lane = 0;
+  if (r->other.int_pending) {
+    launch_other_slot_integration(r);
+    HIPCHK(hipEventRecord(r->ev_fence, r->lane_stream[0]));
+    r->fence_due = true;
+  }
 }
 // ... and both lanes have run dry (the one host wait of a setter that rewrites device memory the kernels read)
 void drain_lanes(Radtran *r) {
@@ -438,6 +454,7 @@ void swap_slot(Radtran *r) {
   for (int k = 0; k < 8; k++) spec[k]->swap(o.spec[k]);
   r->d_small.swap(o.d_small); r->d_flux_n.swap(o.d_flux_n); r->d_done.swap(o.d_done);
   std::swap(r->col_upload, o.col_upload);
+  std::swap(r->int_pending, o.int_pending); std::swap(r->pending_pipelined, o.pending_pipelined); std::swap(r->pending_ip, o.pending_ip);
 }
 
 // futils gauss_legendre (setup only, clima_eqns.f90:26-41)
@@ -988,11 +1005,12 @@ long radiate_grid_waves(const PlanIn &in, const LaunchPlan &pl) {
 // not current and on that slot's lane?  THE rule, every condition of it, as plain values: the call may keep its results
 // back (defer_ok: defer_allowed, the capture state included); nobody has waited for or joined the previous pipelined call
 // since it was enqueued; its dominant kernel carries no event pair (sampled: a timed launch runs alone); the fields on the
-// device are current (stale ones are uploaded behind a join and a host wait); no integration is pending (it reads the
-// current slot's spectra on lane 0); the integration fits the one-launch kernel (the other form's partial sums are
-// shared); and the mode says so: 1 never, 2 always, 0 (automatic) when the grid does not fit the device in one residency
-// round of two waves per SIMD -- a smaller call is launch-bound, and the tests pin its launch sequence.  Everything else
-// joins first and stays in the current slot.
+// device are current (stale ones are uploaded behind a join and a host wait); no integration is pending that a call
+// which was not pipelined kept back (a pipelined call's own stays in its slot for the next call into that slot and
+// keeps nobody from going beside: radtran_radiate_resident feeds in only the former); the integration fits the
+// one-launch kernel (the other form's partial sums are shared); and the mode says so: 1 never, 2 always, 0 (automatic)
+// when the grid does not fit the device in one residency round of two waves per SIMD -- a smaller call is launch-bound,
+// and the tests pin its launch sequence.  Everything else joins first and stays in the current slot.
 struct TwoInFlight {
   int mode;
   bool defer_ok, prev_unjoined, sampled, fields_dirty, int_pending, integrates_in_one_launch;
@@ -1023,13 +1041,16 @@ bool two_in_flight(Radtran *r, bool prev_unjoined, bool int_pending) {
   q.defer_ok = !stream_capturing(r);
   return two_in_flight_allowed(q);
 }
-// ... were the previous call unjoined: the handle pipelines two, so its full resident calls integrate at once
+// ... were the previous call unjoined: the handle pipelines two, so its full resident calls alternate between the slots
+// and each keeps its integration back in its own
 bool pipelining_two(Radtran *r) { return two_in_flight(r, true, false); }
 
-// THE place where a pending integration is resolved.  With the prep parameters of a compute_opacity call that is about
-// to launch its prep pass (and clears nothing there): both in one grid where k_prep_integrate covers them -- returns
-// true, the prep pass is launched.  Otherwise (prep null: everything else that enqueues work or reads results, through
-// settle_device_batch) the integration alone, with the parameters stored when its call was enqueued -- returns false.
+// THE place where the current slot's pending integration is resolved.  With the prep parameters of a compute_opacity
+// call that is about to launch its prep pass (and clears nothing there): both in one grid where k_prep_integrate covers
+// them -- returns true, the prep pass is launched.  Otherwise (prep null: everything else that enqueues work or reads
+// results, through settle_device_batch) the integration alone, with the parameters stored when its call was enqueued --
+// returns false.  A call beside the previous one (LaneScope) finds here what the call two before it left in the slot it
+// takes, and launches it on that slot's lane; everyone else joins first, which sends the other slot's out ahead.
 bool resolve_pending_integration(Radtran *r, const PrepParams *prep = nullptr) {
   join_lanes(r);   // (whoever comes here enqueues work or reads results: the other lane's call first)
   if (!r->int_pending) return false;
@@ -1043,6 +1064,12 @@ bool resolve_pending_integration(Radtran *r, const PrepParams *prep = nullptr) {
   { KernelTimer t(r, 3); launch_integrate(r->pending_ip, r->stream); HIPCHK(hipGetLastError()); t.stop(); }
   r->standalone_integrations++;
   return false;
+}
+// ... and the other slot's, at a join (join_lanes): alone, on lane 0
+void launch_other_slot_integration(Radtran *r) {
+  r->other.int_pending = false;
+  { KernelTimer t(r, 3); launch_integrate(r->other.pending_ip, r->lane_stream[0]); HIPCHK(hipGetLastError()); t.stop(); }
+  r->standalone_integrations++;
 }
 
 // The current slot's column block is the handle's latest column: an upload went to the slot its next call was expected
@@ -1071,7 +1098,11 @@ void ensure_column(Radtran *r) {
 
 // plan -> prep -> opacity (or the fused grid) -> two-stream -> integrate -> reduce, on the buffers `b` names
 // defer: the caller returns without anyone reading a result, so the integration may wait for the next call's prep launch
-void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused = true, bool defer = false) {
+// (DEFER_FOR_A_MERGE, a pipelined call of a handle that keeps two in flight: only where this call's own prep pass
+// cleared nothing -- the next call into the slot has this call's shape, and behind a prep pass that clears the kept-back
+// integration would only be the same launch later on the same lane, which measured 1.6 us per call slower at config 5)
+enum Defer { DEFER_NEVER = 0, DEFER_ALWAYS, DEFER_FOR_A_MERGE };
+void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool compute_opacity, bool allow_fused = true, Defer defer = DEFER_NEVER) {
   char why[CLIMA_ERR_LEN + 1];   // (a one-launch batch left its optical properties in the arena, another shard's pass covers other bins)
   if (!compute_opacity && refuse(r, "radiate", NEED_OPACITIES, why)) throw HipFail{why};
   r->timer_calls++;
@@ -1136,9 +1167,11 @@ void enqueue_radiate(Radtran *r, const CallBufs &b, bool compute_solar, bool com
   const bool reduce = r->comm && resident;
   const IntegrateParams ip = make_integrate_params(r, b, compute_solar, reduce);
   r->holds.rows_enqueued(ip.host_out != nullptr);
-  if (defer && resident && !reduce && !ip.host_out && integrate_fits_one_launch(ip.nchunk) && defer_eligible(r)) {
+  const bool may_defer = defer == DEFER_ALWAYS || (defer == DEFER_FOR_A_MERGE && !plan.prep_clears);
+  if (may_defer && resident && !reduce && !ip.host_out && integrate_fits_one_launch(ip.nchunk) && defer_eligible(r)) {
     r->pending_ip = ip;
     r->int_pending = true;
+    r->pending_pipelined = false;   // (radtran_radiate_resident marks a pipelined call's)
   } else {
     KernelTimer t(r, 3); launch_integrate(ip, r->stream); HIPCHK(hipGetLastError()); t.stop();
   }
@@ -2109,11 +2142,15 @@ void radtran_radiate_resident(void *ptr, const int *compute_solar, const int *co
   if (refuse(r, "radiate_resident", NEED_COLUMN, err)) return;
   TRY
   const bool cs = *compute_solar != 0, co = *compute_opacity != 0;
-  // Two calls in flight (two_in_flight_allowed): where the handle pipelines two, a full call integrates at once -- the
-  // other lane's grid covers that bubble -- and, when nobody has joined the previous such call, runs beside it: in the
-  // other slot, on the other lane.  Every other call joins first (enqueue_radiate) and stays where the handle is.
+  // Two calls in flight (two_in_flight_allowed): where the handle pipelines two, a full call, when nobody has joined the
+  // previous such call, runs beside it: in the other slot, on the other lane.  Every other call joins first
+  // (enqueue_radiate) and stays where the handle is.  Either way the call keeps its integration back IN ITS SLOT -- where
+  // its prep pass cleared nothing: DEFER_FOR_A_MERGE --, and the call that next takes the slot -- two calls on, on the
+  // same lane -- launches it with its own prep pass as one grid (resolve_pending_integration inside the LaneScope): a
+  // lane's chain is [integrate(i-2) | prep(i)] -> fused(i).  Only an integration kept back by a call that was not
+  // pipelined keeps the next call from going beside (it joins and takes it along where it is).
   upload_fields(r);   // (stale fields: behind a join and a host wait, as the call itself would; then it decides)
-  const bool beside = cs && co && two_in_flight(r, r->holds.unjoined, r->int_pending);
+  const bool beside = cs && co && two_in_flight(r, r->holds.unjoined, r->int_pending && !r->pending_pipelined);
   const bool two = beside || (cs && co && pipelining_two(r));
   if (beside) {
     ensure_other_slot(r);
@@ -2121,7 +2158,8 @@ void radtran_radiate_resident(void *ptr, const int *compute_solar, const int *co
     r->lane ^= 1;
     try {
       LaneScope lane(r, r->lane);
-      enqueue_radiate(r, resident_bufs(r), cs, co, true, false);
+      enqueue_radiate(r, resident_bufs(r), cs, co, true, DEFER_FOR_A_MERGE);
+      r->pending_pipelined = r->int_pending;
     } catch (...) {
       // the handle is again what it was: its buffers the previous call's slot (whatever reached the other lane is
       // joined like a call: LaneScope left its event behind it)
@@ -2132,7 +2170,8 @@ void radtran_radiate_resident(void *ptr, const int *compute_solar, const int *co
     }
     r->holds.call_pipelined(true);
   } else {
-    enqueue_radiate(r, resident_bufs(r), cs, co, true, /*defer=*/!two);
+    enqueue_radiate(r, resident_bufs(r), cs, co, true, two ? DEFER_FOR_A_MERGE : DEFER_ALWAYS);
+    r->pending_pipelined = two && r->int_pending;
     if (two) r->holds.call_pipelined(false);
   }
   CATCH(err)

@@ -582,8 +582,12 @@ void radtran_fused_fallbacks_get(void *ptr, int *count);
  * it first, alone, exactly as the call itself would have.  Results are bitwise the same either way.  Never on a
  * bin-sharded handle or one with a communicator, with radtran_profile_set(1), while the handle's stream is being
  * captured, or once radtran_flux_device_ptr has been called (its caller reads the rows in stream order, unannounced).
- * Nor where the handle keeps two calls in flight (radtran_calls_in_flight_set below): those calls integrate at once.
- * merged_integrations_get: pending integrations that went out with the next prep pass / alone. */
+ * Where the handle keeps two calls in flight (radtran_calls_in_flight_set below) a call's integration stays in its call
+ * slot and goes out with the prep pass of the next call INTO THAT SLOT, two calls on; whatever joins launches both
+ * slots' pending integrations alone, the older call's first.
+ * merged_integrations_get: pending integrations that went out with a later prep pass / alone, on either slot.  N >= 2
+ * pipelined calls of a shape that merges and one radtran_synchronize: (N - 2, 2) where two are in flight -- the older
+ * of the last two is launched too, not dropped -- against (N - 1, 1) one at a time. */
 void radtran_defer_integration_set(void *ptr, const int *enable);
 void radtran_defer_integration_get(void *ptr, int *enabled);
 void radtran_merged_integrations_get(void *ptr, int *merged, int *standalone);
@@ -596,11 +600,17 @@ void clima_test_defer_allowed(const int *switch_on, const int *shard_world, cons
  * and solar fluxes runs BESIDE the previous such call, in the slot that is not current, when it may keep its results
  * back (the conditions of radtran_defer_integration_set above), when nobody has waited for or joined the previous call
  * since it was enqueued, when its dominant kernel carries no event pair (radtran_profile_set(2): a timed launch runs
- * alone), and when the mode allows it.  Such calls integrate at once; none is kept back.  Everything else -- every
- * other call, every getter, radtran_synchronize, the batches, the Jacobians, a setter that rewrites device memory --
- * first joins: the handle's stream waits for an event behind the other stream's work (no host wait), and the handle's
- * buffers are those of the slot the latest call took.  radtran_upload_column between pipelined calls goes to the slot
- * its next call will take.  Results are bitwise those of mode 1.
+ * alone), and when the mode allows it.  Such a call, where its own prep pass cleared nothing, keeps its frequency
+ * integration back in its slot, and the call that next takes the slot -- two calls on, on the same stream -- launches
+ * it in one grid with its own prep pass (k_prep_integrate): two launches per call on each stream,
+ * `[integrate(i-2) | prep(i)] -> fused(i)`.  Where the prep pass clears the spectra (never merged) the call integrates
+ * at once, and a kept-back integration that meets such a pass goes out first, alone, on that stream.  An integration
+ * pending from a call that was not pipelined keeps the next call from running beside; a slot's own pipelined one does
+ * not.  Everything else -- every other call, every getter, radtran_synchronize, the batches, the Jacobians, a setter
+ * that rewrites device memory -- first joins: the handle's stream waits for an event behind the other stream's work (no
+ * host wait), the other slot's pending integration goes out on it, alone, and the handle's buffers are those of the
+ * slot the latest call took.  radtran_upload_column between pipelined calls goes to the slot its next call will take.
+ * Results are bitwise those of mode 1.
  *   mode 0 (default): automatic -- when the call's grid does not fit the device in one residency round of two waves per
  *          SIMD (waves of the fused grid, or of the separate form's opacity launch, > 8 x compute units); smaller calls
  *          are launch-bound and keep the chain described above
