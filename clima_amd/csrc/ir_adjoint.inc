@@ -27,29 +27,18 @@
 // Levels, layers, rows and k are TOA-first as in ir_green.inc.  fun[f] = 2 level + (0 up | 1 down), the functionals of
 // a requested level side by side: f = a ndir + (its place among the directions asked for).
 
-__global__ __launch_bounds__(64) void k_adjoint_rows(IrAdjointParams p) {
-  const GreenParams &gp = p.g;
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const int nz = gp.nz, nl = nz + 1, N = 2 * nz, nseg = (N + 63) / 64, nfun = p.nfun;
-  size_t qtau, qg; int bi, g;
-  green_q(gp, q, qtau, qg, bi, g);
-  const bool hard = gp.has_hard_surface != 0;
-  const double emis = hard ? gp.emissivity[gp.ir_lo + bi] : 0.0, Rsfc = hard ? 1.0 - emis : 0.0;
-  const double w = gp.wbin[g];
-  double *wk = p.work + (size_t)q * adjoint_work_rows(nfun) * N;
-  double *w_c = wk, *w_rd = wk + N, *w_a = wk + (size_t)2 * N, *w_y = wk + (size_t)3 * N, *w_lam = wk + (size_t)4 * N;
-  auto layer = [&](const int n) {     // layer n, or the virtual layer above / below the column (green_layer_of)
-    const int nc = min(max(n, 0), nz - 1);
-    return green_layer_of(gp, gp.tau[qtau + nc], gp.w0[qtau + nc], gp.g[qg + nc], n, Rsfc);
-  };
-
-  // ---- 1. the transposed system's rows and their elimination
+// Step 1 of k_adjoint_rows, shared with k_opr_adjoint (ir_opr_sens.inc): the transposed system's rows from the layers' e's
+// (layer_e(n): those of layer n, or of the virtual layer above / below the column) and their elimination; c', 1 / pivot and
+// D(r-1) go to w_c, w_rd, w_a (N = 2 nz doubles each).  One wave, lane = row.
+template <class LayerE>
+__device__ __forceinline__ void adjoint_eliminate(const int nz, const int lane, LayerE layer_e, double *w_c, double *w_rd, double *w_a) {
+  const int N = 2 * nz, nseg = (N + 63) / 64;
   double c_in = 0.0;
   for (int seg = 0; seg < nseg; seg++) {
     const int r = seg * 64 + lane, n = r >> 1;
     const bool on = r < N;
     // row r pairs the layers (n-1, n) when even, (n, n+1) when odd; so do its neighbours r-1, r+1 the other way round
-    const E4 ea = layer(n - 1).e, eb = layer(n).e, ec = layer(n + 1).e;
+    const E4 ea = layer_e(n - 1), eb = layer_e(n), ec = layer_e(n + 1);
     // (both kinds of row of both pairs, evaluated once for the whole wave as in k_green_factor)
     double Ae1, Be1, De1, Ao1, Bo1, Do1, Ae2, Be2, De2, Ao2, Bo2, Do2;
     green_row_even(ea, eb, Ae1, Be1, De1); green_row_odd(ea, eb, Ao1, Bo1, Do1);
@@ -82,6 +71,26 @@ __global__ __launch_bounds__(64) void k_adjoint_rows(IrAdjointParams p) {
     if (on) { w_c[r] = cp; w_rd[r] = rd; w_a[r] = a; }
     c_in = __shfl(cp, 63);
   }
+}
+
+__global__ __launch_bounds__(64) void k_adjoint_rows(IrAdjointParams p) {
+  const GreenParams &gp = p.g;
+  const int q = blockIdx.x, lane = threadIdx.x;
+  const int nz = gp.nz, nl = nz + 1, N = 2 * nz, nseg = (N + 63) / 64, nfun = p.nfun;
+  size_t qtau, qg; int bi, g;
+  green_q(gp, q, qtau, qg, bi, g);
+  const bool hard = gp.has_hard_surface != 0;
+  const double emis = hard ? gp.emissivity[gp.ir_lo + bi] : 0.0, Rsfc = hard ? 1.0 - emis : 0.0;
+  const double w = gp.wbin[g];
+  double *wk = p.work + (size_t)q * adjoint_work_rows(nfun) * N;
+  double *w_c = wk, *w_rd = wk + N, *w_a = wk + (size_t)2 * N, *w_y = wk + (size_t)3 * N, *w_lam = wk + (size_t)4 * N;
+  auto layer = [&](const int n) {     // layer n, or the virtual layer above / below the column (green_layer_of)
+    const int nc = min(max(n, 0), nz - 1);
+    return green_layer_of(gp, gp.tau[qtau + nc], gp.w0[qtau + nc], gp.g[qg + nc], n, Rsfc);
+  };
+
+  // ---- 1. the transposed system's rows and their elimination
+  adjoint_eliminate(nz, lane, [&](const int n) { return layer(n).e; }, w_c, w_rd, w_a);
 
   // ---- 2. per functional: lambda
   for (int f = 0; f < nfun; f++) {

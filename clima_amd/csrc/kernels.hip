@@ -3752,6 +3752,7 @@ void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s) {
 #include "ir_green.inc"
 #include "solar_batch.inc"
 #include "ir_adjoint.inc"
+#include "ir_opr_sens.inc"
 #ifndef CLIMA_WITHOUT_IR_ROWS_APPLY   // (tests/test_ir_spectra_batch_abi.py: the other kernels' assembly with and without it)
 #include "ir_rows_apply.inc"
 #endif

@@ -3405,6 +3405,160 @@ void radtran_ir_spectra_batch_vjp(void *ptr, const int *ncol, const double *T_su
   CATCH(err)
 }
 
+// Gradient of a loss on one column's IR spectra (and their sums over the bins) in the stored tau, w0, g: one adjoint and one
+// forward two-stream solve per (bin, g-point) on the stored opacities (ir_opr_sens.inc).  include/clima_radtran_hip.h has
+// the contract.  What both forms refuse, in the header's order; `lv`: the levels TOA-first.  false: the call can run
+static bool ir_opr_refused(Radtran *r, const char *who, int dim_T, int nsel, const int *spec_level, const void *T_surface, const void *T,
+                           const void *const gs[2], const void *const gn[2], const void *const out[3], std::vector<int> &lv, char *err) {
+  const std::string pre = std::string(who) + ": ";
+  const int nz = r->nz, nl = nz + 1;
+  if (dim_T != nz) { set_err(err, pre + "\"T\" has the dimension " + std::to_string(dim_T) + ", not nz = " + std::to_string(nz)); return true; }
+  if (nsel < 1) { set_err(err, pre + "nsel must be at least 1 (nsel = " + std::to_string(nsel) + ")"); return true; }
+  if (!spec_level) { set_err(err, pre + "\"spec_level\" is a required argument"); return true; }
+  lv.assign((size_t)nsel, 0);
+  for (int a = 0; a < nsel; a++) {
+    const int v = spec_level[a];
+    if (v < 1 || v > nl) {
+      set_err(err, pre + "spec_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
+      return true;
+    }
+    lv[a] = nz - (v - 1);
+  }
+  if (!gs[0] && !gs[1] && !gn[0] && !gn[1]) { set_err(err, pre + "none of g_ir_fup, g_ir_fdn, g_fup_n, g_fdn_n was given"); return true; }
+  if (!out[0] && !out[1] && !out[2]) { set_err(err, pre + "none of grad_tau, grad_w0, grad_g was given"); return true; }
+  if (!T) { set_err(err, pre + "\"T\" is a required argument"); return true; }
+  if (!T_surface) { set_err(err, pre + "\"T_surface\" is a required argument"); return true; }
+  return false;
+}
+// ... and of the handle, once the arguments stand: a bin shard or a communicator, no opacities, the work buffer's bound
+static bool ir_opr_handle_refused(Radtran *r, const char *who, char *err) {
+  const std::string pre = std::string(who) + ": ";
+  if (ir_rows_shard_refused(r, pre, err)) return true;
+  if (refuse(r, who, NEED_OPACITIES, err)) return true;
+  const int NQ = r->ir_n * r->ng;
+  const size_t n_work = ir_opr_work_count(r->nz, NQ), n_part = ir_opr_part_count(r->nz, NQ);
+  if (sizeof(double) * ((double)n_work + (double)n_part) > IR_ADJOINT_MAX_BYTES) {
+    set_err(err, pre + "the work buffer of " + std::to_string(NQ) + " (bin, g-point) pairs of nz = " + std::to_string(r->nz) + " layers would take " +
+                     std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " + std::to_string((long long)IR_ADJOINT_MAX_BYTES));
+    return true;
+  }
+  return false;
+}
+// The pass itself: device arrays in, device arrays out (each of `out` the whole array of radtran_opr_get's layout, or null),
+// enqueued on the handle's stream behind ready_stored_opacities.  The bins outside the IR channel are zeroed here.
+static void ir_opr_enqueue(Radtran *r, const std::vector<int> &lv, const double *d_Ts, const double *d_T, const double *const gs[2],
+                           const double *const gn[2], double *const out[3]) {
+  const int nz = r->nz, nsel = (int)lv.size(), NQ = r->ir_n * r->ng;
+  const size_t counts[3] = {r->d_tau.n, r->d_tau.n, r->d_g.n};
+  for (int k = 0; k < 3; k++)
+    if (out[k]) HIPCHK(hipMemsetAsync(out[k], 0, sizeof(double) * counts[k], r->stream));
+  if (r->ir_n < 1) return;
+  const size_t n_work = ir_opr_work_count(nz, NQ), n_part = ir_opr_part_count(nz, NQ);
+  // the level list goes up from pageable memory: the runtime has taken its copy of `lv` when the call returns, so an
+  // enqueue-only call right behind this one cannot change what this one reads (a shared pinned block could: its copy
+  // executes later); the device buffers themselves are reused in stream order
+  r->d_green_idx.reserve(nsel); r->d_adjoint.reserve(n_work + n_part);
+  HIPCHK(hipMemcpyAsync(r->d_green_idx.p, lv.data(), sizeof(int) * nsel, hipMemcpyHostToDevice, r->stream));
+  IrOprParams p;
+  std::memset(&p, 0, sizeof(p));
+  GreenParams &g = p.g;
+  g.nz = nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
+  g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
+  g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
+  g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
+  p.T = d_T; p.Ts = d_Ts; p.bplanck = nullptr;
+  p.nsel = nsel; p.gs_ld = r->ir.nw; p.level = r->d_green_idx.p;
+  p.gs_up = gs[0]; p.gs_dn = gs[1]; p.gn_up = gn[0]; p.gn_dn = gn[1];
+  p.work = r->d_adjoint.p; p.part_g = p.work + n_work;
+  p.grad_tau = out[0]; p.grad_w0 = out[1]; p.grad_g = out[2];
+  launch_ir_opr_sens(p, r->stream);
+  HIPCHK(hipGetLastError());
+}
+
+void radtran_ir_spectra_opr_vjp_device(void *ptr, const double *d_T_surface, const int *dim_T, const double *d_T, const int *nsel_,
+                                       const int *spec_level, const double *d_g_ir_fup, const double *d_g_ir_fdn, const double *d_g_fup_n,
+                                       const double *d_g_fdn_n, double *d_grad_tau, double *d_grad_w0, double *d_grad_g,
+                                       const void *producer_stream, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const char *who = "ir_spectra_opr_vjp_device";
+  const double *const gs[2] = {d_g_ir_fup, d_g_ir_fdn}, *const gn[2] = {d_g_fup_n, d_g_fdn_n};
+  const void *const gsv[2] = {d_g_ir_fup, d_g_ir_fdn}, *const gnv[2] = {d_g_fup_n, d_g_fdn_n}, *const outv[3] = {d_grad_tau, d_grad_w0, d_grad_g};
+  double *const out[3] = {d_grad_tau, d_grad_w0, d_grad_g};
+  std::vector<int> lv;
+  if (ir_opr_refused(r, who, *dim_T, *nsel_, spec_level, d_T_surface, d_T, gsv, gnv, outv, lv, err)) return;
+  if (ir_rows_not_device(r, std::string(who) + ": ", {{"T_surface", d_T_surface}, {"T", d_T}, {"g_ir_fup", d_g_ir_fup}, {"g_ir_fdn", d_g_ir_fdn},
+                                                      {"g_fup_n", d_g_fup_n}, {"g_fdn_n", d_g_fdn_n}, {"grad_tau", d_grad_tau},
+                                                      {"grad_w0", d_grad_w0}, {"grad_g", d_grad_g}}, err)) return;
+  if (ir_opr_handle_refused(r, who, err)) return;
+  TRY
+  ready_stored_opacities(r);
+  wait_for_producer(r, producer_stream);
+  ir_opr_enqueue(r, lv, d_T_surface, d_T, gs, gn, out);
+  CATCH(err)
+}
+
+// ... with host arrays, synchronous: the column and the cotangents go up, the gradients come back through the pinned block
+void radtran_ir_spectra_opr_vjp(void *ptr, const double *T_surface, const int *dim_T, const double *T, const int *nsel_,
+                                const int *spec_level, const double *g_ir_fup, const double *g_ir_fdn, const double *g_fup_n,
+                                const double *g_fdn_n, double *grad_tau, double *grad_w0, double *grad_g, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const char *who = "ir_spectra_opr_vjp";
+  const std::string pre = std::string(who) + ": ";
+  const double *const gs[2] = {g_ir_fup, g_ir_fdn}, *const gn[2] = {g_fup_n, g_fdn_n};
+  const void *const gsv[2] = {g_ir_fup, g_ir_fdn}, *const gnv[2] = {g_fup_n, g_fdn_n}, *const outv[3] = {grad_tau, grad_w0, grad_g};
+  double *const out[3] = {grad_tau, grad_w0, grad_g};
+  std::vector<int> lv;
+  if (ir_opr_refused(r, who, *dim_T, *nsel_, spec_level, T_surface, T, gsv, gnv, outv, lv, err)) return;
+  const int nz = r->nz, nsel = *nsel_;
+  for (int j = 0; j <= nz; j++) {
+    const double v = j < nz ? T[j] : *T_surface;
+    if (!(std::isfinite(v) && v > 0.0)) {
+      set_err(err, pre + "temperatures must be finite and positive (" + (j < nz ? "T(" + std::to_string(j + 1) + ")" : std::string("T_surface")) +
+                       " = " + std::to_string(v) + ")");
+      return;
+    }
+  }
+  if (ir_opr_handle_refused(r, who, err)) return;
+  TRY
+  ready_stored_opacities(r);
+  const size_t spec = (size_t)r->ir.nw * nsel, sums = (size_t)nsel;
+  const size_t counts[3] = {r->d_tau.n, r->d_tau.n, r->d_g.n};
+  r->d_bT.reserve(nz); r->d_bTs.reserve(1);
+  HIPCHK(hipMemcpyAsync(r->d_bT.p, T, sizeof(double) * nz, hipMemcpyHostToDevice, r->stream));
+  HIPCHK(hipMemcpyAsync(r->d_bTs.p, T_surface, sizeof(double), hipMemcpyHostToDevice, r->stream));
+  r->d_rows_out.reserve(std::max<size_t>(1, 2 * (spec + sums)));
+  const double *dgs[2] = {nullptr, nullptr}, *dgn[2] = {nullptr, nullptr};
+  {
+    double *at = r->d_rows_out.p;
+    for (int d = 0; d < 2; d++) {
+      if (gs[d]) {
+        if (spec) HIPCHK(hipMemcpyAsync(at, gs[d], sizeof(double) * spec, hipMemcpyHostToDevice, r->stream));
+        dgs[d] = at; at += spec;
+      }
+      if (gn[d]) {
+        HIPCHK(hipMemcpyAsync(at, gn[d], sizeof(double) * sums, hipMemcpyHostToDevice, r->stream));
+        dgn[d] = at; at += sums;
+      }
+    }
+  }
+  size_t total = 0;
+  for (int k = 0; k < 3; k++) total += out[k] ? counts[k] : 0;
+  r->d_bout.reserve(total);
+  double *d_out[3] = {nullptr, nullptr, nullptr};
+  {
+    double *at = r->d_bout.p;
+    for (int k = 0; k < 3; k++)
+      if (out[k]) { d_out[k] = at; at += counts[k]; }
+  }
+  ir_opr_enqueue(r, lv, r->d_bTs.p, r->d_bT.p, dgs, dgn, d_out);
+  for (int k = 0; k < 3; k++)
+    if (out[k]) rows_to_host(r, d_out[k], out[k], counts[k]);
+  HIPCHK(hipStreamSynchronize(r->stream));
+  CATCH(err)
+}
+
 // What every column batch refuses before anything else, with the texts of radtran_toa_fluxes_batch
 static bool batch_refused(Radtran *r, const int *ncol, const int *has_particles, char *err) {
   if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return true; }
@@ -4468,6 +4622,71 @@ void clima_test_ir_adjoint(const int *nz_, const int *ng_, const double *tau, co
     for (int k = 0; k < nl; k++) {      // the kernel writes (bin, a, j = nz - k)
       dfup[(size_t)a * nl + k] = out[a + (size_t)nr * (nz - k)];
       dfdn[(size_t)a * nl + k] = out[arr + a + (size_t)nr * (nz - k)];
+    }
+  CATCH(err)
+}
+
+// Test hook of the optical-property gradient (ir_opr_sens.inc), in the shape of clima_test_ir_adjoint: one column's tau /
+// w0 / g (the same for every g-point, weights wbin), its Planck values bplanck (nz+1, TOA-first) and nrow levels (0..nz,
+// TOA-first) -> d fup(level(a)) / d tau(n), / d w0(n), / d g(n) and the same of fdn, (nrow, nz) row after row, n TOA-first,
+// summed over the g-points.  ONE launch of the production kernels: every (row, direction) is a bin of its own with the
+// column's opacities and a unit cotangent on that row and direction alone.
+void clima_test_ir_opr_sens(const int *nz_, const int *ng_, const double *tau, const double *w0, const double *g,
+                            const double *bplanck, const double *ir_par, const double *wbin, const int *nrow_, const int *level,
+                            double *up_tau, double *up_w0, double *up_g, double *dn_tau, double *dn_w0, double *dn_g, char *err) {
+  clear_err(err);
+  TRY
+  const int nz = *nz_, ng = *ng_, nl = nz + 1, nr = *nrow_, nb = 2 * nr, NQ = nb * ng;
+  if (nz < 1 || ng < 1 || ng > 32 || nr < 1) throw HipFail{"clima_test_ir_opr_sens: bad nz / ng / nrow"};
+  for (int a = 0; a < nr; a++)
+    if (level[a] < 0 || level[a] > nz) throw HipFail{"clima_test_ir_opr_sens: bad level"};
+  const size_t ntau = (size_t)NQ * nz, ngg = (size_t)nb * nz;
+  std::vector<double> h_tau(ntau), h_w0(ntau), h_g(ngg), h_gs(2 * (size_t)nb * nr, 0.0);
+  for (int c = 0; c < NQ; c++)
+    for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau[i]; h_w0[(size_t)c * nz + i] = w0[i]; }
+  for (int b = 0; b < nb; b++)
+    for (int i = 0; i < nz; i++) h_g[(size_t)b * nz + i] = g[i];
+  for (int a = 0; a < nr; a++) {
+    h_gs[(size_t)(2 * a) + (size_t)nb * a] = 1.0;                               // up: bin 2a
+    h_gs[(size_t)nb * nr + (size_t)(2 * a + 1) + (size_t)nb * a] = 1.0;         // down: bin 2a+1
+  }
+  DevBuf<double> d_tau, d_w0, d_g, d_wbin, d_em, d_bp, d_gs, d_work, d_out;
+  DevBuf<int> d_lv;
+  d_tau.upload(h_tau); d_w0.upload(h_w0); d_g.upload(h_g);
+  d_wbin.upload(std::vector<double>(wbin, wbin + ng)); d_em.upload(std::vector<double>((size_t)nb, ir_par[0]));
+  d_bp.upload(std::vector<double>(bplanck, bplanck + nl)); d_gs.upload(h_gs);
+  d_lv.upload(std::vector<int>(level, level + nr));
+  const size_t n_work = ir_opr_work_count(nz, NQ), n_part = ir_opr_part_count(nz, NQ);
+  d_work.alloc(n_work + n_part); d_work.zero();
+  d_out.alloc(2 * ntau + ngg); d_out.zero();
+  IrOprParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.g.nz = nz; p.g.ng = ng; p.g.n_ir = nb; p.g.NQ = NQ;
+  p.g.tau = d_tau.p; p.g.w0 = d_w0.p; p.g.g = d_g.p; p.g.wbin = d_wbin.p; p.g.emissivity = d_em.p;
+  p.g.has_hard_surface = ir_par[1] != 0.0 ? 1 : 0; p.g.ir_tau_min = ir_par[2];
+  p.bplanck = d_bp.p;
+  p.nsel = nr; p.gs_ld = nb; p.level = d_lv.p;
+  p.gs_up = d_gs.p; p.gs_dn = d_gs.p + (size_t)nb * nr;
+  p.work = d_work.p; p.part_g = p.work + n_work;
+  p.grad_tau = d_out.p; p.grad_w0 = d_out.p + ntau; p.grad_g = d_out.p + 2 * ntau;
+  launch_ir_opr_sens(p, nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  std::vector<double> out(2 * ntau + ngg);
+  HIPCHK(hipMemcpy(out.data(), d_out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost));
+  double *const o_tau[2] = {up_tau, dn_tau}, *const o_w0[2] = {up_w0, dn_w0}, *const o_g[2] = {up_g, dn_g};
+  for (int a = 0; a < nr; a++)
+    for (int d = 0; d < 2; d++) {
+      const int b = 2 * a + d;
+      for (int i = 0; i < nz; i++) {
+        double st = 0.0, sw = 0.0;
+        for (int c = 0; c < ng; c++) {      // the g-points in g order
+          st = st + out[((size_t)b * ng + c) * nz + i];
+          sw = sw + out[ntau + ((size_t)b * ng + c) * nz + i];
+        }
+        o_tau[d][(size_t)a * nz + i] = st; o_w0[d][(size_t)a * nz + i] = sw;
+        o_g[d][(size_t)a * nz + i] = out[2 * ntau + (size_t)b * nz + i];
+      }
     }
   CATCH(err)
 }

@@ -554,6 +554,25 @@ __host__ __device__ inline size_t adjoint_work_rows(int nfun) { return 4 + (size
 inline size_t ir_adjoint_work_count(int nz, int NQ, int nfun) { return (size_t)NQ * adjoint_work_rows(nfun) * 2 * nz; }
 inline size_t ir_adjoint_part_count(int nz, int NQ, int nfun) { return (size_t)NQ * nfun * (nz + 1); }
 void launch_ir_adjoint(const IrAdjointParams &p, hipStream_t s);
+// Gradient of a loss on the IR level fluxes in the stored tau, w0, g (ir_opr_sens.inc, radtran_ir_spectra_opr_vjp): one
+// adjoint and one forward solve per (bin, g-point) on the adjoint's factors.  `g` carries the opacities and the surface
+// fields as in IrAdjointParams (base_T is not read); the test hook gives `bplanck` in place of the temperatures.
+struct IrOprParams {
+  GreenParams g;
+  const double *T, *Ts;                    // the column: (nz) ground-first layers, (1)
+  const double *bplanck;                   // [nz+1] TOA-first, the same for every bin, or null: planck_fcn(avg_freq(bin), T)
+  int nsel, gs_ld;                         // requested levels; the cotangent spectra's leading dimension (nw_ir)
+  const int *level;                        // [nsel] TOA-first, 0..nz
+  const double *gs_up, *gs_dn;             // (gs_ld, nsel) cotangents of the spectra, indexed by the IR channel's bin, or null
+  const double *gn_up, *gn_dn;             // (nsel) cotangents of the sums over the bins (times the bin's width), or null
+  double *work;                            // [NQ][OPR_WORK_ROWS][2 nz]: c', 1 / pivot, sub-diagonal, y / z, lambda, Y
+  double *part_g;                          // [NQ][nz]: a g-point's part of grad_g
+  double *grad_tau, *grad_w0, *grad_g;     // the optical properties' own layouts (radtran_opr_get), or null: not asked for
+};
+constexpr int OPR_WORK_ROWS = 6;
+inline size_t ir_opr_work_count(int nz, int NQ) { return (size_t)NQ * OPR_WORK_ROWS * 2 * nz; }
+inline size_t ir_opr_part_count(int nz, int NQ) { return (size_t)NQ * nz; }
+void launch_ir_opr_sens(const IrOprParams &p, hipStream_t s);
 // IR spectra of many temperature profiles from the adjoint's unit-amplitude rows (ir_rows_apply.inc,
 // radtran_ir_spectra_batch): f(bin, a, c) = sum over j of w(bin, a, j) B(avg_freq(bin), x_c(j)).  The ndir directions
 // asked for stand at places 0 and 1 (w0 / out0 / fn0, then w1 / out1 / fn1); functional F = place nsel + a.

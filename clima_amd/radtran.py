@@ -40,6 +40,39 @@ def _fo(a):
     return np.asfortranarray(a, dtype=np.float64)
 
 
+def grey_sensitivity(opr, grads, ir_tau_min, max_w0):
+    """From `Radtran.ir_spectra_opr_vjp`'s gradients to the response to an added GREY optical depth, per (layer, bin):
+    what a continuum, CIA, a cloud or the custom optical properties add to every g-point alike
+    (src/radtran/clima_radtran_types.f90:869-876: tau = sum of the parts, w0 = min(max_w0, scattering / tau), w0 = 0 where
+    tau <= tau_min).  `opr` is `Radtran.opr()`'s tuple (tau, w0 (nz, ngauss, nw), ...), `grads` the dict with "tau" and
+    "w0" of those shapes.  `ir_tau_min` and `max_w0` are the OPACITY STEP's two constants -- clima_radtran_types.f90:9-11:
+    tau_min = 1e-20 and max_w0 = 0.99999 -- below and at which that step pins w0; `ir_tau_min` here is NOT the two-stream
+    solver's thin-layer switch `Radtran.ir_tau_min` (1e-6 by default): with that value the w0 term of every layer with
+    1e-20 < tau <= 1e-6 would be dropped.  Returns (absorption, scattering),
+    each (nz, nw): the derivative of the loss with respect to an added absorption optical depth of layer n in bin l,
+        sum_i [grad_tau - grad_w0 w0 / tau],
+    and to an added scattering optical depth,
+        sum_i [grad_tau + grad_w0 (1 - w0) / tau],
+    the g-points in g order.  Where the opacity step pins w0 (tau <= ir_tau_min, or w0 at max_w0) the w0 term is dropped.
+    Pure numpy; no handle."""
+    tau, w0 = np.asarray(opr[0], dtype=np.float64), np.asarray(opr[1], dtype=np.float64)
+    for name in ("tau", "w0"):
+        if name not in grads:
+            raise ClimaException('grey_sensitivity: "grads" lacks "%s"' % name)
+        if tau.ndim != 3 or np.shape(grads[name]) != tau.shape or w0.shape != tau.shape:
+            raise ClimaException('grey_sensitivity: "%s" has the shape %s, not that of opr\'s tau %s' % (name, np.shape(grads[name]), tau.shape))
+    g_tau, g_w0 = np.asarray(grads["tau"], dtype=np.float64), np.asarray(grads["w0"], dtype=np.float64)
+    free = (tau > ir_tau_min) & (w0 < max_w0)
+    rtau = 1.0 / np.where(free, tau, 1.0)
+    dab = np.where(free, -(w0 * rtau), 0.0)
+    dsc = np.where(free, (1.0 - w0) * rtau, 0.0)
+    ab, sc = np.zeros((tau.shape[0], tau.shape[2])), np.zeros((tau.shape[0], tau.shape[2]))
+    for i in range(tau.shape[1]):
+        ab = ab + (g_tau[:, i, :] + g_w0[:, i, :] * dab[:, i, :])
+        sc = sc + (g_tau[:, i, :] + g_w0[:, i, :] * dsc[:, i, :])
+    return ab, sc
+
+
 class RTChannel:
     """clima/cython/RTChannel.pyx"""
 
@@ -937,6 +970,102 @@ class Radtran:
             self._ptr, _i(n), T_surface.data_ptr(), _i(nz), _i(n), T.data_ptr(), _i(nsel), addr(w, "w_up"), addr(w, "w_dn"),
             addr(g, "fup"), addr(g, "fdn"), addr(g, "fup_n"), addr(g, "fdn_n"), gTs.data_ptr(), gT.data_ptr(), producer, self._err), sync)
         return gTs, gT
+
+    IR_SPECTRA_OPR_WRT = ("tau", "w0", "g")
+
+    def _ir_spectra_opr_names(self, who, nz, grads, levels, wrt):
+        """What both forms of `ir_spectra_opr_vjp` check alike, with the prefix `who`: the names in `wrt` (-> in the ABI's
+        order), `levels` (-> 1..nz+1 as the ABI takes them) and the keys of `grads` (-> the dict without its None entries);
+        reads IR_SPECTRA_VJP_GRADS and IR_SPECTRA_OPR_WRT alone"""
+        wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+        for name in wrt:
+            if name not in self.IR_SPECTRA_OPR_WRT:
+                raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.IR_SPECTRA_OPR_WRT)))
+        if not wrt:
+            raise ClimaException(who + '"wrt" names none of %s' % ", ".join(self.IR_SPECTRA_OPR_WRT))
+        nl = nz + 1
+        idx = np.atleast_1d(np.asarray(levels))
+        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+            raise ClimaException(who + '"levels" is not a non-empty list of integer level indices')
+        for a, v in enumerate(idx.tolist()):
+            if v < -nl or v >= nl:
+                raise ClimaException(who + "levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
+        rows = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
+        if not isinstance(grads, dict):
+            raise ClimaException(who + '"grads" is not a dict with keys among %s' % ", ".join(self.IR_SPECTRA_VJP_GRADS))
+        for name in grads:
+            if name not in self.IR_SPECTRA_VJP_GRADS:
+                raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.IR_SPECTRA_VJP_GRADS)))
+        given = {k: v for k, v in grads.items() if v is not None}
+        if not given:
+            raise ClimaException(who + '"grads" holds none of %s' % ", ".join(self.IR_SPECTRA_VJP_GRADS))
+        return tuple(name for name in self.IR_SPECTRA_OPR_WRT if name in wrt), rows, given
+
+    def _ir_spectra_opr_request(self, nz, nw_ir, T_surface, T, grads, levels, wrt):
+        """The arrays of `ir_spectra_opr_vjp` as the ABI takes them -- (T_surface (1,), T (nz,), levels 1..nz+1, the four
+        cotangents in the ABI's order (Fortran-ordered float64, None where absent), the names of `wrt` in the ABI's
+        order) -- for a handle of nz layers and nw_ir IR bins; wrong shapes, unknown keys and names, levels outside
+        -(nz+1)..nz and a request without any cotangent are refused by name (reads IR_SPECTRA_VJP_GRADS and
+        IR_SPECTRA_OPR_WRT alone: no handle needed)."""
+        who = "ir_spectra_opr_vjp: "
+        T, Ts = _c(np.atleast_1d(T)), _c(np.atleast_1d(T_surface))
+        if Ts.shape != (1,):
+            raise ClimaException(who + '"T_surface" has the shape %s, not a scalar' % (tuple(np.shape(T_surface)),))
+        if T.shape != (nz,):
+            raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz,)))
+        names, rows, given = Radtran._ir_spectra_opr_names(self, who, nz, grads, levels, wrt)
+        nsel = len(rows)
+        g = [np.asfortranarray(given[k], dtype=np.float64) if k in given else None for k in self.IR_SPECTRA_VJP_GRADS]
+        for k, a in zip(self.IR_SPECTRA_VJP_GRADS, g):
+            want = (nsel,) if k.endswith("_n") else (nw_ir, nsel)
+            if a is not None and a.shape != want:
+                raise ClimaException(who + '"%s" has the shape %s, not %s' % (k, a.shape, want))
+        return Ts, T, rows, g, names
+
+    def ir_spectra_opr_vjp(self, T_surface, T, grads, levels=(-1,), wrt=("tau", "w0", "g")):
+        """The gradient of a loss on one column's IR spectra with respect to the stored optical properties
+        (radtran_ir_spectra_opr_vjp): the column is `radiate(T_surface, T, ..., compute_solar=False, compute_opacity=False)`
+        read at `wrk_ir.fup_a / fdn_a [levels[a], l]` and `fup_n / fdn_n [levels[a]]`; `grads` is a dict of cotangents keyed
+        as `ir_spectra_vjp`'s -- "fup" / "fdn" (nw_ir, nsel), "fup_n" / "fdn_n" (nsel,), an absent one counting as 0.
+        Returns a dict with the names in `wrt`: "tau" and "w0" (nz, ngauss, nw), "g" (nz, nw), Fortran-ordered, in `opr()`'s
+        layout element by element (TOA-first, opacity-bin index, 0 outside the IR channel), the g-point's weight included;
+        tau, w0 and g count as independent inputs.  One adjoint and one forward two-stream solve per (bin, g-point)
+        however many levels; bitwise repeatable; the handle's state is left untouched.  `grey_sensitivity` turns the result
+        into the response to an added grey absorber or scatterer."""
+        nz, nw_ir = self.nz, len(self.ir.freq) - 1
+        Ts, T, rows, g, names = self._ir_spectra_opr_request(nz, nw_ir, T_surface, T, grads, levels, wrt)
+        shapes = dict(tau=(nz, self.ngauss, self.nw), w0=(nz, self.ngauss, self.nw), g=(nz, self.nw))
+        out = {name: np.empty(shapes[name], order="F") for name in names}
+        ptr = lambda a: _d(a) if a is not None else None   # noqa: E731
+        self._L.radtran_ir_spectra_opr_vjp(self._ptr, _d(Ts), _i(nz), _d(T), _i(len(rows)), rows.ctypes.data_as(C.POINTER(C.c_int)),
+                                           ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(out.get("tau")), ptr(out.get("w0")),
+                                           ptr(out.get("g")), self._err)
+        self._check()
+        return out
+
+    def ir_spectra_opr_vjp_tensors(self, T_surface, T, grads, levels=(-1,), wrt=("tau", "w0", "g"), sync=False):
+        """`ir_spectra_opr_vjp` on torch CUDA float64 tensors (radtran_ir_spectra_opr_vjp_device): T_surface (1,), T (nz,),
+        `grads` "fup" / "fdn" (nsel, nw_ir), "fup_n" / "fdn_n" (nsel,), C-contiguous -- the host form's arrays, transposed.
+        Returns a dict of fresh tensors "tau" / "w0" (nw, ngauss, nz), "g" (nw, nz), bit for bit the host form's, transposed;
+        stream ordering and `sync` as in `ir_spectra_batch_tensors`."""
+        import torch
+        who = "ir_spectra_opr_vjp_device"
+        nz, nw_ir = self.nz, len(self.ir.freq) - 1
+        names, rows, g = Radtran._ir_spectra_opr_names(self, who + ": ", nz, grads, levels, wrt)
+        nsel = len(rows)
+        self._ir_tensor_check(who, "T_surface", T_surface, (1,))
+        self._ir_tensor_check(who, "T", T, (nz,))
+        for k, t in g.items():
+            self._ir_tensor_check(who, k, t, (nsel,) if k.endswith("_n") else (nsel, nw_ir))
+        dev = T.device if T.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        shapes = dict(tau=(self.nw, self.ngauss, nz), w0=(self.nw, self.ngauss, nz), g=(self.nw, nz))
+        out = {name: torch.empty(shapes[name], dtype=torch.float64, device=dev) for name in names}
+        addr = lambda d, key: d[key].data_ptr() if key in d else None   # noqa: E731
+        self._on_handle_stream(dev, lambda producer: self._L.radtran_ir_spectra_opr_vjp_device(
+            self._ptr, T_surface.data_ptr(), _i(nz), T.data_ptr(), _i(nsel), rows.ctypes.data_as(C.POINTER(C.c_int)),
+            addr(g, "fup"), addr(g, "fdn"), addr(g, "fup_n"), addr(g, "fdn_n"), addr(out, "tau"), addr(out, "w0"), addr(out, "g"),
+            producer, self._err), sync)
+        return out
 
     def ir_spectra_torch(self, T_surface, T, levels=(-1,), parts=("up",), fluxes=False, weights=None):
         """`ir_spectra_batch_tensors` as a differentiable torch op: the same dict of tensors (without the weights), with

@@ -502,6 +502,42 @@ void radtran_ir_spectra_batch_vjp_device(void *ptr, const int *ncol, const doubl
                                          const double *d_g_fup_n, const double *d_g_fdn_n,
                                          double *d_grad_T_surface, double *d_grad_T,
                                          const void *producer_stream, char *err);
+/* The gradient of a loss on one column's IR spectra in the STORED optical properties (a vector-Jacobian product in tau,
+ * w0, g at fixed temperatures).  The column is T_surface, T(nz) on the stored opacities; what is differentiated is
+ * radiate(..., compute_solar=.false., compute_opacity=.false.) read at wrk_ir%fup_a / fdn_a (spec_level(a), l) and at
+ * fup_n / fdn_n (spec_level(a)); levels 1..nz+1 ground-first, repeats allowed.  The cotangents g_ir_fup / g_ir_fdn (nw_ir,
+ * nsel) and g_fup_n / g_fdn_n (nsel) follow radtran_ir_spectra_batch_vjp: a NULL counts as 0, g_*_n enters as g_n(a)
+ * (freq(l) - freq(l+1)); the Planck values are planck_fcn(avg_freq(l), x(j)).  Outputs in radtran_opr_get's layout, so
+ * that they line up with opr() element by element: grad_tau, grad_w0 (nz, ngauss, nw) and grad_g (nz, nw), TOA-first,
+ * opacity-bin index, 0.0 in the bins outside the IR channel; any one or two may be NULL.  grad_tau(n, i, l) is the
+ * derivative of the loss in the stored tau(n, i, l), the g-point's weight included, grad_w0 likewise; grad_g(n, l) sums
+ * the g-points in g order.  tau, w0 and g are independent inputs, as two_stream_ir takes them (the max_w0 cap and the
+ * tau <= tau_min -> w0 = 0 rule belong to the opacity step, not to this derivative); a layer with tau <= ir_tau_min is
+ * differentiated inside its thin branch (exactly at the switch: unspecified); both surface forms and the per-bin
+ * emissivity are covered; zenith weights are not read.  One adjoint and one forward two-stream solve per (bin, g-point)
+ * whatever nsel is (clima_amd/csrc/ir_opr_sens.inc).  Contract: bitwise repeatable, no atomics, fixed summation orders;
+ * all-zero cotangents give exactly 0.0 (a bin without a cotangent is not solved); a loss on fdn at level nz+1 alone gives
+ * exactly 0; the handle's wrk_ir, wrk_sol, f_total, spectra, stored opacities and fields are left untouched; a pending
+ * deferred integration and a two-in-flight join are settled first; every nz >= 1 and every g-point count of the single
+ * call.  Refused (err; nothing is enqueued or written), naming the argument and its value: a handle that is not
+ * constructed; dim_T /= nz; nsel < 1; a NULL spec_level; a level outside 1..nz+1; no cotangent at all; all three outputs
+ * NULL; a NULL T or T_surface; a temperature that is not finite and positive; a bin shard or a communicator ("needs the
+ * whole spectrum"); no opacities ("ir_spectra_opr_vjp needs opacities: ..."); a work buffer (6 x 2 nz + nz doubles per
+ * (bin, g-point)) above the 4 GiB bound of radtran_ir_jacobian_spectral_rows. */
+void radtran_ir_spectra_opr_vjp(void *ptr, const double *T_surface, const int *dim_T, const double *T,
+                                const int *nsel, const int *spec_level,
+                                const double *g_ir_fup, const double *g_ir_fdn,
+                                const double *g_fup_n, const double *g_fdn_n,
+                                double *grad_tau, double *grad_w0, double *grad_g, char *err);
+/* ... with every array but spec_level in device memory of the handle's device (refused by name otherwise), enqueued on
+ * the handle's stream behind `producer_stream` and final at the next radtran_synchronize, as
+ * radtran_ir_spectra_batch_vjp_device; the temperatures are not checked; bit for bit the host form's gradient. */
+void radtran_ir_spectra_opr_vjp_device(void *ptr, const double *d_T_surface, const int *dim_T, const double *d_T,
+                                       const int *nsel, const int *spec_level,
+                                       const double *d_g_ir_fup, const double *d_g_ir_fdn,
+                                       const double *d_g_fup_n, const double *d_g_fdn_n,
+                                       double *d_grad_tau, double *d_grad_w0, double *d_grad_g,
+                                       const void *producer_stream, char *err);
 /* clima/fortran/Radtran.f90:41-75 (same names and argument lists): the YAML text of
  * OpticalProperties_opacities2yaml (src/radtran/clima_radtran_types.f90:328-430).  _1 allocates
  * the string and returns its length, _2 copies it into out_c (out_len + 1 chars) and frees it.
@@ -756,6 +792,15 @@ void clima_test_ir_response(const int *nz, const int *ng, const double *tau, con
 void clima_test_ir_adjoint(const int *nz, const int *ng, const double *tau, const double *w0, const double *g,
                            const double *ir_par, const double *wbin, const int *nrow, const int *level,
                            double *dfup, double *dfdn, char *err);
+/* The same for the optical-property gradient of radtran_ir_spectra_opr_vjp (ir_opr_sens.inc): that column with the Planck
+ * values bplanck (nz+1, TOA-first) and nrow levels (0..nz, TOA-first) -> up_tau(a, n) = d fup(level(a)) / d tau(n), up_w0,
+ * up_g and dn_* likewise, (nrow, nz) row after row, n TOA-first, summed over the g-points with the weights wbin --
+ * produced by ONE launch of the production kernels (k_opr_adjoint, k_opr_sum_g), each (row, direction) a bin of its own
+ * with a unit cotangent.  nz >= 1. */
+void clima_test_ir_opr_sens(const int *nz, const int *ng, const double *tau, const double *w0, const double *g,
+                            const double *bplanck, const double *ir_par, const double *wbin, const int *nrow,
+                            const int *level, double *up_tau, double *up_w0, double *up_g,
+                            double *dn_tau, double *dn_w0, double *dn_g, char *err);
 
 /* The far accumulation of the response form has two kernels: 0 (default) the matrix-core one (v_mfma_f64_16x16x4_f64),
  * 1 the vector one it replaced.  Process-wide; tests hold the two against each other. */
