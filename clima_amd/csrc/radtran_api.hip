@@ -2289,6 +2289,18 @@ static void green_plan(const double *T, const double *Ts, int n, int nz, GreenPl
   for (size_t s2 = 0; s2 < order.size(); s2++) pl.col_dev[fill[dc[order[s2]]]++] = (int)s2;
 }
 
+// What every kernel of the IR derivative family reads of the handle: the dimensions, the stored opacities, the frequency
+// grids, the emissivity, has_hard_surface and ir_tau_min; everything else of the block is zero, for the caller to fill
+static GreenParams green_params(const Radtran *r) {
+  GreenParams g;
+  std::memset(&g, 0, sizeof(g));
+  g.nz = r->nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = r->ir_n * r->ng;
+  g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
+  g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
+  g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
+  return g;
+}
+
 // The part of the response form that sees the opacities alone (k_green_factor, k_green_unit, k_green_local: ~345 of the
 // ~700 us of GPU work of a 402-layer Jacobian batch): its arrays and launches.  radtran_radiate_ir_batch issues it BEFORE
 // the host looks at the columns when the handle's last batch of this size took the response form -- the plan (~100 us of
@@ -2298,14 +2310,9 @@ static void green_plan(const double *T, const double *Ts, int n, int nz, GreenPl
 // ones.  rocprofv3's kernel trace shows them side by side and each that much slower: the far-form kernel holds 2 x 232
 // registers per SIMD, the general kernel one wave of 512, and the batch took 828-840 us either way.)
 static void green_factor_part(Radtran *r, GreenParams &g) {
-  const int nz = r->nz, ng = r->ng, n_ir = r->ir_n;
-  const int NQ = n_ir * ng;
+  g = green_params(r);
+  const int nz = r->nz, NQ = g.NQ;
   r->d_green.reserve(green_work_views(nz, NQ, nullptr).count);
-  std::memset(&g, 0, sizeof(g));
-  g.nz = nz; g.ng = ng; g.n_ir = n_ir; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
-  g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
-  g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
-  g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
   const GreenWork w = green_work_views(nz, NQ, r->d_green.p);
   g.RW = w.RW; g.IS = w.IS; g.FS = w.FS; g.DS = w.DS; g.D0 = w.D0;
   launch_green_factor(g, r->stream);
@@ -2413,32 +2420,39 @@ static void ir_batch_green(Radtran *r, const GreenPlan &pl, const double *T, con
   r->ir_green_batches++;
 }
 
-// `narr` result arrays of `arr` doubles each, back to back in d_bout from its first-th array on, into the caller's
-// outs[0..narr-1] through the handle's pinned block in pieces, the host copying piece i out while piece i + 1 is still on
-// the link (one copy and then one memcpy of the whole took 95 + 140 us of a 0.93 ms batch call at 403 columns x 403
-// levels).  Returns when all are there.  (The batch and the full Jacobian: three arrays from the start;
-// radtran_ir_jacobian_reduced's total alone: one.)
-static void bout_to_host(Radtran *r, double *const *outs, size_t arr, int narr = 3, int first = 0) {
+// `narr` result arrays of `arr` doubles each, back to back in device memory from d_src on, into the caller's
+// outs[0..narr-1] through the handle's pinned block in `npiece` pieces, the host copying piece i out while piece i + 1 is
+// still on the link (one copy and then one memcpy of the whole took 95 + 140 us of a 0.93 ms batch call at 403 columns x
+// 403 levels).  Returns when all are there.
+constexpr int TO_HOST_PIECES = 6;     // (Radtran::bout_ev holds as many events)
+static void to_host_in_pieces(Radtran *r, const double *d_src, double *const *outs, size_t arr, int narr, int npiece) {
   double *const h_bout = r->h_bout.reserve(narr * arr);
-  constexpr int NPIECE = 6;
-  const size_t total = narr * arr, piece = (total + NPIECE - 1) / NPIECE;
-  const double *d_src = r->d_bout.p + (size_t)first * arr;
+  const size_t total = narr * arr, piece = (total + npiece - 1) / npiece;
   for (auto &e : r->bout_ev)
     if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (int k = 0; k < NPIECE; k++) {
+  for (int k = 0; k < npiece; k++) {
     const size_t lo = std::min(total, (size_t)k * piece), hi = std::min(total, lo + piece);
     if (hi > lo) HIPCHK(hipMemcpyAsync(h_bout + lo, d_src + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
     HIPCHK(hipEventRecord(r->bout_ev[k], r->stream));
   }
-  for (int k = 0; k < NPIECE; k++) {
+  for (int k = 0; k < npiece; k++) {
     const size_t lo = std::min(total, (size_t)k * piece), hi = std::min(total, lo + piece);
     HIPCHK(hipEventSynchronize(r->bout_ev[k]));
-    for (size_t x = lo; x < hi;) {      // (a piece may straddle two of the three arrays)
+    for (size_t x = lo; x < hi;) {      // (a piece may straddle two of the arrays)
       const size_t i = x / arr, n_here = std::min(hi, (i + 1) * arr) - x;
       std::memcpy(outs[i] + (x - i * arr), h_bout + x, sizeof(double) * n_here);
       x += n_here;
     }
   }
+}
+// ... from d_bout's first-th array on (the batch and the full Jacobian: three arrays from the start;
+// radtran_ir_jacobian_reduced's total alone: one)
+static void bout_to_host(Radtran *r, double *const *outs, size_t arr, int narr = 3, int first = 0) {
+  to_host_in_pieces(r, r->d_bout.p + (size_t)first * arr, outs, arr, narr, TO_HOST_PIECES);
+}
+// ... one array of `count` doubles, whole below 32768 of them
+static void rows_to_host(Radtran *r, const double *d_src, double *dst, size_t count) {
+  if (count) to_host_in_pieces(r, d_src, &dst, count, 1, count < 32768 ? 1 : TO_HOST_PIECES);
 }
 
 static void register_host(Radtran *r, void *p, size_t bytes);
@@ -2711,6 +2725,60 @@ void radtran_radiate_solar_batch(void *ptr, const int *ncol, const int *nzen_, c
   CATCH(err)
 }
 
+// What the entry points of the IR derivative family (the Jacobians, the spectra batch, its gradients) check alike; `pre`
+// is the message's prefix ("name: "), and each returns whether the call is refused, its text in `err`.
+// The levels `level` (1..nz+1 ground-first, the argument `name`) as levels from the top in `lv`
+static bool ir_levels_refused(const std::string &pre, const char *name, int nz, int n, const int *level, std::vector<int> &lv, char *err) {
+  lv.assign((size_t)n, 0);
+  for (int a = 0; a < n; a++) {
+    const int v = level[a];
+    if (v < 1 || v > nz + 1) {
+      set_err(err, pre + name + "(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nz + 1));
+      return true;
+    }
+    lv[a] = nz - (v - 1);
+  }
+  return false;
+}
+// the functionals of the levels `lv` in the directions asked for: fun[a ndir + place] = 2 (level from the top) + (0 up | 1 down)
+static std::vector<int> ir_functionals(const std::vector<int> &lv, bool up, bool dn) {
+  std::vector<int> fun;
+  for (const int k : lv) {
+    if (up) fun.push_back(2 * k);
+    if (dn) fun.push_back(2 * k + 1);
+  }
+  return fun;
+}
+static bool ir_T_usable(double v) { return std::isfinite(v) && v > 0.0; }
+static bool ir_T_refusal(const std::string &pre, const std::string &name, double v, char *err) {
+  set_err(err, pre + "temperatures must be finite and positive (" + name + " = " + std::to_string(v) + ")");
+  return true;
+}
+// one column: T(1..nz), then T_surface
+static bool ir_column_T_refused(const std::string &pre, int nz, const double *T_surface, const double *T, char *err) {
+  for (int i = 0; i < nz; i++)
+    if (!ir_T_usable(T[i])) return ir_T_refusal(pre, "T(" + std::to_string(i + 1) + ")", T[i], err);
+  return !ir_T_usable(*T_surface) && ir_T_refusal(pre, "T_surface", *T_surface, err);
+}
+// n columns: per column T_surface(c), then T(1..nz, c)
+static bool ir_batch_T_refused(const std::string &pre, int nz, int n, const double *T_surface, const double *T, char *err) {
+  for (int c = 0; c < n; c++) {
+    if (!ir_T_usable(T_surface[c])) return ir_T_refusal(pre, "T_surface(" + std::to_string(c + 1) + ")", T_surface[c], err);
+    for (int i = 0; i < nz; i++) {
+      const double v = T[(size_t)c * nz + i];
+      if (!ir_T_usable(v)) return ir_T_refusal(pre, "T(" + std::to_string(i + 1) + ", " + std::to_string(c + 1) + ")", v, err);
+    }
+  }
+  return false;
+}
+// a bin shard or a communicator, by name: the adjoint passes need the whole spectrum
+static bool ir_rows_shard_refused(Radtran *r, const std::string &pre, char *err) {
+  if (r->shard_world == 1 && !r->comm) return false;
+  const std::string shard = r->shard_world != 1 ? "a bin shard of " + std::to_string(r->shard_world) : "";
+  set_err(err, pre + "needs the whole spectrum (" + shard + (r->comm ? (shard.empty() ? "a communicator" : ", a communicator") : "") + ")");
+  return true;
+}
+
 // What its two entry points (radtran_ir_jacobian, radtran_ir_jacobian_reduced) refuse alike, after their own extents.
 static bool ir_jacobian_refused(const Radtran *r, const double *T_surface, const double *T, char *err) {
   const int nz = r->nz, nl = nz + 1;
@@ -2833,14 +2901,9 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
   int *mem = csr.data() + ng + 1, *rows = mem + nmem;
   for (int j = 0; j < nl; j++)
     if (group_of_x[j] > 0) mem[fill[group_of_x[j] - 1]++] = nz - j;
-  for (int a = 0; a < nr; a++) {
-    const int v = row_level[a];
-    if (v < 1 || v > nl) {
-      set_err(err, pre + "row_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
-      return;
-    }
-    rows[a] = nz - (v - 1);
-  }
+  std::vector<int> lv;
+  if (ir_levels_refused(pre, "row_level", nz, nr, row_level, lv, err)) return;
+  std::copy(lv.begin(), lv.end(), rows);
   if (ir_jacobian_refused(r, T_surface, T, err)) return;
   TRY
   ready_stored_opacities(r);
@@ -2868,6 +2931,61 @@ void radtran_ir_jacobian_reduced(void *ptr, const double *T_surface, const int *
 // row (ir_adjoint.inc), so none of the response form's limits apply; what bounds the call is its work buffer.
 // include/clima_radtran_hip.h has the contract.
 constexpr double IR_ADJOINT_MAX_BYTES = 4294967296.0;
+// the adjoint work buffer of `count` rows or levels (the `noun`; `count_name` the argument that counts them) in ndir
+// directions: refused, with its size, where it passes IR_ADJOINT_MAX_BYTES
+static bool ir_adjoint_work_refused(Radtran *r, const std::string &pre, const char *noun, const char *count_name, int count, int ndir, char *err) {
+  const int NQ = r->ir_n * r->ng, nfun = count * ndir;
+  const size_t n_work = ir_adjoint_work_count(r->nz, NQ, nfun), n_part = ir_adjoint_part_count(r->nz, NQ, nfun);
+  if (sizeof(double) * ((double)n_work + (double)n_part) <= IR_ADJOINT_MAX_BYTES) return false;
+  set_err(err, pre + "the work buffer of " + count_name + " = " + std::to_string(count) + " " + noun + " in " + std::to_string(ndir) +
+                   " direction(s) would take " + std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " +
+                   std::to_string((long long)IR_ADJOINT_MAX_BYTES) + ": ask for fewer " + noun + " per call");
+  return true;
+}
+// A small index list up into d_green_idx.  A call that may only enqueue (`enqueue_only`) sends it from pageable memory: a
+// copy from memory that is not pinned is performed synchronously (hip_runtime_api.h, hipMemcpyAsync), so `v` has been
+// read when the call returns and a call right behind this one cannot change what this one reads -- the handle's shared
+// pinned block could be rewritten before a copy from it executes.  The price: the host waits until the stream has
+// reached the copy.  A synchronous host form returns only when its copies have run, so it may use the pinned block
+// (from its start: nothing else of the call may be staged there), which costs no wait.  The device buffer itself is
+// reused in stream order.
+static const int *ir_upload_indices(Radtran *r, const std::vector<int> &v, bool enqueue_only) {
+  const int *src = v.data();
+  if (!enqueue_only) {
+    int *h = reinterpret_cast<int *>(green_stage(r, sizeof(int) * v.size()));
+    std::copy(v.begin(), v.end(), h);
+    src = h;
+  }
+  r->d_green_idx.reserve(v.size());
+  HIPCHK(hipMemcpyAsync(r->d_green_idx.p, src, sizeof(int) * v.size(), hipMemcpyHostToDevice, r->stream));
+  return r->d_green_idx.p;
+}
+// The adjoint pass on the stored opacities: the rows of the nrow x ndir functionals d_fun (`up`: the up direction is
+// among them) into d_out_up / d_out_dn ((nw_ir, nrow, nz+1) each; null: the direction is not among them), with the Planck
+// derivatives at d_base_T (by level from the top) as amplitudes -- null: unit amplitudes, the rows are the spectra
+// batch's weights themselves.  Enqueued on the handle's stream, behind ready_stored_opacities; `timed`: counted as
+// kernel id 4 (the weights pass of the spectra batches).
+static void ir_adjoint_enqueue(Radtran *r, const int *d_fun, int nrow, int ndir, bool up, const double *d_base_T,
+                               double *d_out_up, double *d_out_dn, bool timed) {
+  const int nfun = nrow * ndir;
+  IrAdjointParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.g = green_params(r);
+  p.g.base_T = d_base_T;
+  const size_t n_work = ir_adjoint_work_count(r->nz, p.g.NQ, nfun), n_part = ir_adjoint_part_count(r->nz, p.g.NQ, nfun);
+  r->d_adjoint.reserve(n_work + n_part);
+  p.nfun = nfun; p.nrow = nrow; p.ndir = ndir; p.dir0 = up ? 0 : 1; p.fun = d_fun;
+  p.work = r->d_adjoint.p; p.part = p.work + n_work;
+  p.out_up = d_out_up; p.out_dn = d_out_dn;
+  if (timed) {
+    KernelTimer t(r, 4);
+    launch_ir_adjoint(p, r->stream);
+    t.stop();
+  } else {
+    launch_ir_adjoint(p, r->stream);
+  }
+  HIPCHK(hipGetLastError());
+}
 void radtran_ir_jacobian_spectral_rows(void *ptr, const double *T_surface, const int *dim_T, const double *T,
                                        const int *nrow, const int *row_level,
                                        const int *dim1, const int *dim2, const int *dim3,
@@ -2885,91 +3003,35 @@ void radtran_ir_jacobian_spectral_rows(void *ptr, const double *T_surface, const
     return;
   }
   if (!jac_up_a && !jac_dn_a) { set_err(err, pre + "neither jac_up_a nor jac_dn_a was given"); return; }
-  const int ndir = (jac_up_a ? 1 : 0) + (jac_dn_a ? 1 : 0), nfun = nr * ndir;
-  std::vector<int> fun((size_t)nfun);
-  for (int a = 0; a < nr; a++) {
-    const int v = row_level[a];
-    if (v < 1 || v > nl) {
-      set_err(err, pre + "row_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
-      return;
-    }
-    int f = a * ndir;
-    if (jac_up_a) fun[f++] = 2 * (nz - (v - 1));
-    if (jac_dn_a) fun[f] = 2 * (nz - (v - 1)) + 1;
-  }
-  for (int j = 0; j <= nz; j++) {
-    const double v = j < nz ? T[j] : *T_surface;
-    if (!(std::isfinite(v) && v > 0.0)) {
-      set_err(err, pre + "temperatures must be finite and positive (" + (j < nz ? "T(" + std::to_string(j + 1) + ")" : std::string("T_surface")) +
-                       " = " + std::to_string(v) + ")");
-      return;
-    }
-  }
-  if (r->shard_world != 1 || r->comm) {
-    const std::string shard = r->shard_world != 1 ? "a bin shard of " + std::to_string(r->shard_world) : "";
-    set_err(err, pre + "needs the whole spectrum (" + shard + (r->comm ? (shard.empty() ? "a communicator" : ", a communicator") : "") + ")");
-    return;
-  }
+  const bool up = jac_up_a != nullptr, dn = jac_dn_a != nullptr;
+  const int ndir = (up ? 1 : 0) + (dn ? 1 : 0);
+  std::vector<int> lv;
+  if (ir_levels_refused(pre, "row_level", nz, nr, row_level, lv, err)) return;
+  if (ir_column_T_refused(pre, nz, T_surface, T, err)) return;
+  if (ir_rows_shard_refused(r, pre, err)) return;
   if (refuse(r, "ir_jacobian_spectral_rows", NEED_OPACITIES, err)) return;
-  const int NQ = r->ir_n * r->ng;
-  const size_t n_work = ir_adjoint_work_count(nz, NQ, nfun), n_part = ir_adjoint_part_count(nz, NQ, nfun);
-  if (sizeof(double) * ((double)n_work + (double)n_part) > IR_ADJOINT_MAX_BYTES) {
-    set_err(err, pre + "the work buffer of nrow = " + std::to_string(nr) + " rows in " + std::to_string(ndir) + " direction(s) would take " +
-                     std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " + std::to_string((long long)IR_ADJOINT_MAX_BYTES) +
-                     ": ask for fewer rows per call");
-    return;
-  }
+  if (ir_adjoint_work_refused(r, pre, "rows", "nrow", nr, ndir, err)) return;
   TRY
   ready_stored_opacities(r);
   const size_t arr = (size_t)nw_ir * nr * nl;
   r->d_bout.reserve(ndir * arr);
   jacobian_of_ir_bins(r, ndir * arr, [&] {
     // through the handle's pinned block: base_T by level k [nl] (radiate.f90:65-69: level k is layer nz-1-k), then the functionals
-    double *hd = reinterpret_cast<double *>(green_stage(r, sizeof(double) * nl + sizeof(int) * nfun));
+    const std::vector<int> fun = ir_functionals(lv, up, dn);
+    double *hd = reinterpret_cast<double *>(green_stage(r, sizeof(double) * nl + sizeof(int) * fun.size()));
     int *hi = reinterpret_cast<int *>(hd + nl);
     for (int k = 0; k < nz; k++) hd[k] = T[nz - 1 - k];
     hd[nz] = *T_surface;
     std::copy(fun.begin(), fun.end(), hi);
-    r->d_green_in.reserve(nl); r->d_green_idx.reserve(nfun); r->d_adjoint.reserve(n_work + n_part);
+    r->d_green_in.reserve(nl); r->d_green_idx.reserve(fun.size());
     HIPCHK(hipMemcpyAsync(r->d_green_in.p, hd, sizeof(double) * nl, hipMemcpyHostToDevice, r->stream));
-    HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * nfun, hipMemcpyHostToDevice, r->stream));
-    IrAdjointParams p;
-    std::memset(&p, 0, sizeof(p));
-    GreenParams &g = p.g;
-    g.nz = nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
-    g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
-    g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
-    g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
-    g.base_T = r->d_green_in.p;
-    p.nfun = nfun; p.nrow = nr; p.ndir = ndir; p.dir0 = jac_up_a ? 0 : 1; p.fun = r->d_green_idx.p;
-    p.work = r->d_adjoint.p; p.part = p.work + n_work;
-    p.out_up = jac_up_a ? r->d_bout.p : nullptr; p.out_dn = jac_dn_a ? r->d_bout.p + (jac_up_a ? arr : 0) : nullptr;
-    launch_ir_adjoint(p, r->stream);
+    HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * fun.size(), hipMemcpyHostToDevice, r->stream));
+    ir_adjoint_enqueue(r, r->d_green_idx.p, nr, ndir, up, r->d_green_in.p, up ? r->d_bout.p : nullptr,
+                       dn ? r->d_bout.p + (up ? arr : 0) : nullptr, false);
   });
-  double *const outs[2] = {jac_up_a ? jac_up_a : jac_dn_a, jac_dn_a};
+  double *const outs[2] = {up ? jac_up_a : jac_dn_a, jac_dn_a};
   bout_to_host(r, outs, arr, ndir);
   CATCH(err)
-}
-
-// `count` doubles from device memory into the caller's array through the handle's pinned block; a large array in pieces,
-// the host copying piece i out while piece i + 1 is still on the link (bout_to_host's way).  Returns when all are there.
-static void rows_to_host(Radtran *r, const double *d_src, double *dst, size_t count) {
-  if (!count) return;
-  double *const h = r->h_bout.reserve(count);
-  const int npiece = count < 32768 ? 1 : 6;
-  const size_t piece = (count + npiece - 1) / npiece;
-  for (auto &e : r->bout_ev)
-    if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (int k = 0; k < npiece; k++) {
-    const size_t lo = std::min(count, (size_t)k * piece), hi = std::min(count, lo + piece);
-    if (hi > lo) HIPCHK(hipMemcpyAsync(h + lo, d_src + lo, sizeof(double) * (hi - lo), hipMemcpyDeviceToHost, r->stream));
-    HIPCHK(hipEventRecord(r->bout_ev[k], r->stream));
-  }
-  for (int k = 0; k < npiece; k++) {
-    const size_t lo = std::min(count, (size_t)k * piece), hi = std::min(count, lo + piece);
-    HIPCHK(hipEventSynchronize(r->bout_ev[k]));
-    if (hi > lo) std::memcpy(dst + lo, h + lo, sizeof(double) * (hi - lo));
-  }
 }
 
 // Per-bin IR spectra (and their sums over the bins) of many temperature profiles on the stored opacities, at requested
@@ -2978,70 +3040,49 @@ static void rows_to_host(Radtran *r, const double *d_src, double *dst, size_t co
 // include/clima_radtran_hip.h has the contract.
 constexpr int IR_ROWS_CHUNK = 512;                     // columns per launch (radtran_radiate_solar_batch's)
 constexpr double IR_ROWS_CHUNK_BYTES = 268435456.0;    // ... fewer where their spectra would take more than this
-// the functionals of the requested levels (fun[a ndir + place] = 2 (level from the top) + (0 up | 1 down)); false, and
-// the level named in `err`, where one lies outside 1..nz+1
-static bool ir_rows_functionals(const std::string &pre, int nz, int nsel, const int *spec_level, bool up, bool dn, std::vector<int> &fun, char *err) {
-  const int nl = nz + 1, ndir = (up ? 1 : 0) + (dn ? 1 : 0);
-  fun.assign((size_t)nsel * ndir, 0);
-  for (int a = 0; a < nsel; a++) {
-    const int v = spec_level[a];
-    if (v < 1 || v > nl) {
-      set_err(err, pre + "spec_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
-      return false;
+// columns per launch where the spectra of `nstaged` directions (`spec` doubles per column each) pass through d_rows_out
+static int ir_rows_chunk(int n, int nstaged, size_t spec) {
+  int CH = std::min(n, IR_ROWS_CHUNK);
+  while (CH > 1 && sizeof(double) * (double)nstaged * spec * CH > IR_ROWS_CHUNK_BYTES) CH = (CH + 1) / 2;
+  return CH;
+}
+// Where the apply pass writes one direction's spectra or sums: into the device array of all columns (`step` doubles per
+// column: a chunk writes its part in place), or into a staging area that every chunk fills from its start (step 0);
+// p null: not formed
+struct IrRowsDst { double *p; size_t step; };
+// The apply pass of the spectra batch: the columns (d_T, d_Ts) [0, n) times the weights w[0..ndir) in chunks of CH columns
+// (kernel id 5 counts them all), direction d's spectra to spec_dst[d] and their sums over the bins to sum_dst[d].  After
+// each chunk `chunk_done` (where given) is told where the chunk's spectra o[d] and sums f[d] lie.
+using IrRowsChunkDone = std::function<void(int c0, int nc, double *const *o, double *const *f)>;
+static void ir_rows_apply(Radtran *r, int n, int CH, int nsel, int ndir, const double *d_T, const double *d_Ts, const double *const w[2],
+                          const IrRowsDst spec_dst[2], const IrRowsDst sum_dst[2], const IrRowsChunkDone &chunk_done) {
+  const size_t sums = (size_t)nsel;
+  for (int c0 = 0; c0 < n; c0 += CH) {
+    const int nc = std::min(CH, n - c0);
+    double *o[2], *f[2];
+    for (int d = 0; d < 2; d++) {
+      o[d] = spec_dst[d].p ? spec_dst[d].p + spec_dst[d].step * c0 : nullptr;
+      f[d] = sum_dst[d].p ? sum_dst[d].p + sum_dst[d].step * c0 : nullptr;
     }
-    int f = a * ndir;
-    if (up) fun[f++] = 2 * (nz - (v - 1));
-    if (dn) fun[f] = 2 * (nz - (v - 1)) + 1;
+    if (r->ir_n > 0) {
+      IrRowsApplyParams q;
+      std::memset(&q, 0, sizeof(q));
+      q.n_ir = r->ir_n; q.nsel = nsel; q.nz = r->nz; q.ncol = nc; q.ndir = ndir;
+      q.l0 = r->ir.ind_start + r->ir_lo; q.ir_lo = r->ir_lo;
+      q.freq = r->d_freq.p; q.ir_freq = r->ir.d_freq.p;
+      q.T = d_T + (size_t)c0 * r->nz; q.Ts = d_Ts + c0;
+      q.w0 = w[0]; q.w1 = w[1];
+      q.out0 = o[0]; q.out1 = o[1]; q.fn0 = f[0]; q.fn1 = f[1];
+      KernelTimer t(r, 5);
+      launch_ir_rows_apply(q, r->stream);
+      HIPCHK(hipGetLastError());
+      t.stop();
+    } else {
+      for (int d = 0; d < 2; d++)
+        if (f[d]) HIPCHK(hipMemsetAsync(f[d], 0, sizeof(double) * sums * nc, r->stream));   // (no IR bins: empty spectra, sums of nothing)
+    }
+    if (chunk_done) chunk_done(c0, nc, o, f);
   }
-  return true;
-}
-// the adjoint work buffer of nsel levels in ndir directions: false, and its size in `err`, where it passes IR_ADJOINT_MAX_BYTES
-static bool ir_rows_work_fits(Radtran *r, const std::string &pre, int nsel, int ndir, char *err) {
-  const int NQ = r->ir_n * r->ng, nfun = nsel * ndir;
-  const size_t n_work = ir_adjoint_work_count(r->nz, NQ, nfun), n_part = ir_adjoint_part_count(r->nz, NQ, nfun);
-  if (sizeof(double) * ((double)n_work + (double)n_part) <= IR_ADJOINT_MAX_BYTES) return true;
-  set_err(err, pre + "the work buffer of nsel = " + std::to_string(nsel) + " levels in " + std::to_string(ndir) + " direction(s) would take " +
-                   std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " + std::to_string((long long)IR_ADJOINT_MAX_BYTES) +
-                   ": ask for fewer levels per call");
-  return false;
-}
-// The weights of the stored opacities: one adjoint pass with unit amplitudes into d_w_up / d_w_dn ((nw_ir, nsel, nz+1) each;
-// null: the direction is not among `fun`).  Enqueued on the handle's stream, behind ready_stored_opacities; kernel id 4.
-static void ir_rows_weights(Radtran *r, const std::vector<int> &fun, int nsel, int ndir, bool up, double *d_w_up, double *d_w_dn) {
-  if (r->ir_n < 1) return;
-  const int nz = r->nz, NQ = r->ir_n * r->ng, nfun = nsel * ndir;
-  const size_t n_work = ir_adjoint_work_count(nz, NQ, nfun), n_part = ir_adjoint_part_count(nz, NQ, nfun);
-  int *hi = reinterpret_cast<int *>(green_stage(r, sizeof(int) * nfun));
-  std::copy(fun.begin(), fun.end(), hi);
-  r->d_green_idx.reserve(nfun); r->d_adjoint.reserve(n_work + n_part);
-  HIPCHK(hipMemcpyAsync(r->d_green_idx.p, hi, sizeof(int) * nfun, hipMemcpyHostToDevice, r->stream));
-  IrAdjointParams p;
-  std::memset(&p, 0, sizeof(p));
-  GreenParams &g = p.g;
-  g.nz = nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
-  g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
-  g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
-  g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
-  g.base_T = nullptr;      // unit amplitudes: the rows are the weights themselves
-  p.nfun = nfun; p.nrow = nsel; p.ndir = ndir; p.dir0 = up ? 0 : 1; p.fun = r->d_green_idx.p;
-  p.work = r->d_adjoint.p; p.part = p.work + n_work;
-  p.out_up = d_w_up; p.out_dn = d_w_dn;
-  KernelTimer t(r, 4);
-  launch_ir_adjoint(p, r->stream);
-  HIPCHK(hipGetLastError());
-  t.stop();
-}
-// nc columns (d_T, d_Ts) times the weights w0 / w1 of the ndir directions; the caller adds out0 / out1 and fn0 / fn1
-static IrRowsApplyParams ir_rows_apply_params(Radtran *r, int nsel, int ndir, int nc, const double *d_T, const double *d_Ts,
-                                              const double *w0, const double *w1) {
-  IrRowsApplyParams q;
-  std::memset(&q, 0, sizeof(q));
-  q.n_ir = r->ir_n; q.nsel = nsel; q.nz = r->nz; q.ncol = nc; q.ndir = ndir;
-  q.l0 = r->ir.ind_start + r->ir_lo; q.ir_lo = r->ir_lo;
-  q.freq = r->d_freq.p; q.ir_freq = r->ir.d_freq.p;
-  q.T = d_T; q.Ts = d_Ts;
-  q.w0 = w0; q.w1 = w1;
-  return q;
 }
 void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surface, const int *dim1_T, const int *dim2_T,
                               const double *T, const int *nsel_, const int *spec_level, double *ir_fup, double *ir_fdn,
@@ -3057,8 +3098,8 @@ void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surfac
   const bool up = ir_fup || fup_n || w_up, dn = ir_fdn || fdn_n || w_dn;
   if (!up && !dn) { set_err(err, pre + "none of ir_fup, ir_fdn, fup_n, fdn_n, w_up, w_dn was given"); return; }
   const int ndir = (up ? 1 : 0) + (dn ? 1 : 0);
-  std::vector<int> fun;
-  if (!ir_rows_functionals(pre, nz, nsel, spec_level, up, dn, fun, err)) return;
+  std::vector<int> lv;
+  if (ir_levels_refused(pre, "spec_level", nz, nsel, spec_level, lv, err)) return;
   if (n == 0 && (ir_fup || ir_fdn || fup_n || fdn_n)) {
     set_err(err, pre + "ncol = 0 gives the weights alone, but " + (ir_fup ? "ir_fup" : ir_fdn ? "ir_fdn" : fup_n ? "fup_n" : "fdn_n") + " was asked for");
     return;
@@ -3066,79 +3107,48 @@ void radtran_ir_spectra_batch(void *ptr, const int *ncol, const double *T_surfac
   if (n > 0) {
     if (!T) { set_err(err, pre + "\"T\" is a required argument (ncol = " + std::to_string(n) + ")"); return; }
     if (!T_surface) { set_err(err, pre + "\"T_surface\" is a required argument (ncol = " + std::to_string(n) + ")"); return; }
-    for (int c = 0; c < n; c++) {
-      if (!(std::isfinite(T_surface[c]) && T_surface[c] > 0.0)) {
-        set_err(err, pre + "temperatures must be finite and positive (T_surface(" + std::to_string(c + 1) + ") = " + std::to_string(T_surface[c]) + ")");
-        return;
-      }
-      for (int i = 0; i < nz; i++) {
-        const double v = T[(size_t)c * nz + i];
-        if (!(std::isfinite(v) && v > 0.0)) {
-          set_err(err, pre + "temperatures must be finite and positive (T(" + std::to_string(i + 1) + ", " + std::to_string(c + 1) + ") = " + std::to_string(v) + ")");
-          return;
-        }
-      }
-    }
+    if (ir_batch_T_refused(pre, nz, n, T_surface, T, err)) return;
   }
-  if (r->shard_world != 1 || r->comm) {
-    const std::string shard = r->shard_world != 1 ? "a bin shard of " + std::to_string(r->shard_world) : "";
-    set_err(err, pre + "needs the whole spectrum (" + shard + (r->comm ? (shard.empty() ? "a communicator" : ", a communicator") : "") + ")");
-    return;
-  }
+  if (ir_rows_shard_refused(r, pre, err)) return;
   if (refuse(r, "ir_spectra_batch", NEED_OPACITIES, err)) return;
-  if (!ir_rows_work_fits(r, pre, nsel, ndir, err)) return;
+  if (ir_adjoint_work_refused(r, pre, "levels", "nsel", nsel, ndir, err)) return;
   TRY
   ready_stored_opacities(r);
   // the weights: (nw_ir, nsel, nz+1) per direction asked for, up before down
   const size_t arr_w = (size_t)nw_ir * nsel * nl;
   r->d_rows_w.reserve(std::max<size_t>(1, ndir * arr_w));
   double *const d_w_up = up ? r->d_rows_w.p : nullptr, *const d_w_dn = dn ? r->d_rows_w.p + (up ? arr_w : 0) : nullptr;
-  ir_rows_weights(r, fun, nsel, ndir, up, d_w_up, d_w_dn);
+  if (r->ir_n > 0) ir_adjoint_enqueue(r, ir_upload_indices(r, ir_functionals(lv, up, dn), false), nsel, ndir, up, nullptr, d_w_up, d_w_dn, true);
   if (w_up) rows_to_host(r, d_w_up, w_up, arr_w);
   if (w_dn) rows_to_host(r, d_w_dn, w_dn, arr_w);
   if (n > 0) {
     r->d_bT.reserve((size_t)n * nz); r->d_bTs.reserve(n);
     HIPCHK(hipMemcpyAsync(r->d_bT.p, T, sizeof(double) * (size_t)n * nz, hipMemcpyHostToDevice, r->stream));
     HIPCHK(hipMemcpyAsync(r->d_bTs.p, T_surface, sizeof(double) * n, hipMemcpyHostToDevice, r->stream));
-    // columns per launch: bounds the spectra held in device memory
-    int CH = std::min(n, IR_ROWS_CHUNK);
-    while (CH > 1 && sizeof(double) * (double)ndir * nw_ir * nsel * CH > IR_ROWS_CHUNK_BYTES) CH = (CH + 1) / 2;
     const size_t spec = (size_t)nw_ir * nsel, sums = (size_t)nsel;      // per column and direction
+    const int CH = ir_rows_chunk(n, ndir, spec);
     r->d_rows_out.reserve(std::max<size_t>(1, (size_t)ndir * (spec + sums) * CH));
     double *const outs[2] = {up ? ir_fup : ir_fdn, dn && up ? ir_fdn : nullptr};
     double *const fns[2] = {up ? fup_n : fdn_n, dn && up ? fdn_n : nullptr};
-    for (int c0 = 0; c0 < n; c0 += CH) {
-      const int nc = std::min(CH, n - c0);
-      double *const d_spec = r->d_rows_out.p, *const d_sum = d_spec + (size_t)ndir * spec * nc;
-      if (r->ir_n > 0) {
-        IrRowsApplyParams q = ir_rows_apply_params(r, nsel, ndir, nc, r->d_bT.p + (size_t)c0 * nz, r->d_bTs.p + c0, r->d_rows_w.p,
-                                                   ndir == 2 ? r->d_rows_w.p + arr_w : nullptr);
-        q.out0 = d_spec; q.out1 = ndir == 2 ? d_spec + spec * nc : nullptr;
-        q.fn0 = fns[0] ? d_sum : nullptr; q.fn1 = fns[1] ? d_sum + sums * nc : nullptr;
-        KernelTimer t(r, 5);
-        launch_ir_rows_apply(q, r->stream);
-        HIPCHK(hipGetLastError());
-        t.stop();
-      } else {
-        HIPCHK(hipMemsetAsync(d_sum, 0, sizeof(double) * ndir * sums * nc, r->stream));   // (no IR bins: empty spectra, sums of nothing)
-      }
-      for (int d = 0; d < ndir; d++) {
-        if (outs[d]) rows_to_host(r, d_spec + (size_t)d * spec * nc, outs[d] + spec * c0, spec * nc);
-        if (fns[d]) rows_to_host(r, d_sum + (size_t)d * sums * nc, fns[d] + sums * c0, sums * nc);
-      }
+    // every chunk is staged in d_rows_out, the directions' spectra before their sums, and copied back from there
+    const double *const w[2] = {r->d_rows_w.p, ndir == 2 ? r->d_rows_w.p + arr_w : nullptr};
+    double *const stage = r->d_rows_out.p, *const stage_n = stage + (size_t)ndir * spec * CH;
+    IrRowsDst spec_dst[2], sum_dst[2];
+    for (int d = 0; d < 2; d++) {
+      spec_dst[d] = {d < ndir ? stage + (size_t)d * spec * CH : nullptr, 0};
+      sum_dst[d] = {fns[d] ? stage_n + (size_t)d * sums * CH : nullptr, 0};
     }
+    ir_rows_apply(r, n, CH, nsel, ndir, r->d_bT.p, r->d_bTs.p, w, spec_dst, sum_dst, [&](int c0, int nc, double *const *o, double *const *f) {
+      for (int d = 0; d < ndir; d++) {
+        if (outs[d]) rows_to_host(r, o[d], outs[d] + spec * c0, spec * nc);
+        if (fns[d]) rows_to_host(r, f[d], fns[d] + sums * c0, sums * nc);
+      }
+    });
   }
   HIPCHK(hipStreamSynchronize(r->stream));
   CATCH(err)
 }
 
-// what the spectra batches and their gradient refuse of a handle: a bin shard or a communicator, by name
-static bool ir_rows_shard_refused(Radtran *r, const std::string &pre, char *err) {
-  if (r->shard_world == 1 && !r->comm) return false;
-  const std::string shard = r->shard_world != 1 ? "a bin shard of " + std::to_string(r->shard_world) : "";
-  set_err(err, pre + "needs the whole spectrum (" + shard + (r->comm ? (shard.empty() ? "a communicator" : ", a communicator") : "") + ")");
-  return true;
-}
 // the first of `args` that is given and is not device memory of the handle's device, named in `err` (toa_fluxes_batch_dev's check)
 struct NamedPtr { const char *name; const void *p; };
 static bool ir_rows_not_device(Radtran *r, const std::string &pre, std::initializer_list<NamedPtr> args, char *err) {
@@ -3185,8 +3195,8 @@ void radtran_ir_spectra_batch_device(void *ptr, const int *ncol, const double *d
     return;
   }
   const int ndir = (up ? 1 : 0) + (dn ? 1 : 0);
-  std::vector<int> fun;
-  if (!ir_rows_functionals(pre, nz, nsel, spec_level, up, dn, fun, err)) return;
+  std::vector<int> lv;
+  if (ir_levels_refused(pre, "spec_level", nz, nsel, spec_level, lv, err)) return;
   if (n == 0 && (flux_up || flux_dn)) {
     set_err(err, pre + "ncol = 0 gives the weights alone, but " + (d_ir_fup ? "ir_fup" : d_ir_fdn ? "ir_fdn" : d_fup_n ? "fup_n" : "fdn_n") + " was asked for");
     return;
@@ -3200,7 +3210,7 @@ void radtran_ir_spectra_batch_device(void *ptr, const int *ncol, const double *d
   if (ir_rows_shard_refused(r, pre, err)) return;
   if (!given) {
     if (refuse(r, "ir_spectra_batch_device", NEED_OPACITIES, err)) return;
-    if (!ir_rows_work_fits(r, pre, nsel, ndir, err)) return;
+    if (ir_adjoint_work_refused(r, pre, "levels", "nsel", nsel, ndir, err)) return;
   }
   TRY
   if (given) settle_device_batch(r); else ready_stored_opacities(r);
@@ -3214,44 +3224,26 @@ void radtran_ir_spectra_batch_device(void *ptr, const int *ncol, const double *d
     double *own = nullptr;
     if ((up && !d_w_up) || (dn && !d_w_dn)) { r->d_rows_w.reserve(std::max<size_t>(1, ndir * arr_w)); own = r->d_rows_w.p; }
     double *const wu = up ? (d_w_up ? d_w_up : own) : nullptr, *const wd = dn ? (d_w_dn ? d_w_dn : own + (up ? arr_w : 0)) : nullptr;
-    ir_rows_weights(r, fun, nsel, ndir, up, wu, wd);
+    if (r->ir_n > 0) ir_adjoint_enqueue(r, ir_upload_indices(r, ir_functionals(lv, up, dn), true), nsel, ndir, up, nullptr, wu, wd, true);
     w[0] = up ? wu : wd; w[1] = up && dn ? wd : nullptr;
   }
   if (n > 0) {
     const size_t spec = (size_t)nw_ir * nsel, sums = (size_t)nsel;      // per column and direction
     double *const outs[2] = {up ? d_ir_fup : d_ir_fdn, dn && up ? d_ir_fdn : nullptr};
     double *const fns[2] = {up ? d_fup_n : d_fdn_n, dn && up ? d_fdn_n : nullptr};
-    // a sum asked for without its spectrum: the spectra of such a direction pass through d_rows_out, in the host form's chunks
-    bool staged[2];
+    // straight into the caller's arrays; a sum asked for without its spectrum: the spectra of such a direction pass
+    // through d_rows_out, in the host form's chunks
     int nstaged = 0;
-    for (int d = 0; d < ndir; d++) { staged[d] = !outs[d]; nstaged += staged[d] ? 1 : 0; }
-    int CH = std::min(n, IR_ROWS_DEVICE_CHUNK);
-    if (nstaged) {
-      CH = std::min(n, IR_ROWS_CHUNK);
-      while (CH > 1 && sizeof(double) * (double)nstaged * nw_ir * nsel * CH > IR_ROWS_CHUNK_BYTES) CH = (CH + 1) / 2;
-      r->d_rows_out.reserve(std::max<size_t>(1, (size_t)nstaged * spec * CH));
+    for (int d = 0; d < ndir; d++) nstaged += outs[d] ? 0 : 1;
+    const int CH = nstaged ? ir_rows_chunk(n, nstaged, spec) : std::min(n, IR_ROWS_DEVICE_CHUNK);
+    if (nstaged) r->d_rows_out.reserve(std::max<size_t>(1, (size_t)nstaged * spec * CH));
+    double *stage = r->d_rows_out.p;
+    IrRowsDst spec_dst[2] = {{nullptr, 0}, {nullptr, 0}}, sum_dst[2] = {{fns[0], sums}, {fns[1], sums}};
+    for (int d = 0; d < ndir; d++) {
+      if (outs[d]) spec_dst[d] = {outs[d], spec};
+      else { spec_dst[d] = {stage, 0}; stage += spec * CH; }
     }
-    for (int c0 = 0; c0 < n; c0 += CH) {
-      const int nc = std::min(CH, n - c0);
-      if (r->ir_n > 0) {
-        IrRowsApplyParams q = ir_rows_apply_params(r, nsel, ndir, nc, d_T + (size_t)c0 * nz, d_T_surface + c0, w[0], w[1]);
-        double *stage = r->d_rows_out.p;
-        double *o[2] = {nullptr, nullptr};
-        for (int d = 0; d < ndir; d++) {
-          if (staged[d]) { o[d] = stage; stage += spec * nc; }
-          else o[d] = outs[d] + spec * c0;
-        }
-        q.out0 = o[0]; q.out1 = o[1];
-        q.fn0 = fns[0] ? fns[0] + sums * c0 : nullptr; q.fn1 = fns[1] ? fns[1] + sums * c0 : nullptr;
-        KernelTimer t(r, 5);
-        launch_ir_rows_apply(q, r->stream);
-        HIPCHK(hipGetLastError());
-        t.stop();
-      } else {
-        for (int d = 0; d < ndir; d++)
-          if (fns[d]) HIPCHK(hipMemsetAsync(fns[d] + sums * c0, 0, sizeof(double) * sums * nc, r->stream));   // (no IR bins: sums of nothing)
-      }
-    }
+    ir_rows_apply(r, n, CH, nsel, ndir, d_T, d_T_surface, w, spec_dst, sum_dst, nullptr);
   }
   CATCH(err)
 }
@@ -3292,7 +3284,7 @@ static void ir_rows_vjp_enqueue(Radtran *r, int n, int nsel, const double *d_Ts,
 }
 // what both gradient forms refuse, with the batch's wording; false: the call can run
 static bool ir_rows_vjp_refused(Radtran *r, const std::string &pre, int n, int dim1_T, int dim2_T, int nsel, const void *T_surface,
-                                const void *T, const void *const w[2], const void *const gs[2], const void *const gn[2],
+                                const void *T, const double *const w[2], const double *const gs[2], const double *const gn[2],
                                 const void *grad_T_surface, const void *grad_T, char *err) {
   if (n < 1) { set_err(err, pre + "ncol must be at least 1 (ncol = " + std::to_string(n) + ")"); return true; }
   if (dim1_T != r->nz || dim2_T != n) { set_err(err, "\"T\" has the wrong input dimension."); return true; }
@@ -3321,8 +3313,7 @@ void radtran_ir_spectra_batch_vjp_device(void *ptr, const int *ncol, const doubl
   GUARD_BUILT(r, ptr, err);
   const std::string pre = "ir_spectra_batch_vjp_device: ";
   const double *const w[2] = {d_w_up, d_w_dn}, *const gs[2] = {d_g_ir_fup, d_g_ir_fdn}, *const gn[2] = {d_g_fup_n, d_g_fdn_n};
-  const void *const wv[2] = {d_w_up, d_w_dn}, *const gsv[2] = {d_g_ir_fup, d_g_ir_fdn}, *const gnv[2] = {d_g_fup_n, d_g_fdn_n};
-  if (ir_rows_vjp_refused(r, pre, *ncol, *dim1_T, *dim2_T, *nsel_, d_T_surface, d_T, wv, gsv, gnv, d_grad_T_surface, d_grad_T, err)) return;
+  if (ir_rows_vjp_refused(r, pre, *ncol, *dim1_T, *dim2_T, *nsel_, d_T_surface, d_T, w, gs, gn, d_grad_T_surface, d_grad_T, err)) return;
   if (ir_rows_not_device(r, pre, {{"T_surface", d_T_surface}, {"T", d_T}, {"w_up", d_w_up}, {"w_dn", d_w_dn}, {"g_ir_fup", d_g_ir_fup},
                                   {"g_ir_fdn", d_g_ir_fdn}, {"g_fup_n", d_g_fup_n}, {"g_fdn_n", d_g_fdn_n},
                                   {"grad_T_surface", d_grad_T_surface}, {"grad_T", d_grad_T}}, err)) return;
@@ -3333,6 +3324,23 @@ void radtran_ir_spectra_batch_vjp_device(void *ptr, const int *ncol, const doubl
   CATCH(err)
 }
 
+// The host cotangents gs / gn ([up, down], `spec` / `sums` doubles per column, null where absent) of the nc columns from c0
+// on, up into d_rows_out back to back (the caller has reserved it); dgs / dgn: where each lies on the device
+static void ir_stage_cotangents(Radtran *r, size_t spec, size_t sums, int c0, int nc, const double *const gs[2], const double *const gn[2],
+                                const double *dgs[2], const double *dgn[2]) {
+  double *at = r->d_rows_out.p;
+  for (int d = 0; d < 2; d++) {
+    dgs[d] = dgn[d] = nullptr;
+    if (gs[d]) {
+      if (spec) HIPCHK(hipMemcpyAsync(at, gs[d] + spec * c0, sizeof(double) * spec * nc, hipMemcpyHostToDevice, r->stream));
+      dgs[d] = at; at += spec * nc;
+    }
+    if (gn[d]) {
+      HIPCHK(hipMemcpyAsync(at, gn[d] + sums * c0, sizeof(double) * sums * nc, hipMemcpyHostToDevice, r->stream));
+      dgn[d] = at; at += sums * nc;
+    }
+  }
+}
 // ... with host arrays, synchronous: T and the weights go up whole, the cotangents and the gradient in chunks of columns
 // bounded like the batch's, the gradient back through the pinned block
 void radtran_ir_spectra_batch_vjp(void *ptr, const int *ncol, const double *T_surface, const int *dim1_T, const int *dim2_T,
@@ -3344,21 +3352,8 @@ void radtran_ir_spectra_batch_vjp(void *ptr, const int *ncol, const double *T_su
   const std::string pre = "ir_spectra_batch_vjp: ";
   const int nz = r->nz, nl = nz + 1, nw_ir = r->ir.nw, n = *ncol, nsel = *nsel_;
   const double *const w[2] = {w_up, w_dn}, *const gs[2] = {g_ir_fup, g_ir_fdn}, *const gn[2] = {g_fup_n, g_fdn_n};
-  const void *const wv[2] = {w_up, w_dn}, *const gsv[2] = {g_ir_fup, g_ir_fdn}, *const gnv[2] = {g_fup_n, g_fdn_n};
-  if (ir_rows_vjp_refused(r, pre, n, *dim1_T, *dim2_T, nsel, T_surface, T, wv, gsv, gnv, grad_T_surface, grad_T, err)) return;
-  for (int c = 0; c < n; c++) {
-    if (!(std::isfinite(T_surface[c]) && T_surface[c] > 0.0)) {
-      set_err(err, pre + "temperatures must be finite and positive (T_surface(" + std::to_string(c + 1) + ") = " + std::to_string(T_surface[c]) + ")");
-      return;
-    }
-    for (int i = 0; i < nz; i++) {
-      const double v = T[(size_t)c * nz + i];
-      if (!(std::isfinite(v) && v > 0.0)) {
-        set_err(err, pre + "temperatures must be finite and positive (T(" + std::to_string(i + 1) + ", " + std::to_string(c + 1) + ") = " + std::to_string(v) + ")");
-        return;
-      }
-    }
-  }
+  if (ir_rows_vjp_refused(r, pre, n, *dim1_T, *dim2_T, nsel, T_surface, T, w, gs, gn, grad_T_surface, grad_T, err)) return;
+  if (ir_batch_T_refused(pre, nz, n, T_surface, T, err)) return;
   TRY
   settle_device_batch(r);
   bool use[2];
@@ -3378,24 +3373,13 @@ void radtran_ir_spectra_batch_vjp(void *ptr, const int *ncol, const double *T_su
       dw[d] = at; at += arr_w;
     }
   }
-  int CH = std::min(n, IR_ROWS_CHUNK);
-  while (CH > 1 && sizeof(double) * (double)ndir * nw_ir * nsel * CH > IR_ROWS_CHUNK_BYTES) CH = (CH + 1) / 2;
+  const int CH = ir_rows_chunk(n, ndir, spec);
   r->d_rows_out.reserve(std::max<size_t>(1, (size_t)ndir * (spec + sums) * CH));
   r->d_bout.reserve((size_t)nl * CH);
   for (int c0 = 0; c0 < n; c0 += CH) {
     const int nc = std::min(CH, n - c0);
-    const double *dgs[2] = {nullptr, nullptr}, *dgn[2] = {nullptr, nullptr};
-    double *at = r->d_rows_out.p;
-    for (int d = 0; d < 2; d++) {
-      if (gs[d]) {
-        if (spec) HIPCHK(hipMemcpyAsync(at, gs[d] + spec * c0, sizeof(double) * spec * nc, hipMemcpyHostToDevice, r->stream));
-        dgs[d] = at; at += spec * nc;
-      }
-      if (gn[d]) {
-        HIPCHK(hipMemcpyAsync(at, gn[d] + sums * c0, sizeof(double) * sums * nc, hipMemcpyHostToDevice, r->stream));
-        dgn[d] = at; at += sums * nc;
-      }
-    }
+    const double *dgs[2], *dgn[2];
+    ir_stage_cotangents(r, spec, sums, c0, nc, gs, gn, dgs, dgn);
     double *const d_gT = r->d_bout.p, *const d_gTs = d_gT + (size_t)nz * nc;
     ir_rows_vjp_enqueue(r, nc, nsel, r->d_bTs.p + c0, r->d_bT.p + (size_t)c0 * nz, dw, dgs, dgn, d_gTs, d_gT);
     rows_to_host(r, d_gT, grad_T + (size_t)c0 * nz, (size_t)nz * nc);
@@ -3409,21 +3393,13 @@ void radtran_ir_spectra_batch_vjp(void *ptr, const int *ncol, const double *T_su
 // forward two-stream solve per (bin, g-point) on the stored opacities (ir_opr_sens.inc).  include/clima_radtran_hip.h has
 // the contract.  What both forms refuse, in the header's order; `lv`: the levels TOA-first.  false: the call can run
 static bool ir_opr_refused(Radtran *r, const char *who, int dim_T, int nsel, const int *spec_level, const void *T_surface, const void *T,
-                           const void *const gs[2], const void *const gn[2], const void *const out[3], std::vector<int> &lv, char *err) {
+                           const double *const gs[2], const double *const gn[2], double *const out[3], std::vector<int> &lv, char *err) {
   const std::string pre = std::string(who) + ": ";
-  const int nz = r->nz, nl = nz + 1;
+  const int nz = r->nz;
   if (dim_T != nz) { set_err(err, pre + "\"T\" has the dimension " + std::to_string(dim_T) + ", not nz = " + std::to_string(nz)); return true; }
   if (nsel < 1) { set_err(err, pre + "nsel must be at least 1 (nsel = " + std::to_string(nsel) + ")"); return true; }
   if (!spec_level) { set_err(err, pre + "\"spec_level\" is a required argument"); return true; }
-  lv.assign((size_t)nsel, 0);
-  for (int a = 0; a < nsel; a++) {
-    const int v = spec_level[a];
-    if (v < 1 || v > nl) {
-      set_err(err, pre + "spec_level(" + std::to_string(a + 1) + ") = " + std::to_string(v) + " is outside 1.." + std::to_string(nl));
-      return true;
-    }
-    lv[a] = nz - (v - 1);
-  }
+  if (ir_levels_refused(pre, "spec_level", nz, nsel, spec_level, lv, err)) return true;
   if (!gs[0] && !gs[1] && !gn[0] && !gn[1]) { set_err(err, pre + "none of g_ir_fup, g_ir_fdn, g_fup_n, g_fdn_n was given"); return true; }
   if (!out[0] && !out[1] && !out[2]) { set_err(err, pre + "none of grad_tau, grad_w0, grad_g was given"); return true; }
   if (!T) { set_err(err, pre + "\"T\" is a required argument"); return true; }
@@ -3454,20 +3430,12 @@ static void ir_opr_enqueue(Radtran *r, const std::vector<int> &lv, const double 
     if (out[k]) HIPCHK(hipMemsetAsync(out[k], 0, sizeof(double) * counts[k], r->stream));
   if (r->ir_n < 1) return;
   const size_t n_work = ir_opr_work_count(nz, NQ), n_part = ir_opr_part_count(nz, NQ);
-  // the level list goes up from pageable memory: the runtime has taken its copy of `lv` when the call returns, so an
-  // enqueue-only call right behind this one cannot change what this one reads (a shared pinned block could: its copy
-  // executes later); the device buffers themselves are reused in stream order
-  r->d_green_idx.reserve(nsel); r->d_adjoint.reserve(n_work + n_part);
-  HIPCHK(hipMemcpyAsync(r->d_green_idx.p, lv.data(), sizeof(int) * nsel, hipMemcpyHostToDevice, r->stream));
+  r->d_adjoint.reserve(n_work + n_part);
   IrOprParams p;
   std::memset(&p, 0, sizeof(p));
-  GreenParams &g = p.g;
-  g.nz = nz; g.ng = r->ng; g.n_ir = r->ir_n; g.ir_lo = r->ir_lo; g.ir_start = r->ir.ind_start; g.NQ = NQ;
-  g.tau = r->d_tau.p; g.w0 = r->d_w0.p; g.g = r->d_g.p; g.wbin = r->d_wbin.p;
-  g.freq = r->d_freq.p; g.ir_freq = r->ir.d_freq.p; g.emissivity = r->d_emis.p;
-  g.has_hard_surface = r->has_hard_surface ? 1 : 0; g.ir_tau_min = r->ir_tau_min;
+  p.g = green_params(r);
   p.T = d_T; p.Ts = d_Ts; p.bplanck = nullptr;
-  p.nsel = nsel; p.gs_ld = r->ir.nw; p.level = r->d_green_idx.p;
+  p.nsel = nsel; p.gs_ld = r->ir.nw; p.level = ir_upload_indices(r, lv, true);   // (the device form only enqueues; the host form goes the same way)
   p.gs_up = gs[0]; p.gs_dn = gs[1]; p.gn_up = gn[0]; p.gn_dn = gn[1];
   p.work = r->d_adjoint.p; p.part_g = p.work + n_work;
   p.grad_tau = out[0]; p.grad_w0 = out[1]; p.grad_g = out[2];
@@ -3483,10 +3451,9 @@ void radtran_ir_spectra_opr_vjp_device(void *ptr, const double *d_T_surface, con
   GUARD_BUILT(r, ptr, err);
   const char *who = "ir_spectra_opr_vjp_device";
   const double *const gs[2] = {d_g_ir_fup, d_g_ir_fdn}, *const gn[2] = {d_g_fup_n, d_g_fdn_n};
-  const void *const gsv[2] = {d_g_ir_fup, d_g_ir_fdn}, *const gnv[2] = {d_g_fup_n, d_g_fdn_n}, *const outv[3] = {d_grad_tau, d_grad_w0, d_grad_g};
   double *const out[3] = {d_grad_tau, d_grad_w0, d_grad_g};
   std::vector<int> lv;
-  if (ir_opr_refused(r, who, *dim_T, *nsel_, spec_level, d_T_surface, d_T, gsv, gnv, outv, lv, err)) return;
+  if (ir_opr_refused(r, who, *dim_T, *nsel_, spec_level, d_T_surface, d_T, gs, gn, out, lv, err)) return;
   if (ir_rows_not_device(r, std::string(who) + ": ", {{"T_surface", d_T_surface}, {"T", d_T}, {"g_ir_fup", d_g_ir_fup}, {"g_ir_fdn", d_g_ir_fdn},
                                                       {"g_fup_n", d_g_fup_n}, {"g_fdn_n", d_g_fdn_n}, {"grad_tau", d_grad_tau},
                                                       {"grad_w0", d_grad_w0}, {"grad_g", d_grad_g}}, err)) return;
@@ -3507,19 +3474,11 @@ void radtran_ir_spectra_opr_vjp(void *ptr, const double *T_surface, const int *d
   const char *who = "ir_spectra_opr_vjp";
   const std::string pre = std::string(who) + ": ";
   const double *const gs[2] = {g_ir_fup, g_ir_fdn}, *const gn[2] = {g_fup_n, g_fdn_n};
-  const void *const gsv[2] = {g_ir_fup, g_ir_fdn}, *const gnv[2] = {g_fup_n, g_fdn_n}, *const outv[3] = {grad_tau, grad_w0, grad_g};
   double *const out[3] = {grad_tau, grad_w0, grad_g};
   std::vector<int> lv;
-  if (ir_opr_refused(r, who, *dim_T, *nsel_, spec_level, T_surface, T, gsv, gnv, outv, lv, err)) return;
+  if (ir_opr_refused(r, who, *dim_T, *nsel_, spec_level, T_surface, T, gs, gn, out, lv, err)) return;
   const int nz = r->nz, nsel = *nsel_;
-  for (int j = 0; j <= nz; j++) {
-    const double v = j < nz ? T[j] : *T_surface;
-    if (!(std::isfinite(v) && v > 0.0)) {
-      set_err(err, pre + "temperatures must be finite and positive (" + (j < nz ? "T(" + std::to_string(j + 1) + ")" : std::string("T_surface")) +
-                       " = " + std::to_string(v) + ")");
-      return;
-    }
-  }
+  if (ir_column_T_refused(pre, nz, T_surface, T, err)) return;
   if (ir_opr_handle_refused(r, who, err)) return;
   TRY
   ready_stored_opacities(r);
@@ -3529,20 +3488,8 @@ void radtran_ir_spectra_opr_vjp(void *ptr, const double *T_surface, const int *d
   HIPCHK(hipMemcpyAsync(r->d_bT.p, T, sizeof(double) * nz, hipMemcpyHostToDevice, r->stream));
   HIPCHK(hipMemcpyAsync(r->d_bTs.p, T_surface, sizeof(double), hipMemcpyHostToDevice, r->stream));
   r->d_rows_out.reserve(std::max<size_t>(1, 2 * (spec + sums)));
-  const double *dgs[2] = {nullptr, nullptr}, *dgn[2] = {nullptr, nullptr};
-  {
-    double *at = r->d_rows_out.p;
-    for (int d = 0; d < 2; d++) {
-      if (gs[d]) {
-        if (spec) HIPCHK(hipMemcpyAsync(at, gs[d], sizeof(double) * spec, hipMemcpyHostToDevice, r->stream));
-        dgs[d] = at; at += spec;
-      }
-      if (gn[d]) {
-        HIPCHK(hipMemcpyAsync(at, gn[d], sizeof(double) * sums, hipMemcpyHostToDevice, r->stream));
-        dgn[d] = at; at += sums;
-      }
-    }
-  }
+  const double *dgs[2], *dgn[2];
+  ir_stage_cotangents(r, spec, sums, 0, 1, gs, gn, dgs, dgn);
   size_t total = 0;
   for (int k = 0; k < 3; k++) total += out[k] ? counts[k] : 0;
   r->d_bout.reserve(total);
@@ -4521,6 +4468,30 @@ void clima_test_solar_batch(const int *nz_, const int *ng_, const int *force_nw,
 }
 void clima_test_solar_batch_cases_per_block(const int *ncol, int *cases) { *cases = solar_batch_cases_per_block(*ncol); }
 
+// What the three IR test hooks below run on: one column's tau / w0 / g as `nbin` IR bins of ng g-points each, every g-point
+// of every bin carrying the same column, on the device with wbin and the emissivity, and the GreenParams of such a handle
+// (ir_par = {emissivity, has_hard_surface, ir_tau_min}; no frequency grids: the hooks hand the Planck terms over)
+namespace {
+struct TestIrColumn {
+  DevBuf<double> tau, w0, g, wbin, em;
+  GreenParams params;
+  TestIrColumn(int nz, int ng, int nbin, const double *tau_, const double *w0_, const double *g_, const double *ir_par, const double *wbin_) {
+    const int NQ = nbin * ng;
+    std::vector<double> h_tau((size_t)NQ * nz), h_w0((size_t)NQ * nz), h_g((size_t)nbin * nz);
+    for (int c = 0; c < NQ; c++)
+      for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau_[i]; h_w0[(size_t)c * nz + i] = w0_[i]; }
+    for (int b = 0; b < nbin; b++)
+      for (int i = 0; i < nz; i++) h_g[(size_t)b * nz + i] = g_[i];
+    tau.upload(h_tau); w0.upload(h_w0); g.upload(h_g);
+    wbin.upload(std::vector<double>(wbin_, wbin_ + ng)); em.upload(std::vector<double>((size_t)nbin, ir_par[0]));
+    std::memset(&params, 0, sizeof(params));
+    params.nz = nz; params.ng = ng; params.n_ir = nbin; params.NQ = NQ;
+    params.tau = tau.p; params.w0 = w0.p; params.g = g.p; params.wbin = wbin.p; params.emissivity = em.p;
+    params.has_hard_surface = ir_par[1] != 0.0 ? 1 : 0; params.ir_tau_min = ir_par[2];
+  }
+};
+}  // namespace
+
 // Test hook of the response form (ir_green.inc), the counterpart of clima_test_two_stream for it: one column's tau / w0 /
 // g (the same for every g-point, weights wbin) and ndev deviations (level k TOA-first, k = nz the surface; change of the
 // Planck value there) -> per deviation the change of the level fluxes (TOA-first), sum over the g-points, exactly as the
@@ -4537,27 +4508,20 @@ void clima_test_ir_response(const int *nz_, const int *ng_, const double *tau, c
   for (int i = 0; i < ndev; i++) { order[i] = i; if (dev_k[i] < 0 || dev_k[i] > nz) throw HipFail{"clima_test_ir_response: bad level"}; }
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return dev_k[a] < dev_k[b]; });
   const int ndev_pad = green_ndev_pad(ndev);
-  std::vector<double> h_tau((size_t)ng * nz), h_w0((size_t)ng * nz), h_db(ndev_pad + 64, 0.0);
-  for (int c = 0; c < ng; c++)
-    for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau[i]; h_w0[(size_t)c * nz + i] = w0[i]; }
+  std::vector<double> h_db(ndev_pad + 64, 0.0);
   std::vector<int> hi(ndev_pad, 0), mdev, mblk;
   for (int d = 0; d < ndev; d++) { hi[d] = dev_k[order[d]]; h_db[d] = dev_db[order[d]]; }
   green_mixed_list(std::vector<int>(hi.begin(), hi.begin() + ndev), nz, mdev, mblk);
   const int nmix = (int)mdev.size();
   hi.insert(hi.end(), mdev.begin(), mdev.end());
   hi.insert(hi.end(), mblk.begin(), mblk.end());
-  DevBuf<double> d_tau, d_w0, d_g, d_wbin, d_em, d_db, d_work;
+  TestIrColumn col(nz, ng, 1, tau, w0, g, ir_par, wbin);
+  DevBuf<double> d_db, d_work;
   DevBuf<int> d_idx;
-  d_tau.upload(h_tau); d_w0.upload(h_w0); d_g.upload(std::vector<double>(g, g + nz));
-  d_wbin.upload(std::vector<double>(wbin, wbin + ng)); d_em.upload(std::vector<double>{ir_par[0]});
   d_db.upload(h_db); d_idx.upload(hi);
   const size_t work = green_work_views(nz, ng, nullptr).count;
   d_work.alloc(work + (size_t)ndev_pad * 2 * nl); d_work.zero();   // ... and the one array of partial sums behind them
-  GreenParams gp;
-  std::memset(&gp, 0, sizeof(gp));
-  gp.nz = nz; gp.ng = ng; gp.n_ir = 1; gp.ir_lo = 0; gp.ir_start = 0; gp.NQ = ng;
-  gp.tau = d_tau.p; gp.w0 = d_w0.p; gp.g = d_g.p; gp.wbin = d_wbin.p; gp.emissivity = d_em.p;
-  gp.has_hard_surface = ir_par[1] != 0.0 ? 1 : 0; gp.ir_tau_min = ir_par[2];
+  GreenParams gp = col.params;
   const GreenWork w = green_work_views(nz, ng, d_work.p);
   gp.RW = w.RW; gp.IS = w.IS; gp.FS = w.FS; gp.DS = w.DS; gp.D0 = w.D0;
   gp.partial = d_work.p + work;
@@ -4595,22 +4559,16 @@ void clima_test_ir_adjoint(const int *nz_, const int *ng_, const double *tau, co
     if (level[a] < 0 || level[a] > nz) throw HipFail{"clima_test_ir_adjoint: bad level"};
     fun[2 * a] = 2 * level[a]; fun[2 * a + 1] = 2 * level[a] + 1;
   }
-  std::vector<double> h_tau((size_t)ng * nz), h_w0((size_t)ng * nz);
-  for (int c = 0; c < ng; c++)
-    for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau[i]; h_w0[(size_t)c * nz + i] = w0[i]; }
-  DevBuf<double> d_tau, d_w0, d_g, d_wbin, d_em, d_work, d_out;
+  TestIrColumn col(nz, ng, 1, tau, w0, g, ir_par, wbin);
+  DevBuf<double> d_work, d_out;
   DevBuf<int> d_fun;
-  d_tau.upload(h_tau); d_w0.upload(h_w0); d_g.upload(std::vector<double>(g, g + nz));
-  d_wbin.upload(std::vector<double>(wbin, wbin + ng)); d_em.upload(std::vector<double>{ir_par[0]});
   d_fun.upload(fun);
   const size_t n_work = ir_adjoint_work_count(nz, ng, nfun), n_part = ir_adjoint_part_count(nz, ng, nfun), arr = (size_t)nr * nl;
   d_work.alloc(n_work + n_part); d_work.zero();
   d_out.alloc(2 * arr); d_out.zero();
   IrAdjointParams p;
   std::memset(&p, 0, sizeof(p));
-  p.g.nz = nz; p.g.ng = ng; p.g.n_ir = 1; p.g.NQ = ng;
-  p.g.tau = d_tau.p; p.g.w0 = d_w0.p; p.g.g = d_g.p; p.g.wbin = d_wbin.p; p.g.emissivity = d_em.p;
-  p.g.has_hard_surface = ir_par[1] != 0.0 ? 1 : 0; p.g.ir_tau_min = ir_par[2];
+  p.g = col.params;
   p.nfun = nfun; p.nrow = nr; p.ndir = 2; p.fun = d_fun.p;
   p.work = d_work.p; p.part = p.work + n_work; p.out_up = d_out.p; p.out_dn = d_out.p + arr;
   launch_ir_adjoint(p, nullptr);
@@ -4641,19 +4599,14 @@ void clima_test_ir_opr_sens(const int *nz_, const int *ng_, const double *tau, c
   for (int a = 0; a < nr; a++)
     if (level[a] < 0 || level[a] > nz) throw HipFail{"clima_test_ir_opr_sens: bad level"};
   const size_t ntau = (size_t)NQ * nz, ngg = (size_t)nb * nz;
-  std::vector<double> h_tau(ntau), h_w0(ntau), h_g(ngg), h_gs(2 * (size_t)nb * nr, 0.0);
-  for (int c = 0; c < NQ; c++)
-    for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau[i]; h_w0[(size_t)c * nz + i] = w0[i]; }
-  for (int b = 0; b < nb; b++)
-    for (int i = 0; i < nz; i++) h_g[(size_t)b * nz + i] = g[i];
+  std::vector<double> h_gs(2 * (size_t)nb * nr, 0.0);
   for (int a = 0; a < nr; a++) {
     h_gs[(size_t)(2 * a) + (size_t)nb * a] = 1.0;                               // up: bin 2a
     h_gs[(size_t)nb * nr + (size_t)(2 * a + 1) + (size_t)nb * a] = 1.0;         // down: bin 2a+1
   }
-  DevBuf<double> d_tau, d_w0, d_g, d_wbin, d_em, d_bp, d_gs, d_work, d_out;
+  TestIrColumn col(nz, ng, nb, tau, w0, g, ir_par, wbin);
+  DevBuf<double> d_bp, d_gs, d_work, d_out;
   DevBuf<int> d_lv;
-  d_tau.upload(h_tau); d_w0.upload(h_w0); d_g.upload(h_g);
-  d_wbin.upload(std::vector<double>(wbin, wbin + ng)); d_em.upload(std::vector<double>((size_t)nb, ir_par[0]));
   d_bp.upload(std::vector<double>(bplanck, bplanck + nl)); d_gs.upload(h_gs);
   d_lv.upload(std::vector<int>(level, level + nr));
   const size_t n_work = ir_opr_work_count(nz, NQ), n_part = ir_opr_part_count(nz, NQ);
@@ -4661,9 +4614,7 @@ void clima_test_ir_opr_sens(const int *nz_, const int *ng_, const double *tau, c
   d_out.alloc(2 * ntau + ngg); d_out.zero();
   IrOprParams p;
   std::memset(&p, 0, sizeof(p));
-  p.g.nz = nz; p.g.ng = ng; p.g.n_ir = nb; p.g.NQ = NQ;
-  p.g.tau = d_tau.p; p.g.w0 = d_w0.p; p.g.g = d_g.p; p.g.wbin = d_wbin.p; p.g.emissivity = d_em.p;
-  p.g.has_hard_surface = ir_par[1] != 0.0 ? 1 : 0; p.g.ir_tau_min = ir_par[2];
+  p.g = col.params;
   p.bplanck = d_bp.p;
   p.nsel = nr; p.gs_ld = nb; p.level = d_lv.p;
   p.gs_up = d_gs.p; p.gs_dn = d_gs.p + (size_t)nb * nr;

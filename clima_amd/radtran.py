@@ -40,6 +40,61 @@ def _fo(a):
     return np.asfortranarray(a, dtype=np.float64)
 
 
+# What the IR derivative family's requests check alike.  `who` is the message's whole prefix ("name: ").
+def _level_rows(who, nz, levels):
+    """numpy-style `levels` into the ground-first level axis -> 1..nz+1 as the ABI takes them"""
+    nl = nz + 1
+    idx = np.atleast_1d(np.asarray(levels))
+    if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
+        raise ClimaException(who + '"levels" is not a non-empty list of integer level indices')
+    for a, v in enumerate(idx.tolist()):
+        if v < -nl or v >= nl:
+            raise ClimaException(who + "levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
+    return np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
+
+
+def _names_among(who, arg, given, allowed):
+    """the names `given` for the argument `arg` (one or several), in the order of `allowed` (the ABI's)"""
+    given = (given,) if isinstance(given, str) else tuple(given)
+    for name in given:
+        if name not in allowed:
+            raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(allowed)))
+    if not given:
+        raise ClimaException(who + '"%s" names none of %s' % (arg, ", ".join(allowed)))
+    return tuple(name for name in allowed if name in given)
+
+
+def _keys_among(who, arg, d, allowed):
+    if not isinstance(d, dict):
+        raise ClimaException(who + '"%s" is not a dict with keys among %s' % (arg, ", ".join(allowed)))
+    for name in d:
+        if name not in allowed:
+            raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(allowed)))
+
+
+def _one_column(who, nz, T_surface, T):
+    """(T_surface (1,), T (nz,)) of one column"""
+    T, Ts = _c(np.atleast_1d(T)), _c(np.atleast_1d(T_surface))
+    if Ts.shape != (1,):
+        raise ClimaException(who + '"T_surface" has the shape %s, not a scalar' % (tuple(np.shape(T_surface)),))
+    if T.shape != (nz,):
+        raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz,)))
+    return Ts, T
+
+
+def _column_batch(who, nz, T_surface, T, least):
+    """(T_surface (ncol,), T (nz, ncol) Fortran-ordered) of at least `least` columns; a 1-D T is one column"""
+    T, Ts = np.asfortranarray(T, dtype=np.float64), _c(np.atleast_1d(T_surface))
+    if Ts.ndim != 1:
+        raise ClimaException(who + '"T_surface" has the shape %s, not (ncol,)' % (Ts.shape,))
+    if T.ndim == 1 and len(Ts) == 1:
+        T = np.asfortranarray(T[:, None])
+    n = len(Ts)
+    if n < least or T.shape != (nz, n):
+        raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz, max(n, least))))
+    return Ts, T
+
+
 def grey_sensitivity(opr, grads, ir_tau_min, max_w0):
     """From `Radtran.ir_spectra_opr_vjp`'s gradients to the response to an added GREY optical depth, per (layer, bin):
     what a continuum, CIA, a cloud or the custom optical properties add to every g-point alike
@@ -679,26 +734,9 @@ class Radtran:
         ABI's order) -- for a handle of nz layers; wrong shapes, unknown parts and levels outside -(nz+1)..nz are refused
         by name (reads IR_JACOBIAN_SPECTRAL_PARTS alone: no handle needed)"""
         who = "ir_jacobian_spectral: "
-        T, Ts = _c(np.atleast_1d(T)), _c(np.atleast_1d(T_surface))
-        if Ts.shape != (1,):
-            raise ClimaException(who + '"T_surface" has the shape %s, not a scalar' % (tuple(np.shape(T_surface)),))
-        if T.shape != (nz,):
-            raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz,)))
-        parts = (parts,) if isinstance(parts, str) else tuple(parts)
-        for name in parts:
-            if name not in self.IR_JACOBIAN_SPECTRAL_PARTS:
-                raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.IR_JACOBIAN_SPECTRAL_PARTS)))
-        if not parts:
-            raise ClimaException(who + '"parts" names none of %s' % ", ".join(self.IR_JACOBIAN_SPECTRAL_PARTS))
-        nl = nz + 1
-        idx = np.atleast_1d(np.asarray(levels))
-        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
-            raise ClimaException(who + '"levels" is not a non-empty list of integer level indices')
-        for a, v in enumerate(idx.tolist()):
-            if v < -nl or v >= nl:
-                raise ClimaException(who + "levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
-        rows = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
-        return Ts, T, rows, tuple(name for name in self.IR_JACOBIAN_SPECTRAL_PARTS if name in parts)
+        Ts, T = _one_column(who, nz, T_surface, T)
+        names = _names_among(who, "parts", parts, self.IR_JACOBIAN_SPECTRAL_PARTS)
+        return Ts, T, _level_rows(who, nz, levels), names
 
     def ir_jacobian_spectral(self, T_surface, T, levels=(-1,), parts=("up",)):
         """Rows of `ir_jacobian` before the sum over the bins (radtran_ir_jacobian_spectral_rows): a dict name ->
@@ -725,32 +763,12 @@ class Radtran:
         needed).  T_surface None with T None: no columns, the weights alone."""
         who = "ir_spectra_batch: "
         if T is None and T_surface is None:
-            T, Ts = np.empty((nz, 0), order="F"), np.empty(0)
-        else:
-            T, Ts = np.asfortranarray(T, dtype=np.float64), _c(np.atleast_1d(T_surface))
-        if Ts.ndim != 1:
-            raise ClimaException(who + '"T_surface" has the shape %s, not (ncol,)' % (Ts.shape,))
-        if T.ndim == 1 and len(Ts) == 1:
-            T = np.asfortranarray(T[:, None])
-        if T.shape != (nz, len(Ts)):
-            raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz, len(Ts))))
-        parts = (parts,) if isinstance(parts, str) else tuple(parts)
-        for name in parts:
-            if name not in self.IR_SPECTRA_BATCH_PARTS:
-                raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.IR_SPECTRA_BATCH_PARTS)))
-        if not parts:
-            raise ClimaException(who + '"parts" names none of %s' % ", ".join(self.IR_SPECTRA_BATCH_PARTS))
+            T, T_surface = np.empty((nz, 0), order="F"), np.empty(0)
+        Ts, T = _column_batch(who, nz, T_surface, T, 0)
+        names = _names_among(who, "parts", parts, self.IR_SPECTRA_BATCH_PARTS)
         if len(Ts) == 0 and not weights:
             raise ClimaException(who + "no columns and weights=False: nothing is asked for")
-        nl = nz + 1
-        idx = np.atleast_1d(np.asarray(levels))
-        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
-            raise ClimaException(who + '"levels" is not a non-empty list of integer level indices')
-        for a, v in enumerate(idx.tolist()):
-            if v < -nl or v >= nl:
-                raise ClimaException(who + "levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
-        rows = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
-        return Ts, T, rows, tuple(name for name in self.IR_SPECTRA_BATCH_PARTS if name in parts)
+        return Ts, T, _level_rows(who, nz, levels), names
 
     def ir_spectra_batch(self, T_surface, T, levels=(-1,), parts=("up",), fluxes=False, weights=False):
         """Per-bin IR spectra of many temperature profiles on the stored opacities (radtran_ir_spectra_batch): column c is
@@ -788,20 +806,10 @@ class Radtran:
         layers and nw_ir IR bins; unknown keys, wrong shapes, a cotangent without its weights and a request without any
         cotangent are refused by name (reads the two name lists alone: no handle needed)."""
         who = "ir_spectra_vjp: "
-        T, Ts = np.asfortranarray(T, dtype=np.float64), _c(np.atleast_1d(T_surface))
-        if Ts.ndim != 1:
-            raise ClimaException(who + '"T_surface" has the shape %s, not (ncol,)' % (Ts.shape,))
-        if T.ndim == 1 and len(Ts) == 1:
-            T = np.asfortranarray(T[:, None])
+        Ts, T = _column_batch(who, nz, T_surface, T, 1)
         n = len(Ts)
-        if n < 1 or T.shape != (nz, n):
-            raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz, max(n, 1))))
-        for d, allowed, what in ((weights, self.IR_SPECTRA_VJP_WEIGHTS, "weights"), (grads, self.IR_SPECTRA_VJP_GRADS, "grads")):
-            if not isinstance(d, dict):
-                raise ClimaException(who + '"%s" is not a dict with keys among %s' % (what, ", ".join(allowed)))
-            for name in d:
-                if name not in allowed:
-                    raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(allowed)))
+        _keys_among(who, "weights", weights, self.IR_SPECTRA_VJP_WEIGHTS)
+        _keys_among(who, "grads", grads, self.IR_SPECTRA_VJP_GRADS)
         w = [np.asfortranarray(weights[k], dtype=np.float64) if weights.get(k) is not None else None for k in self.IR_SPECTRA_VJP_WEIGHTS]
         g = [np.asfortranarray(grads[k], dtype=np.float64) if grads.get(k) is not None else None for k in self.IR_SPECTRA_VJP_GRADS]
         if w[0] is None and w[1] is None:
@@ -887,20 +895,8 @@ class Radtran:
         import torch
         who = "ir_spectra_batch_device"
         nz, nl, nw_ir = self.nz, self.nz + 1, len(self.ir.freq) - 1
-        parts = (parts,) if isinstance(parts, str) else tuple(parts)
-        for name in parts:
-            if name not in self.IR_SPECTRA_BATCH_PARTS:
-                raise ClimaException('%s: "%s" is not one of %s' % (who, name, ", ".join(self.IR_SPECTRA_BATCH_PARTS)))
-        names = tuple(name for name in self.IR_SPECTRA_BATCH_PARTS if name in parts)
-        if not names:
-            raise ClimaException('%s: "parts" names none of %s' % (who, ", ".join(self.IR_SPECTRA_BATCH_PARTS)))
-        idx = np.atleast_1d(np.asarray(levels))
-        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
-            raise ClimaException('%s: "levels" is not a non-empty list of integer level indices' % who)
-        for a, v in enumerate(idx.tolist()):
-            if v < -nl or v >= nl:
-                raise ClimaException("%s: levels[%d] = %d is outside %d..%d" % (who, a, v, -nl, nl - 1))
-        rows = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
+        names = _names_among(who + ": ", "parts", parts, self.IR_SPECTRA_BATCH_PARTS)
+        rows = _level_rows(who + ": ", nz, levels)
         nsel = len(rows)
         n = int(T_surface.shape[0]) if isinstance(T_surface, torch.Tensor) and T_surface.dim() == 1 else -1
         self._ir_tensor_check(who, "T_surface", T_surface, (max(n, 1),))
@@ -940,12 +936,8 @@ class Radtran:
         import torch
         who = "ir_spectra_batch_vjp_device"
         nz, nl, nw_ir = self.nz, self.nz + 1, len(self.ir.freq) - 1
-        for d, allowed, what in ((weights, self.IR_SPECTRA_VJP_WEIGHTS, "weights"), (grads, self.IR_SPECTRA_VJP_GRADS, "grads")):
-            if not isinstance(d, dict):
-                raise ClimaException('%s: "%s" is not a dict with keys among %s' % (who, what, ", ".join(allowed)))
-            for name in d:
-                if name not in allowed:
-                    raise ClimaException('%s: "%s" is not one of %s' % (who, name, ", ".join(allowed)))
+        _keys_among(who + ": ", "weights", weights, self.IR_SPECTRA_VJP_WEIGHTS)
+        _keys_among(who + ": ", "grads", grads, self.IR_SPECTRA_VJP_GRADS)
         w = {k: v for k, v in weights.items() if v is not None}
         g = {k: v for k, v in grads.items() if v is not None}
         if not w:
@@ -977,29 +969,13 @@ class Radtran:
         """What both forms of `ir_spectra_opr_vjp` check alike, with the prefix `who`: the names in `wrt` (-> in the ABI's
         order), `levels` (-> 1..nz+1 as the ABI takes them) and the keys of `grads` (-> the dict without its None entries);
         reads IR_SPECTRA_VJP_GRADS and IR_SPECTRA_OPR_WRT alone"""
-        wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
-        for name in wrt:
-            if name not in self.IR_SPECTRA_OPR_WRT:
-                raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.IR_SPECTRA_OPR_WRT)))
-        if not wrt:
-            raise ClimaException(who + '"wrt" names none of %s' % ", ".join(self.IR_SPECTRA_OPR_WRT))
-        nl = nz + 1
-        idx = np.atleast_1d(np.asarray(levels))
-        if idx.ndim != 1 or idx.size < 1 or idx.dtype.kind not in "iu":
-            raise ClimaException(who + '"levels" is not a non-empty list of integer level indices')
-        for a, v in enumerate(idx.tolist()):
-            if v < -nl or v >= nl:
-                raise ClimaException(who + "levels[%d] = %d is outside %d..%d" % (a, v, -nl, nl - 1))
-        rows = np.ascontiguousarray(np.where(idx < 0, idx + nl, idx) + 1, dtype=np.int32)
-        if not isinstance(grads, dict):
-            raise ClimaException(who + '"grads" is not a dict with keys among %s' % ", ".join(self.IR_SPECTRA_VJP_GRADS))
-        for name in grads:
-            if name not in self.IR_SPECTRA_VJP_GRADS:
-                raise ClimaException(who + '"%s" is not one of %s' % (name, ", ".join(self.IR_SPECTRA_VJP_GRADS)))
+        names = _names_among(who, "wrt", wrt, self.IR_SPECTRA_OPR_WRT)
+        rows = _level_rows(who, nz, levels)
+        _keys_among(who, "grads", grads, self.IR_SPECTRA_VJP_GRADS)
         given = {k: v for k, v in grads.items() if v is not None}
         if not given:
             raise ClimaException(who + '"grads" holds none of %s' % ", ".join(self.IR_SPECTRA_VJP_GRADS))
-        return tuple(name for name in self.IR_SPECTRA_OPR_WRT if name in wrt), rows, given
+        return names, rows, given
 
     def _ir_spectra_opr_request(self, nz, nw_ir, T_surface, T, grads, levels, wrt):
         """The arrays of `ir_spectra_opr_vjp` as the ABI takes them -- (T_surface (1,), T (nz,), levels 1..nz+1, the four
@@ -1008,11 +984,7 @@ class Radtran:
         -(nz+1)..nz and a request without any cotangent are refused by name (reads IR_SPECTRA_VJP_GRADS and
         IR_SPECTRA_OPR_WRT alone: no handle needed)."""
         who = "ir_spectra_opr_vjp: "
-        T, Ts = _c(np.atleast_1d(T)), _c(np.atleast_1d(T_surface))
-        if Ts.shape != (1,):
-            raise ClimaException(who + '"T_surface" has the shape %s, not a scalar' % (tuple(np.shape(T_surface)),))
-        if T.shape != (nz,):
-            raise ClimaException(who + '"T" has the shape %s, not %s' % (T.shape, (nz,)))
+        Ts, T = _one_column(who, nz, T_surface, T)
         names, rows, given = Radtran._ir_spectra_opr_names(self, who, nz, grads, levels, wrt)
         nsel = len(rows)
         g = [np.asfortranarray(given[k], dtype=np.float64) if k in given else None for k in self.IR_SPECTRA_VJP_GRADS]

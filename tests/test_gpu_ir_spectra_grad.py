@@ -363,6 +363,29 @@ def test_06_a_side_stream_without_a_host_sync(small_tables):
     assert bool(torch.isfinite(grad)) and float(grad) != 0.0
 
 
+def test_06_two_enqueued_calls_keep_their_own_levels(small_tables):
+    """Two calls that only enqueue, with different `levels`, right behind each other on a handle whose producer stream is
+    still busy: each computes its weights for its own levels (a staging block the calls share would be rewritten by
+    the second call before the first one's copy has run)"""
+    import torch
+    nz, n = 33, 3
+    r, col = _handle(small_tables, nz, True)
+    Ts, T = _profiles(col, nz, n, 12)
+    dTs, dT = _dev(Ts), _dev(T)
+    asked = ((-1,), (0,))
+    want = [r.ir_spectra_batch_tensors(dTs, dT, levels=lv, parts=("up", "dn"), sync=True) for lv in asked]
+    assert not want[0]["fup"].equal(want[1]["fup"])
+    torch.cuda.synchronize()
+    torch.cuda._sleep(50_000_000)          # tens of milliseconds of the current stream (half a second on a 100 MHz counter)
+    got = [r.ir_spectra_batch_tensors(dTs, dT, levels=lv, parts=("up", "dn"), sync=False) for lv in asked]
+    torch.cuda.synchronize()
+    r.synchronize()
+    for lv, w, g in zip(asked, want, got):
+        assert sorted(g) == sorted(w) == ["fdn", "fup"]
+        for k in w:
+            assert g[k].cpu().numpy().tobytes() == w[k].cpu().numpy().tobytes(), (lv, k)
+
+
 # ------------------------------------------------------------------ 7
 def test_07_refusals(hip_lib, small_tables):
     import torch
