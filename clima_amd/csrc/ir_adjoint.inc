@@ -15,14 +15,14 @@
 //
 // k_adjoint_rows: one wave per q = (bin, g-point), the rows 64 at a time (lane = row).
 //   1. once per q: the rows' coefficients from the layers' e's (green_layer_of, green_row_even / _odd) and the
-//      elimination c'_r = A(r+1) / (B(r) - D(r-1) c'_{r-1}) as k_green_factor's scan of 2 x 2 matrices; c', 1 / pivot
-//      and D(r-1) go to the wave's work rows (each lane reads back only what it wrote).
-//   2. per functional: y_r = (c_r - D(r-1) y_{r-1}) / pivot_r, an affine scan downwards from the segment that holds
-//      c's two rows (y is 0 above it), then lambda_r = y_r - c'_r lambda_{r+1}, an affine scan upwards.
+//      elimination c'_r = A(r+1) / (B(r) - D(r-1) c'_{r-1}) by k_green_factor's scan of 2 x 2 matrices (green_prefix_scan,
+//      green_rcp_pivot); c', 1 / pivot and D(r-1) go to the wave's work rows (each lane reads back only what it wrote).
+//   2. per functional: y_r = (c_r - D(r-1) y_{r-1}) / pivot_r, an affine scan (affine_scan) downwards from the segment that
+//      holds c's two rows (y is 0 above it), then lambda_r = y_r - c'_r lambda_{r+1}, an affine scan upwards.
 //   3. lane = level k: the six rows 2k-3 .. 2k+2 of dE/d bplanck(k), formed as k_green_unit forms them, against
 //      every functional's lambda, plus ds/d bplanck(k), times the g-point's weight -> part[q][functional][k].
 // k_adjoint_sum adds the g-points of a bin in g order (bitwise repeatable, no atomics), multiplies by the Planck
-// derivative dB/dT(avg_freq(bin), T_k) -- k_green_dbdt's overflow-free form, NOT times the bin's width -- and writes
+// derivative dB/dT(avg_freq(bin), T_k) -- adjoint_dbdt = planck_dbdt, NOT times the bin's width -- and writes
 // out(bin, a, j), the bin fastest, j = nz - k ground-first (x(1) = T_surface).
 // Levels, layers, rows and k are TOA-first as in ir_green.inc.  fun[f] = 2 level + (0 up | 1 down), the functionals of
 // a requested level side by side: f = a ndir + (its place among the directions asked for).
@@ -51,22 +51,7 @@ __device__ __forceinline__ void adjoint_eliminate(const int nz, const int lane, 
     if (!on) { a = 0.0; B = 1.0; }
     GreenM P = {0.0, s, -a, B};
     if (!on) { P.m11 = 1.0; P.m12 = 0.0; P.m21 = 0.0; P.m22 = 1.0; }
-    green_norm(P);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      GreenM T;
-      T.m11 = __shfl_up(P.m11, d); T.m12 = __shfl_up(P.m12, d); T.m21 = __shfl_up(P.m21, d); T.m22 = __shfl_up(P.m22, d);
-      if (lane >= d) {
-        const GreenM o = P;
-        P.m11 = o.m11 * T.m11 + o.m12 * T.m21; P.m12 = o.m11 * T.m12 + o.m12 * T.m22;
-        P.m21 = o.m21 * T.m11 + o.m22 * T.m21; P.m22 = o.m21 * T.m12 + o.m22 * T.m22;
-        green_norm(P);
-      }
-    }
-    const double c_scan = (P.m11 * c_in + P.m12) / (P.m21 * c_in + P.m22);    // c' of this row by the scan
-    double c_prev = __shfl_up(c_scan, 1);
-    if (lane == 0) c_prev = c_in;
-    const double rd = rcp_nr(B - a * c_prev);                                 // ... and by the recurrence's own step
+    const double rd = green_rcp_pivot(green_prefix_scan(P, lane), c_in, a, B, lane);
     const double cp = on ? s * rd : 0.0;
     if (on) { w_c[r] = cp; w_rd[r] = rd; w_a[r] = a; }
     c_in = __shfl(cp, 63);
@@ -77,16 +62,12 @@ __global__ __launch_bounds__(64) void k_adjoint_rows(IrAdjointParams p) {
   const GreenParams &gp = p.g;
   const int q = blockIdx.x, lane = threadIdx.x;
   const int nz = gp.nz, nl = nz + 1, N = 2 * nz, nseg = (N + 63) / 64, nfun = p.nfun;
-  size_t qtau, qg; int bi, g;
-  green_q(gp, q, qtau, qg, bi, g);
-  const bool hard = gp.has_hard_surface != 0;
-  const double emis = hard ? gp.emissivity[gp.ir_lo + bi] : 0.0, Rsfc = hard ? 1.0 - emis : 0.0;
-  const double w = gp.wbin[g];
+  const GreenQ Q = green_q(gp, q);
   double *wk = p.work + (size_t)q * adjoint_work_rows(nfun) * N;
   double *w_c = wk, *w_rd = wk + N, *w_a = wk + (size_t)2 * N, *w_y = wk + (size_t)3 * N, *w_lam = wk + (size_t)4 * N;
   auto layer = [&](const int n) {     // layer n, or the virtual layer above / below the column (green_layer_of)
-    const int nc = min(max(n, 0), nz - 1);
-    return green_layer_of(gp, gp.tau[qtau + nc], gp.w0[qtau + nc], gp.g[qg + nc], n, Rsfc);
+    const GreenLayerIn in = green_layer_in(gp, Q, n);
+    return green_layer_of(gp, in.tau, in.w0, in.g, n, Q.Rsfc);
   };
 
   // ---- 1. the transposed system's rows and their elimination
@@ -106,13 +87,8 @@ __global__ __launch_bounds__(64) void k_adjoint_rows(IrAdjointParams p) {
       const bool on = r < N;
       const double rd = on ? w_rd[r] : 0.0, a = on ? w_a[r] : 0.0;
       const double rhs = r == r0 ? c0 : r == r0 + 1 ? c1 : 0.0;
-      double al = rhs * rd, be = on ? -a * rd : 1.0;       // y_r = al + be y(last row before this lane's prefix)
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const double ta = __shfl_up(al, d), tb = __shfl_up(be, d);
-        if (lane >= d) { al = al + be * ta; be = be * tb; }
-      }
-      const double y = al + be * y_in;
+      const Affine m = affine_scan<false>({rhs * rd, on ? -a * rd : 1.0}, lane);       // y_r = al + be y(last row before this lane's prefix)
+      const double y = m.al + m.be * y_in;
       if (on) w_y[r] = y;
       y_in = __shfl(y, 63);
     }
@@ -120,13 +96,8 @@ __global__ __launch_bounds__(64) void k_adjoint_rows(IrAdjointParams p) {
     for (int seg = nseg - 1; seg >= 0; seg--) {
       const int r = seg * 64 + lane;
       const bool on = r < N;
-      double al = (on && seg >= seg0) ? w_y[r] : 0.0, be = on ? -w_c[r] : 1.0;   // lambda_r = al + be lambda(first row after this lane's suffix)
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const double ta = __shfl_down(al, d), tb = __shfl_down(be, d);
-        if (lane + d < 64) { al = al + be * ta; be = be * tb; }
-      }
-      const double lm = al + be * lam_in;
+      const Affine m = affine_scan<true>({(on && seg >= seg0) ? w_y[r] : 0.0, on ? -w_c[r] : 1.0}, lane);   // lambda_r = al + be lambda(first row after this lane's suffix)
+      const double lm = m.al + m.be * lam_in;
       if (on) lam[r] = lm;
       lam_in = __shfl(lm, 0);
     }
@@ -158,8 +129,8 @@ __global__ __launch_bounds__(64) void k_adjoint_rows(IrAdjointParams p) {
       cmb[j] = PI * (b0 + b1 * (Ly[j].tau - Ly[j].rq));
     }
     // the virtual layer under the column carries the surface term as its upper source value (:236-247)
-    if (k == nz) cp0[2] = hard ? emis * PI : PI * (1.0 + (Ly[1].thin ? 0.0 : 0.5 / Ly[1].tau));
-    if (k == nz - 1 && !hard) cp0[3] = PI * (Ly[2].thin ? 0.0 : -0.5 / Ly[2].tau);
+    if (k == nz) cp0[2] = Q.hard ? Q.emis * PI : PI * (1.0 + (Ly[1].thin ? 0.0 : 0.5 / Ly[1].tau));
+    if (k == nz - 1 && !Q.hard) cp0[3] = PI * (Ly[2].thin ? 0.0 : -0.5 / Ly[2].tau);
     double E[6];
 #pragma unroll
     for (int t = 0; t < 6; t++) {
@@ -186,20 +157,15 @@ __global__ __launch_bounds__(64) void k_adjoint_rows(IrAdjointParams p) {
         if (lv == 0) s = k == 0 ? cp0[2] : k == 1 ? cp0[1] : 0.0;
         else if (k == lv - 1) s = dn ? cmb[2] : cpb[2];
         else if (k == lv) s = dn ? cmb[1] : cpb[1];
-        v = w * (v + s);
+        v = Q.w * (v + s);
       }
       part[(size_t)f * nl + k] = v;
     }
   }
 }
 
-// dB/dT at (avg_freq, T): k_green_dbdt's form (large x takes e to 0, small x keeps its digits through expm1), per Hz
-__device__ __forceinline__ double adjoint_dbdt(double avg_freq, double T) {
-  const double x = ((PLANK * avg_freq) / K_BOLTZ_SI) / T;
-  const double K = 1.0e3 * ((2.0 * PLANK * (avg_freq * avg_freq * avg_freq)) / (C_LIGHT * C_LIGHT));
-  const double e = exp(-x), em = expm1(-x);
-  return K * ((x / em) * (e / em)) / T;
-}
+// dB/dT at (avg_freq, T), per Hz, under the name the adjoint family's kernels call it by: ir_green.inc's planck_dbdt
+__device__ __forceinline__ double adjoint_dbdt(double avg_freq, double T) { return planck_dbdt(avg_freq, T); }
 
 // thread (bin, functional, k), the bin fastest: the g-points in g order, the amplitude (1 when base_T is null: the
 // test hook's unit amplitudes), out_up / out_dn (n_ir, nrow, nz+1) with j = nz - k

@@ -55,11 +55,25 @@ __device__ __forceinline__ GreenLayer green_layer_of(const GreenParams &p, doubl
   L.thin = tau <= p.ir_tau_min;
   return L;
 }
-__device__ __forceinline__ void green_q(const GreenParams &p, int q, size_t &qtau, size_t &qg, int &bi, int &g) {
-  bi = q / p.ng; g = q - bi * p.ng;
-  const int l = p.ir_start + p.ir_lo + bi;
-  qtau = ((size_t)l * p.ng + g) * p.nz;
-  qg = (size_t)l * p.nz;
+// What every kernel of one q = (bin, g-point) starts from: where its layers' tau / w0 (qtau) and g (qg) stand, the bin's
+// surface (emis and Rsfc are 0 without a hard surface) and the g-point's weight
+struct GreenQ { size_t qtau, qg; int bi, g; bool hard; double emis, Rsfc, w; };
+__device__ __forceinline__ GreenQ green_q(const GreenParams &p, int q) {
+  GreenQ Q;
+  Q.bi = q / p.ng; Q.g = q - Q.bi * p.ng;
+  const int l = p.ir_start + p.ir_lo + Q.bi;
+  Q.qtau = ((size_t)l * p.ng + Q.g) * p.nz;
+  Q.qg = (size_t)l * p.nz;
+  Q.hard = p.has_hard_surface != 0;
+  Q.emis = Q.hard ? p.emissivity[p.ir_lo + Q.bi] : 0.0; Q.Rsfc = Q.hard ? 1.0 - Q.emis : 0.0;
+  Q.w = p.wbin[Q.g];
+  return Q;
+}
+// the three inputs of layer n on clamped indices: a virtual layer (n < 0, n >= nz) loads its neighbour's and uses none
+struct GreenLayerIn { double tau, w0, g; };
+__device__ __forceinline__ GreenLayerIn green_layer_in(const GreenParams &p, const GreenQ &Q, int n) {
+  const int nc = min(max(n, 0), p.nz - 1);
+  return {p.tau[Q.qtau + nc], p.w0[Q.qtau + nc], p.g[Q.qg + nc]};
 }
 // second equation of the interface (u above, v below): row 2n of layer n = v
 __device__ __forceinline__ void green_row_even(const E4 &u, const E4 &v, double &A, double &B, double &D) {
@@ -78,6 +92,54 @@ __device__ __forceinline__ void green_norm(GreenM &m) {
     m.m11 = __builtin_ldexp(m.m11, e); m.m12 = __builtin_ldexp(m.m12, e);
     m.m21 = __builtin_ldexp(m.m21, e); m.m22 = __builtin_ldexp(m.m22, e);
   }
+}
+// Inclusive prefix scan of the rows' matrices over the wave's lanes, normalised at every step: lane's P becomes
+// P(lane) ... P(1) P(0) (a later row multiplies from the left).  A lane past the last row brings the identity.
+__device__ __forceinline__ GreenM green_prefix_scan(GreenM P, const int lane) {
+  green_norm(P);
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    GreenM T;
+    T.m11 = __shfl_up(P.m11, d); T.m12 = __shfl_up(P.m12, d); T.m21 = __shfl_up(P.m21, d); T.m22 = __shfl_up(P.m22, d);
+    if (lane >= d) {
+      const GreenM o = P;
+      P.m11 = o.m11 * T.m11 + o.m12 * T.m21; P.m12 = o.m11 * T.m12 + o.m12 * T.m22;
+      P.m21 = o.m21 * T.m11 + o.m22 * T.m21; P.m22 = o.m21 * T.m12 + o.m22 * T.m22;
+      green_norm(P);
+    }
+  }
+  return P;
+}
+// 1 / pivot of this lane's row, B - A c'(row before): c' of every row by the scanned map applied to c_in (c' of the last
+// row before the segment), the row before this lane's taken from its neighbour, then the recurrence's own step
+__device__ __forceinline__ double green_rcp_pivot(const GreenM &P, const double c_in, const double A, const double B, const int lane) {
+  const double c_scan = (P.m11 * c_in + P.m12) / (P.m21 * c_in + P.m22);
+  double c_prev = __shfl_up(c_scan, 1);
+  if (lane == 0) c_prev = c_in;
+  return rcp_nr(B - A * c_prev);
+}
+
+// The affine map x -> al + be x, and its inclusive scan over the wave's lanes: upwards in the lane index (DOWN = false)
+// lane's map becomes map(lane) o ... o map(0), the whole prefix as a map of what enters lane 0; downwards (DOWN = true)
+// map(lane) o ... o map(63), the suffix as a map of what enters lane 63.
+struct Affine { double al, be; };
+template <bool DOWN>
+__device__ __forceinline__ Affine affine_scan(Affine m, const int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const double ta = DOWN ? __shfl_down(m.al, d) : __shfl_up(m.al, d), tb = DOWN ? __shfl_down(m.be, d) : __shfl_up(m.be, d);
+    if (DOWN ? lane + d < 64 : lane >= d) { m.al = m.al + m.be * ta; m.be = m.be * tb; }
+  }
+  return m;
+}
+
+// dB/dT at (avg_freq, T), per Hz.  With x = h nu / k T and e = exp(-x), dB/dT = K (x / T) e^x / (e^x - 1)^2 =
+// K (x / expm1(-x)) (e / expm1(-x)) / T: large x takes e to 0 (no overflow, no NaN), small x keeps its digits through expm1
+__device__ __forceinline__ double planck_dbdt(double avg_freq, double T) {
+  const double x = ((PLANK * avg_freq) / K_BOLTZ_SI) / T;
+  const double K = 1.0e3 * ((2.0 * PLANK * (avg_freq * avg_freq * avg_freq)) / (C_LIGHT * C_LIGHT));
+  const double e = exp(-x), em = expm1(-x);
+  return K * ((x / em) * (e / em)) / T;
 }
 
 // mantissa in +-[0.5, 1) times 2^e (e integral, kept as a double beside the other level / row quantities)
@@ -110,10 +172,9 @@ __device__ __forceinline__ double green_exp2i(double x) { return __builtin_ldexp
 __global__ __launch_bounds__(64) void k_green_factor(GreenParams p) {
   const int q = blockIdx.x, lane = threadIdx.x;
   const int nz = p.nz, nl = nz + 1, N = 2 * nz, nseg = (N + 63) / 64;
-  size_t qtau, qg; int bi, g;
-  green_q(p, q, qtau, qg, bi, g);
-  const double Rsfc = p.has_hard_surface ? 1.0 - p.emissivity[p.ir_lo + bi] : 0.0;
-  const double w = p.wbin[g];
+  const GreenQ Q = green_q(p, q);
+  const size_t qtau = Q.qtau, qg = Q.qg;
+  const double Rsfc = Q.Rsfc, w = Q.w;
   double *rw = p.RW + (size_t)q * GREEN_RW * N;
   double *is = p.IS + (size_t)q * GREEN_IS * nl;
   // ---- downwards: c', 1/den, phi (kept in z's place until the way back), the running products
@@ -125,8 +186,8 @@ __global__ __launch_bounds__(64) void k_green_factor(GreenParams p) {
     const int r = seg * 64 + lane, la = (r >> 1) - 1 + (r & 1);
 #pragma unroll
     for (int h = 0; h < 2; h++) {
-      const int nc = min(max(la + h, 0), nz - 1);
-      nx_tau[h] = p.tau[qtau + nc]; nx_w0[h] = p.w0[qtau + nc]; nx_g[h] = p.g[qg + nc];
+      const GreenLayerIn in = green_layer_in(p, Q, la + h);
+      nx_tau[h] = in.tau; nx_w0[h] = in.w0; nx_g[h] = in.g;
     }
   };
   load_layers(0);
@@ -147,22 +208,7 @@ __global__ __launch_bounds__(64) void k_green_factor(GreenParams p) {
     }
     GreenM P = {0.0, D, -A, B};
     if (!on) { P.m11 = 1.0; P.m12 = 0.0; P.m21 = 0.0; P.m22 = 1.0; }
-    green_norm(P);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      GreenM T;
-      T.m11 = __shfl_up(P.m11, d); T.m12 = __shfl_up(P.m12, d); T.m21 = __shfl_up(P.m21, d); T.m22 = __shfl_up(P.m22, d);
-      if (lane >= d) {
-        const GreenM o = P;     // (this lane's row comes after: it multiplies from the left)
-        P.m11 = o.m11 * T.m11 + o.m12 * T.m21; P.m12 = o.m11 * T.m12 + o.m12 * T.m22;
-        P.m21 = o.m21 * T.m11 + o.m22 * T.m21; P.m22 = o.m21 * T.m12 + o.m22 * T.m22;
-        green_norm(P);
-      }
-    }
-    const double c_scan = (P.m11 * c_in + P.m12) / (P.m21 * c_in + P.m22);    // c' of this row by the scan
-    double c_prev = __shfl_up(c_scan, 1);
-    if (lane == 0) c_prev = c_in;
-    const double rd = rcp_nr(B - A * c_prev);                                 // ... and by the recurrence's own step
+    const double rd = green_rcp_pivot(green_prefix_scan(P, lane), c_in, A, B, lane);
     const double cp = D * rd, ph = -A * rd;
     if (on) { rw[r] = cp; rw[(size_t)N + r] = rd; rw[(size_t)2 * N + r] = ph; }
     c_in = __shfl(cp, 63);
@@ -213,13 +259,8 @@ __global__ __launch_bounds__(64) void k_green_factor(GreenParams p) {
     double ph_next = __shfl_down(ph, 1);
     if (lane == 63) ph_next = ph_in;
     const double kap = (on && r < N - 1) ? cp * ph_next : 0.0;
-    double za = 1.0, zb = -kap;               // z_r = za + zb z(first row after this lane's suffix)
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const double ta = __shfl_down(za, d), tb = __shfl_down(zb, d);
-      if (lane + d < 64) { za = za + zb * ta; zb = zb * tb; }
-    }
-    const double z = za + zb * z_in;
+    const Affine zm = affine_scan<true>({1.0, -kap}, lane);      // z_r = al + be z(first row after this lane's suffix)
+    const double z = zm.al + zm.be * z_in;
     if (on) rw[(size_t)2 * N + r] = z;
     z_in = __shfl(z, 0); ph_in = __shfl(ph, 0);
     // level n+1: its above form sits on row 2n+1 (needs c' of row 2n), its below form on row 2n (needs phi z of row 2n+1)
@@ -253,10 +294,9 @@ __global__ __launch_bounds__(256) void k_green_unit(GreenParams p) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x, q = blockIdx.y;
   const int nz = p.nz, nl = nz + 1, N = 2 * nz;
   if (k > nz) return;
-  size_t qtau, qg; int bi, g;
-  green_q(p, q, qtau, qg, bi, g);
-  const bool hard = p.has_hard_surface != 0;
-  const double emis = hard ? p.emissivity[p.ir_lo + bi] : 0.0, Rsfc = hard ? 1.0 - emis : 0.0;
+  const GreenQ Q = green_q(p, q);
+  const bool hard = Q.hard;
+  const double emis = Q.emis, Rsfc = Q.Rsfc;
   GreenLayer Ly[4];
   double cp0[4], cpb[4], cm0[4], cmb[4];
   // every load of the thread up front, on clamped indices (what lies outside is not used)
@@ -264,8 +304,8 @@ __global__ __launch_bounds__(256) void k_green_unit(GreenParams p) {
   double in_tau[4], in_w0[4], in_g[4], rd6[6], cp6[6];
 #pragma unroll
   for (int j = 0; j < 4; j++) {
-    const int nc = min(max(k - 2 + j, 0), nz - 1);
-    in_tau[j] = p.tau[qtau + nc]; in_w0[j] = p.w0[qtau + nc]; in_g[j] = p.g[qg + nc];
+    const GreenLayerIn in = green_layer_in(p, Q, k - 2 + j);
+    in_tau[j] = in.tau; in_w0[j] = in.w0; in_g[j] = in.g;
   }
 #pragma unroll
   for (int t = 0; t < 6; t++) {
@@ -321,7 +361,7 @@ __global__ __launch_bounds__(256) void k_green_unit(GreenParams p) {
       Y[t] = ynext;
     }
   }
-  const double w = p.wbin[g];
+  const double w = Q.w;
   double *ds = p.DS + (size_t)q * GREEN_DS * nl + k;
   {
     // above: Y(ra) x prod_{m < ra} (-c'_m) against the level's 1 / prod_{m < 2n+1}; below: d'(rb) / prod_{m <= rb} phi_m
@@ -413,9 +453,7 @@ __global__ __launch_bounds__(256) void k_green_db(GreenParams p) {
 }
 
 // 6'. the exact Jacobian's amplitudes (radtran_ir_jacobian): the Planck DERIVATIVES at the deviations' base temperatures,
-//     times the bin's width -- the limit of k_green_db's differences over the step.  With x = h nu / k T and e = exp(-x),
-//     dB/dT = K (x / T) e^x / (e^x - 1)^2 = K (x / expm1(-x)) (e / expm1(-x)) / T: large x takes e to 0 (no overflow, no
-//     NaN), small x keeps its digits through expm1.  DB[bin][dev]
+//     times the bin's width -- the limit of k_green_db's differences over the step (planck_dbdt).  DB[bin][dev]
 __global__ __launch_bounds__(256) void k_green_dbdt(GreenParams p) {
   const int dev = blockIdx.x * blockDim.x + threadIdx.x, bi = blockIdx.y;
   if (dev >= p.ndev_pad) return;
@@ -423,11 +461,7 @@ __global__ __launch_bounds__(256) void k_green_dbdt(GreenParams p) {
   if (dev < p.ndev) {
     const int l = p.ir_start + p.ir_lo + bi, ll = p.ir_lo + bi;
     const double avg_freq = 0.5 * (p.freq[l] + p.freq[l + 1]);
-    const double T = p.base_T[p.dev_k[dev]];
-    const double x = ((PLANK * avg_freq) / K_BOLTZ_SI) / T;
-    const double K = 1.0e3 * ((2.0 * PLANK * (avg_freq * avg_freq * avg_freq)) / (C_LIGHT * C_LIGHT));
-    const double e = exp(-x), em = expm1(-x);
-    v = K * ((x / em) * (e / em)) / T;
+    v = planck_dbdt(avg_freq, p.base_T[p.dev_k[dev]]);
     v *= p.ir_freq[ll] - p.ir_freq[ll + 1];
   }
   p.DB[(size_t)bi * p.ndev_pad + dev] = v;

@@ -1,5 +1,5 @@
-// ir_opr_sens.inc -- included by kernels.hip (inside namespace clima, after ir_adjoint.inc, whose transposed solve it
-// repeats and whose row helpers in ir_green.inc it uses) in its first compilation only.
+// ir_opr_sens.inc -- included by kernels.hip (inside namespace clima, after ir_adjoint.inc, whose elimination
+// (adjoint_eliminate) it calls, with the row helpers and scans of ir_green.inc) in its first compilation only.
 //
 // Gradient of a scalar loss on the IR level fluxes with respect to the STORED optical properties tau, w0, g
 // (radtran_ir_spectra_opr_vjp), at fixed temperatures.  Per (bin, g-point) two_stream_ir
@@ -14,12 +14,12 @@
 // lambda, Y and the direct terms, then back through Gamma, exp(-lambda tau), lambda, gam1, gam2 and 1/(gam1+gam2).
 //
 // k_opr_adjoint: one wave per q = (bin, g-point), lane = row (64 at a time), then lane = layer.
-//   1. the transposed system's rows and their elimination: k_adjoint_rows' step 1 (c', 1 / pivot, D(r-1) -> work rows).
+//   1. the transposed system's rows and their elimination: adjoint_eliminate (c', 1 / pivot, D(r-1) -> work rows).
 //   2. the combined right-hand side  sum over a, direction of cotangent(bin, a) x that functional's two non-zeros, and
 //      lambda by k_adjoint_rows' two affine scans.
 //   3. the forward solution Y of M Y = E(bplanck) from the factors already held: M^T = L' U' (L' = pivots and D(r-1),
 //      U' = unit upper with c'), so M = U'^T L'^T:  z_r = E_r - c'_{r-1} z_{r-1} downwards, Y_r = (z_r - D(r) Y_{r+1}) /
-//      pivot_r upwards -- two more affine scans, no second elimination.
+//      pivot_r upwards -- two more affine scans (affine_scan), no second elimination.
 //   4. lane = layer n: the reverse sweep above; wbin(g) x the result -> grad_tau / grad_w0 (n, g, bin) and the g-point's
 //      part of grad_g.
 // k_opr_sum_g adds the g-points of grad_g in g order (bitwise repeatable, no atomics).
@@ -76,11 +76,11 @@ __global__ __launch_bounds__(64) void k_opr_adjoint(IrOprParams p) {
   const GreenParams &gp = p.g;
   const int q = blockIdx.x, lane = threadIdx.x;
   const int nz = gp.nz, N = 2 * nz, nseg = (N + 63) / 64, nsel = p.nsel;
-  size_t qtau, qg; int bi, g;
-  green_q(gp, q, qtau, qg, bi, g);
-  const bool hard = gp.has_hard_surface != 0;
-  const double emis = hard ? gp.emissivity[gp.ir_lo + bi] : 0.0, Rsfc = hard ? 1.0 - emis : 0.0;
-  const double w = gp.wbin[g];
+  const GreenQ Q = green_q(gp, q);
+  const size_t qtau = Q.qtau, qg = Q.qg;
+  const int bi = Q.bi;
+  const bool hard = Q.hard;
+  const double emis = Q.emis, w = Q.w;
   double *wk = p.work + (size_t)q * OPR_WORK_ROWS * N;
   double *w_c = wk, *w_rd = wk + N, *w_a = wk + (size_t)2 * N, *w_y = wk + (size_t)3 * N, *w_lam = wk + (size_t)4 * N,
          *w_Y = wk + (size_t)5 * N;
@@ -128,15 +128,15 @@ __global__ __launch_bounds__(64) void k_opr_adjoint(IrOprParams p) {
     return p.bplanck ? p.bplanck[kc] : planck_fcn(avg_freq, kc < nz ? p.T[nz - 1 - kc] : p.Ts[0]);   // (radiate.f90:65-69: level k is layer nz-1-k)
   };
   auto layer = [&](const int n) {     // layer n, or the virtual layer above / below the column
-    const int nc = min(max(n, 0), nz - 1);
-    return opr_layer_of(gp, gp.tau[qtau + nc], gp.w0[qtau + nc], gp.g[qg + nc], n, Rsfc);
+    const GreenLayerIn in = green_layer_in(gp, Q, n);
+    return opr_layer_of(gp, in.tau, in.w0, in.g, n, Q.Rsfc);
   };
   // the surface term (:236-247), the upper source value of the virtual layer under the column; Lb = layer nz-1
   auto surface = [&](const OprLayer &Lb, const double Bs) {
     return hard ? emis * PI * Bs : PI * (Bs + 0.5 * Lb.b1);
   };
 
-  // ---- 1. the transposed system's rows and their elimination: k_adjoint_rows' step 1, on this file's e's
+  // ---- 1. the transposed system's rows and their elimination, on this file's e's
   adjoint_eliminate(nz, lane, [&](const int n) { return layer(n).e; }, w_c, w_rd, w_a);
   // (c' and D(r-1) are read by the neighbouring lanes from here on)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -163,13 +163,8 @@ __global__ __launch_bounds__(64) void k_opr_adjoint(IrOprParams p) {
           rhs = rhs + ((r & 1) ? -(c0 * e.e4) : c0 * e.e3);
         }
       }
-      double al = rhs * rd, be = on ? -a * rd : 1.0;       // y_r = al + be y(last row before this lane's prefix)
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const double ta = __shfl_up(al, d), tb = __shfl_up(be, d);
-        if (lane >= d) { al = al + be * ta; be = be * tb; }
-      }
-      const double y = al + be * y_in;
+      const Affine m = affine_scan<false>({rhs * rd, on ? -a * rd : 1.0}, lane);       // y_r = al + be y(last row before this lane's prefix)
+      const double y = m.al + m.be * y_in;
       if (on) w_y[r] = y;
       y_in = __shfl(y, 63);
     }
@@ -177,13 +172,8 @@ __global__ __launch_bounds__(64) void k_opr_adjoint(IrOprParams p) {
     for (int seg = nseg - 1; seg >= 0; seg--) {
       const int r = seg * 64 + lane;
       const bool on = r < N;
-      double al = on ? w_y[r] : 0.0, be = on ? -w_c[r] : 1.0;   // lambda_r = al + be lambda(first row after this lane's suffix)
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const double ta = __shfl_down(al, d), tb = __shfl_down(be, d);
-        if (lane + d < 64) { al = al + be * ta; be = be * tb; }
-      }
-      const double lm = al + be * lam_in;
+      const Affine m = affine_scan<true>({on ? w_y[r] : 0.0, on ? -w_c[r] : 1.0}, lane);   // lambda_r = al + be lambda(first row after this lane's suffix)
+      const double lm = m.al + m.be * lam_in;
       if (on) w_lam[r] = lm;
       lam_in = __shfl(lm, 0);
     }
@@ -206,13 +196,9 @@ __global__ __launch_bounds__(64) void k_opr_adjoint(IrOprParams p) {
         if (la + 1 == nz) v.cp0 = surface(u, Bm);
         E = (r & 1) ? v.e.e2 * (v.cp0 - u.cpb) - v.e.e4 * (v.cm0 - u.cmb) : u.e.e3 * (v.cp0 - u.cpb) + u.e.e1 * (u.cmb - v.cm0);
       }
-      double al = E, be = (on && r > 0) ? -w_c[r - 1] : (on ? 0.0 : 1.0);    // z_r = al + be z(last row before this lane's prefix)
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const double ta = __shfl_up(al, d), tb = __shfl_up(be, d);
-        if (lane >= d) { al = al + be * ta; be = be * tb; }
-      }
-      const double z = al + be * z_in;
+      // z_r = al + be z(last row before this lane's prefix)
+      const Affine m = affine_scan<false>({E, (on && r > 0) ? -w_c[r - 1] : (on ? 0.0 : 1.0)}, lane);
+      const double z = m.al + m.be * z_in;
       if (on) w_y[r] = z;
       z_in = __shfl(z, 63);
     }
@@ -221,13 +207,9 @@ __global__ __launch_bounds__(64) void k_opr_adjoint(IrOprParams p) {
       const int r = seg * 64 + lane;
       const bool on = r < N;
       const double rd = on ? w_rd[r] : 0.0, an = (on && r + 1 < N) ? w_a[r + 1] : 0.0;
-      double al = on ? w_y[r] * rd : 0.0, be = on ? -an * rd : 1.0;           // Y_r = al + be Y(first row after this lane's suffix)
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const double ta = __shfl_down(al, d), tb = __shfl_down(be, d);
-        if (lane + d < 64) { al = al + be * ta; be = be * tb; }
-      }
-      const double Yr = al + be * Y_in;
+      // Y_r = al + be Y(first row after this lane's suffix)
+      const Affine m = affine_scan<true>({on ? w_y[r] * rd : 0.0, on ? -an * rd : 1.0}, lane);
+      const double Yr = m.al + m.be * Y_in;
       if (on) w_Y[r] = Yr;
       Y_in = __shfl(Yr, 0);
     }

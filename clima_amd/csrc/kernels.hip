@@ -34,7 +34,16 @@
 //   k_pack_bounds      the per-column bounds blocks of a bounds batch out of device memory (albedo, emissivity, zenith
 //                      angles, photon scale factor: what twostream_p_body's BND instances and k_twostream read).
 //
-// All arithmetic is IEEE binary64.  No MFMA: there is no dense contraction on this path.
+//   k_adjoint_rows, k_adjoint_sum   (ir_adjoint.inc) rows of the per-bin IR temperature Jacobian by one transposed solve
+//                      per (bin, g-point, functional), then the g-points' sum times the Planck derivative.
+//   k_opr_adjoint, k_opr_sum_g   (ir_opr_sens.inc) gradient of a loss on the IR level fluxes in the stored tau, w0, g: the
+//                      same transposed solve, the forward solution from its factors, a reverse sweep of one layer.
+//   k_rows_apply, k_rows_integrate   (ir_rows_apply.inc) IR spectra of many temperature profiles as the adjoint's rows
+//                      of weights times Planck values, and their sums over the bins.
+//   k_vjp_rows         (ir_rows_vjp.inc) the temperature gradient of that batch: one dB/dT per (bin, level, column).
+//
+// All arithmetic is IEEE binary64.  The radiate() path has no dense contraction and issues no MFMA; the response
+// kernels' accumulation (ir_green.inc) is one and issues v_mfma_f64_16x16x4_f64.
 #include "radtran_dev.h"
 #include <algorithm>
 #include <cstring>
@@ -1485,6 +1494,16 @@ __device__ __forceinline__ E4 make_e(double G, double x) {
   return e;
 }
 
+// ---- What k_twostream_ir_batch and k_twostream_sol_batch (solar_batch.inc) share as functions.  (The elimination of a
+// chunk's rows, its upward sweeps, its map and the suffix products of the maps are each kernel's own text, equal up to the
+// last row: as functions they did not keep the kernels' bits, profiles/device_steps_refactor.txt.)
+// one staged row's sum over the NW g-point waves of a group, in g order, onto what the groups before it left
+template <int NW>
+__device__ __forceinline__ double chunk_gsum(const double *sF, const int row, const int nl, const int n, double sum) {
+#pragma unroll
+  for (int w = 0; w < NW; w++) sum = sum + sF[(size_t)(row * NW + w) * (nl + 1) + n];
+  return sum;
+}
 struct TsLds {
   double *G, *X, *E0, *E1, *U, *V;
   double *Bp;    // [nz+1] Planck
@@ -2906,6 +2925,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_twostream_ir_batch(TwoStreamPara
 #pragma unroll
         for (int t = 0; t < L; t++) {
           const double Bt = Bf[t], Bb = Bf[t + 1];
+          // (times 1 / tau where k_green_unit and opr_source divide: formed once per (bin, g-point), 0 marking a thin slot)
           const double b1n = (Bb - Bt) * itau[t];               // :216-227
           const double b0n = (itau[t] == 0.0) ? 0.5 * (Bt + Bb) : Bt;
           const double cp0 = PI * (b0n + b1n * rq[t]);          // :229-232, norm = 2 pi * 1/2
@@ -2984,13 +3004,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_twostream_ir_batch(TwoStreamPara
         const size_t o = (size_t)(c0 + cj) * p.b_out + (size_t)ll * nl + (nz - n);
         double fu = 0.0, fd = 0.0;
         if (g0 > 0) { fu = p.ir_fup_a[o]; fd = p.ir_fdn_a[o]; }
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-          fu = fu + sF[(size_t)(0 * NW + w) * (nl + 1) + n];
-          fd = fd + sF[(size_t)(1 * NW + w) * (nl + 1) + n];
-        }
-        p.ir_fup_a[o] = fu;
-        p.ir_fdn_a[o] = fd;
+        p.ir_fup_a[o] = chunk_gsum<NW>(sF, 0, nl, n, fu);
+        p.ir_fdn_a[o] = chunk_gsum<NW>(sF, 1, nl, n, fd);
       }
     }
   }
@@ -2998,13 +3013,22 @@ __global__ __launch_bounds__(64 * NW, 1) void k_twostream_ir_batch(TwoStreamPara
   }
 }
 
-// false when the configuration is outside what the kernel covers: more than 8 layer slots per lane (nz > 512)
-// or an LDS image beyond 160 KiB.  force_nw (test hook): 4 selects the four-wave form for 1-4 slots too.
 #ifndef CLIMA_BOUNDS_TU
+// The launch rules of both batch kernels.  Waves (g-points at a time) per block: 8 up to 4 layer slots and 8 g-points, 4
+// (one per SIMD, the whole register file) beyond; force_nw (test hook): 4 selects the four-wave form for 1-4 slots too.
+static int batch_waves(int slots, int ng, int force_nw) { return (slots > 4 || ng > 8 || force_nw == 4) ? 4 : 8; }
+// Columns or cases of a block: enough blocks to fill the chip a few times over, each with a worthwhile run (tile) of them
+static int batch_items_per_block(int n, int tile) {
+  int per = (n + 3) / 4;
+  if (per < tile) per = std::min(n, tile);
+  return per;
+}
+// false when the configuration is outside what the kernel covers: more than 8 layer slots per lane (nz > 512)
+// or an LDS image beyond 160 KiB.  force_nw: batch_waves'.
 bool launch_twostream_ir_batch(TwoStreamParams &p, int ncol, hipStream_t s, int force_nw) {
   const int lmax = std::max((p.nz + 63) / 64, p.force_slots);
   if (lmax > 8 || p.n_ir <= 0 || ncol <= 0 || p.ng < 1) return false;
-  const int nw = (lmax > 4 || p.ng > 8 || force_nw == 4) ? 4 : 8;
+  const int nw = batch_waves(lmax, p.ng, force_nw);
   const size_t lds = sizeof(double) * ((size_t)IRB_TILE * ((size_t)p.nz + 1) + (size_t)4 * nw * ((size_t)p.nz + 2) + (nw == 8 ? 2 * WSCAN_STEPS * 64 * nw : 0));
   if (lds > 160 * 1024) return false;
   using Kern = void (*)(TwoStreamParams, int, int);
@@ -3013,9 +3037,7 @@ bool launch_twostream_ir_batch(TwoStreamParams &p, int ncol, hipStream_t s, int 
                                 k_twostream_ir_batch<5, 4>, k_twostream_ir_batch<6, 4>, k_twostream_ir_batch<7, 4>, k_twostream_ir_batch<8, 4>};
   const Kern k = nw == 8 ? kern8[lmax - 1] : kern4[lmax - 1];
   if (!ensure_max_lds((const void *)k)) return false;
-  // enough blocks to fill the chip a few times over, each with a worthwhile run of columns
-  int cpb = (ncol + 3) / 4;
-  if (cpb < IRB_TILE) cpb = std::min(ncol, IRB_TILE);
+  const int cpb = batch_items_per_block(ncol, IRB_TILE);
   const dim3 grid(p.n_ir, 1, (ncol + cpb - 1) / cpb), blk(64 * nw);
   hipLaunchKernelGGL(k, grid, blk, lds, s, p, ncol, cpb);  // layer slots per lane = ceil(nz/64)
   return true;

@@ -4,7 +4,9 @@
 //
 // The solar counterpart of k_twostream_ir_batch, with the same decomposition: lane q owns layers [q nz/64, (q+1) nz/64),
 // a short chunk is padded from the top with zero-thickness slots, L = ceil(nz/64) slots per lane, the g-points of a bin
-// are the waves of a block and are summed in g order.
+// are the waves of a block and are summed in g order.  The g-points' sum (chunk_gsum) and the launch rules (batch_waves,
+// batch_items_per_block) are kernels.hip's, called by both; the chunk steps below are this kernel's own text, equal to
+// k_twostream_ir_batch's up to the last row (there the surface row, here the flux condition in every lane).
 //
 // In two_stream_solar (src/radtran/clima_radtran_twostream.f90:10-154) the delta-Eddington scaling, gam1, gam2, lambda,
 // Gamma, exp(-lambda tau), the e's and the whole matrix above the surface row do not depend on u0 (twostream_p_body
@@ -27,8 +29,7 @@
 // photons_sol * photon_scale_factor * diurnal_fac and amean's unit factors (clima_radtran_radiate.f90:164-179), applied
 // to the sum over the g-points as the single call applies them.
 
-// waves per block and LDS bytes of the instance that launch_twostream_sol_batch picks
-static int solb_waves(int slots, int ng, int force_nw) { return (slots > 4 || ng > 8 || force_nw == 4) ? 4 : 8; }
+// LDS bytes of the instance of nw waves
 static size_t solb_lds(int nz, int nw) { return sizeof(double) * (size_t)2 * 3 * nw * ((size_t)nz + 2); }
 
 template <int L, int NW>
@@ -276,12 +277,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_twostream_sol_batch(SolBatchPara
       const size_t o = (size_t)c * p.out_stride + (size_t)ll * nl + (nz - n);
       double fu = 0.0, fd = 0.0, am = 0.0;
       if (g0 > 0) { fu = p.fup[o]; fd = p.fdn[o]; am = p.amean[o]; }
-#pragma unroll
-      for (int w = 0; w < NW; w++) {
-        fu = fu + sF[(size_t)(0 * NW + w) * (nl + 1) + n];
-        fd = fd + sF[(size_t)(1 * NW + w) * (nl + 1) + n];
-        am = am + sF[(size_t)(2 * NW + w) * (nl + 1) + n];
-      }
+      fu = chunk_gsum<NW>(sF, 0, nl, n, fu); fd = chunk_gsum<NW>(sF, 1, nl, n, fd); am = chunk_gsum<NW>(sF, 2, nl, n, am);
       if (last_group) {
         fu = fu * scale * p.diurnal_fac;
         fd = fd * scale * p.diurnal_fac;
@@ -296,21 +292,16 @@ __global__ __launch_bounds__(64 * NW, 1) void k_twostream_sol_batch(SolBatchPara
   }
 }
 
-// The launcher's rule for the cases of a block: enough blocks to fill the chip a few times over, each with a worthwhile
-// run of cases (launch_twostream_ir_batch's)
+// The launcher's rule for the cases of a block (tests size their batches by it)
 constexpr int SOLB_TILE = 8;
-int solar_batch_cases_per_block(int ncase) {
-  int cpb = (ncase + 3) / 4;
-  if (cpb < SOLB_TILE) cpb = std::min(ncase, SOLB_TILE);
-  return cpb;
-}
+int solar_batch_cases_per_block(int ncase) { return batch_items_per_block(ncase, SOLB_TILE); }
 
 // false when the configuration is outside what the kernel covers: more than 8 layer slots per lane (nz > 512), more
-// than MAX_ZEN angles or an LDS image beyond 160 KiB.  force_nw (test hook): 4 selects the four-wave form for 1-4 slots too.
+// than MAX_ZEN angles or an LDS image beyond 160 KiB.  force_nw: batch_waves'.
 bool launch_twostream_sol_batch(SolBatchParams &p, hipStream_t s, int force_nw) {
   const int lmax = (p.nz + 63) / 64;
   if (lmax > 8 || p.n_sol <= 0 || p.ncase <= 0 || p.ng < 1 || p.nzen < 1 || p.nzen > MAX_ZEN) return false;
-  const int nw = solb_waves(lmax, p.ng, force_nw);
+  const int nw = batch_waves(lmax, p.ng, force_nw);
   const size_t lds = solb_lds(p.nz, nw);
   constexpr int LDS_MAX = 160 * 1024 - (int)sizeof(double) * EXP2_N;   // (the exp table is static LDS on top)
   if (lds > (size_t)LDS_MAX) return false;
