@@ -7,7 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "libclima_radtran_hip.so")
 SOURCES = ["kernels.hip", "kernels_bounds.hip", "radtran_api.hip", "radtran_loader.hip"]
-DEPS = SOURCES + ["radtran_dev.h", "sort_network_64.inc", "rorr_xys_asm.inc", "ir_green.inc", "solar_batch.inc", "ir_adjoint.inc", "ir_opr_sens.inc", "ir_rows_apply.inc", "ir_rows_vjp.inc", os.path.join("..", "..", "include", "clima_radtran_hip.h")]
+DEPS = SOURCES + ["radtran_dev.h", "sort_network_64.inc", "rorr_xys_asm.inc", "ir_green.inc", "solar_batch.inc", "ir_adjoint.inc", "ir_opr_sens.inc", "sol_opr_sens.inc", "ir_rows_apply.inc", "ir_rows_vjp.inc", os.path.join("..", "..", "include", "clima_radtran_hip.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # The kernels take their parameter blocks by value; hipcc reads them straight from the kernel-argument
 # segment (scalar loads) only while a block has at most `instcombine-max-copied-from-constant-users` uses

@@ -38,6 +38,8 @@
 //                      per (bin, g-point, functional), then the g-points' sum times the Planck derivative.
 //   k_opr_adjoint, k_opr_sum_g   (ir_opr_sens.inc) gradient of a loss on the IR level fluxes in the stored tau, w0, g: the
 //                      same transposed solve, the forward solution from its factors, a reverse sweep of one layer.
+//   k_sol_opr_adjoint, k_sol_opr_sum_g   (sol_opr_sens.inc) gradient of a loss on the solar fup, fdn, amean in the stored tau,
+//                      w0, g and the surface albedo: one transposed and one forward solve for all zenith angles and levels.
 //   k_rows_apply, k_rows_integrate   (ir_rows_apply.inc) IR spectra of many temperature profiles as the adjoint's rows
 //                      of weights times Planck values, and their sums over the bins.
 //   k_vjp_rows         (ir_rows_vjp.inc) the temperature gradient of that batch: one dB/dT per (bin, level, column).
@@ -3775,6 +3777,7 @@ void launch_batch_spectra(const BatchSpectraParams &p, hipStream_t s) {
 #include "solar_batch.inc"
 #include "ir_adjoint.inc"
 #include "ir_opr_sens.inc"
+#include "sol_opr_sens.inc"
 #ifndef CLIMA_WITHOUT_IR_ROWS_APPLY   // (tests/test_ir_spectra_batch_abi.py: the other kernels' assembly with and without it)
 #include "ir_rows_apply.inc"
 #endif

@@ -3506,6 +3506,144 @@ void radtran_ir_spectra_opr_vjp(void *ptr, const double *T_surface, const int *d
   CATCH(err)
 }
 
+// Gradient of a loss on the solar spectra (fup, fdn, amean and the sums of fup, fdn over the bins) in the stored tau, w0, g
+// and in the surface albedo, under the handle's zenith angles, albedo and scale factors: one adjoint and one forward
+// two-stream solve per (bin, g-point) on the stored opacities (sol_opr_sens.inc).  include/clima_radtran_hip.h has the
+// contract.  What both forms refuse of their arguments; `lv`: the levels TOA-first.  false: the call can run
+static bool sol_opr_refused(Radtran *r, const char *who, int nsel, const int *spec_level, const double *const gs[3],
+                            const double *const gn[2], double *const out[4], std::vector<int> &lv, char *err) {
+  const std::string pre = std::string(who) + ": ";
+  if (nsel < 1) { set_err(err, pre + "nsel must be at least 1 (nsel = " + std::to_string(nsel) + ")"); return true; }
+  if (!spec_level) { set_err(err, pre + "\"spec_level\" is a required argument"); return true; }
+  if (ir_levels_refused(pre, "spec_level", r->nz, nsel, spec_level, lv, err)) return true;
+  if (!gs[0] && !gs[1] && !gs[2] && !gn[0] && !gn[1]) {
+    set_err(err, pre + "none of g_sol_fup, g_sol_fdn, g_sol_amean, g_fup_n, g_fdn_n was given");
+    return true;
+  }
+  if (!out[0] && !out[1] && !out[2] && !out[3]) { set_err(err, pre + "none of grad_tau, grad_w0, grad_g, grad_albedo was given"); return true; }
+  return false;
+}
+// ... and of the handle, once the arguments stand: a bin shard or a communicator, no solar bins (a property of the handle,
+// so before what it holds), no opacities, the work buffer's bound
+static bool sol_opr_handle_refused(Radtran *r, const char *who, char *err) {
+  const std::string pre = std::string(who) + ": ";
+  if (ir_rows_shard_refused(r, pre, err)) return true;
+  if (r->sol.nw < 1 || r->sol_n < 1) { set_err(err, pre + "the handle has no solar bins (nw_sol = " + std::to_string(r->sol.nw) + ")"); return true; }
+  if (refuse(r, who, NEED_OPACITIES, err)) return true;
+  const int nzen = (int)r->zenith_u.size();
+  if (nzen < 1) { set_err(err, pre + "the handle has no zenith angle (nzen = " + std::to_string(nzen) + ")"); return true; }
+  const int NQ = r->sol_n * r->ng;
+  const size_t n_work = sol_opr_work_count(r->nz, NQ), n_part = sol_opr_part_count(r->nz, NQ);
+  if (sizeof(double) * ((double)n_work + (double)n_part) > IR_ADJOINT_MAX_BYTES) {
+    set_err(err, pre + "the work buffer of " + std::to_string(NQ) + " (bin, g-point) pairs of nz = " + std::to_string(r->nz) + " layers would take " +
+                     std::to_string(sizeof(double) * (n_work + n_part)) + " bytes, more than " + std::to_string((long long)IR_ADJOINT_MAX_BYTES));
+    return true;
+  }
+  return false;
+}
+// doubles of the four outputs: grad_tau, grad_w0, grad_g (radtran_opr_get's layout), grad_albedo (nw_sol)
+static void sol_opr_counts(Radtran *r, size_t counts[4]) {
+  counts[0] = r->d_tau.n; counts[1] = r->d_tau.n; counts[2] = r->d_g.n; counts[3] = (size_t)r->sol.nw;
+}
+// The pass itself: device arrays in, device arrays out (each of `out` the whole array, or null), enqueued on the handle's
+// stream behind ready_stored_opacities.  The bins outside the solar channel are zeroed here.
+static void sol_opr_enqueue(Radtran *r, const std::vector<int> &lv, const double *const gs[3], const double *const gn[2],
+                            double *const out[4]) {
+  const int nz = r->nz, nsel = (int)lv.size(), NQ = r->sol_n * r->ng;
+  size_t counts[4];
+  sol_opr_counts(r, counts);
+  for (int k = 0; k < 4; k++)
+    if (out[k]) HIPCHK(hipMemsetAsync(out[k], 0, sizeof(double) * counts[k], r->stream));
+  const size_t n_work = sol_opr_work_count(nz, NQ), n_part = sol_opr_part_count(nz, NQ);
+  r->d_adjoint.reserve(n_work + n_part);
+  SolOprParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.nz = nz; p.ng = r->ng; p.n_sol = r->sol_n; p.sol_lo = r->sol_lo; p.sol_start = r->sol.ind_start; p.NQ = NQ;
+  p.nzen = (int)r->zenith_u.size();
+  p.tau = r->d_tau.p; p.w0 = r->d_w0.p; p.g = r->d_g.p; p.wbin = r->d_wbin.p;
+  p.zen_u = r->d_zen_u.p; p.zen_w = r->d_zen_w.p; p.zen_iu = r->d_zen_iu.p;
+  p.albedo = r->d_albedo.p; p.photons_sol = r->d_photons.p;
+  p.am_f1 = r->d_am_f1.p; p.am_f2 = r->d_am_f2.p; p.am_dw = r->d_am_dw.p;
+  p.scale = r->photon_scale_factor * r->diurnal_fac;
+  p.sol_freq = r->sol.d_freq.p;
+  p.nsel = nsel; p.gs_ld = r->sol.nw; p.level = ir_upload_indices(r, lv, true);
+  p.gs_up = gs[0]; p.gs_dn = gs[1]; p.gs_am = gs[2]; p.gn_up = gn[0]; p.gn_dn = gn[1];
+  p.work = r->d_adjoint.p; p.part_g = p.work + n_work; p.part_alb = p.part_g + (size_t)NQ * nz;
+  p.grad_tau = out[0]; p.grad_w0 = out[1]; p.grad_g = out[2]; p.grad_albedo = out[3];
+  launch_sol_opr_sens(p, r->stream);
+  HIPCHK(hipGetLastError());
+}
+
+void radtran_sol_spectra_opr_vjp_device(void *ptr, const int *nsel_, const int *spec_level, const double *d_g_sol_fup,
+                                        const double *d_g_sol_fdn, const double *d_g_sol_amean, const double *d_g_fup_n,
+                                        const double *d_g_fdn_n, double *d_grad_tau, double *d_grad_w0, double *d_grad_g,
+                                        double *d_grad_albedo, const void *producer_stream, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const char *who = "sol_spectra_opr_vjp_device";
+  const double *const gs[3] = {d_g_sol_fup, d_g_sol_fdn, d_g_sol_amean}, *const gn[2] = {d_g_fup_n, d_g_fdn_n};
+  double *const out[4] = {d_grad_tau, d_grad_w0, d_grad_g, d_grad_albedo};
+  std::vector<int> lv;
+  if (sol_opr_refused(r, who, *nsel_, spec_level, gs, gn, out, lv, err)) return;
+  if (ir_rows_not_device(r, std::string(who) + ": ", {{"g_sol_fup", d_g_sol_fup}, {"g_sol_fdn", d_g_sol_fdn}, {"g_sol_amean", d_g_sol_amean},
+                                                      {"g_fup_n", d_g_fup_n}, {"g_fdn_n", d_g_fdn_n}, {"grad_tau", d_grad_tau},
+                                                      {"grad_w0", d_grad_w0}, {"grad_g", d_grad_g}, {"grad_albedo", d_grad_albedo}}, err)) return;
+  if (sol_opr_handle_refused(r, who, err)) return;
+  TRY
+  ready_stored_opacities(r);
+  wait_for_producer(r, producer_stream);
+  sol_opr_enqueue(r, lv, gs, gn, out);
+  CATCH(err)
+}
+
+// ... with host arrays, synchronous: the cotangents go up, the gradients come back through the pinned block
+void radtran_sol_spectra_opr_vjp(void *ptr, const int *nsel_, const int *spec_level, const double *g_sol_fup, const double *g_sol_fdn,
+                                 const double *g_sol_amean, const double *g_fup_n, const double *g_fdn_n, double *grad_tau,
+                                 double *grad_w0, double *grad_g, double *grad_albedo, char *err) {
+  clear_err(err);
+  GUARD_BUILT(r, ptr, err);
+  const char *who = "sol_spectra_opr_vjp";
+  const double *const gs[3] = {g_sol_fup, g_sol_fdn, g_sol_amean}, *const gn[2] = {g_fup_n, g_fdn_n};
+  double *const out[4] = {grad_tau, grad_w0, grad_g, grad_albedo};
+  std::vector<int> lv;
+  if (sol_opr_refused(r, who, *nsel_, spec_level, gs, gn, out, lv, err)) return;
+  if (sol_opr_handle_refused(r, who, err)) return;
+  TRY
+  ready_stored_opacities(r);
+  const int nsel = *nsel_;
+  const size_t spec = (size_t)r->sol.nw * nsel, sums = (size_t)nsel;
+  r->d_rows_out.reserve(std::max<size_t>(1, 3 * spec + 2 * sums));
+  const double *dgs[3] = {nullptr, nullptr, nullptr}, *dgn[2] = {nullptr, nullptr};
+  {
+    double *at = r->d_rows_out.p;
+    for (int k = 0; k < 3; k++)
+      if (gs[k]) {
+        HIPCHK(hipMemcpyAsync(at, gs[k], sizeof(double) * spec, hipMemcpyHostToDevice, r->stream));
+        dgs[k] = at; at += spec;
+      }
+    for (int k = 0; k < 2; k++)
+      if (gn[k]) {
+        HIPCHK(hipMemcpyAsync(at, gn[k], sizeof(double) * sums, hipMemcpyHostToDevice, r->stream));
+        dgn[k] = at; at += sums;
+      }
+  }
+  size_t counts[4], total = 0;
+  sol_opr_counts(r, counts);
+  for (int k = 0; k < 4; k++) total += out[k] ? counts[k] : 0;
+  r->d_bout.reserve(total);
+  double *d_out[4] = {nullptr, nullptr, nullptr, nullptr};
+  {
+    double *at = r->d_bout.p;
+    for (int k = 0; k < 4; k++)
+      if (out[k]) { d_out[k] = at; at += counts[k]; }
+  }
+  sol_opr_enqueue(r, lv, dgs, dgn, d_out);
+  for (int k = 0; k < 4; k++)
+    if (out[k]) rows_to_host(r, d_out[k], out[k], counts[k]);
+  HIPCHK(hipStreamSynchronize(r->stream));
+  CATCH(err)
+}
+
 // What every column batch refuses before anything else, with the texts of radtran_toa_fluxes_batch
 static bool batch_refused(Radtran *r, const int *ncol, const int *has_particles, char *err) {
   if (*ncol < 1) { set_err(err, "\"T\" has the wrong input dimension."); return true; }
@@ -4638,6 +4776,80 @@ void clima_test_ir_opr_sens(const int *nz_, const int *ng_, const double *tau, c
         o_tau[d][(size_t)a * nz + i] = st; o_w0[d][(size_t)a * nz + i] = sw;
         o_g[d][(size_t)a * nz + i] = out[2 * ntau + (size_t)b * nz + i];
       }
+    }
+  CATCH(err)
+}
+
+// Test hook of the solar optical-property gradient (sol_opr_sens.inc), in the shape of clima_test_ir_opr_sens with
+// clima_test_solar_batch's inputs: one column's tau / w0 / g (the same for every g-point, weights wbin), nzen zenith
+// angles with their weights, the surface reflectance rsfc and nrow levels (0..nz, TOA-first) -> the derivatives of fup,
+// fdn and amean at level(a) in tau(n), w0(n), g(n) ((nrow, nz) row after row, n TOA-first, summed over the g-points) and in
+// rsfc ((nrow)).  ONE launch of the production kernels with unit stellar flux and unit factors: every (row, quantity) is a
+// solar bin of its own with the column's opacities and a unit cotangent on that row and quantity alone.
+void clima_test_sol_opr_sens(const int *nz_, const int *ng_, const double *tau, const double *w0, const double *g,
+                             const double *wbin, const int *nzen_, const double *zen_u, const double *zen_w, const double *rsfc,
+                             const int *nrow_, const int *level, double *up_tau, double *up_w0, double *up_g, double *up_rsfc,
+                             double *dn_tau, double *dn_w0, double *dn_g, double *dn_rsfc, double *am_tau, double *am_w0,
+                             double *am_g, double *am_rsfc, char *err) {
+  clear_err(err);
+  TRY
+  const int nz = *nz_, ng = *ng_, nr = *nrow_, nzen = *nzen_, nb = 3 * nr, NQ = nb * ng;
+  if (nz < 1 || ng < 1 || ng > 32 || nr < 1 || nzen < 1 || nzen > MAX_ZEN) throw HipFail{"clima_test_sol_opr_sens: bad nz / ng / nrow / nzen"};
+  for (int a = 0; a < nr; a++)
+    if (level[a] < 0 || level[a] > nz) throw HipFail{"clima_test_sol_opr_sens: bad level"};
+  const size_t ntau = (size_t)NQ * nz, ngg = (size_t)nb * nz;
+  std::vector<double> h_tau(ntau), h_w0(ntau), h_g(ngg), h_zen((size_t)3 * nzen), h_gs(3 * (size_t)nb * nr, 0.0);
+  for (int c = 0; c < NQ; c++)
+    for (int i = 0; i < nz; i++) { h_tau[(size_t)c * nz + i] = tau[i]; h_w0[(size_t)c * nz + i] = w0[i]; }
+  for (int b = 0; b < nb; b++)
+    for (int i = 0; i < nz; i++) h_g[(size_t)b * nz + i] = g[i];
+  for (int z = 0; z < nzen; z++) { h_zen[z] = zen_u[z]; h_zen[nzen + z] = zen_w[z]; h_zen[2 * nzen + z] = 1.0 / zen_u[z]; }
+  for (int a = 0; a < nr; a++)
+    for (int k = 0; k < 3; k++) h_gs[(size_t)k * nb * nr + (size_t)(3 * a + k) + (size_t)nb * a] = 1.0;   // quantity k of row a: bin 3a + k
+  DevBuf<double> d_tau, d_w0, d_g, d_wbin, d_zen, d_alb, d_ones, d_freq, d_gs, d_work, d_out;
+  DevBuf<int> d_lv;
+  d_tau.upload(h_tau); d_w0.upload(h_w0); d_g.upload(h_g);
+  d_wbin.upload(std::vector<double>(wbin, wbin + ng));
+  d_zen.upload(h_zen);
+  d_alb.upload(std::vector<double>((size_t)nb, *rsfc));
+  d_ones.upload(std::vector<double>((size_t)nb, 1.0));
+  d_freq.upload(std::vector<double>((size_t)nb + 1, 0.0));
+  d_gs.upload(h_gs);
+  d_lv.upload(std::vector<int>(level, level + nr));
+  const size_t n_work = sol_opr_work_count(nz, NQ), n_part = sol_opr_part_count(nz, NQ);
+  d_work.alloc(n_work + n_part); d_work.zero();
+  d_out.alloc(2 * ntau + ngg + nb); d_out.zero();
+  SolOprParams p;
+  std::memset(&p, 0, sizeof(p));
+  p.nz = nz; p.ng = ng; p.n_sol = nb; p.NQ = NQ; p.nzen = nzen;
+  p.tau = d_tau.p; p.w0 = d_w0.p; p.g = d_g.p; p.wbin = d_wbin.p;
+  p.zen_u = d_zen.p; p.zen_w = d_zen.p + nzen; p.zen_iu = d_zen.p + 2 * nzen;
+  p.albedo = d_alb.p; p.photons_sol = d_ones.p; p.am_f1 = d_ones.p; p.am_f2 = d_ones.p; p.am_dw = d_ones.p; p.scale = 1.0;
+  p.sol_freq = d_freq.p;
+  p.nsel = nr; p.gs_ld = nb; p.level = d_lv.p;
+  p.gs_up = d_gs.p; p.gs_dn = d_gs.p + (size_t)nb * nr; p.gs_am = d_gs.p + (size_t)2 * nb * nr;
+  p.work = d_work.p; p.part_g = p.work + n_work; p.part_alb = p.part_g + (size_t)NQ * nz;
+  p.grad_tau = d_out.p; p.grad_w0 = d_out.p + ntau; p.grad_g = d_out.p + 2 * ntau; p.grad_albedo = d_out.p + 2 * ntau + ngg;
+  launch_sol_opr_sens(p, nullptr);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipDeviceSynchronize());
+  std::vector<double> out(2 * ntau + ngg + nb);
+  HIPCHK(hipMemcpy(out.data(), d_out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost));
+  double *const o_tau[3] = {up_tau, dn_tau, am_tau}, *const o_w0[3] = {up_w0, dn_w0, am_w0}, *const o_g[3] = {up_g, dn_g, am_g},
+         *const o_r[3] = {up_rsfc, dn_rsfc, am_rsfc};
+  for (int a = 0; a < nr; a++)
+    for (int k = 0; k < 3; k++) {
+      const int b = 3 * a + k;
+      for (int i = 0; i < nz; i++) {
+        double st = 0.0, sw = 0.0;
+        for (int c = 0; c < ng; c++) {      // the g-points in g order
+          st = st + out[((size_t)b * ng + c) * nz + i];
+          sw = sw + out[ntau + ((size_t)b * ng + c) * nz + i];
+        }
+        o_tau[k][(size_t)a * nz + i] = st; o_w0[k][(size_t)a * nz + i] = sw;
+        o_g[k][(size_t)a * nz + i] = out[2 * ntau + (size_t)b * nz + i];
+      }
+      o_r[k][a] = out[2 * ntau + ngg + b];
     }
   CATCH(err)
 }

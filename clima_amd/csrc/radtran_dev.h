@@ -573,6 +573,32 @@ constexpr int OPR_WORK_ROWS = 6;
 inline size_t ir_opr_work_count(int nz, int NQ) { return (size_t)NQ * OPR_WORK_ROWS * 2 * nz; }
 inline size_t ir_opr_part_count(int nz, int NQ) { return (size_t)NQ * nz; }
 void launch_ir_opr_sens(const IrOprParams &p, hipStream_t s);
+// Gradient of a loss on the solar level values fup, fdn, amean in the stored tau, w0, g and in the surface albedo
+// (sol_opr_sens.inc, radtran_sol_spectra_opr_vjp): one adjoint and one forward solve per (bin, g-point) whatever the
+// numbers of zenith angles and levels.  q = (bin - sol_lo) * ng + g; the per-bin arrays are indexed by the solar channel's bin.
+struct SolOprParams {
+  int nz, ng, n_sol, sol_lo, sol_start, NQ;  // this launch's solar bins sol_lo ..; channel -> opacity-bin offset
+  int nzen;
+  const double *tau, *w0, *g, *wbin;       // opr (TOA-first layers), g-point weights
+  const double *zen_u, *zen_w, *zen_iu;    // [nzen] each: u0, its weight, 1 / u0
+  const double *albedo;                    // [nw_sol]
+  const double *photons_sol;               // [nw_sol], unscaled
+  const double *am_f1, *am_f2, *am_dw;     // per solar bin amean unit factors (radiate.f90:174-178)
+  double scale;                            // photon scale factor x diurnal_fac
+  const double *sol_freq;                  // solar channel [nw_sol+1] (the widths of the sums' cotangents)
+  int nsel, gs_ld;                         // requested levels; the cotangent spectra's leading dimension (nw_sol)
+  const int *level;                        // [nsel] TOA-first, 0..nz
+  const double *gs_up, *gs_dn, *gs_am;     // (gs_ld, nsel) cotangents of the three spectra, or null
+  const double *gn_up, *gn_dn;             // (nsel) cotangents of the sums over the bins (times the bin's width), or null
+  double *work;                            // [NQ][SOL_OPR_WORK_ROWS][2 nz]: k_opr_adjoint's six rows, (cp0 | cpb), (cm0 | cmb), (tauc | direct)
+  double *part_g, *part_alb;               // [NQ][nz], [NQ]: a g-point's part of grad_g and of grad_albedo
+  double *grad_tau, *grad_w0, *grad_g;     // the optical properties' own layouts (radtran_opr_get), or null: not asked for
+  double *grad_albedo;                     // [nw_sol], or null
+};
+constexpr int SOL_OPR_WORK_ROWS = 9;
+inline size_t sol_opr_work_count(int nz, int NQ) { return (size_t)NQ * SOL_OPR_WORK_ROWS * 2 * nz; }
+inline size_t sol_opr_part_count(int nz, int NQ) { return (size_t)NQ * (nz + 1); }
+void launch_sol_opr_sens(const SolOprParams &p, hipStream_t s);
 // IR spectra of many temperature profiles from the adjoint's unit-amplitude rows (ir_rows_apply.inc,
 // radtran_ir_spectra_batch): f(bin, a, c) = sum over j of w(bin, a, j) B(avg_freq(bin), x_c(j)).  The ndir directions
 // asked for stand at places 0 and 1 (w0 / out0 / fn0, then w1 / out1 / fn1); functional F = place nsel + a.

@@ -131,6 +131,9 @@ SIGNATURES = {
     "radtran_ir_spectra_opr_vjp": [_vp, _dp, _ip, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _err],
     "radtran_ir_spectra_opr_vjp_device": [_vp, _vp, _ip, _vp, _ip, _ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _err],   # device addresses; the level list is the host's
     "clima_test_ir_adjoint": [_ip, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _err],
+    "radtran_sol_spectra_opr_vjp": [_vp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _err],
+    "radtran_sol_spectra_opr_vjp_device": [_vp, _ip, _ip, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _err],   # device addresses; the level list is the host's
+    "clima_test_sol_opr_sens": [_ip, _ip, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _ip, _ip] + [_dp] * 12 + [_err],
     "clima_test_ir_opr_sens": [_ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _err],
     "clima_test_ir_response": [_ip, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _err],
     "radtran_set_bolometric_flux_wrapper": [_vp, _dp],

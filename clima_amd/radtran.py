@@ -1039,6 +1039,83 @@ class Radtran:
             producer, self._err), sync)
         return out
 
+    SOL_SPECTRA_OPR_GRADS = ("fup", "fdn", "amean", "fup_n", "fdn_n")
+    SOL_SPECTRA_OPR_WRT = ("tau", "w0", "g", "albedo")
+
+    def _sol_spectra_opr_names(self, who, nz, grads, levels, wrt):
+        """What both forms of `sol_spectra_opr_vjp` check alike, with the prefix `who`: the names in `wrt` (-> in the ABI's
+        order), `levels` (-> 1..nz+1 as the ABI takes them) and the keys of `grads` (-> the dict without its None entries);
+        reads SOL_SPECTRA_OPR_GRADS and SOL_SPECTRA_OPR_WRT alone"""
+        names = _names_among(who, "wrt", wrt, self.SOL_SPECTRA_OPR_WRT)
+        rows = _level_rows(who, nz, levels)
+        _keys_among(who, "grads", grads, self.SOL_SPECTRA_OPR_GRADS)
+        given = {k: v for k, v in grads.items() if v is not None}
+        if not given:
+            raise ClimaException(who + '"grads" holds none of %s' % ", ".join(self.SOL_SPECTRA_OPR_GRADS))
+        return names, rows, given
+
+    def _sol_spectra_opr_request(self, nz, nw_sol, grads, levels, wrt):
+        """The arrays of `sol_spectra_opr_vjp` as the ABI takes them -- (levels 1..nz+1, the five cotangents in the ABI's
+        order (Fortran-ordered float64, None where absent), the names of `wrt` in the ABI's order) -- for a handle of nz
+        layers and nw_sol solar bins; wrong shapes, unknown keys and names, levels outside -(nz+1)..nz and a request
+        without any cotangent are refused by name (reads SOL_SPECTRA_OPR_GRADS and SOL_SPECTRA_OPR_WRT alone: no handle
+        needed)."""
+        who = "sol_spectra_opr_vjp: "
+        names, rows, given = Radtran._sol_spectra_opr_names(self, who, nz, grads, levels, wrt)
+        nsel = len(rows)
+        g = [np.asfortranarray(given[k], dtype=np.float64) if k in given else None for k in self.SOL_SPECTRA_OPR_GRADS]
+        for k, a in zip(self.SOL_SPECTRA_OPR_GRADS, g):
+            want = (nsel,) if k.endswith("_n") else (nw_sol, nsel)
+            if a is not None and a.shape != want:
+                raise ClimaException(who + '"%s" has the shape %s, not %s' % (k, a.shape, want))
+        return rows, g, names
+
+    def sol_spectra_opr_vjp(self, grads, levels=(-1,), wrt=("tau", "w0", "g", "albedo")):
+        """The gradient of a loss on the solar spectra with respect to the stored optical properties and the surface albedo
+        (radtran_sol_spectra_opr_vjp): what is differentiated is `radiate(..., compute_solar=True, compute_opacity=False)`
+        under the handle's zenith angles and weights, albedo, photon scale factor and diurnal factor, read at
+        `wrk_sol.fup_a / fdn_a / amean [levels[a], l]` and `wrk_sol.fup_n / fdn_n [levels[a]]`, in the call's own units;
+        `grads` is a dict of cotangents -- "fup" / "fdn" / "amean" (nw_sol, nsel), "fup_n" / "fdn_n" (nsel,), an absent one
+        counting as 0.  Returns a dict with the names in `wrt`: "tau" and "w0" (nz, ngauss, nw), "g" (nz, nw),
+        Fortran-ordered, in `opr()`'s layout element by element (TOA-first, opacity-bin index, 0 outside the solar
+        channel), the g-point's weight included, and "albedo" (nw_sol,); tau, w0 and g count as independent inputs, the
+        delta-Eddington scaling is differentiated.  One adjoint and one forward two-stream solve per (bin, g-point)
+        however many levels and zenith angles; bitwise repeatable; the handle's state is left untouched.
+        `grey_sensitivity` works on the result as on `ir_spectra_opr_vjp`'s."""
+        nz, nw_sol = self.nz, len(self.sol.freq) - 1
+        rows, g, names = self._sol_spectra_opr_request(nz, nw_sol, grads, levels, wrt)
+        shapes = dict(tau=(nz, self.ngauss, self.nw), w0=(nz, self.ngauss, self.nw), g=(nz, self.nw), albedo=(nw_sol,))
+        out = {name: np.empty(shapes[name], order="F") for name in names}
+        ptr = lambda a: _d(a) if a is not None else None   # noqa: E731
+        self._L.radtran_sol_spectra_opr_vjp(self._ptr, _i(len(rows)), rows.ctypes.data_as(C.POINTER(C.c_int)),
+                                            ptr(g[0]), ptr(g[1]), ptr(g[2]), ptr(g[3]), ptr(g[4]), ptr(out.get("tau")),
+                                            ptr(out.get("w0")), ptr(out.get("g")), ptr(out.get("albedo")), self._err)
+        self._check()
+        return out
+
+    def sol_spectra_opr_vjp_tensors(self, grads, levels=(-1,), wrt=("tau", "w0", "g", "albedo"), sync=False):
+        """`sol_spectra_opr_vjp` on torch CUDA float64 tensors (radtran_sol_spectra_opr_vjp_device): `grads` "fup" / "fdn" /
+        "amean" (nsel, nw_sol), "fup_n" / "fdn_n" (nsel,), C-contiguous -- the host form's arrays, transposed.  Returns a
+        dict of fresh tensors "tau" / "w0" (nw, ngauss, nz), "g" (nw, nz), "albedo" (nw_sol,), bit for bit the host form's,
+        transposed; stream ordering and `sync` as in `ir_spectra_batch_tensors`."""
+        import torch
+        who = "sol_spectra_opr_vjp_device"
+        nz, nw_sol = self.nz, len(self.sol.freq) - 1
+        names, rows, g = Radtran._sol_spectra_opr_names(self, who + ": ", nz, grads, levels, wrt)
+        nsel = len(rows)
+        for k, t in g.items():
+            self._ir_tensor_check(who, k, t, (nsel,) if k.endswith("_n") else (nsel, nw_sol))
+        first = next(iter(g.values()))
+        dev = first.device if first.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        shapes = dict(tau=(self.nw, self.ngauss, nz), w0=(self.nw, self.ngauss, nz), g=(self.nw, nz), albedo=(nw_sol,))
+        out = {name: torch.empty(shapes[name], dtype=torch.float64, device=dev) for name in names}
+        addr = lambda d, key: d[key].data_ptr() if key in d else None   # noqa: E731
+        self._on_handle_stream(dev, lambda producer: self._L.radtran_sol_spectra_opr_vjp_device(
+            self._ptr, _i(nsel), rows.ctypes.data_as(C.POINTER(C.c_int)),
+            addr(g, "fup"), addr(g, "fdn"), addr(g, "amean"), addr(g, "fup_n"), addr(g, "fdn_n"),
+            addr(out, "tau"), addr(out, "w0"), addr(out, "g"), addr(out, "albedo"), producer, self._err), sync)
+        return out
+
     def ir_spectra_torch(self, T_surface, T, levels=(-1,), parts=("up",), fluxes=False, weights=None):
         """`ir_spectra_batch_tensors` as a differentiable torch op: the same dict of tensors (without the weights), with
         gradients flowing to `T_surface` (ncol,) and `T` (ncol, nz) through `ir_spectra_vjp_tensors` -- the exact gradient

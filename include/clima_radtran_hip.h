@@ -538,6 +538,43 @@ void radtran_ir_spectra_opr_vjp_device(void *ptr, const double *d_T_surface, con
                                        const double *d_g_fup_n, const double *d_g_fdn_n,
                                        double *d_grad_tau, double *d_grad_w0, double *d_grad_g,
                                        const void *producer_stream, char *err);
+/* The gradient of a loss on the SOLAR spectra in the STORED optical properties and in the surface albedo (a
+ * vector-Jacobian product in tau, w0, g and surface_albedo).  What is differentiated is radiate(..., compute_solar=.true.,
+ * compute_opacity=.false.) on the stored opacities under the handle's current zenith_u, zenith_weights, surface_albedo,
+ * photon_scale_factor and diurnal_fac, read at wrk_sol%fup_a / fdn_a / amean (spec_level(a), l) and at wrk_sol%fup_n /
+ * fdn_n (spec_level(a)); levels 1..nz+1 ground-first, any order, repeats allowed.  Everything is in the call's own units:
+ * photons_sol, the photon scale factor and diurnal_fac, and amean's unit factors (clima_radtran_radiate.f90:164-179).  The
+ * cotangents g_sol_fup / g_sol_fdn / g_sol_amean are (nw_sol, nsel), the bin fastest in rtchannel_freq_get order; g_fup_n /
+ * g_fdn_n (nsel) enter as g_n(a) (freq(l) - freq(l+1)); a NULL counts as 0.  Outputs: grad_tau, grad_w0 (nz, ngauss, nw)
+ * and grad_g (nz, nw) in radtran_opr_get's layout, TOA-first, opacity-bin index, 0.0 in the bins outside the solar channel,
+ * the g-point's weight included, grad_g summed over the g-points in g order; grad_albedo (nw_sol), the derivative in
+ * surface_albedo(l), a by-product of the same solve; any of the four may be NULL, not all.  tau, w0 and g are independent
+ * inputs, as two_stream_solar takes them: its delta-Eddington scaling is part of the function and is differentiated, the
+ * opacity step's max_w0 cap and tau_min rule are not.  One adjoint and one forward two-stream solve per (bin, g-point)
+ * whatever nsel and the number of zenith angles are (clima_amd/csrc/sol_opr_sens.inc).  Contract: bitwise repeatable, no
+ * atomics, fixed summation orders (the angles in their order inside a g-point, the g-points in g order); all-zero
+ * cotangents give exactly 0.0 (a bin without a cotangent is not solved); a loss on fdn at level nz+1 alone gives exactly
+ * 0 (direct(1) = u0 is a constant); the handle's wrk_ir, wrk_sol, f_total, spectra, stored opacities and fields are left
+ * untouched; a pending deferred integration and a two-in-flight join are settled first; every nz >= 1 and every g-point
+ * count of the single call, the handle's zenith angles.  In a (bin, g-point) without any scattering (w0 = 0 in every layer)
+ * the cotangents of fdn give exactly 0 in the albedo.  Where lambda = 1 / u0 exactly in a layer the derivative is
+ * unspecified (the forward call divides by lambda^2 - 1 / u0^2 there as well).  Refused (err; nothing is enqueued or
+ * written), naming the argument and its value: a handle that is not constructed; nsel < 1; a NULL spec_level; a level
+ * outside 1..nz+1; no cotangent at all; all four outputs NULL; a bin shard or a communicator ("needs the whole
+ * spectrum"); a handle without solar bins; no opacities ("sol_spectra_opr_vjp needs opacities: ..."); a work buffer (9 x
+ * 2 nz + nz + 1 doubles per (bin, g-point)) above the 4 GiB bound of radtran_ir_jacobian_spectral_rows. */
+void radtran_sol_spectra_opr_vjp(void *ptr, const int *nsel, const int *spec_level,
+                                 const double *g_sol_fup, const double *g_sol_fdn, const double *g_sol_amean,
+                                 const double *g_fup_n, const double *g_fdn_n,
+                                 double *grad_tau, double *grad_w0, double *grad_g, double *grad_albedo, char *err);
+/* ... with every array but spec_level in device memory of the handle's device (refused by name otherwise), enqueued on
+ * the handle's stream behind `producer_stream` and final at the next radtran_synchronize, as
+ * radtran_ir_spectra_opr_vjp_device; bit for bit the host form's gradient. */
+void radtran_sol_spectra_opr_vjp_device(void *ptr, const int *nsel, const int *spec_level,
+                                        const double *d_g_sol_fup, const double *d_g_sol_fdn, const double *d_g_sol_amean,
+                                        const double *d_g_fup_n, const double *d_g_fdn_n,
+                                        double *d_grad_tau, double *d_grad_w0, double *d_grad_g, double *d_grad_albedo,
+                                        const void *producer_stream, char *err);
 /* clima/fortran/Radtran.f90:41-75 (same names and argument lists): the YAML text of
  * OpticalProperties_opacities2yaml (src/radtran/clima_radtran_types.f90:328-430).  _1 allocates
  * the string and returns its length, _2 copies it into out_c (out_len + 1 chars) and frees it.
@@ -801,6 +838,20 @@ void clima_test_ir_opr_sens(const int *nz, const int *ng, const double *tau, con
                             const double *bplanck, const double *ir_par, const double *wbin, const int *nrow,
                             const int *level, double *up_tau, double *up_w0, double *up_g,
                             double *dn_tau, double *dn_w0, double *dn_g, char *err);
+
+/* The same for the solar optical-property gradient of radtran_sol_spectra_opr_vjp (sol_opr_sens.inc): the column of
+ * clima_test_solar_batch as one solar bin with nzen zenith angles (zen_u, zen_w), the surface reflectance rsfc (1) and
+ * nrow levels (0..nz, TOA-first) -> up_tau(a, n) = d fup(level(a)) / d tau(n), up_w0, up_g ((nrow, nz) row after row, n
+ * TOA-first), up_rsfc(a) = d fup(level(a)) / d rsfc, and dn_* (fdn), am_* (amean) likewise, summed over the zenith angles
+ * with their weights and over the g-points with the weights wbin -- produced by ONE launch of the production kernels
+ * (k_sol_opr_adjoint, k_sol_opr_sum_g) with unit stellar flux and unit factors, each (row, quantity) a bin of its own with
+ * a unit cotangent.  nz >= 1. */
+void clima_test_sol_opr_sens(const int *nz, const int *ng, const double *tau, const double *w0, const double *g,
+                             const double *wbin, const int *nzen, const double *zen_u, const double *zen_w, const double *rsfc,
+                             const int *nrow, const int *level,
+                             double *up_tau, double *up_w0, double *up_g, double *up_rsfc,
+                             double *dn_tau, double *dn_w0, double *dn_g, double *dn_rsfc,
+                             double *am_tau, double *am_w0, double *am_g, double *am_rsfc, char *err);
 
 /* The far accumulation of the response form has two kernels: 0 (default) the matrix-core one (v_mfma_f64_16x16x4_f64),
  * 1 the vector one it replaced.  Process-wide; tests hold the two against each other. */
