@@ -3570,6 +3570,11 @@ void launch_integrate(const IntegrateParams &p, hipStream_t s) {
     hipLaunchKernelGGL(k_integrate_one, dim3((nl + INT_LV - 1) / INT_LV, 4, p.ncol > 0 ? p.ncol : 1), dim3(INT_LV * INT_CG), integrate_lds_bytes(p.nchunk), s, p);
     return;
   }
+  launch_integrate_two(p, s);
+}
+
+// the two-launch form: any bin count, one column, the rows into device memory only
+void launch_integrate_two(const IntegrateParams &p, hipStream_t s) {
   hipLaunchKernelGGL(k_integrate_partial, dim3(p.nchunk, 4), dim3(256), 0, s, p);
   hipLaunchKernelGGL(k_integrate_final, dim3(1), dim3(1024), 0, s, p);
 }

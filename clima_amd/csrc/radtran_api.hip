@@ -4558,6 +4558,87 @@ void clima_test_two_stream(const int *nz_, const int *ng_, const int *form, cons
   CATCH(err)
 }
 
+// Test hook of the sums over the bins: the production integration kernels on per-bin arrays, channels and owned ranges
+// given directly, no handle.  ir_dims / sol_dims = {bins of the channel, first owned bin (0-based), owned bins}, freq
+// [bins + 1]; the per-bin arrays [ncol][bins][nz+1] dense, staged on the device spec_stride doubles apart per column
+// with NaN between the columns.  form 0: launch_integrate as a call issues it (nchunk of the larger owned range, one
+// launch or two by integrate_fits_one_launch); 1: launch_integrate_two whatever the bin count.  Both: flux_n
+// [ncol][4][nz+1] goes in (flux_stride apart on the device) and comes back -- with do_solar = 0 its solar rows stay, or
+// are put back from flux_part --, flux_part (optional, one column) [4][nz+1] likewise.  2: launch_integrate_batch on the
+// IR arrays: flux_n [4][nz+1] is read for f_total, out [3][col0 + ncol][nz+1] goes in and comes back with the rows
+// from col0 on written.  tests/test_gpu_integration_sums.py holds what comes back to exact rational sums.
+void clima_test_integrate(const int *form_, const int *nz_, const int *ncol_, const int *spec_stride_, const int *flux_stride_,
+                          const int *ir_dims, const double *ir_freq, const int *sol_dims, const double *sol_freq,
+                          const double *ir_fup_a, const double *ir_fdn_a, const double *sol_fup_a, const double *sol_fdn_a,
+                          const int *do_solar, double *flux_n, double *flux_part, const int *col0_, double *out, char *err) {
+  clear_err(err);
+  TRY
+  const int form = *form_, nz = *nz_, nl = nz + 1, ncol = *ncol_, col0 = *col0_;
+  const int nw[2] = {ir_dims[0], sol_dims[0]}, lo[2] = {ir_dims[1], sol_dims[1]}, cnt[2] = {ir_dims[2], sol_dims[2]};
+  const size_t spec_stride = (size_t)*spec_stride_, flux_stride = (size_t)*flux_stride_;
+  if (form < 0 || form > 2 || nz < 1 || ncol < 1 || col0 < 0) throw HipFail{"clima_test_integrate: bad form / nz / ncol / col0"};
+  const int nch = form == 2 ? 1 : 2;   // the batch form sums the IR channel only
+  for (int c = 0; c < nch; c++)
+    if (nw[c] < 1 || lo[c] < 0 || cnt[c] < 0 || lo[c] + cnt[c] > nw[c]) throw HipFail{"clima_test_integrate: an owned range outside its channel"};
+  if (spec_stride < (size_t)std::max(nw[0], nch == 2 ? nw[1] : 0) * nl || (form != 2 && flux_stride < (size_t)4 * nl))
+    throw HipFail{"clima_test_integrate: a stride shorter than a column"};
+  const int nchunk = integrate_chunks(form == 2 ? cnt[0] : std::max(cnt[0], cnt[1]));
+  const bool two = form == 1 || (form == 0 && !integrate_fits_one_launch(nchunk));
+  if (two && ncol != 1) throw HipFail{"clima_test_integrate: the two-launch form takes one column"};
+  if (form != 2 && flux_part && ncol != 1) throw HipFail{"clima_test_integrate: flux_part belongs to one column"};
+  // (integrate_block keeps or puts back the solar rows of the FIRST column's flux_n whatever the column: a batch always computes them)
+  if (form != 2 && !*do_solar && ncol != 1) throw HipFail{"clima_test_integrate: do_solar = 0 takes one column"};
+  const double gap = std::numeric_limits<double>::quiet_NaN();
+  auto staged = [&](const double *src, size_t per_col, size_t stride, int n) {   // n columns `stride` apart, NaN between them
+    std::vector<double> h(stride * n, gap);
+    for (int c = 0; c < n; c++) std::copy(src + per_col * c, src + per_col * (c + 1), h.begin() + stride * c);
+    return h;
+  };
+  const double *spec[4] = {ir_fup_a, ir_fdn_a, sol_fup_a, sol_fdn_a};
+  DevBuf<double> d_spec[4], d_freq[2], d_flux, d_part, d_partial, d_out;
+  for (int a = 0; a < 2 * nch; a++) d_spec[a].upload(staged(spec[a], (size_t)nw[a / 2] * nl, spec_stride, ncol));
+  d_freq[0].upload(std::vector<double>(ir_freq, ir_freq + nw[0] + 1));
+  if (nch == 2) d_freq[1].upload(std::vector<double>(sol_freq, sol_freq + nw[1] + 1));
+  if (form == 2) {
+    const size_t out_arr = (size_t)(col0 + ncol) * nl;
+    d_flux.upload(std::vector<double>(flux_n, flux_n + (size_t)4 * nl));
+    d_out.upload(std::vector<double>(out, out + 3 * out_arr));
+    d_partial.upload(std::vector<double>((size_t)ncol * 2 * nchunk * nl, gap));
+    BatchIntegrateParams bp;
+    std::memset(&bp, 0, sizeof(bp));
+    bp.nz = nz; bp.ir_lo = lo[0]; bp.ir_n = cnt[0]; bp.nchunk = nchunk; bp.col0 = col0;
+    bp.fup_a = d_spec[0].p; bp.fdn_a = d_spec[1].p; bp.spec_stride = spec_stride;
+    bp.freq = d_freq[0].p; bp.partial = d_partial.p; bp.flux_n = d_flux.p; bp.out = d_out.p; bp.out_arr = out_arr;
+    launch_integrate_batch(bp, ncol, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, d_out.p, sizeof(double) * 3 * out_arr, hipMemcpyDeviceToHost));
+  } else {
+    d_flux.upload(staged(flux_n, (size_t)4 * nl, flux_stride, ncol));
+    if (flux_part) d_part.upload(std::vector<double>(flux_part, flux_part + (size_t)4 * nl));
+    d_partial.upload(std::vector<double>((size_t)4 * nchunk * nl, gap));
+    IntegrateParams ip;
+    std::memset(&ip, 0, sizeof(ip));
+    ip.ncol = ncol; ip.bs.res = spec_stride; ip.bs.flux = flux_stride;
+    ip.nz = nz; ip.nw_ir = nw[0]; ip.nw_sol = nw[1];
+    ip.ir_lo = lo[0]; ip.ir_n = cnt[0]; ip.sol_lo = lo[1]; ip.sol_n = cnt[1];
+    ip.do_solar = *do_solar != 0;
+    ip.ir_fup_a = d_spec[0].p; ip.ir_fdn_a = d_spec[1].p; ip.sol_fup_a = d_spec[2].p; ip.sol_fdn_a = d_spec[3].p;
+    ip.ir_freq = d_freq[0].p; ip.sol_freq = d_freq[1].p;
+    ip.flux_n = d_flux.p; ip.flux_part = flux_part ? d_part.p : nullptr;
+    ip.partial = d_partial.p; ip.nchunk = nchunk;
+    if (form == 0) launch_integrate(ip, nullptr);
+    else launch_integrate_two(ip, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    std::vector<double> h(flux_stride * ncol);
+    HIPCHK(hipMemcpy(h.data(), d_flux.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+    for (int c = 0; c < ncol; c++) std::copy(h.begin() + flux_stride * c, h.begin() + flux_stride * c + (size_t)4 * nl, flux_n + (size_t)4 * nl * c);
+    if (flux_part) HIPCHK(hipMemcpy(flux_part, d_part.p, sizeof(double) * 4 * nl, hipMemcpyDeviceToHost));
+  }
+  CATCH(err)
+}
+
 // Test hook of k_twostream_sol_batch, the counterpart of clima_test_two_stream for it: one column's tau / w0 / g (nz,
 // TOA-first; the same for every one of the ng g-points, weights wbin) as one solar bin, `ncol` cases of nzen angles
 // (zen_u, zen_w (nzen, ncol)) and surface reflectance rsfc (ncol) through the production kernel with unit stellar flux

@@ -767,6 +767,8 @@ bool launch_twostream_bounds(TwoStreamParams &p, const TsPlan &t, hipStream_t s)
 // (meta_nsrc: a device int, any value >= 1)
 bool launch_fused_twostream_only(TwoStreamParams &ts, int slots, const int *meta_nsrc, hipStream_t s, bool half = false, bool paired = false);
 void launch_integrate(const IntegrateParams &p, hipStream_t s);
+// what launch_integrate launches where integrate_fits_one_launch() does not hold (k_integrate_partial, k_integrate_final)
+void launch_integrate_two(const IntegrateParams &p, hipStream_t s);
 // one call's integration and the next call's prep pass as ONE grid (k_prep_integrate), where prep_integrate_merges() holds
 bool prep_integrate_merges(const PrepParams &pp, const IntegrateParams &ip);
 void launch_prep_integrate(const PrepParams &pp, const IntegrateParams &ip, hipStream_t s);

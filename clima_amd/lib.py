@@ -120,6 +120,7 @@ SIGNATURES = {
     "clima_test_device_rcp": [_ip, _dp, _dp, _err],
     "clima_test_wave_scan": [_ip, _dp, _dp, _dp, _err],
     "clima_test_two_stream": [_ip, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _err],
+    "clima_test_integrate": [_ip, _ip, _ip, _ip, _ip, _ip, _dp, _ip, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _dp, _err],
     "clima_test_green_far_form_set": [_ip],
     "radtran_batch_pin_results_set": [_vp, _ip],
     "radtran_batch_pin_results_get": [_vp, _ip],

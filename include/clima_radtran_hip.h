@@ -853,6 +853,25 @@ void clima_test_sol_opr_sens(const int *nz, const int *ng, const double *tau, co
                              double *dn_tau, double *dn_w0, double *dn_g, double *dn_rsfc,
                              double *am_tau, double *am_w0, double *am_g, double *am_rsfc, char *err);
 
+/* test hook: the sums over the bins, fup_n(i) = sum_l fup_a(i,l) * (freq(l) - freq(l+1)) (clima_radtran_radiate.f90:184-192),
+ * by the PRODUCTION integration kernels on arrays given directly, without a handle.  ir_dims / sol_dims = {bins of the
+ * channel, first owned bin (0-based), owned bins}; ir_freq / sol_freq (bins + 1); the per-bin arrays (nz+1, bins, ncol)
+ * column-major, ground-first as the kernels hold them; on the device the columns lie spec_stride (>= bins * (nz+1))
+ * doubles apart.
+ *   form 0: the launcher of every radiate call (k_integrate_one, or k_integrate_partial + k_integrate_final above 5440
+ *           owned bins in a channel: one column); 1: that two-launch pair at any bin count (one column).
+ *           flux_n (nz+1, 4, ncol) is read and written (flux_stride >= 4 * (nz+1) apart on the device): the rows ir up, ir
+ *           down, solar up, solar down; with do_solar = 0 the solar rows stay as given, or become flux_part's where
+ *           flux_part (nz+1, 4; optional, one column; read and written) is given (do_solar = 0: one column).  col0 and out
+ *           are not used.
+ *   form 2: the batch pair (k_integrate_partial_b, k_integrate_final_b) on ir_fup_a / ir_fdn_a; the solar arguments and
+ *           flux_stride are not used, flux_n (nz+1, 4) is read for f_total, out (nz+1, col0 + ncol, 3) = fup_n, fdn_n,
+ *           f_total is read and written: the columns from col0 on are the results. */
+void clima_test_integrate(const int *form, const int *nz, const int *ncol, const int *spec_stride, const int *flux_stride,
+                          const int *ir_dims, const double *ir_freq, const int *sol_dims, const double *sol_freq,
+                          const double *ir_fup_a, const double *ir_fdn_a, const double *sol_fup_a, const double *sol_fdn_a,
+                          const int *do_solar, double *flux_n, double *flux_part, const int *col0, double *out, char *err);
+
 /* The far accumulation of the response form has two kernels: 0 (default) the matrix-core one (v_mfma_f64_16x16x4_f64),
  * 1 the vector one it replaced.  Process-wide; tests hold the two against each other. */
 void clima_test_green_far_form_set(const int *vector_form);
